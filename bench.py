@@ -42,6 +42,14 @@ roofline.traffic / roofline.step_traffic (HBM bytes per launch / per step): the 
 of this script under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, 8 steps each) before this process touches the GPU
 (live_traffic(); VV_BENCH_LIVE_TRAFFIC=0, --no-extra-legs or N > 1: the committed passes of profiles/pmc_latest.json instead, labelled as such).
 Prints ONE JSON line on rank 0.
+
+A plain run (no --full) does only what the headline needs: set-up, the settle and W warm-up steps and the K timed steps of the end-to-end
+leg, without kernel timing, and the line with `value` / `ms_per_step` / `final_loss` / `config`.  --full adds everything else described
+above -- the live PMC passes, the box calibration, kernel durations and the roofline, the extra legs (--no-extra-legs trims them as before),
+the other operand type, the N > 1 schedule and fresh-process legs, the sampler's serial rate and the CPU baselines.
+--dump-outputs DIR: after the timed steps, what the timed path hands its caller -- loss and violations of the last step, the parameters
+and their momentum histories after it -- as DIR/<name>.npy (float32 / float64; an array larger than 2^22 elements as a fixed, seeded
+sample of 2^22 of them).  The inputs are seeded: two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -175,6 +183,23 @@ def box_record(box, ms_per_step, gemm_ms_in_step):
             "note": "a calibration of the box, not of the code: the top-level figures are the probe right AFTER the timed leg (steady state); "
                     "ms_per_step_at_ref = ms_per_step - gemm_ms_in_step x (1 - gemm_tflops / ref_gemm_tflops), gemm_ms_in_step = the two GEMM "
                     "kernels' durations"}
+
+
+DUMP_MAX_ELEMS = 1 << 22       # per array: W and its history of the largest workload (shipped, 4096 x 4096) are sampled, 2 x 16 MB
+
+
+def dump_outputs(out_dir, eng, loss, viol):
+    """--dump-outputs: what the timed path hands its caller after its last step -- loss and violations, the parameters and their momentum
+    histories (vv_params_get) -- as out_dir/<name>.npy.  An array of more than DUMP_MAX_ELEMS elements is written as the elements at a
+    fixed, seeded, sorted sample of its flat indices (the same sample in every run of the same workload)."""
+    os.makedirs(out_dir, exist_ok=True)
+    W, b, hW, hb = eng.params_get()
+    arrays = {"loss": np.array([loss], np.float64), "violations": np.array([viol], np.float64),
+              "W": W, "b": b, "W_history": hW, "b_history": hb}
+    for name, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def live_traffic(cfg_argv, first_timeout_s=300.0, timeout_s=150.0):
@@ -348,11 +373,17 @@ def main():
     ap.add_argument("--prefetch-depth", type=int, default=128,
                     help="batches the sampler keeps ahead of the consumer (the reference: 1).  128 (29 MB of index batches) covers the stretches of up to several hundred steps in "
                          "which the sampler -- 0.09 ms per batch at the median against a 0.21 ms step since round 5 (0.13 before), with the host's occasional slow stretches -- falls behind (profiles/r02_long_run.txt, r05_sampler_rates.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other measurement of this script (module docstring); off: the timed leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--settle-ms", type=float, default=50.0,
                     help="untimed steps of the same workload, this many ms of them, in front of the W warm-up steps of every "
                          "leg: the device needs ~25 ms of continuous work after an idle spell (set-up, a host-side leg) before "
                          "its step time is steady (profiles/r02_step_ablations.txt, 3.).  0 = none: W warm-up steps only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extra_legs, args.no_cpu_baseline = True, True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process -- which has not imported torch or touched HIP, and
@@ -456,7 +487,7 @@ def main():
     elif smode == "rank":
         # ---- per-rank samplers: the reference's sampler, one instance per rank, batch B_PER_GPU, its own rand() stream and
         # starting record.  Beside it rank 0 measures what ONE logical sampler of the global batch delivers (the bound of 'node').
-        if rank == 0:
+        if rank == 0 and args.full:
             sn = vv.Sampler(ds.video_id, ds.n_shots, ds.row_base, **skw)
             sn.prefetch_start(depth=args.prefetch_depth, threads=args.sampler_threads, shm_name=None, consumers=1)
             for _ in range(3): sn.next()
@@ -523,14 +554,16 @@ def main():
         batches = np.stack([smp2.next()[item_begin:item_begin + B_PER_GPU] for _ in range(n_res)])
         smp2.close()
     # raw rate of the sampler by itself (calling thread, no pipeline), for the record
-    smp3 = vv.Sampler(ds.video_id, ds.n_shots, ds.row_base, **skw)
-    smp3.next()
-    t0 = time.perf_counter()
-    n3 = max(3, 24 // world)
-    for _ in range(n3):
+    sampler_serial_ms = None
+    if args.full:
+        smp3 = vv.Sampler(ds.video_id, ds.n_shots, ds.row_base, **skw)
         smp3.next()
-    sampler_serial_ms = (time.perf_counter() - t0) / n3 * 1e3
-    smp3.close()
+        t0 = time.perf_counter()
+        n3 = max(3, 24 // world)
+        for _ in range(n3):
+            smp3.next()
+        sampler_serial_ms = (time.perf_counter() - t0) / n3 * 1e3
+        smp3.close()
 
     W0, b0 = init_weights(SEED, D, F)
     # Everything (kernels of the context and the collective) is issued under ONE explicit, non-default torch stream:
@@ -739,13 +772,13 @@ def main():
     run = Run(args.prec, args.dedup == "on")
     # The timed leg times the two GEMMs only when the other kernels' durations come from the per-step leg below (cfg 2: a GEMM
     # is the dominant kernel by 3x; a timed dispatch costs ~5 us of stream time, 7 of them on every 4th of 20 steps 4 %).
-    main_prof = "gemm" if (not args.no_extra_legs and args.workload == "cfg2") else "all"
+    main_prof = ("gemm" if (not args.no_extra_legs and args.workload == "cfg2") else "all") if args.full else False
     if shipped:
         S = max(1, int(args.settle_ms / 0.5))
     # Box calibration: two fixed probes of the library -- the benchmark's forward GEMM instantiation on contiguous random
     # rows, a 1 GiB streaming copy -- right before the settle steps of the timed leg and right after it: what THIS device delivers now.
     box = None
-    if rank == 0 and os.environ.get("VV_BENCH_NO_BOX") != "1":
+    if rank == 0 and args.full and os.environ.get("VV_BENCH_NO_BOX") != "1":
         box = {"before": run.eng.box_probe()}
     elapsed, kern, diag_ms = run.timed(main_source, per_step_events=diag, profile=main_prof)
     if box is not None:
@@ -756,6 +789,8 @@ def main():
         print("host ms in forward_backward_ring (warm-up included): " + " ".join("%.3f" % x for x in host_ms), file=sys.stderr)
     t_main_done = time.perf_counter()
     loss, viol = run.eng.loss()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.eng, loss, viol)
     extra = {}
     if not args.no_extra_legs:
         run.reset(args.dedup == "on")
@@ -841,7 +876,7 @@ def main():
                                              "in the compute stream" if sharded_inline else "on the communication stream, the next forward GEMM gated on one flag")}
     # the other operand type, end to end (configs[4] is quoted for bf16 operands while the product defaults to f16: --workload cfg5 always
     # shows both; their parity bounds against the fp32 CPU path are tests/test_gpu_cfg5.py's -- f16 1e-3, bf16 4e-3 on the embeddings)
-    if (not args.no_extra_legs or args.workload == "cfg5") and not shipped:
+    if args.full and (not args.no_extra_legs or args.workload == "cfg5") and not shipped:
         other = "bf16" if args.prec == "f16" else "f16"
         if mode != "stale":
             run2 = Run(other, args.dedup == "on")
@@ -878,7 +913,7 @@ def main():
                                                 "VV_COMM_TIMEOUT": os.environ.get("VV_COMM_TIMEOUT", "30")}, limit)
             child[name]["wall_s"] = round(time.perf_counter() - t_leg, 2)
         leg_helper.close()
-    if shipped and not no_hint:
+    if shipped and args.full and not no_hint:
         # vv_update_hint + option "wgrad_update" (default): the solver's rule applied in the weight-gradient GEMM's epilogue (one split of K at this
         # shape) -- bit-identical parameters.  Timed beside the line: the update as its own launch (option 0), the form of rounds 3-4.
         run3 = Run(args.prec, args.dedup == "on")
@@ -907,74 +942,76 @@ def main():
         else:
             U = float(R)
         gemm_flop = 2.0 * U * F * D
-        live = {k: v[0] for k, v in kern.items() if v[1] > 0} or {"wgrad_gemm": 1e-9}
-        dom = max(live, key=live.get)
-        dom_ms = live[dom]
-        if dom in ("fwd_gemm", "wgrad_gemm"):
-            ach = gemm_flop / (dom_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "kernel": dom, "achieved": ach, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": ach / MFMA_PEAK_TFLOPS, "algorithmic_flop_per_launch": gemm_flop,
-                    "dense_equivalent_flop_per_launch": dense_flop,
-                    "dense_equivalent_achieved": dense_flop / (dom_ms * 1e-3) / 1e12}
-        else:
-            if args.dedup == "on" and DROPOUT == 0 and dom == "segsum":
-                # k_seg_bwd: reads every distinct row's ip2 row (fp32) and the 16-byte record of every instance once, the two
-                # vectors of every item once; writes a 16-bit gradient row per distinct row
-                nbytes = U * D * 4.0 + R * 16.0 + B_PER_GPU * 2 * D * 4.0 + U * D * 2.0
-            elif args.dedup == "on" and DROPOUT == 0:
-                # k_score_fwd / k_score_stream: reads every instance's ip2 row (fp32) once; writes a record per instance and two
-                # vectors per item
-                nbytes = R * D * 4.0 + R * 16.0 + B_PER_GPU * 2 * D * 4.0
+        roof, live = None, {}
+        if kern:                             # (--full: kernel durations of the timed leg)
+            live = {k: v[0] for k, v in kern.items() if v[1] > 0} or {"wgrad_gemm": 1e-9}
+            dom = max(live, key=live.get)
+            dom_ms = live[dom]
+            if dom in ("fwd_gemm", "wgrad_gemm"):
+                ach = gemm_flop / (dom_ms * 1e-3) / 1e12
+                roof = {"bound": "mfma", "kernel": dom, "achieved": ach, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": ach / MFMA_PEAK_TFLOPS, "algorithmic_flop_per_launch": gemm_flop,
+                        "dense_equivalent_flop_per_launch": dense_flop,
+                        "dense_equivalent_achieved": dense_flop / (dom_ms * 1e-3) / 1e12}
             else:
-                # k_score_loss: reads every instance's ip2 row (fp32) once, writes its 16-bit gradient row once
-                nbytes = R * D * 4.0 + R * D * 2.0
-            ach = nbytes / (dom_ms * 1e-3) / 1e9
-            roof = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ach / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": nbytes}
-        roof["avg_launch_ms"] = dom_ms
-        roof["dedup_factor"] = R / U
-        pmc, pmc_src, pk, pmc_live = None, None, {}, False
-        pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        committed = {}
-        if os.path.exists(pmc_path) and args.workload == "cfg2":      # (the committed PMC passes are of the cfg-2 kernels)
-            try:
-                pj = json.load(open(pmc_path))
-                committed = pj.get("dedup_" + args.dedup, {})
-                pmc_src = "profiles/pmc_latest.json (" + pj.get("_source", pj.get("source", "rocprofv3 PMC passes")) + ")"
-            except Exception:
-                committed = {}
-        if live_pmc and dom in live_pmc:
-            pk, pmc_live = live_pmc, True
-        else:
-            pk = committed
-        pmc = pk.get(dom, {}).get("hbm_bytes_per_launch")
-        roof["traffic"] = pmc
-        # the whole step's HBM bytes by the same PMC passes beside what the de-duplicated algorithm needs
-        if pk and args.workload == "cfg2" and args.dedup == "on" and DROPOUT == 0:
-            try:
-                step_k = ("fwd_gemm", "score_loss", "segsum", "wgrad_gemm", "reduce_sgd")
-                pmc_step = sum(pk[k]["hbm_bytes_per_launch"] for k in step_k)
-                h_b = 2.0 if (os.environ.get("VV_H16", "1") != "0") else 4.0
-                s_b = 2.0 if (os.environ.get("VV_SLAB16", "1") != "0") else 4.0
-                alg = (2.0 * U * F * 2 + 3.0 * U * D * h_b + 2.0 * U * D * 2 + 2.0 * 8 * D * F * s_b + 4.0 * D * F * 4 + 2.0 * D * F * 2)
-                roof["step_traffic"] = {"pmc_bytes_per_step": pmc_step, "algorithmic_bytes_per_step": alg, "ratio": pmc_step / alg if alg else None,
-                                        "kernels": {k: pk[k]["hbm_bytes_per_launch"] for k in step_k},
-                                        "algorithmic": "2 U F 2 (rows gathered by both GEMMs) + 3 U D h (ip2 written once, read by the score and the segment "
-                                                       "kernel; h = 2 B as f16) + 2 U D 2 (dYu) + 2 S D F s (split-K partial products, s = 2 B as f16) + "
-                                                       "4 D F 4 (W and history, read and written) + 2 D F 2 (the 16-bit copy of W)",
-                                        "note": "pmc: the sum over the step's five kernels, " + ("measured by this invocation's own PMC passes" if pmc_live else
-                                                "the committed passes of profiles/pmc_latest.json, not measured by this run")}
-            except Exception:
-                pass
-        if pmc is None:
-            roof["traffic_note"] = None
-        elif pmc_live:
-            roof["traffic_note"] = "HBM bytes per launch of this kernel, " + live_pmc_note
-            if committed.get(dom):
-                roof["traffic_committed_profile"] = committed[dom].get("hbm_bytes_per_launch")
-        else:
-            roof["traffic_note"] = ("HBM bytes per launch from rocprofv3 PMC passes recorded in %s -- a committed profile of this kernel, NOT measured "
-                                    "by this run (live passes: %s)" % (pmc_src, live_pmc_note))
+                if args.dedup == "on" and DROPOUT == 0 and dom == "segsum":
+                    # k_seg_bwd: reads every distinct row's ip2 row (fp32) and the 16-byte record of every instance once, the two
+                    # vectors of every item once; writes a 16-bit gradient row per distinct row
+                    nbytes = U * D * 4.0 + R * 16.0 + B_PER_GPU * 2 * D * 4.0 + U * D * 2.0
+                elif args.dedup == "on" and DROPOUT == 0:
+                    # k_score_fwd / k_score_stream: reads every instance's ip2 row (fp32) once; writes a record per instance and two
+                    # vectors per item
+                    nbytes = R * D * 4.0 + R * 16.0 + B_PER_GPU * 2 * D * 4.0
+                else:
+                    # k_score_loss: reads every instance's ip2 row (fp32) once, writes its 16-bit gradient row once
+                    nbytes = R * D * 4.0 + R * D * 2.0
+                ach = nbytes / (dom_ms * 1e-3) / 1e9
+                roof = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ach / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": nbytes}
+            roof["avg_launch_ms"] = dom_ms
+            roof["dedup_factor"] = R / U
+            pmc, pmc_src, pk, pmc_live = None, None, {}, False
+            pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
+            committed = {}
+            if os.path.exists(pmc_path) and args.workload == "cfg2":      # (the committed PMC passes are of the cfg-2 kernels)
+                try:
+                    pj = json.load(open(pmc_path))
+                    committed = pj.get("dedup_" + args.dedup, {})
+                    pmc_src = "profiles/pmc_latest.json (" + pj.get("_source", pj.get("source", "rocprofv3 PMC passes")) + ")"
+                except Exception:
+                    committed = {}
+            if live_pmc and dom in live_pmc:
+                pk, pmc_live = live_pmc, True
+            else:
+                pk = committed
+            pmc = pk.get(dom, {}).get("hbm_bytes_per_launch")
+            roof["traffic"] = pmc
+            # the whole step's HBM bytes by the same PMC passes beside what the de-duplicated algorithm needs
+            if pk and args.workload == "cfg2" and args.dedup == "on" and DROPOUT == 0:
+                try:
+                    step_k = ("fwd_gemm", "score_loss", "segsum", "wgrad_gemm", "reduce_sgd")
+                    pmc_step = sum(pk[k]["hbm_bytes_per_launch"] for k in step_k)
+                    h_b = 2.0 if (os.environ.get("VV_H16", "1") != "0") else 4.0
+                    s_b = 2.0 if (os.environ.get("VV_SLAB16", "1") != "0") else 4.0
+                    alg = (2.0 * U * F * 2 + 3.0 * U * D * h_b + 2.0 * U * D * 2 + 2.0 * 8 * D * F * s_b + 4.0 * D * F * 4 + 2.0 * D * F * 2)
+                    roof["step_traffic"] = {"pmc_bytes_per_step": pmc_step, "algorithmic_bytes_per_step": alg, "ratio": pmc_step / alg if alg else None,
+                                            "kernels": {k: pk[k]["hbm_bytes_per_launch"] for k in step_k},
+                                            "algorithmic": "2 U F 2 (rows gathered by both GEMMs) + 3 U D h (ip2 written once, read by the score and the segment "
+                                                           "kernel; h = 2 B as f16) + 2 U D 2 (dYu) + 2 S D F s (split-K partial products, s = 2 B as f16) + "
+                                                           "4 D F 4 (W and history, read and written) + 2 D F 2 (the 16-bit copy of W)",
+                                            "note": "pmc: the sum over the step's five kernels, " + ("measured by this invocation's own PMC passes" if pmc_live else
+                                                    "the committed passes of profiles/pmc_latest.json, not measured by this run")}
+                except Exception:
+                    pass
+            if pmc is None:
+                roof["traffic_note"] = None
+            elif pmc_live:
+                roof["traffic_note"] = "HBM bytes per launch of this kernel, " + live_pmc_note
+                if committed.get(dom):
+                    roof["traffic_committed_profile"] = committed[dom].get("hbm_bytes_per_launch")
+            else:
+                roof["traffic_note"] = ("HBM bytes per launch from rocprofv3 PMC passes recorded in %s -- a committed profile of this kernel, NOT measured "
+                                        "by this run (live passes: %s)" % (pmc_src, live_pmc_note))
         out = {
             "metric": "triplets/sec (whole node), 4096->%d-d embed, batch %d/GPU, C5, Nn%d" % (D, B_PER_GPU, NN),
             "value": value, "unit": "triplets/s", "n_gpus": world, "steps": K, "warmup": Wm,
@@ -1032,8 +1069,8 @@ def main():
                                               "(one-update delayed gradients: NOT the reference's algorithm)"}[mode]},
             "roofline": roof,
             "box": box_record(box, ms, live.get("fwd_gemm", 0.0) + live.get("wgrad_gemm", 0.0)),
-            "kernels_ms": {k: round(v, 4) for k, v in live.items()},
-            "kernel_timing": ("HIP events on the kernels' dispatch packets, every %d-th of the %d timed steps (%d samples per kernel)"
+            "kernels_ms": {k: round(v, 4) for k, v in live.items()} if kern else None,
+            "kernel_timing": None if not kern else ("HIP events on the kernels' dispatch packets, every %d-th of the %d timed steps (%d samples per kernel)"
                               % (max(5, K // 8), K, max([v[1] for v in kern.values()] or [0])))
                              + ("; the forward GEMM (the dominant kernel: the roofline's) inside the timed region itself, the other kernels "
                                 "on the same steps of the per-step leg (step_ms_stats)" if main_prof == "gemm" else ""),
@@ -1074,7 +1111,7 @@ def main():
                 out["value_overlap_schedule"] = {"value": ov["value"], "ms_per_step": ov["ms_per_step"], "final_loss": ov["final_loss"],
                                                  "source": "schedules.legs.overlap: the same K steps on resident batches, a fresh engine and communicator"}
             else:
-                out["value_overlap_schedule"] = {"value": None, "error": (ov or {}).get("error", "not run (--no-extra-legs, or another --comm)")}
+                out["value_overlap_schedule"] = {"value": None, "error": (ov or {}).get("error", "not run (no --full, --no-extra-legs, or another --comm)")}
             if mode != "overlap":
                 dev.append("schedule %s, not the north star's second-stream overlap (value_overlap_schedule)%s"
                            % (mode, "; picked by --allreduce auto as the fastest exact schedule measured here" if auto_pick else ""))
@@ -1086,7 +1123,7 @@ def main():
                                                 "source": "node_sampler_leg: ONE logical sampler draws the global batch of %d as a single reference process would "
                                                           "(video_sampled_shots_data_layer.cpp:768-909), end to end, fresh processes" % Bg}
             else:
-                out["value_reference_batch"] = {"value": None, "error": (ns or {}).get("error", "not run (--no-extra-legs)")}
+                out["value_reference_batch"] = {"value": None, "error": (ns or {}).get("error", "not run (no --full, or --no-extra-legs)")}
             if smode != "node":
                 dev.append("per-rank samplers (N independent reference batches of %d), not SURVEY 8(e)'s one logical batch of %d "
                            "(value_reference_batch; bound by the sampler's serial walk)" % (B_PER_GPU, Bg))

@@ -1,16 +1,21 @@
 """CPU tests of the C++ facade's protobuf stand-in (caffe_facade/src/proto_lite.cpp): its binary wire
 format is checked in both directions against the REAL protobuf runtime (google.protobuf, with the
 reference's field numbers re-declared here through descriptor_pb2), its text parser against the
-reference's own project files when /root/reference is present, and Net::FilterNet's phase rules."""
+reference's own project files (rebuilt from the fixtures tests/golden/mednet_train_graph.json and
+tests/golden/shipped_solver.json), and Net::FilterNet's phase rules."""
+import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "caffe_facade", "build", "proto_tool")
-REF = "/root/reference/projects/videovec_embedding"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from prototxt_parse import parse_prototxt, train_topology   # noqa: E402  (tests/prototxt_parse.py)
 
 
 @pytest.fixture(scope="module")
@@ -109,20 +114,72 @@ def test_unknown_wire_fields_are_preserved(tool, pb, tmp_path):
     assert b"c" in (tmp_path / "u2.bin").read_bytes()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+def _layer_text(l, phase):
+    """One V1 `layers { ... }` block of a layer as tests/golden/mednet_train_graph.json records it (prototxt_parse.train_topology)."""
+    p = l["param"]
+    out = ['  name: "%s"' % l["name"], "  type: %s" % l["type"]]
+    out += ['  bottom: "%s"' % x for x in l["bottom"]] + ['  top: "%s"' % x for x in l["top"]]
+    out += ["  blobs_lr: %r" % x for x in p.get("blobs_lr", [])] + ["  weight_decay: %r" % x for x in p.get("weight_decay", [])]
+    out += ["  loss_weight: %r" % x for x in p.get("loss_weight", [])]
+    blocks = {"VIDEO_SAMPLED_SHOTS_DATA": ("video_sampled_shots_data_param", [k for k in p]),
+              "VIDEO_SHOT_WINDOW_TEST_DATA": ("video_shot_window_test_data_param", ["batch_size"]),
+              "SLICE": ("slice_param", ["slice_dim"]), "CONCAT": ("concat_param", ["concat_dim"]),
+              "INNER_PRODUCT": ("inner_product_param", ["num_output"]), "DROPOUT": ("dropout_param", ["dropout_ratio"]),
+              "ELTWISE": ("eltwise_param", ["operation", "coeff"]), "SUM": ("sum_param", ["sum_num_output"]),
+              "MAX_MARGIN_LOSS": ("max_margin_loss_param", ["margin", "norm"])}
+    if l["type"] in blocks:
+        name, keys = blocks[l["type"]]
+        body = []
+        for k in keys:
+            for v in (p[k] if isinstance(p[k], list) else [p[k]]):
+                body.append("    %s: %s" % ("num_output" if k == "sum_num_output" else k, v))
+        out += ["  %s {" % name] + body + ["  }"]
+    if phase:
+        out += ["  include {", "    phase: %s" % phase, "  }"]
+    return "layers {\n" + "\n".join(out) + "\n}\n"
+
+
+def _shipped_net_text():
+    """The reference's training net (TRAIN and TEST phases) as a prototxt, rebuilt from tests/golden/mednet_train_graph.json: the layers
+    both phases share carry no rule, the others an include rule of their phase; the order within each phase is the recorded one."""
+    g = json.load(open(os.path.join(GOLDEN, "mednet_train_graph.json")))
+    train, test = g["layers"], g["test_layers"]
+    shared = [l for l in train if l in test]
+    assert shared == [l for l in test if l in train]
+    text, i, j = 'name: "%s"\n' % g["name"], 0, 0
+    for s in shared + [None]:
+        while i < len(train) and train[i] != s:
+            text += _layer_text(train[i], "TRAIN"); i += 1
+        while j < len(test) and test[j] != s:
+            text += _layer_text(test[j], "TEST"); j += 1
+        if s is not None:
+            text += _layer_text(s, None); i += 1; j += 1
+    return g, text
+
+
+def _shipped_solver_text():
+    """The reference's solver file, rebuilt from tests/golden/shipped_solver.json."""
+    s = json.load(open(os.path.join(GOLDEN, "shipped_solver.json")))
+    return "".join("%s: %s\n" % (k, v if not isinstance(v, str) or k in s["enum_fields"] else '"%s"' % v) for k, v in s["fields"].items())
+
+
 def test_reference_project_files_parse_and_filter(tool, tmp_path):
     # the shipped net: 37 layers in TRAIN phase, 10 in TEST (SURVEY.md section 0 / 3.3)
-    for phase, n in (("TRAIN", 37), ("TEST", 10)):
+    g, net = _shipped_net_text()
+    (tmp_path / "net.prototxt").write_text(net)
+    for phase, n, want in (("TRAIN", 37, g["layers"]), ("TEST", 10, g["test_layers"])):
         out = tmp_path / ("%s.prototxt" % phase)
-        subprocess.run([tool, "filter", os.path.join(REF, "mednet_embedding_train.prototxt"), phase, str(out)],
+        subprocess.run([tool, "filter", str(tmp_path / "net.prototxt"), phase, str(out)],
                        check=True, capture_output=True)
         txt = out.read_text()
         assert txt.count("\nlayers {") + txt.startswith("layers {") == n
+        assert train_topology(parse_prototxt(txt), phase)["layers"] == want
     txt = (tmp_path / "TRAIN.prototxt").read_text()
     for frag in ("batch_size: 128", "num_negative_samples: 10", "max_same_video_negs: 6", "context_type: WINDOW",
                  "dropout_ratio: 0.9", "margin: 2", "norm: L2", "coeff: 0.25", "num_output: 4096"):
         assert frag in txt, frag
-    subprocess.run([tool, "text2bin", "SolverParameter", os.path.join(REF, "mednet_embedding_train_solver.prototxt"),
+    (tmp_path / "solver.prototxt").write_text(_shipped_solver_text())
+    subprocess.run([tool, "text2bin", "SolverParameter", str(tmp_path / "solver.prototxt"),
                     str(tmp_path / "s.bin")], check=True)
     subprocess.run([tool, "bin2text", "SolverParameter", str(tmp_path / "s.bin"), str(tmp_path / "s.txt")], check=True)
     s = (tmp_path / "s.txt").read_text()

@@ -38,7 +38,7 @@ def test_bench_two_ranks_on_one_device(mode):
     ar = "sync" if mode == "torch-sync" else mode.replace("peer-", "")          # (peer-auto: --allreduce auto = sharded over this transport)
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                        "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--allreduce", ar, "--sampler", "node", "--settle-ms", "2"] + extra + (["--no-extra-legs"] if mode != "stale" else []), 600, env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -66,7 +66,7 @@ def test_bench_fallbacks_keep_the_run_alive():
         env = dict(os.environ, VV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
         r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", "29531" if tag == "ring" else "29533",
-                            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
                             "--no-extra-legs", "--sampler", "node", "--settle-ms", "2"], 600, env)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -81,7 +81,7 @@ def test_bench_per_rank_samplers_is_the_default_for_two_ranks():
     env = dict(os.environ, VV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29535", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--settle-ms", "2"], 600, env)
+                        "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--settle-ms", "2"], 600, env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -119,7 +119,7 @@ def test_bench_bare_command_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(VV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                        "--no-cpu-baseline", "--settle-ms", "2"], 900, env)
+                        "--full", "--no-cpu-baseline", "--settle-ms", "2"], 900, env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -152,7 +152,7 @@ def test_bench_leg_process_that_fails_leaves_an_error_string_not_a_dead_job():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(VV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", VV_BENCH_TEST_PEER_AS="no-such-transport")
     r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--settle-ms", "2"], 900, env)
+                        "--full", "--no-cpu-baseline", "--settle-ms", "2"], 900, env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert "error" in d["peer_transport_leg"] and d["peer_transport_leg"]["error"], d["peer_transport_leg"]
@@ -164,7 +164,7 @@ def test_bench_bare_command_a_dead_rank_fails_the_job():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(VV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", VV_BENCH_TEST_FAIL_RANK="1", VV_LAUNCH_GRACE="5")
     r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-extra-legs", "--settle-ms", "2"], 300, env)
+                        "--full", "--no-cpu-baseline", "--no-extra-legs", "--settle-ms", "2"], 300, env)
     assert r.returncode == 7, (r.returncode, r.stderr[-2000:])
     assert "rank 1 exited with code 7" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -182,7 +182,7 @@ def test_bench_eight_ranks_overlap_node_sampler_matches_one_process_at_the_globa
     env.update(VV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     K, Wm, settle_ms = 3, 1, 0.5                                   # settle steps = ceil(0.5 / 0.25) = 2 -> 6 iterations
     r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", str(K), "--warmup", str(Wm),
-                        "--no-cpu-baseline", "--no-extra-legs", "--allreduce", "overlap", "--sampler", "node",
+                        "--full", "--no-cpu-baseline", "--no-extra-legs", "--allreduce", "overlap", "--sampler", "node",
                         "--settle-ms", str(settle_ms), "--sampler-threads", "2"], 1500, env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -2,11 +2,12 @@
 # needs the lab build of the library (make -C videovector_amd/csrc lab): the ablated kernels are not in the product library
 export VV_LIB=${GRAFT_REPO_ROOT:-/root/repo}/videovector_amd/lib/libvideovec_lab.so
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"    # where the results go
 run() { # label, env...
-  env "${@:2}" timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs > gpurun_out/ab.log 2>&1
+  env "${@:2}" timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs > $OUT/ab.log 2>&1
   echo "$1: $(python3 -c "
 import json
-l=[x for x in open('gpurun_out/ab.log') if x.startswith('{')]
+l=[x for x in open('$OUT/ab.log') if x.startswith('{')]
 d=json.loads(l[-1]); print(round(d['ms_per_step'],4), d['kernels_ms']['wgrad_gemm'])")"
 }
 run "full                      " A=1

@@ -28,17 +28,17 @@ for task in "$@"; do
     lds)        # what an LDS fragment read costs beside the partner wave's MFMAs (tools/lab/lds_issue_lab.hip)
       timeout 300 tools/lab/lds_issue_lab > $O/r06_${TAG}_lds_issue.txt 2>&1; cat $O/r06_${TAG}_lds_issue.txt ;;
     driver)     # the driver's command line, twice
-      for i in 1 2; do timeout 900 python bench.py --steps 20 --warmup 5 > $O/r06_${TAG}_bench_driver_args_$i.json 2>> $O/r06_${TAG}_bench.err; done
+      for i in 1 2; do timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r06_${TAG}_bench_driver_args_$i.json 2>> $O/r06_${TAG}_bench.err; done
       summ $O/r06_${TAG}_bench_driver_args_*.json ;;
     default)    # the defaults (200 steps), all legs
-      timeout 900 python bench.py > $O/r06_${TAG}_bench.json 2>> $O/r06_${TAG}_bench.err; summ $O/r06_${TAG}_bench.json ;;
+      timeout 900 python bench.py --full > $O/r06_${TAG}_bench.json 2>> $O/r06_${TAG}_bench.err; summ $O/r06_${TAG}_bench.json ;;
     quick)      # the step alone, 400 steps, three times
-      for i in 1 2 3; do timeout 600 python bench.py --no-extra-legs --no-cpu-baseline --steps 400 > $O/r06_${TAG}_quick_$i.json 2>> $O/r06_${TAG}_bench.err; done
+      for i in 1 2 3; do timeout 600 python bench.py --full --no-extra-legs --no-cpu-baseline --steps 400 > $O/r06_${TAG}_quick_$i.json 2>> $O/r06_${TAG}_bench.err; done
       summ $O/r06_${TAG}_quick_*.json ;;
     mq31)       # lab build: 192-row forward tiles (216 workgroups) against 176-row tiles (236), alternating
       for i in 1 2 3; do
         for mq in 0 31; do
-          VV_LIB=$LAB VV_PH_MQ=$mq timeout 600 python bench.py --no-extra-legs --no-cpu-baseline --steps 400 > $O/r06_${TAG}_mq${mq}_$i.json 2>> $O/r06_${TAG}_bench.err
+          VV_LIB=$LAB VV_PH_MQ=$mq timeout 600 python bench.py --full --no-extra-legs --no-cpu-baseline --steps 400 > $O/r06_${TAG}_mq${mq}_$i.json 2>> $O/r06_${TAG}_bench.err
         done
       done
       summ $O/r06_${TAG}_mq*.json ;;
@@ -47,7 +47,7 @@ for task in "$@"; do
       for i in 1 2 3; do
         n=0
         for arm in "${ARMS[@]}"; do
-          env VV_LIB=$LAB $arm timeout 600 python bench.py --no-extra-legs --no-cpu-baseline --steps 400 $AB_ARGS > $O/r06_${TAG}_ablab${n}_$i.json 2>> $O/r06_${TAG}_bench.err
+          env VV_LIB=$LAB $arm timeout 600 python bench.py --full --no-extra-legs --no-cpu-baseline --steps 400 $AB_ARGS > $O/r06_${TAG}_ablab${n}_$i.json 2>> $O/r06_${TAG}_bench.err
           n=$((n + 1))
         done
       done
@@ -57,7 +57,7 @@ for task in "$@"; do
       for i in 1 2 3; do
         n=0
         for arm in "${ARMS[@]}"; do
-          env $arm timeout 600 python bench.py --no-extra-legs --no-cpu-baseline --steps 400 $AB_ARGS > $O/r06_${TAG}_ab${n}_$i.json 2>> $O/r06_${TAG}_bench.err
+          env $arm timeout 600 python bench.py --full --no-extra-legs --no-cpu-baseline --steps 400 $AB_ARGS > $O/r06_${TAG}_ab${n}_$i.json 2>> $O/r06_${TAG}_bench.err
           n=$((n + 1))
         done
       done
@@ -71,34 +71,34 @@ for task in "$@"; do
       for i in 1 2; do
         n=0
         for arm in "${ARMS[@]}"; do
-          env $arm timeout 900 python bench.py --workload cfg5 --no-extra-legs --no-cpu-baseline --steps 30 --warmup 5 > $O/r06_${TAG}_ab5_${n}_$i.json 2>> $O/r06_${TAG}_bench.err
+          env $arm timeout 900 python bench.py --full --workload cfg5 --no-extra-legs --no-cpu-baseline --steps 30 --warmup 5 > $O/r06_${TAG}_ab5_${n}_$i.json 2>> $O/r06_${TAG}_bench.err
           n=$((n + 1))
         done
       done
       echo "arms: ${AB_ENVS}"; summ $O/r06_${TAG}_ab5_*.json ;;
     diag)       # the driver's 20-step region, step by step (VV_BENCH_DIAG: one HIP event per step + the host time of every call)
-      VV_BENCH_DIAG=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs > $O/r06_${TAG}_diag.json 2> $O/r06_${TAG}_diag.err; grep -E "main-leg|host ms" $O/r06_${TAG}_diag.err | cut -c1-600; summ $O/r06_${TAG}_diag.json ;;
+      VV_BENCH_DIAG=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs > $O/r06_${TAG}_diag.json 2> $O/r06_${TAG}_diag.err; grep -E "main-leg|host ms" $O/r06_${TAG}_diag.err | cut -c1-600; summ $O/r06_${TAG}_diag.json ;;
     smoke)
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/r06_${TAG}_smoke.txt 2>&1; tail -5 $O/r06_${TAG}_smoke.txt ;;
     cfg5)
-      timeout 900 python bench.py --workload cfg5 --steps 30 --warmup 5 --no-cpu-baseline > $O/r06_${TAG}_bench_cfg5.json 2>> $O/r06_${TAG}_bench.err; summ $O/r06_${TAG}_bench_cfg5.json ;;
+      timeout 900 python bench.py --full --workload cfg5 --steps 30 --warmup 5 --no-cpu-baseline > $O/r06_${TAG}_bench_cfg5.json 2>> $O/r06_${TAG}_bench.err; summ $O/r06_${TAG}_bench_cfg5.json ;;
     shipped)
-      timeout 900 python bench.py --workload shipped --steps 200 --warmup 20 --no-cpu-baseline > $O/r06_${TAG}_bench_shipped.json 2>> $O/r06_${TAG}_bench.err; summ $O/r06_${TAG}_bench_shipped.json ;;
+      timeout 900 python bench.py --full --workload shipped --steps 200 --warmup 20 --no-cpu-baseline > $O/r06_${TAG}_bench_shipped.json 2>> $O/r06_${TAG}_bench.err; summ $O/r06_${TAG}_bench_shipped.json ;;
     final)      # the closing session: bench legs, rocprofv3 kernel trace + HBM PMC passes (dedup on / off), SQ counters, sampler rates, facade rate
       P0=$O/r06_${TAG}
-      timeout 1200 python bench.py > ${P0}_bench.json 2> ${P0}_bench.err; echo "bench exit $?" >> ${P0}_bench.err
-      timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > ${P0}_bench_driver_args.json 2>> ${P0}_bench.err
-      timeout 600 python bench.py --dedup off --no-cpu-baseline --no-extra-legs > ${P0}_bench_dense.json 2>> ${P0}_bench.err
-      timeout 600 python bench.py --prec bf16 --no-cpu-baseline --no-extra-legs > ${P0}_bench_bf16.json 2>> ${P0}_bench.err
-      timeout 600 python bench.py --workload cfg5 --no-cpu-baseline --no-extra-legs --steps 40 --warmup 5 > ${P0}_bench_cfg5.json 2>> ${P0}_bench.err
-      timeout 600 python bench.py --workload shipped --steps 200 --warmup 20 --no-cpu-baseline > ${P0}_bench_shipped.json 2>> ${P0}_bench.err
+      timeout 1200 python bench.py --full > ${P0}_bench.json 2> ${P0}_bench.err; echo "bench exit $?" >> ${P0}_bench.err
+      timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > ${P0}_bench_driver_args.json 2>> ${P0}_bench.err
+      timeout 600 python bench.py --full --dedup off --no-cpu-baseline --no-extra-legs > ${P0}_bench_dense.json 2>> ${P0}_bench.err
+      timeout 600 python bench.py --full --prec bf16 --no-cpu-baseline --no-extra-legs > ${P0}_bench_bf16.json 2>> ${P0}_bench.err
+      timeout 600 python bench.py --full --workload cfg5 --no-cpu-baseline --no-extra-legs --steps 40 --warmup 5 > ${P0}_bench_cfg5.json 2>> ${P0}_bench.err
+      timeout 600 python bench.py --full --workload shipped --steps 200 --warmup 20 --no-cpu-baseline > ${P0}_bench_shipped.json 2>> ${P0}_bench.err
       rm -rf $O/prof_r06_${TAG} && mkdir -p $O/prof_r06_${TAG}
       export VV_BENCH_NO_BOX=1       # (the profiled runs: without the box probe, whose GEMM launches carry the product kernel's name)
       for mode in on off; do
         P=$O/prof_r06_${TAG}/dedup_${mode}
-        timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o kt -- python3 bench.py --steps 400 --warmup 5 --no-cpu-baseline --no-extra-legs --dedup $mode > ${P0}_prof_trace_${mode}.log 2>&1
-        timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $P/pmc_fetch -o pf -- python3 bench.py --steps 6 --warmup 2 --settle-ms 0 --no-cpu-baseline --no-extra-legs --dedup $mode > ${P0}_prof_fetch_${mode}.log 2>&1
-        timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $P/pmc_write -o pw -- python3 bench.py --steps 6 --warmup 2 --settle-ms 0 --no-cpu-baseline --no-extra-legs --dedup $mode > ${P0}_prof_write_${mode}.log 2>&1
+        timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o kt -- python3 bench.py --full --steps 400 --warmup 5 --no-cpu-baseline --no-extra-legs --dedup $mode > ${P0}_prof_trace_${mode}.log 2>&1
+        timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $P/pmc_fetch -o pf -- python3 bench.py --full --steps 6 --warmup 2 --settle-ms 0 --no-cpu-baseline --no-extra-legs --dedup $mode > ${P0}_prof_fetch_${mode}.log 2>&1
+        timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $P/pmc_write -o pw -- python3 bench.py --full --steps 6 --warmup 2 --settle-ms 0 --no-cpu-baseline --no-extra-legs --dedup $mode > ${P0}_prof_write_${mode}.log 2>&1
         python3 tools/summarize_prof.py $P > ${P0}_kernel_trace_and_pmc_summary_dedup_${mode}.txt 2>&1
         cp $(find $P/trace -name "*kernel_stats.csv" | head -1) ${P0}_kernel_stats_dedup_${mode}.csv
       done
@@ -108,7 +108,7 @@ for task in "$@"; do
                  "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD" \
                  "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS"; do
         i=$((i+1))
-        timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/prof_r06_${TAG}/sq_on_$i -o sq -- python3 bench.py --steps 6 --warmup 2 --settle-ms 0 --no-cpu-baseline --no-extra-legs > ${P0}_sq_on_$i.log 2>&1
+        timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/prof_r06_${TAG}/sq_on_$i -o sq -- python3 bench.py --full --steps 6 --warmup 2 --settle-ms 0 --no-cpu-baseline --no-extra-legs > ${P0}_sq_on_$i.log 2>&1
       done
       PROFDIR=$O/prof_r06_${TAG} python3 - > ${P0}_sq_counters_summary.txt <<'PY'
 import csv, glob, collections, os
