@@ -77,20 +77,18 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *                                    while they compute (bit-identical results)
  *   "fuse_update" (VV_FUSE_UPDATE, 1) reduction of the split-K partials and the solver update in one launch (0: two launches)
  *   "fwd_lead" (VV_FWD_LEAD, 1)      the forward GEMM's sibling lead
- *   "fwd_merge" (VV_FWD_MERGE, 0)    the forward GEMM with two phases per barrier pair (bit-identical results; measured not faster)
  *   "wgrad_tr" (VV_WGRAD_TR, 1)      transposed LDS reads in the weight-gradient GEMM (0: the first-round kernel)
  *   "wgrad_lean" (VV_WGRAD_LEAN, 1)  the weight-gradient GEMM's lean instantiations (tables below 4 GiB: gathered rows addressed as base + 32-bit
  *                                    offset, fewer instructions in the loop's LOAD segments; bit-identical results); 0: 64-bit addresses
- *   "score_stream" (VV_SCORE_STREAM, 0)  1: the one-sweep score kernel for every shape
  *   "comm_gate" (VV_COMM_GATE, 1)    the overlapped update gates the next forward GEMM chunk by chunk (0: the stream joins)
  *   "comm_inline" (VV_COMM_INLINE, 1)  the SHARDED update's three steps (reduce-scatter, the rule on this rank's rows, all-gather) are queued
  *                                    on the compute stream itself (0: on the communication stream, the next forward GEMM gated on one flag)
- *   "comm_first_inline" (VV_COMM_FIRST_INLINE, 0)  1: the OVERLAPPED update's first F-chunk (exchange, rule, publish) is queued on the compute stream,
- *                                    the others on the communication stream (measured slower on one rank: off by default)
  *   "wgrad_update" (VV_WGRAD_UPDATE, 1)  a step announced by vv_update_hint whose weight-gradient GEMM has one split of K applies the solver's
  *                                    rule in that GEMM's epilogue (bit-identical parameters; 0: the update as its own launch)
  *   "comm_chunks" (VV_COMM_CHUNKS, 3)  F-chunks of the overlapped update, 1 .. 4
  *   "comm_test_delay_us" (VV_COMM_TEST_DELAY_US, 0)  TEST HOOK: holds the communication stream this long in front of every chunk
+ * Retired options -- "fwd_merge", "score_stream", "comm_first_inline": their alternatives were measured, lost and removed.  They read as 0,
+ * the value the library always runs with; setting 0 is accepted, any other value is VV_ERR_ARG.  Their environment variables are not read.
  * Ablated / experimental kernels (timing studies whose results may be wrong) are NOT reachable through this library: they and their
  * switches exist only in the lab build (make -C videovector_amd/csrc lab).  Unknown name: VV_ERR_ARG. */
 int vv_set_option(vv_ctx* ctx, const char* name, double value);

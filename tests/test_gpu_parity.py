@@ -213,6 +213,23 @@ def test_wgrad_transposed_lds_reads_match_scalar_reads(vv):
     assert np.array_equal(out[0], out[1])
 
 
+@pytest.mark.parametrize("name,env", [("fwd_merge", "VV_FWD_MERGE"), ("score_stream", "VV_SCORE_STREAM"),
+                                      ("comm_first_inline", "VV_COMM_FIRST_INLINE")])
+def test_retired_options_read_zero_and_accept_only_zero(vv, monkeypatch, name, env):
+    # the options whose alternatives were removed: they read as the value the library always ran with, 0, accept it, refuse any other,
+    # and their environment variables are no longer read
+    monkeypatch.setenv(env, "1")
+    eng = vv.Engine(0, "f16")
+    assert eng.get_option(name) == 0
+    eng.set_option(name, 0)
+    with pytest.raises(vv.VVError, match="retired"):
+        eng.set_option(name, 1)
+    assert eng.get_option(name) == 0
+    eng.set_option("fwd_lead", 0)                 # (a live option next to them still takes its value)
+    assert eng.get_option("fwd_lead") == 0
+    eng.close()
+
+
 @pytest.mark.parametrize("prec", ["f16", "bf16"])
 def test_dropout_with_explicit_mask_and_options(vv, oracle, prec):
     B, C, Nn, F, D = 16, 5, 3, 256, 64

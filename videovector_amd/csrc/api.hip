@@ -17,7 +17,7 @@
 
 #include "vv_ctx.h"
 
-namespace vv { int gemm_variant(); bool ablate_on(); thread_local const KernelOpts* g_ko = nullptr; }
+namespace vv { bool ablate_on(); thread_local const KernelOpts* g_ko = nullptr; }
 // every entry point that launches kernels: the device of the context, and ITS kernel options for the launchers on this thread
 #define VV_ENTER(c) do { HIPCHK(hipSetDevice((c)->device)); vv::g_ko = &(c)->ko; \
     if ((c)->comm && vv::comm_failed((c)->comm)) return fail(VV_ERR_HIP, "the data-parallel exchange failed: %s", vv::comm_error((c)->comm)); } while (0)
@@ -137,8 +137,6 @@ static int create_init(vv_ctx* c) {
   // product options: initial values from the environment, per context (vv_set_option changes them afterwards)
   if (const char* v = opt_env("VV_WGRAD_TR")) c->ko.wgrad_tr = atoi(v) != 0;
   if (const char* v = opt_env("VV_FWD_LEAD")) c->ko.fwd_lead = atoi(v);
-  if (const char* v = opt_env("VV_FWD_MERGE")) c->ko.fwd_merge = atoi(v);
-  if (const char* v = opt_env("VV_SCORE_STREAM")) c->ko.score_stream = atoi(v);
   if (const char* v = opt_env("VV_SCORE_PF")) c->ko.score_pf = atoi(v);
   if (const char* v = opt_env("VV_WGRAD_LEAN")) c->ko.wgrad_lean = atoi(v);
   if (const char* v = opt_env("VV_SEG_BWD")) c->seg_bwd = atoi(v) != 0;
@@ -152,16 +150,12 @@ static int create_init(vv_ctx* c) {
   if (const char* v = opt_env("VV_COMM_INLINE")) c->comm_inline = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_TEST_DELAY_US")) c->comm_test_delay_us = atoi(v);
   // lab switches (-DVV_LAB builds only; several of them produce WRONG results by design)
-  if (const char* v = lab_env("VV_GEMM_VARIANT")) c->ko.gemm_variant = atoi(v);
   if (const char* v = lab_env("VV_ABLATE")) c->ko.ablate = atoi(v);
   if (const char* v = lab_env("VV_LAB_FWD_ABL")) c->ko.lab_fwd_abl = atoi(v);
   if (const char* v = lab_env("VV_LAB_WG_ABL")) c->ko.lab_wg_abl = atoi(v);
-  if (const char* v = lab_env("VV_FWD_RING10")) c->ko.fwd_ring10 = atoi(v) != 0;
   if (const char* v = lab_env("VV_PH_MQ")) c->ko.ph_mq = atoi(v);
   if (const char* v = lab_env("VV_SCORE_REG")) c->ko.score_reg = atoi(v);
-  if (const char* v = lab_env("VV_SCORE_WAVES")) c->ko.score_waves = atoi(v);
   if (const char* v = lab_env("VV_SCORE_RR")) c->ko.score_rr = atoi(v);
-  if (const char* v = lab_env("VV_LAB_SCORE_PIPE")) c->ko.lab_score_pipe = atoi(v);
   if (const char* v = lab_env("VV_GUARD_PROACTIVE")) c->guard_proactive = atoi(v) != 0;
   if (const char* v = lab_env("VV_FUSE_KEEP_GRADS")) c->fuse_keep_grads = atoi(v) != 0;
   if (const char* v = lab_env("VV_COMM_SKIP_AR1")) c->comm_skip_ar1 = atoi(v) != 0;
@@ -184,11 +178,9 @@ static int create_init(vv_ctx* c) {
   HIPCHK(hipHostMalloc((void**)&c->U_host, 2 * sizeof(int32_t), hipHostMallocMapped));   // {U, saturated f16 gradient sums}
   c->U_host[0] = c->U_host[1] = 0;
   HIPCHK(hipHostGetDevicePointer((void**)&c->U_host_dev, c->U_host, 0));
-  HIPCHK(hipMalloc(&c->w_gate, (W_CHUNKS_MAX + 2) * W_GATE_STRIDE * sizeof(int32_t)));
-  HIPCHK(hipMemset(c->w_gate, 0, (W_CHUNKS_MAX + 2) * W_GATE_STRIDE * sizeof(int32_t)));
+  HIPCHK(hipMalloc(&c->w_gate, (W_CHUNKS_MAX + 1) * W_GATE_STRIDE * sizeof(int32_t)));
+  HIPCHK(hipMemset(c->w_gate, 0, (W_CHUNKS_MAX + 1) * W_GATE_STRIDE * sizeof(int32_t)));
   c->pub_count = c->w_gate + W_CHUNKS_MAX * W_GATE_STRIDE;      // the arrival counter of the publishing kernels: a line of its own
-  c->pub_count0 = c->pub_count + W_GATE_STRIDE;                 // ... and the one of the FIRST chunk's kernel, which runs on the compute stream beside them
-  if (const char* v = opt_env("VV_COMM_FIRST_INLINE")) c->overlap_first_inline = atoi(v) != 0;
   if (const char* v = opt_env("VV_WGRAD_UPDATE")) c->wgrad_update = atoi(v) != 0;
   { const char* nc = opt_env("VV_COMM_CHUNKS"); if (nc) c->n_chunks = std::max(1, std::min(W_CHUNKS_MAX, atoi(nc))); }
   HIPCHK(hipEventCreateWithFlags(&c->ev_chunk0, hipEventDisableTiming));
@@ -284,11 +276,18 @@ int vv_destroy(vv_ctx* c) {
   return VV_OK;
 }
 
+// Options whose alternatives were retired (include/videovec.h): they read as the value the library always runs with, 0, and accept only it.
+static bool retired_option(const std::string& n) { return n == "fwd_merge" || n == "score_stream" || n == "comm_first_inline"; }
+
 // Per-context switches by name (include/videovec.h).  A name of a lab switch is refused unless the library was built with -DVV_LAB.
 int vv_set_option(vv_ctx* c, const char* name, double value) {
   if (!c || !name) return fail(VV_ERR_ARG, "vv_set_option: ctx / name is NULL");
   const std::string n(name);
   const int iv = (int)value;
+  if (retired_option(n)) {
+    if (iv == 0) return VV_OK;
+    return fail(VV_ERR_ARG, "vv_set_option: option '%s' is retired; only its fixed value 0 is accepted", name);
+  }
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
   if (n == "drop_dedup") { c->drop_dedup = iv != 0; return VV_OK; }
@@ -297,19 +296,15 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
   if (n == "v16") { c->v16 = iv != 0; return VV_OK; }
   if (n == "fuse_update") { c->fuse_update = iv != 0; return VV_OK; }
   if (n == "fwd_lead") { c->ko.fwd_lead = iv; return VV_OK; }
-  if (n == "fwd_merge") { c->ko.fwd_merge = iv; return VV_OK; }
   if (n == "wgrad_tr") { c->ko.wgrad_tr = iv != 0; return VV_OK; }
-  if (n == "score_stream") { c->ko.score_stream = iv; return VV_OK; }
   if (n == "score_pf") { c->ko.score_pf = iv; return VV_OK; }
   if (n == "wgrad_lean") { c->ko.wgrad_lean = iv; return VV_OK; }
   if (n == "comm_gate") { c->comm_gate = iv != 0; return VV_OK; }
   if (n == "comm_inline") { c->comm_inline = iv != 0; return VV_OK; }
-  if (n == "comm_first_inline") { c->overlap_first_inline = iv != 0; return VV_OK; }
   if (n == "wgrad_update") { c->wgrad_update = iv != 0; return VV_OK; }
   if (n == "comm_chunks") { c->n_chunks = std::max(1, std::min(W_CHUNKS_MAX, iv)); return VV_OK; }
   if (n == "comm_test_delay_us") { c->comm_test_delay_us = iv; return VV_OK; }
 #ifdef VV_LAB
-  if (n == "gemm_variant") { c->ko.gemm_variant = iv; return VV_OK; }
   if (n == "ablate") { c->ko.ablate = iv; return VV_OK; }
   if (n == "lab_fwd_abl") { c->ko.lab_fwd_abl = iv; return VV_OK; }
   if (n == "lab_wg_abl") { c->ko.lab_wg_abl = iv; return VV_OK; }
@@ -321,7 +316,8 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
 int vv_get_option(vv_ctx* c, const char* name, double* value) {
   if (!c || !name || !value) return fail(VV_ERR_ARG, "vv_get_option: NULL argument");
   const std::string n(name);
-  if (n == "dedup") *value = c->dedup;
+  if (retired_option(n)) *value = 0;
+  else if (n == "dedup") *value = c->dedup;
   else if (n == "seg_bwd") *value = c->seg_bwd;
   else if (n == "drop_dedup") *value = c->drop_dedup;
   else if (n == "h16") *value = c->h16;
@@ -329,14 +325,11 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "v16") *value = c->v16;
   else if (n == "fuse_update") *value = c->fuse_update;
   else if (n == "fwd_lead") *value = c->ko.fwd_lead;
-  else if (n == "fwd_merge") *value = c->ko.fwd_merge;
   else if (n == "wgrad_tr") *value = c->ko.wgrad_tr;
-  else if (n == "score_stream") *value = c->ko.score_stream;
   else if (n == "score_pf") *value = c->ko.score_pf;
   else if (n == "wgrad_lean") *value = c->ko.wgrad_lean;
   else if (n == "comm_gate") *value = c->comm_gate;
   else if (n == "comm_inline") *value = c->comm_inline;
-  else if (n == "comm_first_inline") *value = c->overlap_first_inline;
   else if (n == "wgrad_update") *value = c->wgrad_update;
   else if (n == "comm_chunks") *value = c->n_chunks;
   else if (n == "comm_test_delay_us") *value = c->comm_test_delay_us;
@@ -842,7 +835,7 @@ static int dd_issue(vv_ctx* c, const int32_t* didx, int idx_on_device, int64_t r
       const int lds_kb = c->dd_lds_kb;
       const int hint = *(volatile int32_t*)c->U_host;
       const long tiles = fwd_gemm_plan(c->R, hint, D, nullptr);
-      da.lds_bytes = lds_kb >= 0 ? lds_kb * 1024 : (c->dd_async && gemm_variant() == 5 && hint > 0 && tiles <= c->n_cu - 16 ? 36 * 1024 : 0);
+      da.lds_bytes = lds_kb >= 0 ? lds_kb * 1024 : (c->dd_async && hint > 0 && tiles <= c->n_cu - 16 ? 36 * 1024 : 0);
     }
     da.R = c->R; da.Rp = c->Rp; da.zero_row = (int32_t)c->n_rows; da.row_limit = (int32_t)row_limit; da.epoch = c->dd_epoch;
     PROFILED(c, "dedup", (launch_dedup(da, ds), launch_dedup_groups(da, ds)));
@@ -934,10 +927,10 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // projection of equal rows is equal, only the mask differs per instance.  Where the segment-wise pair carries the masks (k_score_fwd +
   // k_seg_bwd at D = 512: every instance masks its row as it reads it, the backward sums m_i-weighted terms per distinct row) dropout
   // rides the de-duplicated path; on the other shapes it stays dense (the mask in the forward GEMM's epilogue).  The two executions
-  // evaluate the same mask function (vv_internal.h: DropSpec).  Needs the default two-buffer GEMM kernels.
+  // evaluate the same mask function (vv_internal.h: DropSpec).
   const bool drop_on = cfg->dropout_ratio > 0.f;
   const bool drop_dd = drop_on && c->drop_dedup && c->seg_bwd && score_fwd_dropout_supported(D, C, Nn);
-  const bool dd = c->dedup && (!drop_on || drop_dd) && (gemm_variant() == 0 || (gemm_variant() >= 5 && gemm_variant() <= 8)) && !ablate_on();
+  const bool dd = c->dedup && (!drop_on || drop_dd) && !ablate_on();
   DropSpec dsp;
   if (drop_on) {
     dsp.mode = cfg->dropout_mask ? 2 : 1;
@@ -984,7 +977,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // ip2 as f16 (option "h16"): only where the segment-wise pair reads it -- de-duplicated batches of D = 512 / 1024 (k_score_fwd / k_score_stream /
   // k_seg_bwd carry the f16 row loads; the dense and the generic kernels keep fp32 rows), D % 8 == 0, the phase-staggered forward kernel
   const bool seg_path = dd && c->seg_bwd && (D == 512 || D == 1024);
-  const bool h16 = c->h16 && seg_path && gemm_variant() == 5 && !ablate_on();
+  const bool h16 = c->h16 && seg_path && !ablate_on();
   fa.h16 = h16 ? 1 : 0;
   c->last_h16 = h16;
   fa.drop_ratio = (dd && drop_on) ? 0.f : cfg->dropout_ratio;      // (de-duplicated: H holds the shared pre-dropout rows, the instances mask them)
@@ -998,7 +991,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     // BESIDE the waiting GEMM, or nothing would ever release it); otherwise the stream joins here, as without overlap.
     const long tiles = fwd_gemm_plan(c->R, dd ? fa.R_hint : 0, D, nullptr);
     const bool no_gate = !c->comm_gate;
-    if (!no_gate && gemm_variant() == 5 && !ablate_on() && fwd_gemm_can_gate(fa) && (!dd || fa.R_hint > 0) && tiles <= c->n_cu - 16) {
+    if (!no_gate && !ablate_on() && fwd_gemm_can_gate(fa) && (!dd || fa.R_hint > 0) && tiles <= c->n_cu - 16) {
       fa.gate = c->w_gate; fa.gate_seq = c->upd_seq; fa.gate_err = c->gate_err_dev;
       if (c->grads_sharded) { fa.gate_n = 1; fa.gate_kt[0] = 0; fa.gate_kt[1] = c->Fp / BK; }        // the sharded update publishes once
       else { fa.gate_n = chunk_plan(c); for (int i = 0; i <= fa.gate_n; ++i) fa.gate_kt[i] = c->chunk_kt[i]; }
@@ -1461,43 +1454,24 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
     const int32_t useq = ++c->upd_seq;
     const int nch = chunk_plan(c);               // (the layout k_reduce wrote: same Fp, same plan)
     a.pub_count = c->pub_count; a.pub_seq = useq;
-    // Round 5, an option (overlap_first_inline; OFF by default: measured slower, vv_ctx.h): the FIRST chunk on the compute stream.  The next forward GEMM cannot pass its first
-    // gate before chunk 0 has arrived whatever stream brings it -- on the communication stream it arrived behind the hand-off chain
-    // [event -> that stream wakes -> the collective's launch -> k_sgd on the CUs the waiting GEMM leaves free -> publish], ~17 us during
-    // which the GEMM sat at the gate (profiles/r04_overlap_cost.txt: overlap = sync + 20 us on one rank).  In-stream, chunk 0's exchange and
-    // update are the synchronous schedule's (no hand-off, the whole chip for its k_sgd), the GEMM starts behind them with gate 0 open, and the
-    // chain of chunk 1 runs beside the GEMM's first K-tiles (chunk 0's columns: half of the loop) instead of in front of them.
-    // The other chunks follow chunk 0 through ONE event, recorded behind its kernel: the collectives of a step then run in one order on every
-    // transport (the direct peer transport's meeting points are numbered in host order and must be reached in that order: with chunk 1 free to
-    // start beside chunk 0 its meeting overtook chunk 0's and the ranks waited for each other for good -- the first build of this, caught by
-    // tests/test_gpu_dist.py [peer-overlap]).  RCCL serialises a communicator's collectives anyway.
-    const bool first_inl = c->overlap_first_inline && nch > 1;
-    if (!first_inl) HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
-    struct StreamScope { vv::Comm* k; ~StreamScope() { vv::comm_use_stream(k, nullptr); } } scope{c->comm};
+    HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
     for (int k = 0; k < nch; ++k) {
-      const bool inl = first_inl && k == 0;
-      hipStream_t ks = inl ? c->stream : cs;
-      // (second-stream form) chunk 0 may start as soon as ITS reduction is done (ev_chunk0, fb_impl); the others follow the whole backward pass
-      hipEvent_t after = inl ? nullptr : (first_inl ? (k == 1 ? c->ev_chunk : nullptr)
-                          : (k == 0 ? (c->chunk0_event ? c->ev_chunk0 : c->ev_chunk) : (k == 1 && c->chunk0_event ? c->ev_chunk : nullptr)));
+      // chunk 0 may start as soon as ITS reduction is done (ev_chunk0, fb_impl); the others follow the whole backward pass
+      hipEvent_t after = k == 0 ? (c->chunk0_event ? c->ev_chunk0 : c->ev_chunk) : (k == 1 && c->chunk0_event ? c->ev_chunk : nullptr);
       const int c0 = std::min(c->F, c->chunk_kt[k] * BK), c1 = std::min(c->F, c->chunk_kt[k + 1] * BK);
       const bool last = k == nch - 1;
       const size_t off = (size_t)c->D * c0, n = (size_t)c->D * (c1 - c0) + (last ? (size_t)c->D : 0);
       const int delay_us = c->comm_test_delay_us;
       if (after) HIPCHK(hipStreamWaitEvent(cs, after, 0));
-      if (delay_us > 0) launch_delay(delay_us, ks);      // test hook: a slow exchange, so that the next forward GEMM really waits at its gates
+      if (delay_us > 0) launch_delay(delay_us, cs);      // test hook: a slow exchange, so that the next forward GEMM really waits at its gates
       const bool skip_ar1 = c->comm_skip_ar1;   // (lab) diagnosis: no collective call at world 1
-      vv::comm_use_stream(c->comm, inl ? c->stream : nullptr);
       if (!(skip_ar1 && vv::comm_world(c->comm) == 1) && n > 0 && vv::comm_allreduce(c->comm, c->grads, off, n, nullptr))
         return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
       a.chunked = 1; a.f_begin = c0; a.f_count = c1 - c0; a.do_bias = last; a.set_scale = k == 0;
       a.blk_off = k * (SGD_BLOCKS / nch); a.n_blk = last ? SGD_BLOCKS - a.blk_off : SGD_BLOCKS / nch;      // together: every slot of wmax_blocks
       a.pub_flag = c->w_gate + k * W_GATE_STRIDE;          // the kernel's last workgroup publishes the chunk (SgdArgs::pub_flag)
-      a.pub_count = inl ? c->pub_count0 : c->pub_count;    // (a counter of its own: the chunk-1 kernel may run at the same time)
-      if (k == 0) PROFILED(c, "sgd", launch_sgd(c->prec, a, ks)); else launch_sgd(c->prec, a, ks);     // (an empty chunk: its wmax slots become 0, the bias if it is the last)
-      if (inl) HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
+      if (k == 0) PROFILED(c, "sgd", launch_sgd(c->prec, a, cs)); else launch_sgd(c->prec, a, cs);     // (an empty chunk: its wmax slots become 0, the bias if it is the last)
     }
-    vv::comm_use_stream(c->comm, nullptr);
     if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
     c->grads_pending = false; c->upd_inflight = true; c->upd_unjoined = false;    // (comm_done_event now marks the end of THIS update, behind the old one)
   } else

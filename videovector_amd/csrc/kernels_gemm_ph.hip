@@ -1,7 +1,7 @@
 // kernels_gemm_ph.hip -- phase-staggered MFMA kernels of the videovec training step (gfx950 only).
 //
-// Same products as kernels_gemm.hip (k_fwd_gemm: ip2 = ReLU(X W^T + b), X gathered through the triplet index;
-// k_wgrad_gemm: dW = dY^T X, split-K slabs) on a different schedule.  The first kernels load a whole K-step, wait for it
+// k_fwd_gemm_ph: ip2 = ReLU(X W^T + b), X gathered through the triplet index; k_wgrad_gemm_ph: dW = dY^T X, split-K slabs.
+// The round-1 kernels (of which kernels_gemm.hip keeps the weight gradient's) load a whole K-step, wait for it
 // (vmcnt(0)) and run 64 MFMAs per wave between two barriers: the two waves of a SIMD do the same thing at the same
 // time, so the matrix pipe idles while both read LDS and the LDS idles while both multiply (rocprofv3: matrix pipe busy
 // 33-47 %, half of every wave's life parked at the K-step's wait + barrier).  Here:
@@ -82,7 +82,7 @@ constexpr int PH_LDS_BYTES = 8 * PH_SLOT;      // ring of 8 slots = 128 KiB
 
 // ------------------------------------------------------------------------------- forward ------
 // Half-tile LDS image: [128 rows][64 halves] = 128-B rows of 8 16-B chunks, chunk' = chunk ^ (row & 7)
-// (conflict-free ds_read_b128 fragment reads, as in k_fwd_gemm).  One LDS-DMA wave-instruction = 8 rows.
+// (conflict-free ds_read_b128 fragment reads: tools/lds_banks.py).  One LDS-DMA wave-instruction = 8 rows.
 // MQ = 16-row MFMA tiles per wave and A half: the tile is (64*MQ) x 256 (MQ 4: 256 rows, 3: 192, 2: 128).
 // GATE: the W operand may still be arriving chunk by chunk (FwdArgs::gate).  Every wave checks all chunk flags once at
 // its start -- nothing of its stream is in flight yet, the check costs one round trip -- and when all are set (one GPU,
@@ -94,11 +94,6 @@ constexpr int PH_LDS_BYTES = 8 * PH_SLOT;      // ring of 8 slots = 128 KiB
 // barrier is one more in every wave's sequence: waves 4-7, one barrier behind, pass it one segment later, still behind
 // wave 0's poll.  The poll is a vector load: it drains wave 0's own stream once per chunk (three times per kernel, and
 // only while an update is really still in flight).
-// DEAD (0 / 1): the LAST 16-row MFMA tile of the upper A half (waves 4-7's) is left out -- the tile covers 64 MQ - 16 rows.
-// With MQ = 3 that is 176 rows: 236 instead of 216 workgroups for the benchmark's ~20 650 distinct rows, on 256 CUs.
-// (Rows of the 128-row half-tile image that no wave reads are still staged, from the L2-hot zero row: dropping those
-// LDS-DMA instructions -- the second one of waves 4-7 at 96 live rows -- with per-wave counted waits was measured and made
-// the 192-row kernel 4.6 us SLOWER, profiles/r03_step_ablations.txt.)
 // LEAD (0 / 1): the workgroups of one row tile (its column tiles: two at D = 512) ask for the same gathered lines at the
 // same time, so each line costs BOTH of them a miss -- the second request finds the first still in flight and waits for HBM
 // just as long (tools/lab/fwd_stream_lab.hip: the stream alone 104 us as issued today, 140 us when the siblings read
@@ -112,24 +107,16 @@ constexpr int PH_LDS_BYTES = 8 * PH_SLOT;      // ring of 8 slots = 128 KiB
 // 160 KiB of LDS), and the loop is unrolled by four K-tiles so that every ring position is a constant.
 // DROP: 0 no dropout, 1 the counter-based mask, 2 an explicit mask (FwdArgs::mask) -- separate instantiations: with the choice made per
 // element at run time the epilogue was 700 branches and 50 KB of code, and the dense-size kernel took 17 us longer for it
-// MRG (0 / 1; round 5): TWO phases per barrier pair.  The stamps (profiles/r05_fwd_stamps.txt) put a phase at 192 clocks of matrix pipe
-// plus ~45 of barrier release plus what the partner's load segment overhangs: 512 intervals of ~250.  The fragments of a K-tile already
-// live in registers together (A half 24 + B_lo 16 + B_hi 16 VGPRs), so the four phases pair up without a register more:
-//   M0: read A_lo, B_lo, B_hi | stream steps 0, 1 | barrier | A_lo x B_lo, A_lo x B_hi (24 MFMAs) | barrier
-//   M1: read A_hi             | stream steps 2, 3 | barrier | A_hi x B_hi, A_hi x B_lo (24 MFMAs) | barrier
-// 256 intervals of ~430.  The stream keeps its order and its six half-tiles of distance; the counted waits move: before M1 everything
-// but the four youngest half-tiles (A_hi(t) is the fifth youngest), before M0 everything but the THREE youngest (B_hi(t + 1), issued in
-// M0(t), is the fourth youngest: the one half-tile whose flight is half a K-tile instead of a whole one -- it is a W tile, an L2 hit).
 // O16 (round 6; FwdArgs::h16): ip2 leaves as f16 -- half the bytes of the kernel's store-bound epilogue (42 -> 21 MB at the benchmark's size)
 // and of every later read of it.  A lane's two quads of a 32-column group (ni = 0, 1: columns fq 4 .. + 3 and 16 + fq 4 .. + 3, four halves
 // = two registers each) are regrouped by two v_permlane16_swap into EIGHT consecutive columns per lane -- one 16-byte store where the fp32
 // form issues two: half the store instructions as well (the tail of this epilogue is store-ISSUE-bound, cdna_hip_programming.md T21).
-template <typename T, int DROP, bool VEC, int MQ, int ABL = 0, bool GATE = false, int DEAD = 0, int LEAD = 0, int MRG = 0, bool O16 = false>
+template <typename T, int DROP, bool VEC, int MQ, int ABL = 0, bool GATE = false, int LEAD = 0, bool O16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
   static_assert(!O16 || (VEC && DROP == 0), "the f16 output form exists for the plain forward (D % 8 == 0, no dropout in the epilogue)");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int HROWS = 32 * MQ;               // rows of the lower A half-tile (upper: HROWS - 16 DEAD)
-  constexpr int BMT = 2 * HROWS - 16 * DEAD;   // rows of the output tile
+  constexpr int HROWS = 32 * MQ;               // rows of each A half-tile
+  constexpr int BMT = 2 * HROWS;               // rows of the output tile
   if (ABL & (512 | 2048)) asm volatile("s_memtime s[84:85]\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 s101, s84" ::: "s84", "s85", "s101");   // (lab: time stamps, below)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -162,7 +149,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
     for (int i = 0; i < 2; ++i) {
       const int row = (i * 8 + wave) * 8 + (lane >> 3), lc = (lane & 7) ^ (row & 7);
       const int grow = m0 + (hf ^ hswap) * HROWS + row;
-      const int trow = (row < HROWS - 16 * DEAD * hf && grow < R && !(ABL & 8)) ? a.rows[grow] : a.zero_row;
+      const int trow = (row < HROWS && grow < R && !(ABL & 8)) ? a.rows[grow] : a.zero_row;
       srcA[hf][i] = a.table + (int64_t)trow * Fp + lc * 8;
       srcB[hf][i] = a.Wh + (int64_t)(n0 + hf * 128 + row) * Fp + lc * 8;
     }
@@ -245,8 +232,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
   } else {
     issue(0, 0, 0); issue(0, 1, 1); issue(0, 2, 2); issue(0, 3, 3); issue(1, 0, 4); issue(1, 1, 5);
   }
-  if (MRG) PH_WAIT(6);                         // MRG: A_lo, B_lo AND B_hi of K-tile 0 (all but the three youngest half-tiles)
-  else PH_WAITQ();                             // half-tiles 0, 1 (A_lo, B_lo of K-tile 0) have landed
+  PH_WAITQ();                                  // half-tiles 0, 1 (A_lo, B_lo of K-tile 0) have landed
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();   // waves 4-7 run one segment behind
   if (wm == 1) __builtin_amdgcn_s_setprio(1);  // the younger half loses VALU arbitration otherwise
@@ -258,12 +244,10 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
   i16x8 af[MQ][2], b0[2][2], b1[2][2];
 
   // one phase: LOAD segment (reads + stream + wait), barrier, MFMA segment, barrier
-  const bool dead_hi = DEAD && wm == 1;        // this wave's last tile of the upper A half does not exist
 #define PH_LOAD_A(slot)                                                                              \
   if (!abl_rd) {                                                                                     \
     constexpr int a_slot = (LEAD && ((slot) & 3) == 0) ? PH_RING(J) : (slot);                        \
     _Pragma("unroll") for (int mi = 0; mi < MQ; ++mi) _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) \
-    if (!(DEAD && ((slot) & 3) == 3 && mi == MQ - 1 && dead_hi))                                     \
     af[mi][kk] = *(const i16x8*)(smem + a_slot * PH_SLOT + a_off + mi * 2048 + (((kk * 4 + fq) ^ sw) << 4)); \
   }
 #define PH_LOAD_B(dst, slot)                                                                         \
@@ -274,7 +258,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
   __builtin_amdgcn_sched_barrier(0);                                                                 \
   PH_TS("s[90:91]")                                                                                        \
   if (!abl_mm) _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int mi = 0; mi < MQ; ++mi) \
-    if (!(DEAD && (mh) == 1 && mi == MQ - 1 && dead_hi))                                             \
     _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                 \
       acc[mh][mi][nh][ni] = T::mfma(bfr[ni][kk], af[mi][kk], acc[mh][mi][nh][ni]);                   \
   __builtin_amdgcn_sched_barrier(0);                                                                 \
@@ -300,32 +283,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
     if ((!CHK || h < H) && !abl_st) { issue(h >> 2, q_, slot_); PH_TS("s[86:87]") if (wait) PH_WAITQ(); }  \
     else { PH_TS("s[86:87]") if (wait) PH_WAIT(0); }                                                    \
     PH_TS("s[88:89]")                                                                              \
-  }
-  // MRG: the two MFMA blocks of a merged phase between ONE pair of barriers
-#define PH_MFMA2(mhA, nhA, bfrA, mhB, nhB, bfrB)                                                     \
-  __builtin_amdgcn_s_barrier();                                                                      \
-  __builtin_amdgcn_sched_barrier(0);                                                                 \
-  if (!abl_mm) {                                                                                     \
-    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int mi = 0; mi < MQ; ++mi) \
-      if (!(DEAD && (mhA) == 1 && mi == MQ - 1 && dead_hi))                                          \
-      _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                               \
-        acc[mhA][mi][nhA][ni] = T::mfma(bfrA[ni][kk], af[mi][kk], acc[mhA][mi][nhA][ni]);            \
-    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int mi = 0; mi < MQ; ++mi) \
-      if (!(DEAD && (mhB) == 1 && mi == MQ - 1 && dead_hi))                                          \
-      _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                               \
-        acc[mhB][mi][nhB][ni] = T::mfma(bfrB[ni][kk], af[mi][kk], acc[mhB][mi][nhB][ni]);            \
-  }                                                                                                  \
-  __builtin_amdgcn_sched_barrier(0);                                                                 \
-  __builtin_amdgcn_s_barrier();                                                                      \
-  __builtin_amdgcn_sched_barrier(0);
-  // stream step with the merged schedule's wait in front of M0 (all but the three youngest half-tiles)
-#define PH_STREAM6(tpar, t, p)                                                                       \
-  {                                                                                                  \
-    const int h = 4 * (t) + (p) + 6;                                                                 \
-    constexpr int q_ = ((p) + 2) & 3;                                                                \
-    constexpr int slot_ = (LEAD && q_ == 0) ? PH_RING(J + 3) : 4 * (((tpar) + (((p) + 6) >> 2)) & 1) + q_; \
-    if ((!CHK || h < H) && !abl_st) { issue(h >> 2, q_, slot_); PH_WAIT(6); }                        \
-    else { PH_WAIT(0); }                                                                             \
   }
   // ABL: timing studies only (VV_ABLATE, results wrong): 1 no LDS-DMA stream in the loop, 2 no MFMA, 4 no fragment
   // reads, 8 every gathered row is the (L2-hot) zero row
@@ -371,19 +328,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
       PH_STREAM(PAR, t, 1, false) PH_LOAD_B(b1, 4 * PAR + 2) PH_WAITSF(1) PH_MFMA(0, 1, b1)
 #undef PH_WAITSF
       PH_STREAM(PAR, t, 2, false) PH_LOAD_A(4 * PAR + 3) PH_MFMA(1, 1, b1)
-    } else if constexpr (MRG != 0) {
-      PH_LOAD_A(4 * PAR + 0) PH_LOAD_B(b0, 4 * PAR + 1) PH_LOAD_B(b1, 4 * PAR + 2)
-      PH_STREAM(PAR, t, 0, false) PH_STREAM(PAR, t, 1, true)
-      PH_MFMA2(0, 0, b0, 0, 1, b1)
-      PH_LOAD_A(4 * PAR + 3) PH_STREAM(PAR, t, 2, false)
-      if (GATE && PAR == 0 && t + 2 == gate_at) {                        // B_lo(t + 2) opens a chunk
-        gate_wait(g_next);
-        if (++g_next >= a.gate_n) gated = false;
-        gate_at = gated ? a.gate_kt[g_next] : -1;
-      }
-      PH_STREAM6(PAR, t, 3)
-      PH_MFMA2(1, 1, b1, 1, 0, b0)
-      return;
     } else {
     PH_LOAD_A(4 * PAR + 0) PH_LOAD_B(b0, 4 * PAR + 1) PH_STREAM(PAR, t, 0, true) PH_MFMA(0, 0, b0)
     PH_LOAD_B(b1, 4 * PAR + 2) PH_STREAM(PAR, t, 1, true) PH_MFMA(0, 1, b1)
@@ -416,9 +360,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
 #undef PH_LOAD_A
 #undef PH_LOAD_B
 #undef PH_MFMA
-#undef PH_MFMA2
 #undef PH_STREAM
-#undef PH_STREAM6
 #undef PH_WAITQ
 #undef PH_RING
 
@@ -458,7 +400,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
     for (int mh = 0; mh < 2; ++mh)
 #pragma unroll
       for (int mi = 0; mi < MQ; ++mi) {
-        if (DEAD && mh == 1 && mi == MQ - 1 && dead_hi) continue;        // (wave-uniform)
         const int m = m0 + (mh ^ hswap) * HROWS + wm * 16 * MQ + mi * 16 + frow;
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh) {
@@ -486,7 +427,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
   for (int mh = 0; mh < 2; ++mh)
 #pragma unroll
     for (int mi = 0; mi < MQ; ++mi) {
-      if (DEAD && mh == 1 && mi == MQ - 1 && dead_hi) continue;
       const int m = m0 + (mh ^ hswap) * HROWS + wm * 16 * MQ + mi * 16 + frow;
       if (m >= Rst) continue;
       int64_t ref_row = 0;
@@ -552,138 +492,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph(FwdArgs a) {
 #undef PH_TS_CLOB
 }
 
-#ifdef VV_LAB
-// ------------------------------------------------------------------------------- forward, ten-slot ring (experiment) ----
-// The same kernel with the WHOLE LDS as its ring: ten slots of 16 KiB, half-tiles issued EIGHT ahead of their use (two full
-// K-tiles), counted wait vmcnt(12): six half-tiles (96 KiB per CU) stay in flight across every barrier instead of four.
-// The ablations say the kernel sits on its LDS-DMA stream; if that stream is latency-bound (bytes in flight / round trip),
-// half as many bytes again in flight should show.  Slots are runtime values here (half-tile h lives in slot h mod 10: the
-// pattern repeats every five K-tiles, the loop is unrolled by two).  VV_GEMM_VARIANT=10 selects it (plain forward only).
-template <typename T, int MQ>
-__global__ __launch_bounds__(GEMM_THREADS) void k_fwd_gemm_ph10(FwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NS = 10;
-  constexpr int HROWS = 32 * MQ, BMT = 2 * HROWS;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int Dp = (int)round_up(a.D, D_ALIGN);
-  const int tilesN = Dp / BN;
-  const int R = a.n_dev ? *a.n_dev : a.R;
-  const int nact = a.n_dev ? ((R + BMT - 1) / BMT) * tilesN : (int)gridDim.x;
-  if (a.seq_host && blockIdx.x == 0 && tid == 0) __hip_atomic_store(a.seq_host, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if ((int)blockIdx.x >= nact) return;
-  const int L = ph_xcd_remap(blockIdx.x, nact);
-  const int m0 = (L / tilesN) * BMT, n0 = (L % tilesN) * BN;
-  const int Fp = a.Fp;
-  const uint16_t* srcA[2][2];
-  const uint16_t* srcB[2][2];
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = (i * 8 + wave) * 8 + (lane >> 3), lc = (lane & 7) ^ (row & 7);
-      const int grow = m0 + hf * HROWS + row;
-      const int trow = (row < HROWS && grow < R) ? a.rows[grow] : a.zero_row;
-      srcA[hf][i] = a.table + (int64_t)trow * Fp + lc * 8;
-      srcB[hf][i] = a.Wh + (int64_t)(n0 + hf * 128 + row) * Fp + lc * 8;
-    }
-  f32x4 acc[2][MQ][2][2];
-#pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-#pragma unroll
-    for (int mi = 0; mi < MQ; ++mi)
-#pragma unroll
-      for (int nh = 0; nh < 2; ++nh)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mh][mi][nh][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = Fp / BK;
-  const int H = 4 * nk;
-  auto issue = [&](int kt, int q, int slot) {
-    const uint16_t* const* src = q == 0 ? srcA[0] : q == 1 ? srcB[0] : q == 2 ? srcB[1] : srcA[1];
-    unsigned char* dst = smem + slot * PH_SLOT;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) ph_glds16(src[i] + kt * BK, dst + (i * 8 + wave) * 1024);
-  };
-  // prologue: half-tiles 0 .. 7 (K-tiles 0 and 1) into slots 0 .. 7
-#pragma unroll
-  for (int h = 0; h < 8; ++h) issue(h >> 2, h & 3, h);
-  PH_WAIT(12);                                 // half-tiles 0, 1 have landed
-  __builtin_amdgcn_s_barrier();
-  if (wm == 1) __builtin_amdgcn_s_barrier();
-  if (wm == 1) __builtin_amdgcn_s_setprio(1);
-  const int frow = lane & 15, fq = lane >> 4;
-  const int a_off = (wm * 16 * MQ + frow) * 128;
-  const int b_off = (wn * 32 + frow) * 128;
-  const int sw = frow & 7;
-  i16x8 af[MQ][2], b0[2][2], b1[2][2];
-  int base = 0;                                // slot of half-tile 4 t
-  auto slot_of = [&](int j) { const int x = base + j; return x >= NS ? (x >= 2 * NS ? x - 2 * NS : x - NS) : x; };   // j < 16
-#define P10_LOAD_A(j)                                                                                \
-  { const unsigned char* sp_ = smem + slot_of(j) * PH_SLOT;                                          \
-    _Pragma("unroll") for (int mi = 0; mi < MQ; ++mi) _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) \
-      af[mi][kk] = *(const i16x8*)(sp_ + a_off + mi * 2048 + (((kk * 4 + fq) ^ sw) << 4)); }
-#define P10_LOAD_B(dst, j)                                                                           \
-  { const unsigned char* sp_ = smem + slot_of(j) * PH_SLOT;                                          \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)  \
-      dst[ni][kk] = *(const i16x8*)(sp_ + b_off + ni * 2048 + (((kk * 4 + fq) ^ sw) << 4)); }
-#define P10_MFMA(mh, nh, bfr)                                                                        \
-  __builtin_amdgcn_s_barrier();                                                                      \
-  __builtin_amdgcn_sched_barrier(0);                                                                 \
-  _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int mi = 0; mi < MQ; ++mi) \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                 \
-      acc[mh][mi][nh][ni] = T::mfma(bfr[ni][kk], af[mi][kk], acc[mh][mi][nh][ni]);                   \
-  __builtin_amdgcn_sched_barrier(0);                                                                 \
-  __builtin_amdgcn_s_barrier();                                                                      \
-  __builtin_amdgcn_sched_barrier(0);
-  // stream step of phase (t, p): half-tile 4 t + p + 8 = quadrant p of K-tile t + 2, into the slot of half-tile 4 t + p - 2
-#define P10_STREAM(t, j, p, wait)                                                                    \
-  {                                                                                                  \
-    const int h = 4 * (t) + (p) + 8;                                                                 \
-    if (h < H) { issue((t) + 2, (p), slot_of((j) + 8)); if (wait) PH_WAIT(12); }                     \
-    else if (wait) PH_WAIT(0);                                                                       \
-  }
-  for (int t = 0; t < nk; t += 2) {
-    // K-tile t: half-tiles base + 0 .. 3
-    P10_LOAD_A(0) P10_LOAD_B(b0, 1) P10_STREAM(t, 0, 0, true) P10_MFMA(0, 0, b0)
-    P10_LOAD_B(b1, 2) P10_STREAM(t, 1, 1, true) P10_MFMA(0, 1, b1)
-    P10_LOAD_A(3) P10_STREAM(t, 2, 2, false) P10_MFMA(1, 1, b1)
-    P10_STREAM(t, 3, 3, true) P10_MFMA(1, 0, b0)
-    // K-tile t + 1: half-tiles base + 4 .. 7
-    P10_LOAD_A(4) P10_LOAD_B(b0, 5) P10_STREAM(t + 1, 4, 0, true) P10_MFMA(0, 0, b0)
-    P10_LOAD_B(b1, 6) P10_STREAM(t + 1, 5, 1, true) P10_MFMA(0, 1, b1)
-    P10_LOAD_A(7) P10_STREAM(t + 1, 6, 2, false) P10_MFMA(1, 1, b1)
-    P10_STREAM(t + 1, 7, 3, true) P10_MFMA(1, 0, b0)
-    base += 8; if (base >= NS) base -= NS;
-  }
-  if (wm == 0) __builtin_amdgcn_s_barrier();
-#undef P10_LOAD_A
-#undef P10_LOAD_B
-#undef P10_MFMA
-#undef P10_STREAM
-  const float descale = 1.0f / (a.scales->sx * a.scales->sw_cur);
-  const float lo = a.relu ? 0.f : -INFINITY;
-#pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-#pragma unroll
-    for (int mi = 0; mi < MQ; ++mi) {
-      const int m = m0 + mh * HROWS + wm * 16 * MQ + mi * 16 + frow;
-      if (m >= R) continue;
-#pragma unroll
-      for (int nh = 0; nh < 2; ++nh)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const int n = n0 + nh * 128 + wn * 32 + ni * 16 + fq * 4;
-          if (n >= a.D) continue;
-          float v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = fmaxf(acc[mh][mi][nh][ni][j] * descale + a.bias[n + j], lo);
-          *(float4*)(a.H + (int64_t)m * a.D + n) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    }
-}
-
-#endif  // VV_LAB
 // ------------------------------------------------------------------------------- wgrad --------
 // dW = dY^T X, one split of K per workgroup.  Both operands are k-major in HBM (dY rows / gathered feature rows), so a
 // half-tile is 64 k-rows x 128 columns: 256-B LDS rows of 16 chunks, chunk' = chunk ^ (h(row) << 1) with
@@ -1230,280 +1038,96 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_wgrad_gemm_ph(WgradArgs a) {
 #undef WTS_CLOB
 }
 
-#ifdef VV_LAB
-// ------------------------------------------------------------------------------- weight gradient, four waves ----
-// k_wgrad_gemm_w4: the same product and the same 256 x 256 tile as k_wgrad_gemm_ph with FOUR waves, one per SIMD, each
-// owning a 128 x 128 quadrant (64 accumulator tiles = 256 registers; the fragments live in the other half of the
-// 512-register file a lone wave may use).  Why: the eight-wave kernel reads 28 operand fragments per wave and K-tile
-// (224 KiB of LDS reads per CU and K-tile) for 64 MFMAs each; its ablation (profiles/r02_ph_gemm_ablation.txt) shows
-// the LDS-DMA writes and the fragment reads serialising on the LDS (staging alone 0.145 ms + reads alone 0.111 ms =
-// 0.237 ms with the MFMAs removed, 0.26 ms with them).  A 128 x 128 wave tile needs 16 fragments per 32-deep step for
-// 64 MFMAs: 128 KiB of reads per K-tile.
-//   * stage = one 32-deep K step: four sub-slots of 8 KiB (X_lo, X_hi, Y_lo, Y_hi: 32 k-rows x 128 columns, the image
-//     of k_wgrad_gemm_ph's half-tiles) in a ring of 4 stages (128 KiB); wave (wx, wy) reads X half wx and Y half wy;
-//   * every wave stages 2 of the 8 1-KiB pieces of each sub-slot; stage s+4 is issued right after the barrier that
-//     opens stage s (its sub-slots are the ones stage s's fragments were read from, now in registers everywhere), so three
-//     stages (96 KiB per CU) are in flight across every barrier; one counted wait (vmcnt(16)) and ONE barrier per stage;
-//   * fragments are double-buffered in registers: the reads of stage s+1 are issued between the MFMAs of stage s.
-template <typename T>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_wgrad_gemm_w4(WgradArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int SUB = 8192;                              // one sub-slot: 32 k-rows x 128 halves
-  int32_t* ids = (int32_t*)(smem + PH_LDS_BYTES);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wx = wave & 1, wy = wave >> 1;
-  const int tilesM = a.Dp / BM, tilesN = a.Fp / BN;
-  const int L = ph_xcd_remap(blockIdx.x, gridDim.x);
-  const int tmc = a.tm_count > 0 ? a.tm_count : tilesM;
-  const int tm = a.tm_begin + L % tmc, tn = (L / tmc) % tilesN, sp = L / (tmc * tilesN);
-  const int m0 = tm * BM, n0 = tn * BN;
-  int total_steps = a.Rp / BK, kps = a.ksteps_per_split;
-  if (a.n_dev) {
-    total_steps = (*a.n_dev + BK - 1) / BK;
-    kps = (total_steps + a.S - 1) / a.S;
-  }
-  const int k_begin = sp * kps;
-  int k_end = k_begin + kps;
-  if (k_end > total_steps) k_end = total_steps;
-  const int nk_all = k_end > k_begin ? k_end - k_begin : 0;
-
-  f32x4 acc[8][8];                     // [X tile][Y tile]
-#pragma unroll
-  for (int ni = 0; ni < 8; ++ni)
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // staging: piece p = i*4 + wave (i = 0, 1) of a sub-slot = k-rows 4p .. 4p+3; lane -> (row, 16-byte chunk)
-  const int srow0 = wave * 4 + (lane >> 4), srow1 = srow0 + 16;
-  const int scol0 = ((lane & 15) ^ (ph_h(srow0) << 1)) * 8;
-  const int scol1 = ((lane & 15) ^ (ph_h(srow1) << 1)) * 8;
-  const uint16_t* tb0 = a.table + n0 + scol0;
-  const uint16_t* tb1 = a.table + n0 + scol1;
-  const int g = lane >> 4, li = lane & 15, q4 = li >> 2, pp = li & 3;
-  const int hx = ph_h(8 * g + q4) << 1;
-  const int rd = (8 * g + q4) * 256 + (pp & 1) * 8;
-  int fa[8];                           // fragment tile ti of a sub-slot (both operands share the image)
-#pragma unroll
-  for (int ti = 0; ti < 8; ++ti) fa[ti] = rd + (((ti * 2 + (pp >> 1)) ^ hx) << 4);
-  const unsigned char* xbase = smem + wx * SUB;
-  const unsigned char* ybase = smem + (2 + wy) * SUB;
-
-  for (int c0 = 0; c0 < nk_all; c0 += PH_WG_IDS / BK) {
-    const int nk_c = nk_all - c0 < PH_WG_IDS / BK ? nk_all - c0 : PH_WG_IDS / BK;
-    const int nk = (nk_c + 1) & ~1;                           // even number of K-tiles: the stage count is a multiple of 4
-    const int ns = nk * 2;
-    const int64_t kg0 = (int64_t)(k_begin + c0) * BK;
-    const int live = nk_c * BK;
-    __syncthreads();
-    for (int i = tid; i < nk * BK; i += 256) ids[i] = i < live ? a.rows[kg0 + i] : a.zero_row;
-    __syncthreads();
-    const uint16_t* pa0 = a.dYh + (kg0 + srow0) * a.Dp + m0 + scol0;
-    const uint16_t* pa1 = a.dYh + (kg0 + srow1) * a.Dp + m0 + scol1;
-    const int64_t a_step = (int64_t)32 * a.Dp;
-    // stage st into ring position q: X_lo, X_hi, Y_lo, Y_hi (2 pieces each)
-    auto issue = [&](int st, int q, int id0, int id1) {
-      unsigned char* dst = smem + q * 4 * SUB + wave * 1024;
-      const int64_t r0 = (int64_t)id0 * a.Fp, r1 = (int64_t)id1 * a.Fp;
-      ph_glds16(tb0 + r0, dst);                   ph_glds16(tb1 + r1, dst + 4096);
-      ph_glds16_hi(tb0 + r0, dst + SUB);          ph_glds16_hi(tb1 + r1, dst + SUB + 4096);
-      const uint16_t* y0 = pa0 + st * a_step; const uint16_t* y1 = pa1 + st * a_step;
-      ph_glds16(y0, dst + 2 * SUB);               ph_glds16(y1, dst + 2 * SUB + 4096);
-      ph_glds16_hi(y0, dst + 3 * SUB);            ph_glds16_hi(y1, dst + 3 * SUB + 4096);
-    };
-    // X fragments are single-buffered (tile ni is dead after its eight MFMAs and is reloaded for the next stage right
-    // behind them), Y fragments double-buffered: 32 + 64 registers instead of 128
-    i16x8 xf[8], yf[2][8];
-#define W4_FRAG(dst, base, q, ti)                                                                      \
-    { const unsigned char* p_ = (base) + (q) * 4 * SUB + fa[ti];                                       \
-      const i16x4 lo_ = ph_tr(p_), hi_ = ph_tr(p_ + 1024);                                             \
-      dst = i16x8{lo_[0], lo_[1], lo_[2], lo_[3], hi_[0], hi_[1], hi_[2], hi_[3]}; }
-#define W4_RELOAD(q, ti) W4_FRAG(xf[ti], xbase, ((q) + 1) & 3, ti) W4_FRAG(yf[((q) + 1) & 1][ti], ybase, ((q) + 1) & 3, ti)
-#define W4_GROUP(q, ni, nxt)                                                                           \
-    if ((ni) > 0 && (nxt)) { W4_RELOAD(q, (ni) > 0 ? (ni) - 1 : 0) }                                   \
-    _Pragma("unroll") for (int mi = 0; mi < 8; ++mi) acc[ni][mi] = T::mfma(xf[ni], yf[(q) & 1][mi], acc[ni][mi]); \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                 \
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                               \
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                               \
-    }                                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);
-    // stage s (ring position q, Y fragments in buffer q & 1): wait for stage s+1, open with the barrier, restage the
-    // ring position with stage s+4, reload the fragments for stage s+1 between the MFMAs of stage s
-#define W4_STAGE(q, s, WAITN, more)                                                                    \
-    PH_WAIT(WAITN);                                                                                    \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
-    __builtin_amdgcn_s_barrier();                                                                      \
-    __builtin_amdgcn_sched_barrier(0);                                                                 \
-    if (more) {                                                                                        \
-      issue((s) + 4, q, idn0, idn1);                                                                   \
-      if ((s) + 5 < ns) { idn0 = ids[((s) + 5) * 32 + srow0]; idn1 = ids[((s) + 5) * 32 + srow1]; }    \
-    }                                                                                                  \
-    { const bool nxt_ = (s) + 1 < ns;                                                                  \
-      W4_GROUP(q, 0, nxt_) W4_GROUP(q, 1, nxt_) W4_GROUP(q, 2, nxt_) W4_GROUP(q, 3, nxt_)              \
-      W4_GROUP(q, 4, nxt_) W4_GROUP(q, 5, nxt_) W4_GROUP(q, 6, nxt_) W4_GROUP(q, 7, nxt_)              \
-      if (nxt_) { W4_RELOAD(q, 7) } }                                                                  \
-    __builtin_amdgcn_sched_barrier(0);
-    // prologue: stages 0..3 in flight, stage 0's fragments in buffer 0
-#pragma unroll
-    for (int st = 0; st < 4; ++st) issue(st, st, ids[st * 32 + srow0], ids[st * 32 + srow1]);
-    int idn0 = ns > 4 ? ids[4 * 32 + srow0] : a.zero_row, idn1 = ns > 4 ? ids[4 * 32 + srow1] : a.zero_row;
-    PH_WAIT(24);
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int ti = 0; ti < 8; ++ti) { W4_FRAG(xf[ti], xbase, 0, ti) W4_FRAG(yf[0][ti], ybase, 0, ti) }
-    int s = 0;
-    for (; s + 4 < ns; s += 4) {
-      W4_STAGE(0, s, 16, true)
-      W4_STAGE(1, s + 1, 16, true)
-      W4_STAGE(2, s + 2, 16, true)
-      W4_STAGE(3, s + 3, 16, true)
-    }
-    W4_STAGE(0, s, 16, false)
-    W4_STAGE(1, s + 1, 8, false)
-    W4_STAGE(2, s + 2, 0, false)
-    W4_STAGE(3, s + 3, 0, false)
-#undef W4_FRAG
-#undef W4_RELOAD
-#undef W4_GROUP
-#undef W4_STAGE
-  }
-
-  float* slab = a.slabs + (int64_t)sp * slab_pitch(a.Dp, a.Fp);
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) {
-    const int m = m0 + wy * 128 + mi * 16 + li;
-#pragma unroll
-    for (int ni = 0; ni < 8; ++ni) {
-      const int n = n0 + wx * 128 + ni * 16 + g * 4;
-      const f32x4 v = acc[ni][mi];
-      *(float4*)(slab + (int64_t)m * a.Fp + n) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
-
-template <typename T>
-static void launch_wgrad_w4_t(const WgradArgs& a, hipStream_t s) {
-  static bool once = ((void)hipFuncSetAttribute((const void*)k_wgrad_gemm_w4<T>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, PH_WG_LDS_BYTES), true);
-  (void)once;
-  const dim3 grid((a.tm_count > 0 ? a.tm_count : a.Dp / BM) * (a.Fp / BN) * a.S), block(256);
-  VV_LAUNCH((k_wgrad_gemm_w4<T>), grid, block, PH_WG_LDS_BYTES, s, a);
-}
-void launch_wgrad_gemm_w4(int prec, const WgradArgs& a, hipStream_t s) {
-  if (prec == 0) launch_wgrad_w4_t<F16>(a, s); else launch_wgrad_w4_t<BF16>(a, s);
-}
-#endif  // VV_LAB
-
 // ------------------------------------------------------------------------------- launchers ----
 // (KernelOpts::fwd_lead = 0: sibling workgroups ask for their gathered rows at the same moment again)
 
-template <typename T, int DROP, bool VEC, int MQ, int DEAD = 0>
+template <typename T, int DROP, bool VEC, int MQ>
 static void launch_fwd_ph_q(const FwdArgs& a, hipStream_t s, long tiles_est) {
-  static bool once = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD>,
+  static bool once = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ>,
                       hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_BYTES), true);
   (void)once;
   const int Dp = (int)round_up(a.D, D_ALIGN);
-  constexpr int BMT = 64 * MQ - 16 * DEAD;
+  constexpr int BMT = 64 * MQ;
   const dim3 grid(((a.R + BMT - 1) / BMT) * (Dp / BN)), block(GEMM_THREADS);
   (void)tiles_est;
-  if constexpr (!DROP && VEC && DEAD == 0) {
+  if constexpr (!DROP && VEC) {
     if (a.h16) {                          // ip2 as f16 (FwdArgs::h16): the same three forms -- sibling lead, gated, plain -- with the narrow epilogue
       constexpr int LDS10 = 10 * PH_SLOT;
       if constexpr (MQ <= 3) {
         if (ko().fwd_lead && Dp / BN > 1 && !a.gate) {
-          static bool once_l16 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 1, 0, true>,
+          static bool once_l16 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, 1, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS10), true);
           (void)once_l16;
-          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 1, 0, true>), grid, block, LDS10, s, a);
+          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, 1, true>), grid, block, LDS10, s, a);
           return;
         }
       }
       if (a.gate) {
-        static bool once_g16 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true, DEAD, 0, 0, true>,
+        static bool once_g16 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true, 0, true>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_BYTES), true);
         (void)once_g16;
-        VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true, DEAD, 0, 0, true>), grid, block, PH_LDS_BYTES, s, a);
+        VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true, 0, true>), grid, block, PH_LDS_BYTES, s, a);
         return;
       }
-      static bool once_p16 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 0, 0, true>,
+      static bool once_p16 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, 0, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_BYTES), true);
       (void)once_p16;
-      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 0, 0, true>), grid, block, PH_LDS_BYTES, s, a);
+      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, 0, true>), grid, block, PH_LDS_BYTES, s, a);
       return;
     }
   }
-  if constexpr (!DROP && VEC && DEAD == 0 && MQ <= 3) {
+  if constexpr (!DROP && VEC && MQ <= 3) {
     // the sibling lead: 78.6-79.7 against 81.7-82.9 us at the benchmark's de-duplicated size (192-row tiles, one round), 215
     // against 218 us for 192-row tiles in three rounds.  Not for 256-row tiles: that instantiation has no registers left for
     // it (256 + 48 bytes of scratch: dense 229 against 183 us, cfg 5 560 against 470 us)
     if (ko().fwd_lead && Dp / BN > 1 && !a.gate) {        // (the gated kernel keeps its static LDS word: no room beside ten slots)
       constexpr int LDS10 = 10 * PH_SLOT;
-      if (ko().fwd_merge) {
-        static bool once_m = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 1, 1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS10), true);
-        (void)once_m;
-        VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 1, 1>), grid, block, LDS10, s, a);
-        return;
-      }
-      static bool once_l = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 1>,
+      static bool once_l = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, 1>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, LDS10), true);
       (void)once_l;
-      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 1>), grid, block, LDS10, s, a);
+      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, 1>), grid, block, LDS10, s, a);
       return;
     }
   }
   if constexpr (!DROP && VEC) {
     if (a.gate) {
-      static bool once_g = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true, DEAD>,
+      static bool once_g = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_BYTES), true);
       (void)once_g;
-      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true, DEAD>), grid, block, PH_LDS_BYTES, s, a);
+      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, true>), grid, block, PH_LDS_BYTES, s, a);
       return;
     }
   }
-  if constexpr (!DROP && VEC && DEAD == 0) {      // (also measured with dropout on the shipped 128-row shape: 68-69 against 64-65 us, and on cfg 5: 465 against 457 us)
-    if (ko().fwd_merge) {
-      static bool once_m0 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 0, 1>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_BYTES), true);
-      (void)once_m0;
-      VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD, 0, 1>), grid, block, PH_LDS_BYTES, s, a);
-      return;
-    }
-  }
-  VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ, 0, false, DEAD>), grid, block, PH_LDS_BYTES, s, a);
+  VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, MQ>), grid, block, PH_LDS_BYTES, s, a);
 }
 // the gated instantiation exists for the plain forward (no dropout, D % 4 == 0): the caller gates only then
 bool fwd_gemm_can_gate(const FwdArgs& a) { return a.drop_ratio == 0.f && a.D % 4 == 0; }
 
-// (lab: KernelOpts::fwd_ring10 selects the ten-slot forward kernel, KernelOpts::ph_mq forces the tile)
+// (lab: KernelOpts::ph_mq forces the tile)
 
 // Tile of the forward GEMM for R rows (R_hint > 0: the distinct-row count of the previous step, the rows the workgroups
 // will really find) and the number of workgroups that get a tile: the least (rounds of 256 workgroups) x (cost of one
 // K-tile of that height); the cost of a K-tile is not proportional to the tile height: the B half-tiles, the barriers and
-// the phase structure do not shrink with it.  Tiles: 256, 192 and 128 rows; 176 (192 without its last 16-row MFMA tile:
-// 236 instead of 216 workgroups on the 256 CUs at the benchmark's ~20 650 distinct rows) only on request (VV_PH_MQ=31):
-// measured on one box, 400 steps each, the 176-row launch took 85.9 us against 84.4 us -- every workgroup of the single
-// round still stages and waits for the same half-tiles, so fewer rows per workgroup shorten nothing, and the 20 extra
-// workgroups take the CUs the grouping kernels of the next step were running on (profiles/r03_step_ablations.txt).
-static const int kTileRows[4] = {256, 192, 176, 128};
-static const int kTileCost[4] = {100, 85, 1000000, 70};
+// the phase structure do not shrink with it.  Tiles: 256, 192 and 128 rows.
+static const int kTileRows[3] = {256, 192, 128};
+static const int kTileCost[3] = {100, 85, 70};
 static int fwd_pick_tile(int R, int R_hint, int D, long* tiles_out) {
   const int Dp = (int)round_up(D, D_ALIGN);
   const int Rh = R_hint > 0 ? (int)std::min<long>(R, R_hint + R_hint / 32 + 64) : R;
   int best = 0; long best_cost = -1;
-  for (int t = 0; t < 4; ++t) {
+  for (int t = 0; t < 3; ++t) {
     const long tiles = ((Rh + kTileRows[t] - 1) / kTileRows[t]) * (long)(Dp / BN);
     const long cost = ((tiles + 255) / 256) * kTileCost[t];
     if (best_cost < 0 || cost < best_cost) { best = t; best_cost = cost; }
   }
-  { const int g_ph_mq = ko().ph_mq; if (g_ph_mq == 4) best = 0; else if (g_ph_mq == 3) best = 1; else if (g_ph_mq == 31) best = 2; else if (g_ph_mq == 2) best = 3; }
+  { const int g_ph_mq = ko().ph_mq; if (g_ph_mq == 4) best = 0; else if (g_ph_mq == 3) best = 1; else if (g_ph_mq == 2) best = 2; }
   if (tiles_out) *tiles_out = ((Rh + kTileRows[best] - 1) / kTileRows[best]) * (long)(Dp / BN);
   return best;
 }
 long fwd_gemm_plan(int R, int R_hint, int D, int* mq_out) {
   long tiles = 0;
   const int t = fwd_pick_tile(R, R_hint, D, &tiles);
-  if (mq_out) *mq_out = t == 0 ? 4 : t == 3 ? 2 : 3;
+  if (mq_out) *mq_out = 4 - t;
   return tiles;
 }
 
@@ -1534,8 +1158,8 @@ static void launch_fwd_ph_t(const FwdArgs& a, hipStream_t s) {
 #define VV_LAB_FWP(N)                                                                                  \
       if (lab_abl == N) {                                                                              \
         if (ko().fwd_lead) {                                                                           \
-          (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, N, false, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT); \
-          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, N, false, 0, 1>), grid, block, 10 * PH_SLOT, s, a);  \
+          (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, N, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT); \
+          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, N, false, 1>), grid, block, 10 * PH_SLOT, s, a);  \
         } else {                                                                                       \
           (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, N>, hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_BYTES); \
           VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, N>), grid, block, PH_LDS_BYTES, s, a);              \
@@ -1549,27 +1173,14 @@ static void launch_fwd_ph_t(const FwdArgs& a, hipStream_t s) {
         (void)fwd_pick_tile(a.R, a.n_dev ? a.R_hint : 0, a.D, &tiles_k);
         const dim3 grid(tiles_k + 40);          // the product launch's grid + the 40 helpers
         if (a.h16) {
-          (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 0, 1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT);
-          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 0, 1, 0, true>), grid, block, 10 * PH_SLOT, s, a);
+          (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT);
+          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 1, true>), grid, block, 10 * PH_SLOT, s, a);
         } else {
-          (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT);
-          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 0, 1>), grid, block, 10 * PH_SLOT, s, a);
+          (void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT);
+          VV_LAUNCH((k_fwd_gemm_ph<T, DROP, VEC, 3, 8192, false, 1>), grid, block, 10 * PH_SLOT, s, a);
         }
         return;
       }
-    }
-  }
-  if constexpr (!DROP && VEC) {
-    if (ko().fwd_ring10 && !a.gate && a.D % 4 == 0 && a.bias && (best == 0 || best == 1)) {
-      const dim3 block(GEMM_THREADS);
-      if (best == 0) {
-        static bool o4 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph10<T, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT), true); (void)o4;
-        VV_LAUNCH((k_fwd_gemm_ph10<T, 4>), dim3(((a.R + 255) / 256) * (Dp / BN)), block, 10 * PH_SLOT, s, a);
-      } else {
-        static bool o3 = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph10<T, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PH_SLOT), true); (void)o3;
-        VV_LAUNCH((k_fwd_gemm_ph10<T, 3>), dim3(((a.R + 191) / 192) * (Dp / BN)), block, 10 * PH_SLOT, s, a);
-      }
-      return;
     }
   }
 #endif
@@ -1577,9 +1188,6 @@ static void launch_fwd_ph_t(const FwdArgs& a, hipStream_t s) {
   (void)fwd_pick_tile(a.R, a.n_dev ? a.R_hint : 0, a.D, &tiles_est);
   if (best == 0) launch_fwd_ph_q<T, DROP, VEC, 4>(a, s, tiles_est);
   else if (best == 1) launch_fwd_ph_q<T, DROP, VEC, 3>(a, s, tiles_est);
-#ifdef VV_LAB
-  else if (best == 2) launch_fwd_ph_q<T, DROP, VEC, 3, 1>(a, s, tiles_est);      // (176-row tile: only on request, KernelOpts::ph_mq = 31)
-#endif
   else launch_fwd_ph_q<T, DROP, VEC, 2>(a, s, tiles_est);
 }
 
@@ -1641,15 +1249,15 @@ void launch_fwd_probe(const FwdArgs& a, hipStream_t s, bool marks) {
   const int Dp = (int)round_up(a.D, D_ALIGN);
   const dim3 grid(((a.R + 191) / 192) * (Dp / BN)), block(GEMM_THREADS);
   if (marks) {
-    static bool once_m = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<F16, 0, true, 3, 2048, false, 0, 1>,
+    static bool once_m = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<F16, 0, true, 3, 2048, false, 1>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS10), true);
     (void)once_m;
-    hipLaunchKernelGGL((k_fwd_gemm_ph<F16, 0, true, 3, 2048, false, 0, 1>), grid, block, LDS10, s, a);
+    hipLaunchKernelGGL((k_fwd_gemm_ph<F16, 0, true, 3, 2048, false, 1>), grid, block, LDS10, s, a);
   } else {
-    static bool once_p = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<F16, 0, true, 3, 0, false, 0, 1>,
+    static bool once_p = ((void)hipFuncSetAttribute((const void*)k_fwd_gemm_ph<F16, 0, true, 3, 0, false, 1>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS10), true);
     (void)once_p;
-    hipLaunchKernelGGL((k_fwd_gemm_ph<F16, 0, true, 3, 0, false, 0, 1>), grid, block, LDS10, s, a);
+    hipLaunchKernelGGL((k_fwd_gemm_ph<F16, 0, true, 3, 0, false, 1>), grid, block, LDS10, s, a);
   }
 }
 

@@ -180,10 +180,6 @@ struct vv_ctx {
   int n_chunks = 3;                 // F-chunks of the overlapped update (env VV_COMM_CHUNKS, 1 .. 4)
   int chunk_kt[5] = {0, 0, 0, 0, 0};    // first K-tile of each chunk for the current Fp (chunk_plan)
   int32_t* pub_count = nullptr;     // device: arrival counter of the publishing SGD kernels (behind the flags)
-  int32_t* pub_count0 = nullptr;    // ... of the first chunk's kernel when that one runs on the compute stream (overlap_first_inline)
-  bool overlap_first_inline = false; // VV_COMM_FIRST_INLINE=1: the overlapped update's first F-chunk (exchange + SGD) in the compute stream, the rest on the communication
-                                    // stream (round 5: built, measured, NOT the default -- one rank over real RCCL 0.2490-0.2501 ms against 0.2401-0.2430 with every
-                                    // chunk on the communication stream: chunk 0 loses its head start behind its own reduction launch, profiles/r05_overlap_cost.txt)
   hipEvent_t ev_chunk0 = nullptr; bool chunk0_event = false;     // the first F-chunk's reduction is done (recorded by fb_impl)
   int32_t* gate_err = nullptr; int32_t* gate_err_dev = nullptr;     // pinned + mapped: a gated forward gave up waiting
   hipEvent_t ev_chunk = nullptr;

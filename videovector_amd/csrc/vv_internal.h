@@ -388,20 +388,14 @@ constexpr int WMAX_SLOTS = 2048;      // slots of one per-block-maxima buffer (k
 // instantiations are compiled only there.
 struct KernelOpts {
   int fwd_lead = 1;        // "fwd_lead" / VV_FWD_LEAD: the forward GEMM's sibling lead (kernels_gemm_ph.hip)
-  int fwd_merge = 0;       // "fwd_merge" / VV_FWD_MERGE: the forward GEMM with two phases per barrier pair (k_fwd_gemm_ph, MRG)
   int wgrad_tr = 1;        // "wgrad_tr" / VV_WGRAD_TR: transposed LDS reads in the weight-gradient GEMM (0: the round-1 kernel)
-  int score_stream = 0;    // "score_stream" / VV_SCORE_STREAM: the one-sweep score kernel for every shape
   int score_pf = 1;        // "score_pf" / VV_SCORE_PF=0: k_score_fwd's first-round workgroups prefetch the second round's rows into L2 (ScoreArgs::prefetch; 23.4 -> 22.8 us)
   int wgrad_lean = 1;      // "wgrad_lean" / VV_WGRAD_LEAN=0: k_wgrad_gemm_ph's lean instantiations (fewer instructions in the LOAD segments: scalar bases + 32-bit lane offsets, LDS addresses as immediates, a K loop without end-of-stream tests); only for tables below 4 GiB
-  int gemm_variant = 5;    // (lab) VV_GEMM_VARIANT: 5 = the phase-staggered kernels; 0 = the round-1 kernels; 6 / 7 / 8 mixtures
   int ablate = 0;          // (lab) VV_ABLATE: ablated instantiations of the dense-size GEMMs (results wrong)
   int lab_fwd_abl = 0;     // (lab) VV_LAB_FWD_ABL: ablations of the 192-row forward kernel at the de-duplicated size (results wrong)
   int lab_wg_abl = 0;      // (lab) VV_LAB_WG_ABL
-  int fwd_ring10 = 0;      // (lab) VV_FWD_RING10: the ten-slot forward kernel
-  int ph_mq = 0;           // (lab) VV_PH_MQ: force the forward tile (2, 3, 4 = 128 / 192 / 256 rows, 31 = 176 rows)
+  int ph_mq = 0;           // (lab) VV_PH_MQ: force the forward tile (2, 3, 4 = 128 / 192 / 256 rows)
   int score_reg = 1;       // (lab) VV_SCORE_REG=0: the LDS-resident score kernel
-  int score_waves = 8;     // (lab) VV_SCORE_WAVES=4
-  int lab_score_pipe = 0;  // (lab) VV_LAB_SCORE_PIPE=1: the persistent, pipelined score kernel (profiles/attic/score_fwd_pipelined.hip.txt)
   int score_rr = 0;        // (lab) VV_SCORE_RR=1: the item-major kernels deal their items round-robin over the XCDs again (kernels_elem.hip: item_of_block)
 };
 extern thread_local const KernelOpts* g_ko;
