@@ -23,7 +23,7 @@ W, b = init_weights(7, D, F)
 eng = vv.Engine(0, sys.argv[1])
 eng.table_synth(ds.seed, ds.n_rows, F)
 eng.params_set(W, b)
-solver = int(sys.argv[2])
+solver, rare = int(sys.argv[2]), int(sys.argv[5])
 out = {}
 losses = []
 for it in range(12):
@@ -32,6 +32,7 @@ for it in range(12):
     cfg = vv.StepConfig(B, C, Nn, lr=0.05, momentum=0.0 if solver == 2 else 0.9, weight_decay=5e-4)     # (AdaGrad takes no momentum, solver.hpp:121-122)
     cfg.set("solver_type", solver)
     if solver == 2: cfg.set("delta", 1e-8)
+    if rare: cfg.set("reg", "L1"); cfg.set("lr_mult", (0.5, 2)); cfg.set("decay_mult", (2, 0))      # (branches of the rule the shipped settings never take)
     eng.forward_backward(cfg, idx)
     if it %% 4 == 1: losses.append(eng.loss())              # loss asked for BEFORE the update: the plain reduction runs
     if it %% 4 == 2: out["dW_before_%%d" %% it] = eng.grads()[0]
@@ -45,20 +46,28 @@ np.savez(sys.argv[3], **out)
 """
 
 
-def _run(tmp_path, prec, solver, fuse, D=512, slab16=0):
-    out = tmp_path / ("o_%s_%d_%d_%d_%d.npz" % (prec, solver, fuse, D, slab16))
+def _run(tmp_path, prec, solver, fuse, D=512, slab16=0, rare=0):
+    out = tmp_path / ("o_%s_%d_%d_%d_%d_%d.npz" % (prec, solver, fuse, D, slab16, rare))
     env = dict(os.environ, VV_FUSE_UPDATE=str(fuse), VV_SLAB16=str(slab16))
-    r = subprocess.run([sys.executable, "-c", CHILD % ROOT, prec, str(solver), str(out), str(D)], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([sys.executable, "-c", CHILD % ROOT, prec, str(solver), str(out), str(D), str(rare)], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     return np.load(out)
 
 
-@pytest.mark.parametrize("prec,solver,D,slab16", [("f16", 0, 512, 0), ("f16", 1, 512, 0), ("f16", 2, 512, 0), ("bf16", 0, 512, 0), ("f16", 0, 1024, 0),
-                                                  ("f16", 0, 512, 1), ("bf16", 1, 1024, 1)])
-def test_fused_update_is_bit_identical(tmp_path, prec, solver, D, slab16):
+def _cases(plain, rare):
+    """parametrize() arguments: the plain cases under their usual ids, then cases with rare = 1 (ids ending in -rare)"""
+    return dict(argvalues=[c + (0,) for c in plain] + [c + (1,) for c in rare],
+                ids=["-".join(map(str, c)) for c in plain] + ["-".join(map(str, c)) + "-rare" for c in rare])
+
+
+@pytest.mark.parametrize("prec,solver,D,slab16,rare", **_cases([("f16", 0, 512, 0), ("f16", 1, 512, 0), ("f16", 2, 512, 0), ("bf16", 0, 512, 0), ("f16", 0, 1024, 0),
+                                                                ("f16", 0, 512, 1), ("bf16", 1, 1024, 1)],
+                                                               [("f16", 0, 512, 0), ("bf16", 1, 512, 0), ("f16", 0, 512, 1)]))
+def test_fused_update_is_bit_identical(tmp_path, prec, solver, D, slab16, rare):
     """(D = 1024: more 16-byte elements than the fused launch has threads -- its loop.  slab16 = 1, round 6: the split-K partial products as f16 x
-    a power of two per tile -- both forms read the same halves and the same factors in the same order)"""
-    a, b = _run(tmp_path, prec, solver, 0, D, slab16), _run(tmp_path, prec, solver, 1, D, slab16)
+    a power of two per tile -- both forms read the same halves and the same factors in the same order.  rare = 1: L1 regularisation,
+    lr_mult (0.5, 2), decay_mult (2, 0) -- branches of the solver's rule that the shipped settings never take)"""
+    a, b = _run(tmp_path, prec, solver, 0, D, slab16, rare), _run(tmp_path, prec, solver, 1, D, slab16, rare)
     assert set(a.files) == set(b.files)
     for k in a.files:
         assert np.array_equal(a[k], b[k]), k
@@ -80,7 +89,7 @@ eng = vv.Engine(0, sys.argv[1])
 eng.set_option("wgrad_update", 1)                        # (the default since the rotated epilogue; set explicitly)
 eng.table_synth(ds.seed, ds.n_rows, F)
 eng.params_set(W, b)
-solver = int(sys.argv[2])
+solver, rare = int(sys.argv[2]), int(sys.argv[7])
 out, losses, refused = {}, [], 0
 for it in range(10):
     idx = smp.next()
@@ -88,6 +97,7 @@ for it in range(10):
     cfg = vv.StepConfig(B, C, Nn, lr=0.05 / (1 + it), momentum=0.0 if solver == 2 else 0.9, weight_decay=5e-4, dropout_ratio=drop, dropout_seed=5)
     cfg.set("solver_type", solver)
     if solver == 2: cfg.set("delta", 1e-8)
+    if rare: cfg.set("reg", "L1"); cfg.set("lr_mult", (0.5, 2)); cfg.set("decay_mult", (2, 0))
     if hint and it != 6: eng.update_hint(cfg)                # (iteration 6: an un-hinted step between hinted ones)
     eng.forward_backward(cfg, idx)
     if it %% 3 == 1: losses.append(eng.loss())              # the loss may be asked for between the two calls
@@ -111,16 +121,17 @@ np.savez(sys.argv[3], **out)
 """
 
 
-@pytest.mark.parametrize("prec,solver,D,drop", [("f16", 0, 4096, 0.9), ("f16", 1, 4096, 0.0), ("f16", 2, 4096, 0.0), ("bf16", 0, 4096, 0.0), ("f16", 0, 512, 0.0)])
-def test_update_in_the_weight_gradient_epilogue_is_bit_identical(tmp_path, prec, solver, D, drop):
+@pytest.mark.parametrize("prec,solver,D,drop,rare", **_cases([("f16", 0, 4096, 0.9), ("f16", 1, 4096, 0.0), ("f16", 2, 4096, 0.0), ("bf16", 0, 4096, 0.0), ("f16", 0, 512, 0.0)],
+                                                              [("f16", 0, 4096, 0.0), ("bf16", 1, 4096, 0.0)]))
+def test_update_in_the_weight_gradient_epilogue_is_bit_identical(tmp_path, prec, solver, D, drop, rare):
     """vv_update_hint: with one split of K -- the shipped 4096 x 4096 matrix at batch 128 -- the weight-gradient GEMM applies
     the solver's rule to the tile in its accumulators and dW is never written.  Parameters, bias, both histories and every loss are bit for bit
     those of the same calls without the hint; between the hinted backward pass and its update only the loss may be read; D = 512 at this batch
-    has several splits: the hint changes nothing there (and refuses nothing)."""
+    has several splits: the hint changes nothing there (and refuses nothing).  rare = 1: as in test_fused_update_is_bit_identical."""
     res = {}
     for hint in (0, 1):
-        out = tmp_path / ("h_%s_%d_%d_%d.npz" % (prec, solver, D, hint))
-        r = subprocess.run([sys.executable, "-c", CHILD_HINT % ROOT, prec, str(solver), str(out), str(D), str(hint), str(drop)],
+        out = tmp_path / ("h_%s_%d_%d_%d_%d.npz" % (prec, solver, D, hint, rare))
+        r = subprocess.run([sys.executable, "-c", CHILD_HINT % ROOT, prec, str(solver), str(out), str(D), str(hint), str(drop), str(rare)],
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         res[hint] = np.load(out)

@@ -683,6 +683,36 @@ static int stage_acquire(vv_ctx* c, size_t bytes, int* slot) {
   return VV_OK;
 }
 
+// The solver's parameters of a step as the update kernels read them (k_sgd, k_reduce_sgd, the weight-gradient GEMM's epilogue)
+static SolverRule solver_rule(const vv_step_cfg& cfg) {
+  SolverRule r;
+  r.rate = cfg.lr; r.momentum = cfg.momentum; r.weight_decay = cfg.weight_decay;
+  r.lr_mult_w = cfg.lr_mult[0]; r.lr_mult_b = cfg.lr_mult[1];
+  r.decay_mult_w = cfg.decay_mult[0]; r.decay_mult_b = cfg.decay_mult[1];
+  r.reg = cfg.reg; r.solver_type = cfg.solver_type; r.delta = cfg.delta;
+  return r;
+}
+
+// A launch just queued on s recomputed the W -> half scale (consumed: FusedUpdArgs / WgradUpd::recompute_scale) and so folded
+// vv_params_set's seed in Scales::wmax_bits into it: clear the seed behind that launch
+static hipError_t clear_wmax_seed(vv_ctx* c, bool consumed, hipStream_t s) {
+  if (!consumed || !c->wmax_seed_live) return hipSuccess;
+  const hipError_t e = hipMemsetAsync(&c->scales->wmax_bits, 0, sizeof(unsigned), s);
+  if (e == hipSuccess) c->wmax_seed_live = false;
+  return e;
+}
+
+// The end of every update: the n_slots per-block maxima it wrote (the buffer the previous update did not write) are what the next
+// W -> half scale update folds; that update is left pending (it rides in the next reduction or is flushed by whoever needs it first)
+static int finish_update(vv_ctx* c, int n_slots) {
+  c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = n_slots;
+  c->scale_pending = true;
+  HIPCHK(hipGetLastError());
+  c->iter++;
+  c->prof_calls++;
+  return VV_OK;
+}
+
 static void flush_scale_update(vv_ctx* c) {
   if (!c->scale_pending) return;
   launch_scale_update(c->prec, c->scales, c->wmax_blocks + c->wmax_cur * WMAX_SLOTS, c->wmax_n, c->stream);
@@ -1172,7 +1202,6 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
                       (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS;
   if (fuse_w) {
-    const vv_step_cfg& uc = c->upd_cfg;
     WgradUpd& u = wa.upd;
     wa.fuse_upd = 1;
     u.W = c->W; u.hW = c->hW; u.Wh = c->Wh; u.scales = c->scales;
@@ -1180,8 +1209,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     u.wmax_prev = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; u.wmax_prev_n = c->wmax_n;
     u.recompute_scale = c->scale_pending ? 1 : 0; u.prec = c->prec;
     u.D = c->D; u.F = c->F;
-    u.rate = uc.lr; u.momentum = uc.momentum; u.weight_decay = uc.weight_decay; u.lr_mult_w = uc.lr_mult[0]; u.decay_mult_w = uc.decay_mult[0];
-    u.delta = uc.delta; u.reg = uc.reg; u.solver_type = uc.solver_type;
+    u.rule = solver_rule(c->upd_cfg);
     u.sg = ra.sg; u.gg = ra.gg; u.ip_scale = ra.ip_scale;
   }
   // f16 split-K partial products (option "slab16"): the phase-staggered kernel with several splits only (one split: the update rides in the
@@ -1194,10 +1222,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   c->red_lazy = false; c->grads_stale = false;        // (the slabs now hold this step's gradient)
   c->grads_lost = false;
   if (fuse_w) {
-    if (wa.upd.recompute_scale && c->wmax_seed_live) {       // vv_params_set's seed has now been folded into a scale: clear it behind the launch
-      HIPCHK(hipMemsetAsync(&c->scales->wmax_bits, 0, sizeof(unsigned), s));
-      c->wmax_seed_live = false;
-    }
+    HIPCHK(clear_wmax_seed(c, wa.upd.recompute_scale, s));
     c->upd_in_wgrad = true; c->upd_wgrad_blocks = (c->Dp / BM) * (c->Fp / BN);
   }
   if (lazy) {
@@ -1350,29 +1375,23 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   float* const wmax_new = c->wmax_blocks + (1 - c->wmax_cur) * WMAX_SLOTS;     // the buffer the previous update did not write
   a.W = c->W; a.b = c->b; a.hW = c->hW; a.hb = c->hb; a.grads = c->grads; a.Wh = c->Wh; a.scales = c->scales; a.wmax_blocks = wmax_new;
   a.D = c->D; a.F = c->F; a.Dp = c->Dp; a.Fp = c->Fp;
-  a.rate = cfg->lr; a.momentum = cfg->momentum; a.weight_decay = cfg->weight_decay;
-  a.lr_mult_w = cfg->lr_mult[0]; a.lr_mult_b = cfg->lr_mult[1];
-  a.decay_mult_w = cfg->decay_mult[0]; a.decay_mult_b = cfg->decay_mult[1];
-  a.reg = cfg->reg; a.solver_type = cfg->solver_type; a.delta = cfg->delta;
+  a.rule = solver_rule(*cfg);
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
   if (c->upd_in_wgrad) {
     // the parameter matrix was updated in the weight-gradient GEMM (vv_update_hint): bias, loss, the guard's report -- k_reduce_sgd's
     // special workgroups alone -- and the bookkeeping of the scale
-    const vv_step_cfg& uc = c->upd_cfg;
-    if (cfg->lr != uc.lr || cfg->momentum != uc.momentum || cfg->weight_decay != uc.weight_decay || cfg->lr_mult[0] != uc.lr_mult[0] ||
-        cfg->decay_mult[0] != uc.decay_mult[0] || cfg->reg != uc.reg || cfg->solver_type != uc.solver_type || cfg->delta != uc.delta)
+    // (what the weight-gradient GEMM applied: WgradUpd::rule -- the bias multipliers may differ, the bias is updated here)
+    const SolverRule h = solver_rule(c->upd_cfg);
+    const SolverRule& r = a.rule;
+    if (r.rate != h.rate || r.momentum != h.momentum || r.weight_decay != h.weight_decay || r.lr_mult_w != h.lr_mult_w ||
+        r.decay_mult_w != h.decay_mult_w || r.reg != h.reg || r.solver_type != h.solver_type || r.delta != h.delta)
       return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
     FusedUpdArgs fa;
     fa.r = c->red_args; fa.g = a; fa.prec = c->prec; fa.no_params = 1; fa.recompute_scale = 0; fa.store_grads = 0;
     c->red_lazy = false; c->grads_stale = false; c->upd_in_wgrad = false;
     c->grads_lost = true;                       // (dW of this step never existed outside the GEMM's registers)
     PROFILED(c, "reduce_sgd", (void)launch_reduce_sgd(fa, c->stream));
-    c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = c->upd_wgrad_blocks;
-    c->scale_pending = true;
-    HIPCHK(hipGetLastError());
-    c->iter++;
-    c->prof_calls++;
-    return VV_OK;
+    return finish_update(c, c->upd_wgrad_blocks);
   }
   if (c->red_lazy && !overlapped) {
     // the reduction is still due: reduce and update in one launch (k_reduce_sgd)
@@ -1385,16 +1404,8 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
     c->red_lazy = false; c->grads_stale = !keep_grads;
     int n_new = 0;
     PROFILED(c, "reduce_sgd", (n_new = launch_reduce_sgd(fa, c->stream)));
-    if (fa.recompute_scale && c->wmax_seed_live) {       // vv_params_set's seed has now been folded into a scale: clear it behind the launch
-      HIPCHK(hipMemsetAsync(&c->scales->wmax_bits, 0, sizeof(unsigned), c->stream));
-      c->wmax_seed_live = false;
-    }
-    c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = n_new;
-    c->scale_pending = true;
-    HIPCHK(hipGetLastError());
-    c->iter++;
-    c->prof_calls++;
-    return VV_OK;
+    HIPCHK(clear_wmax_seed(c, fa.recompute_scale, c->stream));
+    return finish_update(c, n_new);
   }
   if ((rc = reduce_now(c))) return rc;
   flush_scale_update(c);               // two updates in a row without a step between them
@@ -1438,12 +1449,7 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
     }
     c->grads_pending = false; c->upd_inflight = !inl; c->upd_unjoined = false;
     c->params_partial = world > 1;
-    c->scale_pending = true;
-    c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = nb * world;
-    HIPCHK(hipGetLastError());
-    c->iter++;
-    c->prof_calls++;
-    return VV_OK;
+    return finish_update(c, nb * world);
   }
   if (overlapped) {
     // Exact synchronous SGD with the exchange hidden behind the NEXT step's forward GEMM: behind one event of the compute
@@ -1479,12 +1485,7 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   // The next W -> half scale (k_scale_update: folds this kernel's per-block max |w|) is needed by the NEXT k_sgd only.  It
   // is left pending and performed by one extra workgroup of the next step's k_reduce; anything else that touches the
   // scales or the parameters first flushes it as its own launch.
-  c->scale_pending = true;
-  c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = SGD_BLOCKS;
-  HIPCHK(hipGetLastError());
-  c->iter++;
-  c->prof_calls++;
-  return VV_OK;
+  return finish_update(c, SGD_BLOCKS);
 }
 
 int vv_step(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device) {

@@ -1356,9 +1356,10 @@ void launch_final_loss(const float* lp, const float* vp, int B, float scale, flo
 constexpr int RED_DW_BLOCKS = 2048;
 
 // 16 bias columns per block, 16 row groups, 8 independent loads in flight per thread; the
-// partial sums are combined in a fixed order (bit-reproducible, no atomics)
-__device__ __forceinline__ void reduce_db(const ReduceArgs& a, int blk) {
-  __shared__ float part[16][16];
+// partial sums are combined in a fixed order (bit-reproducible, no atomics).  store(d, sum) for each of the
+// block's columns d < D; part: the caller's 16 x 16 floats of LDS
+template <typename Store>
+__device__ __forceinline__ void db_colsum(const ReduceArgs& a, int blk, float (*part)[16], Store store) {
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   const int d = blk * 16 + tx;
   float s = 0.f;
@@ -1381,9 +1382,15 @@ __device__ __forceinline__ void reduce_db(const ReduceArgs& a, int blk) {
     float t = 0.f;
 #pragma unroll
     for (int u = 0; u < 16; ++u) t += part[u][tx];
+    store(d, t);
+  }
+}
+__device__ __forceinline__ void reduce_db(const ReduceArgs& a, int blk) {
+  __shared__ float part[16][16];
+  db_colsum(a, blk, part, [&](int d, float t) {      // (shard-major: every shard's db entries behind its rows)
     if (a.shard_rows > 0) a.grads[(int64_t)(d / a.shard_rows) * ((int64_t)a.shard_rows * a.F + a.shard_rows) + (int64_t)a.shard_rows * a.F + d % a.shard_rows] = t;
     else a.grads[(int64_t)a.D * a.F + d] = t;
-  }
+  });
 }
 
 // loss = scale * sum(loss_part), violations = sum(viol_part); fixed-order (deterministic)
@@ -1426,21 +1433,24 @@ __device__ __forceinline__ void scale_update_body(Scales* sc, const float* wmax_
   float mm = 0.f;
   if (wmax_blocks)
     for (int i = threadIdx.x; i < nblocks; i += 256) mm = fmaxf(mm, wmax_blocks[i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mm;
-  __syncthreads();
+  waves_max_to_lds(mm, red, threadIdx.x >> 6);
   if (threadIdx.x != 0) return;
-  mm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float m = fmaxf(mm, __uint_as_float(sc->wmax_bits));
-  float sw = 1.f;
-  if (prec == 0 && m > 0.f && isfinite(m)) {
-    int e;
-    frexpf(m, &e);                 // m = f * 2^e, f in [0.5, 1)
-    sw = ldexpf(1.f, 12 - e);      // m * sw in [2^11, 2^12)
-  }
-  sc->sw_next = sw;
+  sc->sw_next = half_scale(fmaxf(lds_max<4>(red), __uint_as_float(sc->wmax_bits)), prec);
   sc->wmax_bits = 0u;
+}
+
+// where element (d, f) of dW goes in the gradient buffer: flat, chunk-major (ReduceArgs::n_chunks) or shard-major (ReduceArgs::shard_rows:
+// every shard carries its db entries behind its rows)
+__device__ __forceinline__ int64_t dw_offset(const ReduceArgs& a, int d, int f) {
+  int64_t o = (int64_t)d * a.F + f;
+  if (a.n_chunks > 0) {
+    int cc = 0;
+    while (cc + 1 < a.n_chunks && f >= a.chunk_c0[cc + 1]) ++cc;
+    const int c0 = a.chunk_c0[cc], c1 = a.chunk_c0[cc + 1];
+    o = (int64_t)a.D * c0 + (int64_t)d * (c1 - c0) + (f - c0);
+  }
+  if (a.shard_rows > 0) o += (int64_t)(d / a.shard_rows) * a.shard_rows;
+  return o;
 }
 
 template <bool VEC, bool S16 = false>
@@ -1460,8 +1470,7 @@ __global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
     if (bid >= G - 1 - ndb) { reduce_db(a, bid - (G - 1 - ndb)); return; }
   }
   if (!(a.parts & 1)) return;
-  const float sgf = a.sg_dev ? *a.sg_dev : (a.gg ? a.sg * a.gg->mul : a.sg);   // the scale the 16-bit gradients really carry
-  const float inv = a.ip_scale / (sgf * a.scales->sx);
+  const float inv = grad_unscale(a.ip_scale, a.sg, a.gg, a.sg_dev, a.scales);
   const int64_t slab_sz = slab_pitch(a.Dp, a.Fp);
   const int d0 = a.d_begin, dn = a.d_count > 0 ? a.d_count : a.D;
   if (VEC) {
@@ -1482,15 +1491,7 @@ __global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
 #pragma unroll
         for (int u = 1; u < 8; ++u)
           if (u < a.S) { s.x += t[u].x; s.y += t[u].y; s.z += t[u].z; s.w += t[u].w; }
-        int64_t o = (int64_t)d * a.F + f;
-        if (a.n_chunks > 0) {
-          int cc = 0;
-          while (cc + 1 < a.n_chunks && f >= a.chunk_c0[cc + 1]) ++cc;
-          const int c0 = a.chunk_c0[cc], c1 = a.chunk_c0[cc + 1];
-          o = (int64_t)a.D * c0 + (int64_t)d * (c1 - c0) + (f - c0);
-        }
-        if (a.shard_rows > 0) o += (int64_t)(d / a.shard_rows) * a.shard_rows;
-        *(float4*)(a.grads + o) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+        *(float4*)(a.grads + dw_offset(a, d, f)) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
         continue;
       }
       float4 s = nt_load4(p);
@@ -1515,15 +1516,7 @@ __global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
         const float4 t = *(const float4*)(p + k * slab_sz);
         s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
       }
-      int64_t o = (int64_t)d * a.F + f;
-      if (a.n_chunks > 0) {            // chunk-major (vv_internal.h: ReduceArgs::n_chunks)
-        int cc = 0;
-        while (cc + 1 < a.n_chunks && f >= a.chunk_c0[cc + 1]) ++cc;
-        const int c0 = a.chunk_c0[cc], c1 = a.chunk_c0[cc + 1];
-        o = (int64_t)a.D * c0 + (int64_t)d * (c1 - c0) + (f - c0);
-      }
-      if (a.shard_rows > 0) o += (int64_t)(d / a.shard_rows) * a.shard_rows;       // shard-major: every shard carries its db entries behind its rows
-      *(float4*)(a.grads + o) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+      *(float4*)(a.grads + dw_offset(a, d, f)) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
     }
   } else {
     const int64_t nW = (int64_t)dn * a.F;
@@ -1553,19 +1546,11 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
   if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // (a failed exchange in front: SgdArgs::skip_if)
   const float sw = a.scales->sw_next;
   const int64_t nW = (int64_t)a.D * a.F;
-  const float lr_w = a.rate * a.lr_mult_w, dc_w = a.weight_decay * a.decay_mult_w;
+  const SolverRule& rule = a.rule;
+  const float lr_w = rule.rate * rule.lr_mult_w, dc_w = rule.weight_decay * rule.decay_mult_w;
   float wmax = 0.f;
-  // one parameter element: regulariser, then SGD (solver.cpp:502-531), Nesterov (:599-655) or AdaGrad (:714-781)
-  auto rule = [&](float w, float g, float& h, float lr, float dc) {
-    if (dc != 0.f) g += dc * (a.reg == 2 ? w : (float)((w > 0.f) - (w < 0.f)));
-    float u;
-    if (a.solver_type == 1) { const float h0 = h; h = lr * g + a.momentum * h0; u = (1.f + a.momentum) * h - a.momentum * h0; }
-    else if (a.solver_type == 2) { h += g * g; u = lr * (g / (sqrtf(h) + a.delta)); }
-    else { h = lr * g + a.momentum * h; u = h; }
-    return w - u;
-  };
   auto upd = [&](float w, float g, float& h) {
-    w = rule(w, g, h, lr_w, dc_w);
+    w = rule.step(w, g, h, lr_w, dc_w);
     wmax = fmaxf(wmax, fabsf(w));
     return w;
   };
@@ -1582,10 +1567,9 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
       w.x = upd(w.x, g.x, h.x); w.y = upd(w.y, g.y, h.y); w.z = upd(w.z, g.z, h.z); w.w = upd(w.w, g.w, h.w);
       nt_store4(a.W + o, w);
       nt_store4(a.hW + o, h);
-      const uint32_t lo = T::from_float(w.x * sw) | ((uint32_t)T::from_float(w.y * sw) << 16);
-      const uint32_t hi = T::from_float(w.z * sw) | ((uint32_t)T::from_float(w.w * sw) << 16);
-      if (a.pub_flag) __hip_atomic_store((unsigned long long*)(a.Wh + (int64_t)d * a.Fp + f), ((unsigned long long)hi << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else *(uint2*)(a.Wh + (int64_t)d * a.Fp + f) = make_uint2(lo, hi);
+      const uint2 q = pack_half4<T>(w.x, w.y, w.z, w.w, sw);
+      if (a.pub_flag) __hip_atomic_store((unsigned long long*)(a.Wh + (int64_t)d * a.Fp + f), ((unsigned long long)q.y << 32) | q.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else *(uint2*)(a.Wh + (int64_t)d * a.Fp + f) = q;
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nW; i += (int64_t)gridDim.x * 256) {
@@ -1597,10 +1581,10 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
       a.Wh[(int64_t)d * a.Fp + f] = T::from_float(w * sw);
     }
   }
-  const float lr_b = a.rate * a.lr_mult_b, dc_b = a.weight_decay * a.decay_mult_b;
+  const float lr_b = rule.rate * rule.lr_mult_b, dc_b = rule.weight_decay * rule.decay_mult_b;
   for (int d = blockIdx.x * 256 + threadIdx.x; a.do_bias && d < a.D; d += gridDim.x * 256) {
     float h = a.hb[d];
-    const float bn = rule(a.b[d], a.grads[nW + d], h, lr_b, dc_b);
+    const float bn = rule.step(a.b[d], a.grads[nW + d], h, lr_b, dc_b);
     if (a.pub_flag) __hip_atomic_store(a.b + d, bn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else a.b[d] = bn;
     a.hb[d] = h;
   }
@@ -1608,14 +1592,11 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
   // serialise at ~12 ns each); k_scale_update folds the slots.  (Folding them in this kernel's last workgroup instead --
   // an arrival counter -- was measured: the 1024 counter adds made the kernel 10 us longer, the saved launch is ~3 us.)
   __shared__ float wm[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = wmax;
-  __syncthreads();
+  waves_max_to_lds(wmax, wm, threadIdx.x >> 6);
   if (threadIdx.x == 0) {
     // (published launches: at agent scope like everything else a kernel of the COMPUTE stream reads behind the gates -- the scale
     // workgroup of the next k_reduce folds these slots and is ordered behind this kernel by the gate flag only, not by its end)
-    const float wmb = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+    const float wmb = lds_max<4>(wm);
     if (a.pub_flag) __hip_atomic_store(a.wmax_blocks + a.blk_off + blockIdx.x, wmb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else a.wmax_blocks[a.blk_off + blockIdx.x] = wmb;
     if (blockIdx.x == 0 && a.set_scale) {
@@ -1672,45 +1653,17 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
   const int n_special = ndb + 1;
   const int bid = (int)blockIdx.x < n_special ? (int)gridDim.x - n_special + (int)blockIdx.x : (int)blockIdx.x - n_special;
   const int G = (int)gridDim.x;
-  auto rule = [&](float w, float gr, float& h, float lr, float dc) {       // (k_sgd's)
-    if (dc != 0.f) gr += dc * (g.reg == 2 ? w : (float)((w > 0.f) - (w < 0.f)));
-    float u;
-    if (g.solver_type == 1) { const float h0 = h; h = lr * gr + g.momentum * h0; u = (1.f + g.momentum) * h - g.momentum * h0; }
-    else if (g.solver_type == 2) { h += gr * gr; u = lr * (gr / (sqrtf(h) + g.delta)); }
-    else { h = lr * gr + g.momentum * h; u = h; }
-    return w - u;
-  };
+  const SolverRule& rule = g.rule;
   if (bid == G - 1) { reduce_loss(a); return; }
   if (bid >= G - 1 - ndb) {
     // bias columns: the partials' sum is the gradient (stored), and the bias is updated from it on the spot
     __shared__ float part[16][16];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int d = (bid - (G - 1 - ndb)) * 16 + tx;
-    float s = 0.f;
-    if (d < a.D) {
-      const float* p = a.dbp + d;
-      const int nb = a.db_rows > 0 ? a.db_rows : a.B;
-      int b = ty;
-      for (; b + 112 < nb; b += 128) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(b + 16 * u) * a.D];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-      }
-      for (; b < nb; b += 16) s += p[(int64_t)b * a.D];
-    }
-    part[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && d < a.D) {
-      float t = 0.f;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) t += part[u][tx];
+    db_colsum(a, bid - (G - 1 - ndb), part, [&](int d, float t) {
       a.grads[(int64_t)a.D * a.F + d] = t;
       float h = g.hb[d];
-      g.b[d] = rule(g.b[d], t, h, g.rate * g.lr_mult_b, g.weight_decay * g.decay_mult_b);
+      g.b[d] = rule.step(g.b[d], t, h, rule.rate * rule.lr_mult_b, rule.weight_decay * rule.decay_mult_b);
       g.hb[d] = h;
-    }
+    });
     return;
   }
   // ---- parameter workgroups: 16-byte elements, one per thread at the benchmark's size (2048 workgroups), more for larger matrices
@@ -1761,26 +1714,10 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
   else { if (i < n4) load(i); }
   // the scale of the new half copy
   float sw = g.scales->sw_next;
-  if (fa.recompute_scale) {
-    __shared__ float red[4];
-    float mm = 0.f;
-    for (int k = threadIdx.x; k < fa.wmax_prev_n; k += 256) mm = fmaxf(mm, fa.wmax_prev[k]);
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o2, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mm;
-    __syncthreads();
-    mm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float m = fmaxf(mm, __uint_as_float(g.scales->wmax_bits));     // (vv_params_set's seed; the host clears it behind this launch)
-    sw = 1.f;
-    if (fa.prec == 0 && m > 0.f && isfinite(m)) {
-      int e;
-      frexpf(m, &e);
-      sw = ldexpf(1.f, 12 - e);
-    }
-  }
-  const float sgf = a.sg_dev ? *a.sg_dev : (a.gg ? a.sg * a.gg->mul : a.sg);
-  const float inv = a.ip_scale / (sgf * a.scales->sx);
-  const float lr_w = g.rate * g.lr_mult_w, dc_w = g.weight_decay * g.decay_mult_w;
+  __shared__ float red[4];
+  if (fa.recompute_scale) sw = fold_scale<4>(fa.wmax_prev, fa.wmax_prev_n, g.scales, fa.prec, red, threadIdx.x >> 6);
+  const float inv = grad_unscale(a.ip_scale, a.sg, a.gg, a.sg_dev, a.scales);
+  const float lr_w = rule.rate * rule.lr_mult_w, dc_w = rule.weight_decay * rule.decay_mult_w;
   float wmax = 0.f;
   if constexpr (S16) {
     for (; i < n8; ) {
@@ -1796,7 +1733,7 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
           if (u < a.S) sj += (float)t8[u][j] * sc8[u];
         gr[j] = __fmul_rn(sj, inv);
         hn[j] = hh8[j];
-        wn[j] = rule(w8[j], gr[j], hn[j], lr_w, dc_w);
+        wn[j] = rule.step(w8[j], gr[j], hn[j], lr_w, dc_w);
         wmax = fmaxf(wmax, fabsf(wn[j]));
       }
       if (fa.store_grads) { nt_store4(a.grads + o, make_float4(gr[0], gr[1], gr[2], gr[3])); nt_store4(a.grads + o + 4, make_float4(gr[4], gr[5], gr[6], gr[7])); }
@@ -1804,10 +1741,8 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
       if (i < n8) load8(i);                      // the next element's loads before this one's stores
       nt_store4(g.W + o, make_float4(wn[0], wn[1], wn[2], wn[3])); nt_store4(g.W + o + 4, make_float4(wn[4], wn[5], wn[6], wn[7]));
       nt_store4(g.hW + o, make_float4(hn[0], hn[1], hn[2], hn[3])); nt_store4(g.hW + o + 4, make_float4(hn[4], hn[5], hn[6], hn[7]));
-      uint32_t q[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) q[j] = T::from_float(wn[2 * j] * sw) | ((uint32_t)T::from_float(wn[2 * j + 1] * sw) << 16);
-      *(uint4*)(g.Wh + (int64_t)d * g.Fp + f) = make_uint4(q[0], q[1], q[2], q[3]);
+      const uint2 q0 = pack_half4<T>(wn[0], wn[1], wn[2], wn[3], sw), q1 = pack_half4<T>(wn[4], wn[5], wn[6], wn[7], sw);
+      *(uint4*)(g.Wh + (int64_t)d * g.Fp + f) = make_uint4(q0.x, q0.y, q1.x, q1.y);
     }
   } else
   for (; i < n4; ) {
@@ -1820,26 +1755,17 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
     const float4 gr = make_float4(__fmul_rn(s.x, inv), __fmul_rn(s.y, inv), __fmul_rn(s.z, inv), __fmul_rn(s.w, inv));
     if (fa.store_grads) nt_store4(a.grads + o, gr);
     float4 wn = w, hn = h;
-    wn.x = rule(wn.x, gr.x, hn.x, lr_w, dc_w); wn.y = rule(wn.y, gr.y, hn.y, lr_w, dc_w);
-    wn.z = rule(wn.z, gr.z, hn.z, lr_w, dc_w); wn.w = rule(wn.w, gr.w, hn.w, lr_w, dc_w);
+    wn.x = rule.step(wn.x, gr.x, hn.x, lr_w, dc_w); wn.y = rule.step(wn.y, gr.y, hn.y, lr_w, dc_w);
+    wn.z = rule.step(wn.z, gr.z, hn.z, lr_w, dc_w); wn.w = rule.step(wn.w, gr.w, hn.w, lr_w, dc_w);
     wmax = fmaxf(wmax, fmaxf(fmaxf(fabsf(wn.x), fabsf(wn.y)), fmaxf(fabsf(wn.z), fabsf(wn.w))));
     i += (int64_t)nblk * 256;
     if (i < n4) load(i);                       // the next element's loads before this one's stores
     nt_store4(g.W + o, wn);
     nt_store4(g.hW + o, hn);
-    const uint32_t lo = T::from_float(wn.x * sw) | ((uint32_t)T::from_float(wn.y * sw) << 16);
-    const uint32_t hi = T::from_float(wn.z * sw) | ((uint32_t)T::from_float(wn.w * sw) << 16);
-    *(uint2*)(g.Wh + (int64_t)d * g.Fp + f) = make_uint2(lo, hi);
+    *(uint2*)(g.Wh + (int64_t)d * g.Fp + f) = pack_half4<T>(wn.x, wn.y, wn.z, wn.w, sw);
   }
   __shared__ float wm[4];
-#pragma unroll
-  for (int o2 = 32; o2 > 0; o2 >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o2, 64));
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = wmax;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    g.wmax_blocks[bid] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-    if (bid == 0) { g.scales->sw_cur = sw; if (fa.recompute_scale) g.scales->sw_next = sw; }
-  }
+  update_end<4>(wmax, wm, threadIdx.x >> 6, g.wmax_blocks + bid, bid == 0, g.scales, sw, fa.recompute_scale);
 }
 int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s) {
   const int ndb = (a.r.D + 15) / 16;

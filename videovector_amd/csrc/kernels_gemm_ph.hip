@@ -842,31 +842,12 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_wgrad_gemm_ph(WgradArgs a) {
     float* red8 = (float*)smem;                           // the kernel's dynamic LDS is all 160 KiB of the CU: no static word beside it
     float sw = u.scales->sw_next;
     if (u.recompute_scale) {                              // the scale of the new half copy from the previous update's per-block maxima
-      float mm = 0.f;
-      for (int k = tid; k < u.wmax_prev_n; k += GEMM_THREADS) mm = fmaxf(mm, u.wmax_prev[k]);
-#pragma unroll
-      for (int o2 = 32; o2 > 0; o2 >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o2, 64));
-      if (lane == 0) red8[wave] = mm;
-      __syncthreads();
-      mm = red8[0];
-#pragma unroll
-      for (int w8 = 1; w8 < 8; ++w8) mm = fmaxf(mm, red8[w8]);
-      __syncthreads();
-      const float mx = fmaxf(mm, __uint_as_float(u.scales->wmax_bits));
-      sw = 1.f;
-      if (u.prec == 0 && mx > 0.f && isfinite(mx)) { int e; frexpf(mx, &e); sw = ldexpf(1.f, 12 - e); }
+      sw = fold_scale<8>(u.wmax_prev, u.wmax_prev_n, u.scales, u.prec, red8, wave);
+      __syncthreads();                                    // (red8 is reused)
     }
-    const float sgf = u.gg ? u.sg * u.gg->mul : u.sg;
-    const float inv = u.ip_scale / (sgf * u.scales->sx);
-    const float lr_w = u.rate * u.lr_mult_w, dc_w = u.weight_decay * u.decay_mult_w;
-    auto rule = [&](float w, float gr, float& h) {        // (k_sgd's)
-      if (dc_w != 0.f) gr += dc_w * (u.reg == 2 ? w : (float)((w > 0.f) - (w < 0.f)));
-      float up;
-      if (u.solver_type == 1) { const float h0 = h; h = lr_w * gr + u.momentum * h0; up = (1.f + u.momentum) * h - u.momentum * h0; }
-      else if (u.solver_type == 2) { h += gr * gr; up = lr_w * (gr / (sqrtf(h) + u.delta)); }
-      else { h = lr_w * gr + u.momentum * h; up = h; }
-      return w - up;
-    };
+    const float inv = grad_unscale(u.ip_scale, u.sg, u.gg, nullptr, u.scales);
+    const SolverRule& rule = u.rule;
+    const float lr_w = rule.rate * rule.lr_mult_w, dc_w = rule.weight_decay * rule.decay_mult_w;
     float wmax = 0.f;
     // The tile leaves the accumulators through LDS, 128 rows at a time (a 133 KB image, rows 1040 bytes apart: the sixteen rows a
     // ds_write_b128 touches fall on disjoint banks), and is applied to W in ROW order: a wave's instruction covers 1 KiB of one row of W --
@@ -913,29 +894,17 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_wgrad_gemm_ph(WgradArgs a) {
         for (int q = 0; q < 4; ++q) {
           const float gr = __fmul_rn(v[q], inv);          // (a rounded product, as the slab path stores it: no contraction into the rule)
           float hj = hq[q];
-          wq[q] = rule(wq[q], gr, hj);
+          wq[q] = rule.step(wq[q], gr, hj, lr_w, dc_w);
           hq[q] = hj;
           wmax = fmaxf(wmax, fabsf(wq[q]));
         }
         __builtin_nontemporal_store(wq, (f32x4*)(u.W + o));
         __builtin_nontemporal_store(hq, (f32x4*)(u.hW + o));
-        const uint32_t lo = T::from_float(wq[0] * sw) | ((uint32_t)T::from_float(wq[1] * sw) << 16);
-        const uint32_t hi = T::from_float(wq[2] * sw) | ((uint32_t)T::from_float(wq[3] * sw) << 16);
-        *(uint2*)(u.Wh + (int64_t)m * a.Fp + n) = make_uint2(lo, hi);
+        *(uint2*)(u.Wh + (int64_t)m * a.Fp + n) = pack_half4<T>(wq[0], wq[1], wq[2], wq[3], sw);
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o2, 64));
-    if (lane == 0) red8[wave] = wmax;
-    __syncthreads();
-    if (tid == 0) {
-      float wb = red8[0];
-#pragma unroll
-      for (int w8 = 1; w8 < 8; ++w8) wb = fmaxf(wb, red8[w8]);
-      u.wmax_blocks[blockIdx.x] = wb;
-      if (blockIdx.x == 0) { u.scales->sw_cur = sw; if (u.recompute_scale) u.scales->sw_next = sw; }
-    }
+    update_end<8>(wmax, red8, wave, u.wmax_blocks + blockIdx.x, blockIdx.x == 0, u.scales, sw, u.recompute_scale);
     return;
   }
   if constexpr (M32T) {

@@ -149,10 +149,7 @@ __global__ __launch_bounds__(EB) void k_max_margin_bwd(int count, const float* s
 // the scale of those rows, on the device: max |dY| (k_absmax's float bits) placed in [2^11, 2^12) for f16 -- nothing can
 // leave f16's range, whatever the caller's gradients are; 1 for bf16
 __global__ void k_pick_scale(const unsigned* max_bits, int prec, float* sg_out) {
-  const float m = __uint_as_float(*max_bits);
-  float sg = 1.f;
-  if (prec == 0 && m > 0.f && isfinite(m)) { int e; (void)frexpf(m, &e); sg = ldexpf(1.f, 12 - e); }
-  *sg_out = sg;
+  *sg_out = half_scale(__uint_as_float(*max_bits), prec);
 }
 template <typename T>
 __global__ __launch_bounds__(EB) void k_to_half_rows(const float* src, uint16_t* dst, int64_t rows, int cols, int cols_p, const float* scale_dev) {

@@ -264,6 +264,28 @@ struct SegsumArgs {
   GuardArgs guard;
 };
 
+// The solver's parameters as the three update kernels read them -- k_sgd, k_reduce_sgd and the weight-gradient GEMM's UPD epilogue, which
+// must give bit-identical parameters -- and the rule itself (api.hip: solver_rule fills it from a vv_step_cfg).
+struct SolverRule {
+  float rate, momentum, weight_decay;
+  float lr_mult_w, lr_mult_b, decay_mult_w, decay_mult_b;
+  int reg;                 // 1 L1, 2 L2
+  int solver_type;         // 0 SGD, 1 Nesterov, 2 AdaGrad
+  float delta;             // AdaGrad stability constant
+#ifdef __HIPCC__
+  // one parameter element: regulariser, then SGD (solver.cpp:502-531), Nesterov (:599-655) or AdaGrad (:714-781); h: its history.
+  // lr / dc: the local rate and decay (rate and weight_decay times the blob's multipliers)
+  __device__ __forceinline__ float step(float w, float g, float& h, float lr, float dc) const {
+    if (dc != 0.f) g += dc * (reg == 2 ? w : (float)((w > 0.f) - (w < 0.f)));
+    float u;
+    if (solver_type == 1) { const float h0 = h; h = lr * g + momentum * h0; u = (1.f + momentum) * h - momentum * h0; }
+    else if (solver_type == 2) { h += g * g; u = lr * (g / (sqrtf(h) + delta)); }
+    else { h = lr * g + momentum * h; u = h; }
+    return w - u;
+  }
+#endif
+};
+
 // The solver's update applied in the weight-gradient GEMM's epilogue (one split of K: the tile in the accumulators IS the gradient;
 // api.hip: vv_update_hint).  What k_reduce_sgd does per 16 bytes of W -- unscale, the solver's rule (solver.cpp:502-531 / 599-655 / 714-781),
 // blob.cpp:112-136, the new 16-bit copy, max |w| for the next scale -- done on the 256 x 256 tile while it is in registers: the 4 D F
@@ -274,8 +296,7 @@ struct WgradUpd {
   float* wmax_blocks;                    // one slot per workgroup of the GEMM (this update's per-block max |w|)
   const float* wmax_prev; int wmax_prev_n; int recompute_scale; int prec;      // as FusedUpdArgs
   int D, F;                              // the matrix (tiles are padded to Dp x Fp)
-  float rate, momentum, weight_decay, lr_mult_w, decay_mult_w, delta;
-  int reg, solver_type;
+  SolverRule rule;                       // (the bias multipliers unused: the bias is k_reduce_sgd's)
   float sg; const GradGuard* gg; float ip_scale;          // dW = acc * ip_scale / (sg * gg->mul * sx), as ReduceArgs
 };
 
@@ -344,11 +365,7 @@ struct SgdArgs {
   uint16_t* Wh; Scales* scales;
   float* wmax_blocks;      // [SGD_BLOCKS] per-block max |w| of this update
   int D, F, Dp, Fp;
-  float rate, momentum, weight_decay;
-  float lr_mult_w, lr_mult_b, decay_mult_w, decay_mult_b;
-  int reg;
-  int solver_type;         // 0 SGD, 1 Nesterov, 2 AdaGrad
-  float delta;             // AdaGrad stability constant
+  SolverRule rule;
   // one F-chunk of the update (data-parallel overlap): columns [f_begin, f_begin + f_count) of every row, read from the
   // chunk-major gradient buffer (ReduceArgs::n_chunks; f_count may be 0: nothing but, possibly, the bias);
   // chunked = 0: the whole matrix from the row-major buffer
@@ -551,6 +568,67 @@ __device__ __forceinline__ void gg_end(const GuardArgs& g, float block_max) {
   if (!g.gg || threadIdx.x != 0) return;
   g.slots[((size_t)g.round * 2 + g.producer) * g.nslot + blockIdx.x] = block_max;
   if (block_max > GG_LIMIT) __hip_atomic_store(&g.gg->flag[g.round], g.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- the parameter update, device side: what k_sgd, k_reduce_sgd and the weight-gradient GEMM's UPD epilogue share besides
+// SolverRule::step.  NW: the waves of the workgroup (4 or 8); red: NW floats of LDS the caller owns; wave: this thread's wave index.
+// The scale of a 16-bit copy whose largest magnitude is m: f16 places m in [2^11, 2^12), bf16 needs none
+__device__ __forceinline__ float half_scale(float m, int prec) {
+  float s = 1.f;
+  if (prec == 0 && m > 0.f && isfinite(m)) {
+    int e;
+    (void)frexpf(m, &e);           // m = f 2^e, f in [0.5, 1)
+    s = ldexpf(1.f, 12 - e);
+  }
+  return s;
+}
+// every wave's max of v into red[wave], then a barrier
+__device__ __forceinline__ void waves_max_to_lds(float v, float* red, int wave) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+}
+// the max of red[0 .. NW) (pairwise for four waves, in order for eight: the orders the kernels were tuned with)
+template <int NW>
+__device__ __forceinline__ float lds_max(const float* red) {
+  if constexpr (NW == 4) return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float m = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) m = fmaxf(m, red[w]);
+  return m;
+}
+// The scale of the new half copy, recomputed (FusedUpdArgs::recompute_scale) from the previous update's n per-block maxima and
+// vv_params_set's seed in Scales::wmax_bits (the host clears the seed behind the launch).  Every thread gets it; red is free again
+// only after a barrier.
+template <int NW>
+__device__ __forceinline__ float fold_scale(const float* wmax_prev, int n, const Scales* sc, int prec, float* red, int wave) {
+  float mm = 0.f;
+  for (int k = threadIdx.x; k < n; k += NW * 64) mm = fmaxf(mm, wmax_prev[k]);
+  waves_max_to_lds(mm, red, wave);
+  mm = lds_max<NW>(red);
+  return half_scale(fmaxf(mm, __uint_as_float(sc->wmax_bits)), prec);
+}
+// The end of an update: this workgroup's max |w| to its slot; workgroup 0 (first) records the scale sw its half copy carries,
+// and, when it recomputed that scale, the scale the next update will use
+template <int NW>
+__device__ __forceinline__ void update_end(float wmax, float* red, int wave, float* slot, bool first, Scales* sc, float sw, int recompute_scale) {
+  waves_max_to_lds(wmax, red, wave);
+  if (threadIdx.x == 0) {
+    *slot = lds_max<NW>(red);
+    if (first) { sc->sw_cur = sw; if (recompute_scale) sc->sw_next = sw; }
+  }
+}
+// dW = (the 16-bit operands' product) times this: ip_scale / (sg' sx), sg' the scale the gradients really carry -- chosen on the
+// device (sg_dev), else the host's sg times the guard's final multiplier
+__device__ __forceinline__ float grad_unscale(float ip_scale, float sg, const GradGuard* gg, const float* sg_dev, const Scales* sc) {
+  const float sgf = sg_dev ? *sg_dev : (gg ? sg * gg->mul : sg);
+  return ip_scale / (sgf * sc->sx);
+}
+// four elements of W times sw as four halves of the 16-bit copy
+template <typename T>
+__device__ __forceinline__ uint2 pack_half4(float x, float y, float z, float w, float sw) {
+  return make_uint2(T::from_float(x * sw) | ((uint32_t)T::from_float(y * sw) << 16), T::from_float(z * sw) | ((uint32_t)T::from_float(w * sw) << 16));
 }
 #endif
 
