@@ -318,6 +318,21 @@ class RetrievalStatsLayer : public Layer<Dtype> {
   vector<int32_t> map_ids_, map_cls_;
 };
 
+// RETRIEVAL_RANK_STATS_FIXED_REF (include/caffe/loss_layers.hpp:64-125, retrieval_rank_stats_fixed_ref_layer.cpp):
+// bottoms = query features, query ids, reference features, reference ids; tops = median rank, recall@1, recall@5, recall@10,
+// mean AP (:38-42).  The reference set becomes a device gallery (vv_gallery_create) per Forward; nothing is sorted.
+template <typename Dtype>
+class RetrievalRankStatsFixedRefLayer : public Layer<Dtype> {
+  VV_LAYER_BOILER(RetrievalRankStatsFixedRefLayer, "RETRIEVAL_RANK_STATS_FIXED_REF")
+  virtual int ExactNumBottomBlobs() const { return 4; }
+  virtual int ExactNumTopBlobs() const { return 5; }
+  virtual void LayerSetUp(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top);
+  virtual void Reshape(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top);
+ private:
+  string stats_output_file_;
+  int batch_size_ = 0, feature_dimension_ = 0, num_reference_points_ = 0;
+};
+
 // layer_factory.cpp:177-309: the 13 hot-path types (+SPLIT); LOG(FATAL) on anything else
 template <typename Dtype>
 Layer<Dtype>* GetLayer(const LayerParameter& param);

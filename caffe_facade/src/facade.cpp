@@ -635,6 +635,24 @@ void RetrievalStatsLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>& bottom, vec
 }
 template class RetrievalStatsLayer<float>;
 
+template <typename Dtype>
+void RetrievalRankStatsFixedRefLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>*) {
+  // retrieval_rank_stats_fixed_ref_layer.cpp:21-27.  num_reference_points and source are declared by the parameter message
+  // (caffe.proto:950-954) and read by nothing in the reference layer; they are parsed and ignored here too.
+  stats_output_file_ = this->layer_param_.get_msg("retrieval_rank_stats_fixed_ref_param").get_str("stats_output_file");
+  batch_size_ = bottom[0]->num();
+  CHECK_EQ(batch_size_, bottom[1]->num());
+  feature_dimension_ = bottom[0]->count() / bottom[0]->num();
+  num_reference_points_ = bottom[2]->num();
+  CHECK_EQ(num_reference_points_, bottom[3]->num());
+  CHECK_EQ(feature_dimension_, bottom[2]->count() / bottom[2]->num()) << "query and reference features differ in dimension";
+}
+template <typename Dtype>
+void RetrievalRankStatsFixedRefLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>&, vector<Blob<Dtype>*>* top) {
+  for (int i = 0; i < 5; ++i) (*top)[i]->Reshape(1, 1, 1, 1);                       // :38-42
+}
+template class RetrievalRankStatsFixedRefLayer<float>;
+
 // ------------------------------------------------------------------------------- shape layers --
 template <typename Dtype>
 void SliceLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top) {
@@ -764,6 +782,7 @@ Layer<Dtype>* GetLayer(const LayerParameter& param) {
   if (type == "MAX_MARGIN_LOSS") return new MaxMarginLossLayer<Dtype>(param);
   if (type == "VIDEO_SHOT_WINDOW_TEST_DATA") return new VideoShotWindowTestDataLayer<Dtype>(param);
   if (type == "RETRIEVAL_STATS") return new RetrievalStatsLayer<Dtype>(param);
+  if (type == "RETRIEVAL_RANK_STATS_FIXED_REF") return new RetrievalRankStatsFixedRefLayer<Dtype>(param);
   if (type == "NONE") LOG(FATAL) << "Layer " << name << " has unspecified type.";            // layer_factory.cpp:303
   LOG(FATAL) << "Layer " << name << " has type " << type << ", which is outside the videovec training path built here.";
   return nullptr;

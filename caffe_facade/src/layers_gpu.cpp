@@ -4,6 +4,8 @@
 //
 // These run when a graph is executed layer by layer (Net::ForwardFromTo / BackwardFromTo).  The recognised videovec
 // graphs run as one fused plan instead and never come through here.
+#include <fstream>
+
 #include "caffe/layer.hpp"
 
 namespace caffe {
@@ -343,7 +345,56 @@ void RetrievalStatsLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom,
 template <typename Dtype>
 void RetrievalStatsLayer<Dtype>::Backward_gpu(const vector<Blob<Dtype>*>&, const vector<bool>&, vector<Blob<Dtype>*>*) {}
 
+// ---------------------------------------------------------------------------------------------- RETRIEVAL_RANK_STATS_FIXED_REF
+// retrieval_rank_stats_fixed_ref_layer.cpp:116-233 (Forward_cpu in the reference): similarity, top five and rank counting on the
+// GPU (vv_gallery_*); the host writes the tops and, when asked, the per-query file.
+template <typename Dtype>
+void RetrievalRankStatsFixedRefLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top) {
+  const int nq = batch_size_, nr = num_reference_points_;
+  vector<int32_t> qids((size_t)nq), rids((size_t)nr);
+  for (int i = 0; i < nq; ++i) qids[i] = static_cast<int>(bottom[1]->cpu_data()[i]);        // :171
+  for (int i = 0; i < nr; ++i) rids[i] = static_cast<int>(bottom[3]->cpu_data()[i]);        // :75
+  const bool file = !stats_output_file_.empty();
+  vector<int32_t> best((size_t)nq), t5i(file ? (size_t)nq * 5 : 0);
+  vector<float> ap((size_t)nq), t5d(file ? (size_t)nq * 5 : 0);
+  vv_gallery* g = nullptr;
+  VV_CHECK(vv_gallery_create(X(), bottom[2]->cpu_data(), nr, feature_dimension_, rids.data(), &g));
+  vv_rank_stats st;
+  VV_CHECK(vv_gallery_rank_stats(X(), g, bottom[0]->cpu_data(), nq, qids.data(), &st, best.data(), ap.data(),
+                                 file ? t5i.data() : nullptr, file ? t5d.data() : nullptr));
+  VV_CHECK(vv_gallery_destroy(X(), g));
+  if (file) {
+    CHECK_GE(nr, 5) << "stats_output_file lists five reference items per query (:187-196)";
+    std::ofstream out(stats_output_file_.c_str());
+    CHECK(out.good()) << "Failed to open " << stats_output_file_;
+    out << "#item_id,rank,rec@1,rec@5" << ",ret_id_1,ret_id_2,ret_id_3,ret_id_4,ret_id_5" << std::endl;      // :124-126
+    std::map<int32_t, int> npos;
+    for (int r = 0; r < nr; ++r) ++npos[rids[r]];
+    for (int i = 0; i < nq; ++i) {
+      // rec@1 / rec@5 of a line are ComputeApStats' per-query values (:81-102): the positives among the first one / five items,
+      // the latter over min(positives, 5).  The five nearest items decide both.  (With fewer than five queries the reference
+      // refreshes only the first `batch` of its five slots, `jj < num_samples` at :181; all five are listed here.)
+      const int32_t* t = &t5i[(size_t)i * 5];
+      const float* d = &t5d[(size_t)i * 5];
+      double rec1 = 0, rec5 = 0;
+      for (int j = 0; j < 5; ++j)
+        if (rids[t[j]] == qids[i]) { rec5 += 1; if (j == 0) rec1 += 1; }
+      const auto it = npos.find(qids[i]);
+      if (it != npos.end()) rec5 /= it->second < 5 ? it->second : 5;
+      out << i << "," << qids[i] << "," << best[i] << "," << rec1 << "," << rec5 << ","                      // :185-197
+          << t[0] << "," << t[1] << "," << t[2] << "," << t[3] << "," << t[4] << ","
+          << d[0] << "," << d[1] << "," << d[2] << "," << d[3] << "," << d[4] << std::endl;
+    }
+    out.close();
+  }
+  const float v[5] = {st.median_rank, st.recall_1, st.recall_5, st.recall_10, st.mean_ap};                  // :226-230
+  for (int t = 0; t < 5; ++t) (*top)[t]->mutable_cpu_data()[0] = v[t];
+}
+template <typename Dtype>
+void RetrievalRankStatsFixedRefLayer<Dtype>::Backward_gpu(const vector<Blob<Dtype>*>&, const vector<bool>&, vector<Blob<Dtype>*>*) {}
+
 template class Layer<float>;
+template class RetrievalRankStatsFixedRefLayer<float>;
 template class VideoSampledShotsDataLayer<float>;
 template class VideoShotWindowTestDataLayer<float>;
 template class SliceLayer<float>;

@@ -120,7 +120,7 @@ static const std::vector<MsgDef>& Msgs() {
         OMSG(22, "memory_data_param", "Opaque"), OMSG(34, "mvn_param", "Opaque"),
         OMSG(19, "pooling_param", "Opaque"), OMSG(21, "power_param", "Opaque"),
         OMSG(30, "relu_param", "ReLUParameter"), OMSG(49, "retrieval_rank_stats_param", "Opaque"),
-        OMSG(52, "retrieval_rank_stats_fixed_ref_param", "Opaque"),
+        OMSG(52, "retrieval_rank_stats_fixed_ref_param", "RetrievalRankStatsFixedRefParameter"),
         OMSG(47, "retrieval_stats_param", "RetrievalStatsParameter"), OMSG(38, "sigmoid_param", "Opaque"),
         OMSG(39, "softmax_param", "Opaque"), OMSG(31, "slice_param", "SliceParameter"),
         OMSG(59, "social_pooling_param", "Opaque"), OMSG(46, "sum_param", "SumParameter"),
@@ -142,6 +142,9 @@ static const std::vector<MsgDef>& Msgs() {
        {OPT(1, "source", T_STRING), OPT(4, "batch_size", T_UINT32), OENUM(8, "backend", "DB", "LEVELDB"),
         OPTD(13, "display_all_ids", T_BOOL, "false"), OPTD(14, "include_positives", T_BOOL, "true"),
         OPTD(15, "include_negatives", T_BOOL, "true")}},
+      {"RetrievalRankStatsFixedRefParameter",                                       // :950-954
+       {OPTD(1, "stats_output_file", T_STRING, ""), OPTD(2, "num_reference_points", T_INT32, "0"),
+        OPTD(3, "source", T_STRING, "")}},
       {"RetrievalStatsParameter",                                                   // :955-966
        {OPT(1, "id_to_class_file", T_STRING), OPTD(2, "stats_output_file", T_STRING, ""),
         OPTD(3, "exclude_same_video_shots", T_BOOL, "true"), OPTD(4, "video_level_retrieval", T_BOOL, "false"),

@@ -288,6 +288,42 @@ int vv_retrieval_stats(vv_ctx* ctx, const float* feat, int32_t n, int32_t dim, c
                        const int32_t* map_ids, const int32_t* map_cls, int32_t n_map,
                        int exclude_same_video_shots, float* mean_ap, float* hit_at_1, float* hit_at_5);
 
+/* ---- gallery retrieval: RetrievalRankStatsFixedRefLayer (src/caffe/layers/retrieval_rank_stats_fixed_ref_layer.cpp, declared
+ * include/caffe/loss_layers.hpp:64-125).  Queries are ranked against a fixed reference set ("gallery") that stays on the device.
+ * Distance: d[i][g] = -2 dot(q_i, r_g) in fp32 with fp32 operands (:142-144).  Order: ascending (d, g) -- equal distances by
+ * ascending gallery index (the reference's std::sort, :158-162, leaves ties unspecified; the same rule as vv_retrieval_stats).
+ * The n_q x n_ref distance matrix (distance_matrix_, :30) never exists on the host and never whole on the device: queries are
+ * processed in blocks whose device scratch is at most 1 GiB ("scratch_bytes" of vv_gallery_get), and no row is ever sorted.
+ *
+ * vv_gallery_create: bottom[2] / bottom[3] of the layer (:131-132).  feat: host fp32 [n_ref][dim]; ref_ids: host [n_ref], or NULL
+ * for a gallery used only for vv_gallery_topk.  The id -> item lists the rank statistics need are built here, once.
+ * vv_gallery_from_table: the same gallery from table rows, embedded with the arguments of vv_embed_mean (k = 1 and coeff = NULL:
+ * vv_embed); the fp32 embeddings stay on the device.  rows: host int32 [n][k]. */
+typedef struct vv_gallery vv_gallery;
+int vv_gallery_create(vv_ctx* ctx, const float* feat, int64_t n_ref, int32_t dim, const int32_t* ref_ids, vv_gallery** out);
+int vv_gallery_from_table(vv_ctx* ctx, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu, int l2norm,
+                          const int32_t* ref_ids, vv_gallery** out);
+int vv_gallery_destroy(vv_ctx* ctx, vv_gallery* gallery);
+/* The k nearest reference items of every query (the head of sort_ids, :158-162, without the sort).  q: host fp32 [n_q][dim];
+ * 1 <= k <= 32 and k <= n_ref; idx / dist: host [n_q][k], ascending (d, g). */
+int vv_gallery_topk(vv_ctx* ctx, vv_gallery* gallery, const float* q, int32_t n_q, int32_t k, int32_t* idx, float* dist);
+/* Forward_cpu (:116-233) with ComputeApStats (:62-118): q = bottom[0], q_ids = bottom[1].  A query's positives are the reference
+ * items carrying its id; their full-order ranks are COUNTED (1 + the number of items before the positive), not read off a sorted row.
+ * As in the reference: best_rank starts at 10000 and stays there when no positive ranks earlier (:70, :77-79); recall@1 is a count,
+ * recall@5 / @10 are divided by min(positives, 5) / min(positives, 10) (:81-108); a query without positives contributes AP 0 and
+ * counts in every mean (:95, :226-230); the median is over all queries, the mean of the two middle ranks when n_q is even (:218-224).
+ * Optional per-query outputs (NULL to skip): best_rank [n_q], ap [n_q], top5_idx / top5_dist [n_q][5] (both or neither; the five
+ * nearest items and their distances, what stats_output_file lists, :180-196; index -1 where the gallery has fewer than five). */
+typedef struct { float median_rank, recall_1, recall_5, recall_10, mean_ap; } vv_rank_stats;
+int vv_gallery_rank_stats(vv_ctx* ctx, vv_gallery* gallery, const float* q, int32_t n_q, const int32_t* q_ids,
+                          vv_rank_stats* out, int32_t* best_rank, float* ap, int32_t* top5_idx, float* top5_dist);
+/* Properties of a gallery by name, in the manner of vv_get_option (the reference keeps the counterparts as layer members,
+ * loss_layers.hpp:117-124): "n_ref", "dim", "scratch_bytes" (device scratch currently held for query blocks),
+ * "scratch_limit_bytes", "query_block" (queries per block), "positive_chunk" (positives of one query ranked per pass; a query
+ * with more takes several passes), "last_passes", "last_sim_ms" (device time of the similarity kernels of the last call),
+ * "last_device_ms" (device time of the whole last call, uploads of the query blocks included).  Unknown name: VV_ERR_ARG. */
+int vv_gallery_get(const vv_gallery* gallery, const char* name, double* value);
+
 /* ---- per-layer operators.  The reference's operator interface is Layer<Dtype>::{Forward_gpu, Backward_gpu}
  * (include/caffe/layer.hpp:308-337); its sequential executor (Net::ForwardFromTo / BackwardFromTo, net.cpp:501-578) calls
  * them layer by layer.  Training here runs the fused plan above; these entry points are what the C++ facade's layer classes

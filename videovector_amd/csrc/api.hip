@@ -1660,24 +1660,19 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
 }
 
 // ------------------------------------------------------------------------------- embed --------
-int vv_embed(vv_ctx* c, const int32_t* rows, int64_t n, int relu, int l2norm, float* out) {
-  if (!c || !out || n <= 0) return fail(VV_ERR_ARG, "vv_embed: bad argument");
-  if (!c->table || !c->W) return fail(VV_ERR_STATE, "vv_embed: table and parameters must be set first");
-  if (n > (1ll << 30)) return fail(VV_ERR_ARG, "vv_embed: n too large");
-  { const int rcg = upd_pending_guard(c, "vv_embed"); if (rcg) return rcg; }     // (a hinted step half-way: new half copy, old bias)
-  VV_ENTER(c);
-  { const int rcj = comm_join(c); if (rcj) return rcj; }
+// The two embedding forms with the result left on the device (dout: fp32 [n][D], the caller's): vv_embed / vv_embed_mean
+// download it, vv_gallery_from_table keeps it.  `who` names the entry point in messages.
+static int embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int relu, int l2norm, float* dout) {
   const int D = c->D;
   const int Rp = (int)round_up(n, R_ALIGN);
   std::vector<int32_t> h(Rp, (int32_t)c->n_rows);
   for (int64_t i = 0; i < n; ++i) {
     const int64_t r = rows ? rows[i] : i;
-    if (r < 0 || r >= c->n_rows) return fail(VV_ERR_ARG, "vv_embed: row %lld out of range", (long long)r);
+    if (r < 0 || r >= c->n_rows) return fail(VV_ERR_ARG, "%s: row %lld out of range", who, (long long)r);
     h[i] = (int32_t)r;
   }
-  DevTmp<int32_t> drows; DevTmp<float> dout;
+  DevTmp<int32_t> drows;
   HIPCHK(drows.alloc((size_t)Rp));
-  HIPCHK(dout.alloc((size_t)n * D));
   HIPCHK(hipMemcpyAsync(drows, h.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
   FwdArgs fa;
   fa.table = c->table; fa.rows = drows; fa.Wh = c->Wh; fa.bias = c->b; fa.scales = c->scales;
@@ -1687,20 +1682,13 @@ int vv_embed(vv_ctx* c, const int32_t* rows, int64_t n, int relu, int l2norm, fl
   if (l2norm) launch_row_normalize(dout, (int)n, D, c->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out, dout, (size_t)n * D * 4, hipMemcpyDeviceToHost));
   return VV_OK;
 }
 
-int vv_embed_mean(vv_ctx* c, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu,
-                  int l2norm, float* out) {
-  if (!c || !rows || !out || n <= 0 || k <= 0) return fail(VV_ERR_ARG, "vv_embed_mean: bad argument");
-  if (!c->table || !c->W) return fail(VV_ERR_STATE, "vv_embed_mean: table and parameters must be set first");
-  if (n > (1ll << 24)) return fail(VV_ERR_ARG, "vv_embed_mean: n too large");
-  { const int rcg = upd_pending_guard(c, "vv_embed_mean"); if (rcg) return rcg; }     // (a hinted step half-way: new half copy, old bias)
-  VV_ENTER(c);
-  { const int rcj = comm_join(c); if (rcj) return rcj; }
+static int embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int32_t k, const float* coeff,
+                             int relu, int l2norm, float* dout) {
   for (int64_t i = 0; i < n * k; ++i)
-    if (rows[i] < 0 || rows[i] >= c->n_rows) return fail(VV_ERR_ARG, "vv_embed_mean: row %d out of range", rows[i]);
+    if (rows[i] < 0 || rows[i] >= c->n_rows) return fail(VV_ERR_ARG, "%s: row %d out of range", who, rows[i]);
   int rc = ensure_scratch_rows(c, n);
   if (rc) return rc;
   std::vector<float> hc(k);
@@ -1709,9 +1697,9 @@ int vv_embed_mean(vv_ctx* c, const int32_t* rows, int64_t n, int32_t k, const fl
   const int Rp = (int)round_up(n, R_ALIGN);
   std::vector<int32_t> h(Rp, (int32_t)c->n_rows);
   for (int64_t i = 0; i < n; ++i) h[i] = (int32_t)(c->n_rows + 1 + i);
-  DevTmp<int32_t> drows_in, drows; DevTmp<float> dcoeff, dout;
+  DevTmp<int32_t> drows_in, drows; DevTmp<float> dcoeff;
   HIPCHK(drows_in.alloc((size_t)n * k)); HIPCHK(drows.alloc((size_t)Rp));
-  HIPCHK(dcoeff.alloc((size_t)k)); HIPCHK(dout.alloc((size_t)n * D));
+  HIPCHK(dcoeff.alloc((size_t)k));
   HIPCHK(hipMemcpyAsync(drows_in, rows, (size_t)n * k * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(drows, h.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dcoeff, hc.data(), (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
@@ -1724,7 +1712,37 @@ int vv_embed_mean(vv_ctx* c, const int32_t* rows, int64_t n, int32_t k, const fl
   if (l2norm) launch_row_normalize(dout, (int)n, D, c->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out, dout, (size_t)n * D * 4, hipMemcpyDeviceToHost));
+  return VV_OK;
+}
+
+int vv_embed(vv_ctx* c, const int32_t* rows, int64_t n, int relu, int l2norm, float* out) {
+  if (!c || !out || n <= 0) return fail(VV_ERR_ARG, "vv_embed: bad argument");
+  if (!c->table || !c->W) return fail(VV_ERR_STATE, "vv_embed: table and parameters must be set first");
+  if (n > (1ll << 30)) return fail(VV_ERR_ARG, "vv_embed: n too large");
+  { const int rcg = upd_pending_guard(c, "vv_embed"); if (rcg) return rcg; }     // (a hinted step half-way: new half copy, old bias)
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  DevTmp<float> dout;
+  HIPCHK(dout.alloc((size_t)n * c->D));
+  const int rc = embed_rows_device(c, "vv_embed", rows, n, relu, l2norm, dout);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(out, dout, (size_t)n * c->D * 4, hipMemcpyDeviceToHost));
+  return VV_OK;
+}
+
+int vv_embed_mean(vv_ctx* c, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu,
+                  int l2norm, float* out) {
+  if (!c || !rows || !out || n <= 0 || k <= 0) return fail(VV_ERR_ARG, "vv_embed_mean: bad argument");
+  if (!c->table || !c->W) return fail(VV_ERR_STATE, "vv_embed_mean: table and parameters must be set first");
+  if (n > (1ll << 24)) return fail(VV_ERR_ARG, "vv_embed_mean: n too large");
+  { const int rcg = upd_pending_guard(c, "vv_embed_mean"); if (rcg) return rcg; }     // (a hinted step half-way: new half copy, old bias)
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  DevTmp<float> dout;
+  HIPCHK(dout.alloc((size_t)n * c->D));
+  const int rc = embed_mean_device(c, "vv_embed_mean", rows, n, k, coeff, relu, l2norm, dout);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(out, dout, (size_t)n * c->D * 4, hipMemcpyDeviceToHost));
   return VV_OK;
 }
 
@@ -1770,6 +1788,287 @@ int vv_retrieval_stats(vv_ctx* c, const float* feat, int32_t n, int32_t dim, con
   if (hit1) *hit1 = (float)(s_1 / npos);
   if (hit5) *hit5 = (float)(s_5 / npos);
   return VV_OK;
+}
+
+// ------------------------------------------------------------------------------- gallery ------
+// RetrievalRankStatsFixedRefLayer (retrieval_rank_stats_fixed_ref_layer.cpp): queries ranked against a fixed reference set.
+// The similarity, the selection and the counting run in kernels_retrieval.hip, one query block at a time through a scratch
+// buffer that never exceeds GALLERY_SCRATCH_MAX; the host only walks per-query scalars.
+static constexpr size_t GALLERY_SCRATCH_MAX = (size_t)1 << 30;          // every device buffer a query call needs, together
+static constexpr size_t GALLERY_DIST_MAX = GALLERY_SCRATCH_MAX - ((size_t)40 << 20);   // ... of which the distances
+static constexpr int GALLERY_QB_MAX = 512;                               // rows of one query block at most
+static constexpr int GALLERY_SEG_MAX = 64;                               // gallery segments (workgroups) per row at most
+
+struct vv_gallery {
+  vv_ctx* ctx = nullptr;
+  int64_t n_ref = 0, pitch = 0;          // pitch: floats between two rows of the distance scratch (n_ref rounded up to 64)
+  int dim = 0, Dp = 0;
+  int seg = 0, S = 0;                    // row kernels: items per workgroup (multiple of 1024), workgroups per row
+  int qb_max = 0;                        // rows of a query block the scratch limit allows for this gallery
+  float* feat = nullptr;                 // [n_ref][Dp], columns dim .. Dp-1 zero
+  int32_t* ref_ids = nullptr;            // [n_ref] or NULL (a gallery for top-k only)
+  int32_t* pos_idx = nullptr;            // gallery indices grouped by id (ascending id, ascending index inside one id)
+  std::vector<int32_t> uid, ustart;      // host: the distinct ids, ascending, and where each one's group starts in pos_idx
+  // scratch, grown on demand up to qb_max rows and kept between calls
+  int qb_cap = 0;
+  float *dist = nullptr, *qdev = nullptr, *out_dist = nullptr;
+  uint64_t* part = nullptr; uint32_t* bins = nullptr; int32_t* out_idx = nullptr;
+  int32_t *pstart = nullptr, *pcount = nullptr, *qids = nullptr; RankAcc* acc = nullptr;
+  size_t scratch_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // call begin / end, similarity begin / end (of the block in flight)
+  double last_sim_ms = 0, last_device_ms = 0; int last_passes = 0;
+};
+
+static void gallery_free_scratch(vv_gallery* g) {
+  dfree(g->dist); dfree(g->qdev); dfree(g->out_dist); dfree(g->part); dfree(g->bins); dfree(g->out_idx);
+  dfree(g->pstart); dfree(g->pcount); dfree(g->qids); dfree(g->acc);
+  g->dist = g->qdev = g->out_dist = nullptr; g->part = nullptr; g->bins = nullptr; g->out_idx = nullptr;
+  g->pstart = g->pcount = g->qids = nullptr; g->acc = nullptr;
+  g->qb_cap = 0; g->scratch_bytes = 0;
+}
+
+static int gallery_ensure_scratch(vv_gallery* g, int rows) {
+  if (rows <= g->qb_cap) return VV_OK;
+  gallery_free_scratch(g);
+  const size_t r = (size_t)rows;
+  const size_t b_dist = r * g->pitch * 4, b_q = r * g->Dp * 4, b_part = r * g->S * RT_MAX_K * 8, b_bins = r * 2 * RT_CHUNK * 4,
+               b_out = r * RT_MAX_K * 4, b_row = r * 4, b_acc = r * sizeof(RankAcc);
+  const size_t total = b_dist + b_q + b_part + b_bins + 2 * b_out + 3 * b_row + b_acc;
+  if (total > GALLERY_SCRATCH_MAX) return fail(VV_ERR_STATE, "gallery scratch of %zu bytes exceeds the limit", total);
+  HIPCHK(hipMalloc((void**)&g->dist, b_dist)); HIPCHK(hipMalloc((void**)&g->qdev, b_q));
+  HIPCHK(hipMalloc((void**)&g->part, b_part)); HIPCHK(hipMalloc((void**)&g->bins, b_bins));
+  HIPCHK(hipMalloc((void**)&g->out_idx, b_out)); HIPCHK(hipMalloc((void**)&g->out_dist, b_out));
+  HIPCHK(hipMalloc((void**)&g->pstart, b_row)); HIPCHK(hipMalloc((void**)&g->pcount, b_row)); HIPCHK(hipMalloc((void**)&g->qids, b_row));
+  HIPCHK(hipMalloc((void**)&g->acc, b_acc));
+  HIPCHK(hipMemset(g->qdev, 0, b_q));                       // the K padding of the query rows stays zero from here on
+  g->qb_cap = rows; g->scratch_bytes = total;
+  return VV_OK;
+}
+
+// shape-dependent constants, the feature buffer and the id -> gallery-index lists; g->feat is filled by the caller
+static int gallery_init(vv_ctx* c, vv_gallery* g, int64_t n_ref, int32_t dim, const int32_t* ref_ids) {
+  g->ctx = c; g->n_ref = n_ref; g->dim = dim; g->Dp = (int)round_up(dim, RT_BK); g->pitch = round_up(n_ref, 64);
+  g->seg = (int)round_up((n_ref + GALLERY_SEG_MAX - 1) / GALLERY_SEG_MAX, 1024);
+  if (g->seg < 16384) g->seg = 16384;
+  g->S = (int)((n_ref + g->seg - 1) / g->seg);
+  const size_t per_row = (size_t)g->pitch * 4;
+  g->qb_max = (int)std::min<size_t>(GALLERY_QB_MAX, GALLERY_DIST_MAX / per_row);
+  if (g->qb_max < 1) return fail(VV_ERR_ARG, "vv_gallery: %lld reference items do not fit one query row into the scratch limit", (long long)n_ref);
+  HIPCHK(hipMalloc((void**)&g->feat, (size_t)n_ref * g->Dp * 4));
+  if (g->Dp != dim) HIPCHK(hipMemsetAsync(g->feat, 0, (size_t)n_ref * g->Dp * 4, c->stream));
+  for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&g->ev[i]));
+  if (!ref_ids) return VV_OK;
+  // the id -> index lists, once (the reference re-reads every reference id for every query: ComputeApStats :73-75)
+  std::vector<int32_t> order((size_t)n_ref);
+  for (int64_t i = 0; i < n_ref; ++i) order[i] = (int32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ref_ids[a] < ref_ids[b]; });
+  for (int64_t i = 0; i < n_ref; ++i)
+    if (i == 0 || ref_ids[order[i]] != ref_ids[order[i - 1]]) { g->uid.push_back(ref_ids[order[i]]); g->ustart.push_back((int32_t)i); }
+  g->ustart.push_back((int32_t)n_ref);
+  HIPCHK(hipMalloc((void**)&g->ref_ids, (size_t)n_ref * 4)); HIPCHK(hipMalloc((void**)&g->pos_idx, (size_t)n_ref * 4));
+  HIPCHK(hipMemcpy(g->ref_ids, ref_ids, (size_t)n_ref * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g->pos_idx, order.data(), (size_t)n_ref * 4, hipMemcpyHostToDevice));
+  return VV_OK;
+}
+
+static void gallery_release(vv_gallery* g) {
+  gallery_free_scratch(g);
+  dfree(g->feat); dfree(g->ref_ids); dfree(g->pos_idx);
+  for (int i = 0; i < 4; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
+  delete g;
+}
+
+int vv_gallery_create(vv_ctx* c, const float* feat, int64_t n_ref, int32_t dim, const int32_t* ref_ids, vv_gallery** out) {
+  if (!c || !feat || !out) return fail(VV_ERR_ARG, "vv_gallery_create: NULL argument");
+  if (n_ref < 1 || n_ref > (1ll << 30) || dim < 1 || dim > 8192)
+    return fail(VV_ERR_ARG, "vv_gallery_create: %lld reference items of dimension %d", (long long)n_ref, dim);
+  VV_ENTER(c);
+  vv_gallery* g = new vv_gallery;
+  int rc = gallery_init(c, g, n_ref, dim, ref_ids);
+  if (!rc) {
+    const hipError_t e = hipMemcpy2DAsync(g->feat, (size_t)g->Dp * 4, feat, (size_t)dim * 4, (size_t)dim * 4, (size_t)n_ref,
+                                          hipMemcpyHostToDevice, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) rc = fail(VV_ERR_HIP, "vv_gallery_create: upload failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  if (rc) { gallery_release(g); return rc; }
+  *out = g;
+  return VV_OK;
+}
+
+int vv_gallery_from_table(vv_ctx* c, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu, int l2norm,
+                          const int32_t* ref_ids, vv_gallery** out) {
+  if (!c || !rows || !out || n <= 0 || k <= 0) return fail(VV_ERR_ARG, "vv_gallery_from_table: bad argument");
+  if (!c->table || !c->W) return fail(VV_ERR_STATE, "vv_gallery_from_table: table and parameters must be set first");
+  if (n > (1ll << 24)) return fail(VV_ERR_ARG, "vv_gallery_from_table: n too large");
+  { const int rcg = upd_pending_guard(c, "vv_gallery_from_table"); if (rcg) return rcg; }
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  DevTmp<float> emb;                                                          // [n][D]; copied into the padded rows below
+  HIPCHK(emb.alloc((size_t)n * c->D));
+  int rc = (k == 1 && !coeff) ? embed_rows_device(c, "vv_gallery_from_table", rows, n, relu, l2norm, emb)
+                              : embed_mean_device(c, "vv_gallery_from_table", rows, n, k, coeff, relu, l2norm, emb);
+  if (rc) return rc;
+  vv_gallery* g = new vv_gallery;
+  rc = gallery_init(c, g, n, c->D, ref_ids);
+  if (!rc) {
+    const hipError_t e = hipMemcpy2DAsync(g->feat, (size_t)g->Dp * 4, emb, (size_t)c->D * 4, (size_t)c->D * 4, (size_t)n,
+                                          hipMemcpyDeviceToDevice, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) rc = fail(VV_ERR_HIP, "vv_gallery_from_table: copy failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  if (rc) { gallery_release(g); return rc; }
+  *out = g;
+  return VV_OK;
+}
+
+int vv_gallery_destroy(vv_ctx* c, vv_gallery* g) {
+  if (!c) return fail(VV_ERR_ARG, "vv_gallery_destroy: ctx is NULL");
+  if (!g) return VV_OK;
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_destroy: the gallery belongs to another context");
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  gallery_release(g);
+  return VV_OK;
+}
+
+int vv_gallery_get(const vv_gallery* g, const char* name, double* value) {
+  if (!g || !name || !value) return fail(VV_ERR_ARG, "vv_gallery_get: NULL argument");
+  const std::string n(name);
+  if (n == "n_ref") *value = (double)g->n_ref;
+  else if (n == "dim") *value = g->dim;
+  else if (n == "scratch_bytes") *value = (double)g->scratch_bytes;
+  else if (n == "scratch_limit_bytes") *value = (double)GALLERY_SCRATCH_MAX;
+  else if (n == "query_block") *value = g->qb_max;
+  else if (n == "positive_chunk") *value = RT_CHUNK;
+  else if (n == "last_passes") *value = g->last_passes;
+  else if (n == "last_sim_ms") *value = g->last_sim_ms;
+  else if (n == "last_device_ms") *value = g->last_device_ms;
+  else return fail(VV_ERR_ARG, "vv_gallery_get: unknown name '%s'", name);
+  return VV_OK;
+}
+
+// One query block: rows [q0, q0 + rows) of the host queries to the device, their distances to every reference item into the scratch.
+static int gallery_block_sim(vv_ctx* c, vv_gallery* g, const float* q, int q0, int rows) {
+  HIPCHK(hipMemcpy2DAsync(g->qdev, (size_t)g->Dp * 4, q + (size_t)q0 * g->dim, (size_t)g->dim * 4, (size_t)g->dim * 4, (size_t)rows,
+                          hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(g->ev[2], c->stream));
+  launch_sim_f32(g->qdev, g->feat, g->dist, rows, (int)g->n_ref, g->Dp, g->pitch, c->stream);
+  HIPCHK(hipEventRecord(g->ev[3], c->stream));
+  return VV_OK;
+}
+static int gallery_block_done(vv_ctx* c, vv_gallery* g) {     // after the block's results are on the host (the stream is idle)
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, g->ev[2], g->ev[3]));
+  g->last_sim_ms += ms;
+  return VV_OK;
+}
+static int gallery_call_begin(vv_ctx* c, vv_gallery* g, int n_q) {
+  const int rc = gallery_ensure_scratch(g, std::min(n_q, g->qb_max));
+  if (rc) return rc;
+  g->last_sim_ms = 0; g->last_device_ms = 0; g->last_passes = 0;
+  HIPCHK(hipEventRecord(g->ev[0], c->stream));
+  return VV_OK;
+}
+static int gallery_call_end(vv_ctx* c, vv_gallery* g) {
+  HIPCHK(hipEventRecord(g->ev[1], c->stream));
+  HIPCHK(hipEventSynchronize(g->ev[1]));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+  g->last_device_ms = ms;
+  return VV_OK;
+}
+
+int vv_gallery_topk(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, int32_t k, int32_t* idx, float* dist) {
+  if (!c || !g || !q || !idx || !dist) return fail(VV_ERR_ARG, "vv_gallery_topk: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_topk: the gallery belongs to another context");
+  if (n_q < 1) return fail(VV_ERR_ARG, "vv_gallery_topk: n_q = %d", n_q);
+  if (k < 1 || k > RT_MAX_K) return fail(VV_ERR_ARG, "vv_gallery_topk: k = %d is outside 1 .. %d", k, RT_MAX_K);
+  if (k > g->n_ref) return fail(VV_ERR_ARG, "vv_gallery_topk: k = %d exceeds the gallery's %lld items", k, (long long)g->n_ref);
+  VV_ENTER(c);
+  int rc = gallery_call_begin(c, g, n_q);
+  if (rc) return rc;
+  for (int q0 = 0; q0 < n_q; q0 += g->qb_cap) {
+    const int rows = std::min(g->qb_cap, n_q - q0);
+    if ((rc = gallery_block_sim(c, g, q, q0, rows))) return rc;
+    launch_topk(g->dist, g->pitch, rows, (int)g->n_ref, k, g->seg, g->S, g->part, g->out_idx, g->out_dist, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(idx + (size_t)q0 * k, g->out_idx, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(dist + (size_t)q0 * k, g->out_dist, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = gallery_block_done(c, g))) return rc;
+  }
+  return gallery_call_end(c, g);
+}
+
+int vv_gallery_rank_stats(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, const int32_t* q_ids, vv_rank_stats* out,
+                          int32_t* best_rank, float* ap, int32_t* top5_idx, float* top5_dist) {
+  if (!c || !g || !q || !q_ids || !out) return fail(VV_ERR_ARG, "vv_gallery_rank_stats: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_rank_stats: the gallery belongs to another context");
+  if (!g->ref_ids) return fail(VV_ERR_ARG, "vv_gallery_rank_stats: the gallery was created without reference ids");
+  if (n_q < 1) return fail(VV_ERR_ARG, "vv_gallery_rank_stats: n_q = %d", n_q);
+  if ((top5_idx != nullptr) != (top5_dist != nullptr)) return fail(VV_ERR_ARG, "vv_gallery_rank_stats: top5_idx and top5_dist go together");
+  VV_ENTER(c);
+  int rc = gallery_call_begin(c, g, n_q);
+  if (rc) return rc;
+  const int k5 = (int)std::min<int64_t>(5, g->n_ref);
+  std::vector<int32_t> hstart, hcount, ranks((size_t)n_q), t5i; std::vector<float> t5d;
+  std::vector<RankAcc> hacc;
+  double s1 = 0, s5 = 0, s10 = 0, sap = 0;                                                     // :150
+  for (int q0 = 0; q0 < n_q; q0 += g->qb_cap) {
+    const int rows = std::min(g->qb_cap, n_q - q0);
+    hstart.assign(rows, 0); hcount.assign(rows, 0); hacc.assign(rows, RankAcc{0.0, 10000, 0, 0, 0});   // :68-70
+    int max_p = 0;
+    for (int i = 0; i < rows; ++i) {
+      const auto it = std::lower_bound(g->uid.begin(), g->uid.end(), q_ids[q0 + i]);
+      if (it == g->uid.end() || *it != q_ids[q0 + i]) continue;                                // an id the gallery does not hold
+      const size_t u = it - g->uid.begin();
+      hstart[i] = g->ustart[u]; hcount[i] = g->ustart[u + 1] - g->ustart[u];
+      max_p = std::max(max_p, hcount[i]);
+    }
+    HIPCHK(hipMemcpyAsync(g->pstart, hstart.data(), (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g->pcount, hcount.data(), (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g->qids, q_ids + q0, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g->acc, hacc.data(), (size_t)rows * sizeof(RankAcc), hipMemcpyHostToDevice, c->stream));
+    if ((rc = gallery_block_sim(c, g, q, q0, rows))) return rc;
+    const int passes = (max_p + RT_CHUNK - 1) / RT_CHUNK;
+    g->last_passes = std::max(g->last_passes, passes);
+    for (int pass = 0; pass < passes; ++pass) {
+      HIPCHK(hipMemsetAsync(g->bins, 0, (size_t)rows * 2 * RT_CHUNK * 4, c->stream));
+      launch_rank_pass(g->dist, g->pitch, rows, (int)g->n_ref, g->seg, g->S, g->pos_idx, g->pstart, g->pcount, g->qids, g->ref_ids,
+                       pass, g->bins, g->acc, c->stream);
+    }
+    if (top5_idx) {
+      launch_topk(g->dist, g->pitch, rows, (int)g->n_ref, k5, g->seg, g->S, g->part, g->out_idx, g->out_dist, c->stream);
+      t5i.resize((size_t)rows * k5); t5d.resize((size_t)rows * k5);
+      HIPCHK(hipMemcpyAsync(t5i.data(), g->out_idx, t5i.size() * 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(t5d.data(), g->out_dist, t5d.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hacc.data(), g->acc, (size_t)rows * sizeof(RankAcc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = gallery_block_done(c, g))) return rc;
+    for (int i = 0; i < rows; ++i) {
+      const RankAcc& a = hacc[i];
+      const double ret = hcount[i];
+      double qap = 0, r5 = a.acc5, r10 = a.acc10;
+      if (ret > 0) { qap = a.ap_sum / ret; r5 /= ret < 5 ? ret : 5; r10 /= ret < 10 ? ret : 10; }   // :95-108
+      sap += qap; s1 += a.acc1; s5 += r5; s10 += r10;                                               // :172-176
+      ranks[q0 + i] = a.best;
+      if (best_rank) best_rank[q0 + i] = a.best;
+      if (ap) ap[q0 + i] = (float)qap;
+      if (top5_idx)
+        for (int j = 0; j < 5; ++j) {                          // fewer than five reference items: index -1, distance 0
+          top5_idx[(size_t)(q0 + i) * 5 + j] = j < k5 ? t5i[(size_t)i * k5 + j] : -1;
+          top5_dist[(size_t)(q0 + i) * 5 + j] = j < k5 ? t5d[(size_t)i * k5 + j] : 0.f;
+        }
+    }
+  }
+  std::sort(ranks.begin(), ranks.end());                                                            // :218-224
+  out->median_rank = (float)(n_q % 2 == 0 ? (ranks[n_q / 2 - 1] + ranks[n_q / 2]) / 2.0 : (double)ranks[n_q / 2]);
+  out->recall_1 = (float)(s1 / n_q); out->recall_5 = (float)(s5 / n_q); out->recall_10 = (float)(s10 / n_q);   // :226-230
+  out->mean_ap = (float)(sap / n_q);
+  return gallery_call_end(c, g);
 }
 
 // ------------------------------------------------------------------------------- data parallel -

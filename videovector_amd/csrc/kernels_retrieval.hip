@@ -1,0 +1,341 @@
+// kernels_retrieval.hip -- gallery retrieval: fp32 similarity, streaming top-k and sort-free rank statistics.
+// gfx950 (MI355X, CDNA4) only.  Replaces the hot path of RetrievalRankStatsFixedRefLayer::Forward_cpu
+// (src/caffe/layers/retrieval_rank_stats_fixed_ref_layer.cpp:142-171): the -2 Q R^T product (:142-144), the full
+// std::sort of every query's row (:158-162) and the walk over the sorted row in ComputeApStats (:62-118).
+//
+// Form (DESIGN.md 'Gallery retrieval'): one QUERY BLOCK at a time.  k_sim_f32 writes the block's distances
+// d[q][g] = -2 dot(q, r_g) into a scratch buffer of at most 1 GiB; the row kernels below read that buffer.  A positive's
+// key and the key the counting pass sees for the same pair are therefore the SAME stored float: no second evaluation
+// of a dot product exists whose summation order could differ.
+//
+// Order: every (distance, gallery index) pair becomes one 64-bit key, ascending in (d, g): the distance's bits mapped
+// to an unsigned integer of the same order in the high word, the index in the low word.  Keys of one query are distinct,
+// so "the rank of p" is 1 + the number of keys below p's.  -0.0f is folded into +0.0f when the distance is stored
+// (operator< of the reference's comparator calls them equal).
+#include "vv_internal.h"
+
+namespace vv {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// ---------------------------------------------------------------------------------------------- similarity
+// 128 x 128 output tile per 256-thread workgroup, K advanced 32 at a time.  Wave w owns the 64 x 64 sub-tile
+// (w >> 1, w & 1) as 2 x 2 accumulators of v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fmaf chain).  Operand tiles
+// travel global -> registers -> LDS; the registers are loaded one K-tile ahead of the MFMAs that consume the LDS image.
+// LDS rows are 36 floats (32 + 4 pad): the 16-byte fragment reads of 32 lanes, one row apart, then cover all banks.
+// Lane (r = lane & 31, h = lane >> 5) reads k = 8 kk + 4 h .. + 3 of its row for both operands and feeds element j to
+// MFMA step j, so one MFMA sums k = 8 kk + j and 8 kk + 4 + j: a fixed permutation of K, the same for every output.
+// Q [nq][Dp], G [ng][Dp] row-major, Dp a multiple of 32 with zero padding; out [nq][pitch].
+constexpr int RT_LD = RT_BK + 4;
+
+__global__ __launch_bounds__(256) void k_sim_f32(const float* __restrict__ Q, const float* __restrict__ G,
+                                                 float* __restrict__ out, int nq, int ng, int Dp, int64_t pitch,
+                                                 int mtiles) {
+  __shared__ __attribute__((aligned(16))) float sA[RT_BM * RT_LD];
+  __shared__ __attribute__((aligned(16))) float sB[RT_BN * RT_LD];
+  // query tiles fastest: the workgroups that share a gallery tile run together, so the gallery comes from HBM once per block
+  const int m0 = (int)(blockIdx.x % mtiles) * RT_BM, n0 = (int)(blockIdx.x / mtiles) * RT_BN;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
+
+  // thread t stages float4 (t & 7) of rows (t >> 3) + 32 i, i = 0..3, of both tiles (named registers: an array indexed inside
+  // the K loop's `if` would live in scratch memory).  Rows past the end repeat the last one; they are never stored.
+  const int srow = tid >> 3, c4 = tid & 7, lo = srow * RT_LD + c4 * 4;
+#define RT_ROWPTR(M, base, i, n) ((const float4*)((M) + (int64_t)min((base) + srow + 32 * (i), (n)-1) * Dp) + c4)
+  const float4 *ga0 = RT_ROWPTR(Q, m0, 0, nq), *ga1 = RT_ROWPTR(Q, m0, 1, nq), *ga2 = RT_ROWPTR(Q, m0, 2, nq),
+               *ga3 = RT_ROWPTR(Q, m0, 3, nq);
+  const float4 *gb0 = RT_ROWPTR(G, n0, 0, ng), *gb1 = RT_ROWPTR(G, n0, 1, ng), *gb2 = RT_ROWPTR(G, n0, 2, ng),
+               *gb3 = RT_ROWPTR(G, n0, 3, ng);
+#undef RT_ROWPTR
+  float4 ra0 = ga0[0], ra1 = ga1[0], ra2 = ga2[0], ra3 = ga3[0];
+  float4 rb0 = gb0[0], rb1 = gb1[0], rb2 = gb2[0], rb3 = gb3[0];
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+
+  const int kt_n = Dp / RT_BK;
+  for (int kt = 0; kt < kt_n; ++kt) {
+    __syncthreads();                                   // the previous tile's fragment reads are done
+    *(float4*)&sA[lo] = ra0; *(float4*)&sA[lo + 32 * RT_LD] = ra1; *(float4*)&sA[lo + 64 * RT_LD] = ra2; *(float4*)&sA[lo + 96 * RT_LD] = ra3;
+    *(float4*)&sB[lo] = rb0; *(float4*)&sB[lo + 32 * RT_LD] = rb1; *(float4*)&sB[lo + 64 * RT_LD] = rb2; *(float4*)&sB[lo + 96 * RT_LD] = rb3;
+    __syncthreads();
+    if (kt + 1 < kt_n) {
+      const int o = (kt + 1) * (RT_BK / 4);
+      ra0 = ga0[o]; ra1 = ga1[o]; ra2 = ga2[o]; ra3 = ga3[o];
+      rb0 = gb0[o]; rb1 = gb1[o]; rb2 = gb2[o]; rb3 = gb3[o];
+    }
+#pragma unroll
+    for (int kk = 0; kk < RT_BK / 8; ++kk) {
+      float4 fa[2], fb[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        fa[t] = *(const float4*)&sA[(wm * 64 + t * 32 + r) * RT_LD + kk * 8 + h * 4];
+        fb[t] = *(const float4*)&sB[(wn * 64 + t * 32 + r) * RT_LD + kk * 8 + h * 4];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float a0 = j == 0 ? fa[0].x : j == 1 ? fa[0].y : j == 2 ? fa[0].z : fa[0].w;
+        const float a1 = j == 0 ? fa[1].x : j == 1 ? fa[1].y : j == 2 ? fa[1].z : fa[1].w;
+        const float b0 = j == 0 ? fb[0].x : j == 1 ? fb[0].y : j == 2 ? fb[0].z : fb[0].w;
+        const float b1 = j == 0 ? fb[1].x : j == 1 ? fb[1].y : j == 2 ? fb[1].z : fb[1].w;
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+      }
+    }
+  }
+  // C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int g = n0 + wn * 64 + b * 32 + r;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int q = m0 + wm * 64 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (q < nq && g < ng) out[(int64_t)q * pitch + g] = -2.0f * acc[a][b][e] + 0.0f;      // :142-144; -0 -> +0
+      }
+    }
+}
+
+void launch_sim_f32(const float* Q, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s) {
+  const int mtiles = (nq + RT_BM - 1) / RT_BM, ntiles = (ng + RT_BN - 1) / RT_BN;
+  hipLaunchKernelGGL(k_sim_f32, dim3((unsigned)(mtiles * ntiles)), dim3(256), 0, s, Q, G, out, nq, ng, Dp, pitch, mtiles);
+}
+
+// ---------------------------------------------------------------------------------------------- keys
+__device__ inline uint64_t rt_key(float d, uint32_t g) {
+  uint32_t u = __float_as_uint(d);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)u << 32) | g;
+}
+__device__ inline float rt_key_dist(uint64_t key) {
+  uint32_t u = (uint32_t)(key >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  return __uint_as_float(u);
+}
+constexpr uint64_t RT_NOKEY = ~0ull;
+
+// ---------------------------------------------------------------------------------------------- top-k
+// One wave keeps the k smallest keys it has seen, sorted, ONE PER LANE (lanes >= k hold RT_NOKEY), and offers every new key
+// against the k-th.  After the first few thousand elements almost nothing passes, so the scan runs at the rate of its loads.
+__device__ inline void rt_insert(uint64_t x, uint64_t& mine, int lane, int k) {
+  const int pos = __popcll(__ballot(mine < x));             // sorted: the lanes below x are lanes 0 .. pos-1
+  const uint64_t up = __shfl_up(mine, 1);
+  if (lane == pos) mine = x; else if (lane > pos) mine = up;
+  if (lane >= k) mine = RT_NOKEY;
+}
+// wave-uniform call; `key` differs per lane, `cand` says whether this lane offers it
+__device__ inline void rt_offer(uint64_t key, bool cand, uint64_t& mine, uint64_t& kth, int lane, int k) {
+  uint64_t m = __ballot(cand && key < kth);
+  while (m) {
+    const int src = __ffsll((long long)m) - 1;
+    m &= m - 1;
+    rt_insert(__shfl(key, src), mine, lane, k);
+  }
+  kth = __shfl(mine, k - 1);
+}
+
+// grid (S, rows): workgroup (s, row) scans gallery items [s seg, (s+1) seg) of the row, part[row][s][k] = its k smallest keys
+__global__ __launch_bounds__(256) void k_topk_part(const float* __restrict__ dist, int64_t pitch, int ng, int k, int seg,
+                                                   uint64_t* __restrict__ part) {
+  __shared__ uint64_t sl[4][32];
+  const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int begin = s * seg, end = min(ng, begin + seg);
+  const float* d = dist + (int64_t)row * pitch;
+  uint64_t mine = RT_NOKEY, kth = RT_NOKEY;
+  for (int base = begin; base < end; base += 1024) {               // seg is a multiple of 1024, pitch of 4
+    const int i = base + tid * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < end) v = *(const float4*)(d + i);                      // i + 3 < pitch: the row's pad may be read, never ranked
+    rt_offer(rt_key(v.x, (uint32_t)i), i < end, mine, kth, lane, k);
+    rt_offer(rt_key(v.y, (uint32_t)i + 1), i + 1 < end, mine, kth, lane, k);
+    rt_offer(rt_key(v.z, (uint32_t)i + 2), i + 2 < end, mine, kth, lane, k);
+    rt_offer(rt_key(v.w, (uint32_t)i + 3), i + 3 < end, mine, kth, lane, k);
+  }
+  if (lane < 32) sl[wave][lane] = mine;
+  __syncthreads();
+  if (wave == 0) {
+    for (int w = 1; w < 4; ++w)
+      for (int j = 0; j < k; ++j) rt_insert(sl[w][j], mine, lane, k);
+    if (lane < k) part[((int64_t)row * gridDim.x + s) * k + lane] = mine;
+  }
+}
+// one wave per row: the k smallest of the row's S partial lists
+__global__ __launch_bounds__(64) void k_topk_merge(const uint64_t* __restrict__ part, int S, int k, int32_t* __restrict__ idx,
+                                                   float* __restrict__ dst) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const uint64_t* p = part + (int64_t)row * S * k;
+  uint64_t mine = RT_NOKEY, kth = RT_NOKEY;
+  for (int base = 0; base < S * k; base += 64) {
+    const int i = base + lane;
+    const uint64_t key = i < S * k ? p[i] : RT_NOKEY;
+    rt_offer(key, key != RT_NOKEY, mine, kth, lane, k);
+  }
+  if (lane < k) {
+    idx[(int64_t)row * k + lane] = mine == RT_NOKEY ? -1 : (int32_t)(uint32_t)mine;
+    dst[(int64_t)row * k + lane] = mine == RT_NOKEY ? 0.f : rt_key_dist(mine);
+  }
+}
+void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, uint64_t* part, int32_t* idx,
+                 float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_topk_part, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, part);
+  hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(64), 0, s, part, S, k, idx, dst);
+}
+
+// ---------------------------------------------------------------------------------------------- rank statistics
+// The positives of query `row` are pos_idx[pstart[row] .. + pcount[row]) (gallery indices of the query's id).  A pass takes
+// RT_CHUNK of them: their keys go to LDS, sorted.  Returns how many this pass holds (0: nothing to do); *npad = the power of
+// two the sorted array was padded to with RT_NOKEY.
+__device__ inline int rt_load_sorted(uint64_t* sk, const float* d, const int32_t* pos_idx, int pstart, int pcount, int pass,
+                                     int* npad_out) {
+  const int off = pass * RT_CHUNK;
+  if (off >= pcount) return 0;
+  const int n = min(RT_CHUNK, pcount - off);
+  int npad = 1;
+  while (npad < n) npad <<= 1;
+  for (int j = threadIdx.x; j < npad; j += 256) {
+    uint64_t key = RT_NOKEY;
+    if (j < n) { const int g = pos_idx[pstart + off + j]; key = rt_key(d[g], (uint32_t)g); }
+    sk[j] = key;
+  }
+  __syncthreads();
+  for (int k2 = 2; k2 <= npad; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < npad; i += 256) {
+        const int x = i ^ j;
+        if (x > i) {
+          const uint64_t a = sk[i], b = sk[x];
+          if ((a > b) == ((i & k2) == 0)) { sk[i] = b; sk[x] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  *npad_out = npad;
+  return n;
+}
+
+// grid (S, rows).  Every gallery key of the segment at or below the pass's largest positive key is counted into the bin of
+// its slot among the sorted positives (slot = number of positive keys below it).  bins[row][0][slot]: all items;
+// bins[row][1][slot]: items that are themselves positives of the query -- needed only when the positives span several
+// passes (then a positive's ordinal among ALL positives is not its index in this pass's sorted chunk).
+__global__ __launch_bounds__(256) void k_rank_count(const float* __restrict__ dist, int64_t pitch, int ng, int seg,
+                                                    const int32_t* __restrict__ pos_idx, const int32_t* __restrict__ pstart,
+                                                    const int32_t* __restrict__ pcount, const int32_t* __restrict__ q_ids,
+                                                    const int32_t* __restrict__ ref_ids, int pass, uint32_t* __restrict__ bins) {
+  __shared__ uint64_t sk[RT_CHUNK];
+  __shared__ uint32_t sb[2][RT_CHUNK];
+  const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  const float* d = dist + (int64_t)row * pitch;
+  const int P = pcount[row];
+  int npad = 0;
+  const int n = rt_load_sorted(sk, d, pos_idx, pstart[row], P, pass, &npad);        // uniform over the workgroup
+  if (n == 0) return;
+  for (int j = tid; j < n; j += 256) { sb[0][j] = 0; sb[1][j] = 0; }
+  __syncthreads();
+  const bool multi = P > RT_CHUNK;
+  const int32_t qid = q_ids[row];
+  const uint64_t last = sk[n - 1];
+  const int begin = s * seg, end = min(ng, begin + seg);
+  for (int base = begin; base < end; base += 1024) {
+    const int i = base + tid * 4;
+    if (i >= end) continue;
+    const float4 v = *(const float4*)(d + i);
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t key = rt_key(e[u], (uint32_t)(i + u));
+      if (i + u >= end || key > last) continue;
+      int slot = 0;
+      for (int step = npad >> 1; step > 0; step >>= 1)
+        if (sk[slot + step - 1] < key) slot += step;                // key <= last, so the answer is at most n - 1 < npad
+      atomicAdd(&sb[0][slot], 1u);
+      if (multi && ref_ids[i + u] == qid) atomicAdd(&sb[1][slot], 1u);
+    }
+  }
+  __syncthreads();
+  uint32_t* b = bins + (int64_t)row * 2 * RT_CHUNK;
+  for (int j = tid; j < n; j += 256) {
+    if (sb[0][j]) atomicAdd(&b[j], sb[0][j]);
+    if (sb[1][j]) atomicAdd(&b[RT_CHUNK + j], sb[1][j]);
+  }
+}
+
+// grid (rows).  The inclusive prefix sum of the bins over the sorted positives IS their full-order rank (the bin of slot j
+// holds the keys in (p_{j-1}, p_j], p_j itself included).  ComputeApStats (:62-118) from the ranks, accumulated over passes.
+__global__ __launch_bounds__(256) void k_rank_final(const float* __restrict__ dist, int64_t pitch,
+                                                    const int32_t* __restrict__ pos_idx, const int32_t* __restrict__ pstart,
+                                                    const int32_t* __restrict__ pcount, int pass,
+                                                    const uint32_t* __restrict__ bins, RankAcc* __restrict__ acc) {
+  __shared__ uint64_t sk[RT_CHUNK];
+  __shared__ uint32_t tr[256], tp[256];
+  __shared__ double rap[256];
+  __shared__ int rbest[256], r1[256], r5[256], r10[256];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int P = pcount[row];
+  int npad = 0;
+  const int n = rt_load_sorted(sk, dist + (int64_t)row * pitch, pos_idx, pstart[row], P, pass, &npad);
+  if (n == 0) return;
+  const bool multi = P > RT_CHUNK;
+  const uint32_t* b = bins + (int64_t)row * 2 * RT_CHUNK;
+  constexpr int PER = RT_CHUNK / 256;
+  const int j0 = tid * PER;
+  uint32_t cr[PER], cp[PER], sr = 0, sp = 0;
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int j = j0 + u;
+    cr[u] = j < n ? b[j] : 0; cp[u] = j < n ? b[RT_CHUNK + j] : 0;
+    sr += cr[u]; sp += cp[u];
+  }
+  tr[tid] = sr; tp[tid] = sp;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {                                 // inclusive scan of the thread totals
+    const uint32_t a = tid >= o ? tr[tid - o] : 0, c = tid >= o ? tp[tid - o] : 0;
+    __syncthreads();
+    tr[tid] += a; tp[tid] += c;
+    __syncthreads();
+  }
+  uint32_t rank = tr[tid] - sr, ord = tp[tid] - sp;
+  double ap = 0; int best = 10000, a1 = 0, a5 = 0, a10 = 0;          // :68-70
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int j = j0 + u;
+    rank += cr[u]; ord += cp[u];
+    if (j < n) {
+      const uint32_t ret = multi ? ord : (uint32_t)(j + 1);           // :90 (`ret` after the increment)
+      if ((int64_t)rank < best) best = (int)rank;                     // :77-79
+      a1 += rank <= 1; a5 += rank <= 5; a10 += rank <= 10;            // :81-89
+      ap += (double)ret / (double)rank;                               // :91
+    }
+  }
+  rap[tid] = ap; rbest[tid] = best; r1[tid] = a1; r5[tid] = a5; r10[tid] = a10;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      rap[tid] += rap[tid + o]; rbest[tid] = min(rbest[tid], rbest[tid + o]);
+      r1[tid] += r1[tid + o]; r5[tid] += r5[tid + o]; r10[tid] += r10[tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {                                                      // one workgroup per row and pass, passes in stream order
+    RankAcc a = acc[row];
+    a.ap_sum += rap[0]; a.best = min(a.best, rbest[0]); a.acc1 += r1[0]; a.acc5 += r5[0]; a.acc10 += r10[0];
+    acc[row] = a;
+  }
+}
+
+void launch_rank_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* pos_idx,
+                      const int32_t* pstart, const int32_t* pcount, const int32_t* q_ids, const int32_t* ref_ids, int pass,
+                      uint32_t* bins, RankAcc* acc, hipStream_t s) {
+  hipLaunchKernelGGL(k_rank_count, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, seg, pos_idx, pstart, pcount, q_ids,
+                     ref_ids, pass, bins);
+  hipLaunchKernelGGL(k_rank_final, dim3(rows), dim3(256), 0, s, dist, pitch, pos_idx, pstart, pcount, pass, bins, acc);
+}
+
+}  // namespace vv

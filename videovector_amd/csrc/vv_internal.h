@@ -485,6 +485,22 @@ void launch_patch_rows(uint16_t* table, const int32_t* desc, int64_t n_patch, in
                        int Fp, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Gallery retrieval (kernels_retrieval.hip): fp32 similarity of one query block into a scratch buffer, then row kernels.
+// ---------------------------------------------------------------------------------------------
+constexpr int RT_BM = 128, RT_BN = 128, RT_BK = 32;   // similarity tile; operand rows are padded to a multiple of RT_BK floats
+constexpr int RT_CHUNK = 2048;                        // positives of one query ranked per pass (their sorted keys: 16 KiB of LDS)
+constexpr int RT_MAX_K = 32;
+struct RankAcc { double ap_sum; int32_t best, acc1, acc5, acc10; };   // ComputeApStats' running values of one query
+void launch_sim_f32(const float* Q, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s);
+// seg: gallery items per workgroup (a multiple of 1024), S = ceil(ng / seg); part: uint64 [rows][S][k]
+void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, uint64_t* part, int32_t* idx,
+                 float* dst, hipStream_t s);
+// bins: uint32 [rows][2][RT_CHUNK], zero on entry
+void launch_rank_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* pos_idx,
+                      const int32_t* pstart, const int32_t* pcount, const int32_t* q_ids, const int32_t* ref_ids, int pass,
+                      uint32_t* bins, RankAcc* acc, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // 16-bit operand types
 // ---------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));

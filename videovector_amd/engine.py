@@ -44,6 +44,11 @@ class _BoxProbe(C.Structure):
                 ("copy_bytes", C.c_int64)]
 
 
+class _RankStats(C.Structure):
+    _fields_ = [("median_rank", C.c_float), ("recall_1", C.c_float), ("recall_5", C.c_float), ("recall_10", C.c_float),
+                ("mean_ap", C.c_float)]
+
+
 def load_library():
     """Load libvideovec.so; raises (never falls back) when the HIP library is not built."""
     global _lib
@@ -104,6 +109,12 @@ def load_library():
         "vv_embed": [vp, vp, i64, C.c_int, C.c_int, vp],
         "vv_embed_mean": [vp, vp, i64, i32, vp, C.c_int, C.c_int, vp],
         "vv_retrieval_stats": [vp, vp, i32, i32, vp, vp, vp, i32, C.c_int, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)],
+        "vv_gallery_create": [vp, vp, i64, i32, vp, C.POINTER(vp)],
+        "vv_gallery_from_table": [vp, vp, i64, i32, vp, C.c_int, C.c_int, vp, C.POINTER(vp)],
+        "vv_gallery_destroy": [vp, vp],
+        "vv_gallery_topk": [vp, vp, vp, i32, i32, vp, vp],
+        "vv_gallery_rank_stats": [vp, vp, vp, i32, vp, C.POINTER(_RankStats), vp, vp, vp, vp],
+        "vv_gallery_get": [vp, C.c_char_p, C.POINTER(C.c_double)],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
@@ -119,6 +130,76 @@ def load_library():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class Gallery:
+    """A reference set held on the device by an Engine (RetrievalRankStatsFixedRefLayer's bottom[2] / bottom[3])."""
+
+    def __init__(self, eng, handle):
+        self.eng, self.h = eng, handle
+
+    def get(self, name):
+        v = C.c_double()
+        self.eng._chk(self.eng.L.vv_gallery_get(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    @property
+    def n_ref(self):
+        return int(self.get("n_ref"))
+
+    @property
+    def dim(self):
+        return int(self.get("dim"))
+
+    @property
+    def scratch_bytes(self):
+        return int(self.get("scratch_bytes"))
+
+    def _queries(self, q):
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise VVError("queries must be [n_q][%d]" % self.dim)
+        return q
+
+    def topk(self, q, k):
+        """(idx int32 [n_q][k], dist fp32 [n_q][k]): the k nearest reference items, ascending (distance, index)."""
+        q = self._queries(q)
+        idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
+        dist = np.empty(idx.shape, np.float32)
+        self.eng._chk(self.eng.L.vv_gallery_topk(self.eng.h, self.h, _ptr(q), q.shape[0], int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def rank_stats(self, q, q_ids, per_query=False):
+        """dict(median_rank, recall_1, recall_5, recall_10, mean_ap); with per_query also best_rank [n_q], ap [n_q],
+        top5_idx / top5_dist [n_q][5]."""
+        q = self._queries(q)
+        qid = np.ascontiguousarray(q_ids, dtype=np.int32)
+        if qid.shape != (q.shape[0],):
+            raise VVError("rank_stats: q_ids must be [n_q]")
+        st = _RankStats()
+        n = q.shape[0]
+        br = np.empty(n, np.int32) if per_query else None
+        ap = np.empty(n, np.float32) if per_query else None
+        t5i = np.empty((n, 5), np.int32) if per_query else None
+        t5d = np.empty((n, 5), np.float32) if per_query else None
+        self.eng._chk(self.eng.L.vv_gallery_rank_stats(self.eng.h, self.h, _ptr(q), n, _ptr(qid), C.byref(st), _ptr(br), _ptr(ap),
+                                                       _ptr(t5i), _ptr(t5d)))
+        out = {f: getattr(st, f) for f, _ in _RankStats._fields_}
+        if per_query:
+            out.update(best_rank=br, ap=ap, top5_idx=t5i, top5_dist=t5d)
+        return out
+
+    def close(self):
+        if self.h is not None:
+            h, self.h = self.h, None
+            if self.eng.h:                      # (an engine closed first took its device with it)
+                self.eng._chk(self.eng.L.vv_gallery_destroy(self.eng.h, h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class StepConfig:
@@ -369,6 +450,33 @@ class Engine:
         self._chk(self.L.vv_retrieval_stats(self.h, _ptr(feat), feat.shape[0], feat.shape[1], _ptr(vid), _ptr(mi),
                                             _ptr(mc), len(mi), int(exclude_same_video), *[C.byref(x) for x in o]))
         return tuple(x.value for x in o)
+
+    def gallery(self, feat, ids=None):
+        """A fixed reference set on the device (vv_gallery_create): feat fp32 [n_ref][dim], ids [n_ref] or None (top-k only)."""
+        feat = np.ascontiguousarray(feat, dtype=np.float32)
+        if feat.ndim != 2:
+            raise VVError("gallery: feat must be [n_ref][dim]")
+        rid = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+        if rid is not None and rid.shape != (feat.shape[0],):
+            raise VVError("gallery: ids must be [n_ref]")
+        h = C.c_void_p()
+        self._chk(self.L.vv_gallery_create(self.h, _ptr(feat), feat.shape[0], feat.shape[1], _ptr(rid), C.byref(h)))
+        return Gallery(self, h)
+
+    def gallery_from_table(self, rows, ids=None, coeff=None, relu=True, l2norm=True):
+        """The same from table rows, embedded as embed_mean does ([n][k] rows; [n] rows and no coeff: as embed); the
+        embeddings never leave the device."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim == 1:
+            r = r.reshape(-1, 1)
+        n, k = r.shape
+        cf = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.float32)
+        rid = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+        if rid is not None and rid.shape != (n,):
+            raise VVError("gallery_from_table: ids must be [n]")
+        h = C.c_void_p()
+        self._chk(self.L.vv_gallery_from_table(self.h, _ptr(r), n, k, _ptr(cf), int(relu), int(l2norm), _ptr(rid), C.byref(h)))
+        return Gallery(self, h)
 
     # ---- profiling
     def profile_enable(self, on=True):
