@@ -303,7 +303,9 @@ class VideoShotWindowTestDataLayer : public Layer<Dtype> {
   int batch_size_ = 0, positive_size_ = 0, negative_size_ = 0;
   size_t cursor_ = 0;
 };
-// RETRIEVAL_STATS (retrieval_stats_layer.cpp:19-90): tops = mean AP, hit@1, hit@5
+// RETRIEVAL_STATS (retrieval_stats_layer.cpp:19-90): tops = mean AP, hit@1, hit@5.  A layer that sets neither
+// video_level_retrieval nor stats_output_file calls vv_retrieval_stats (Gram matrix on the device, ranking on the host); one that
+// sets either runs on a device gallery (vv_gallery_class_stats: nothing sorted, no n x n matrix anywhere).
 template <typename Dtype>
 class RetrievalStatsLayer : public Layer<Dtype> {
   VV_LAYER_BOILER(RetrievalStatsLayer, "RETRIEVAL_STATS")
@@ -314,8 +316,15 @@ class RetrievalStatsLayer : public Layer<Dtype> {
   const vector<int32_t>& map_ids() const { return map_ids_; }
   const vector<int32_t>& map_cls() const { return map_cls_; }
   bool exclude_same_video_shots() const { return this->layer_param_.get_msg("retrieval_stats_param").get_bool("exclude_same_video_shots"); }
+  bool gallery_path() const { return gallery_path_; }
+  void set_gallery_path(bool on) { gallery_path_ = on; }
+  // Forward on the gallery path (both executors call it): feat host [n][dim], video_ids [n]; tops = mean AP, hit@1, hit@5
+  void ForwardGallery(const float* feat, int n, int dim, const int32_t* video_ids, float tops[3]);
  private:
   vector<int32_t> map_ids_, map_cls_;
+  string stats_output_file_;
+  bool video_level_ = false, gallery_path_ = false;
+  int max_num_videos_ = 0;
 };
 
 // RETRIEVAL_RANK_STATS_FIXED_REF (include/caffe/loss_layers.hpp:64-125, retrieval_rank_stats_fixed_ref_layer.cpp):

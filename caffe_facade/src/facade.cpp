@@ -610,8 +610,14 @@ template class VideoShotWindowTestDataLayer<float>;
 template <typename Dtype>
 void RetrievalStatsLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>&, vector<Blob<Dtype>*>*) {
   const pl::Message& p = this->layer_param_.get_msg("retrieval_stats_param");
-  CHECK(!p.get_bool("video_level_retrieval")) << "video_level_retrieval is not built";
-  CHECK(p.get_str("stats_output_file").empty()) << "stats_output_file is not built";
+  video_level_ = p.get_bool("video_level_retrieval");
+  stats_output_file_ = p.get_str("stats_output_file");
+  if (video_level_) {
+    max_num_videos_ = (int)p.get_int("max_num_videos");
+    CHECK_GE(max_num_videos_, 1) << "To do video level retrieval ... need min 1 video";       // :53
+  }
+  if (video_level_ || !stats_output_file_.empty()) gallery_path_ = true;
+  map_ids_.clear(); map_cls_.clear();
   std::ifstream f(p.get_str("id_to_class_file"));
   string line;
   while (std::getline(f, line)) {                                  // retrieval_stats_layer.cpp:31-43

@@ -4,7 +4,9 @@
 //
 // These run when a graph is executed layer by layer (Net::ForwardFromTo / BackwardFromTo).  The recognised videovec
 // graphs run as one fused plan instead and never come through here.
+#include <algorithm>
 #include <fstream>
+#include <unordered_map>
 
 #include "caffe/layer.hpp"
 
@@ -336,11 +338,67 @@ void RetrievalStatsLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom,
   const int n = bottom[0]->num();
   vector<int32_t> vids((size_t)n);
   for (int i = 0; i < n; ++i) vids[i] = (int32_t)bottom[1]->cpu_data()[i];
+  if (gallery_path_) {
+    float v[3];
+    ForwardGallery(bottom[0]->cpu_data(), n, Inner(bottom[0]), vids.data(), v);
+    for (int t = 0; t < 3; ++t) (*top)[t]->mutable_cpu_data()[0] = v[t];
+    return;
+  }
   float m = 0, h1 = 0, h5 = 0;
   VV_CHECK(vv_retrieval_stats(X(), bottom[0]->cpu_data(), n, Inner(bottom[0]), vids.data(), map_ids_.data(), map_cls_.data(),
                               (int)map_ids_.size(), exclude_same_video_shots() ? 1 : 0, &m, &h1, &h5));
   const float v[3] = {m, h1, h5};
   for (int t = 0; t < 3; ++t) (*top)[t]->mutable_cpu_data()[0] = v[t];
+}
+// video_level_retrieval (:165-205) and stats_output_file (:149-154, :306-338) on a device gallery.  The pooled items are in
+// ascending video id (the reference: boost::unordered_map order).
+template <typename Dtype>
+void RetrievalStatsLayer<Dtype>::ForwardGallery(const float* feat, int n, int dim, const int32_t* video_ids, float tops[3]) {
+  vv_gallery *shots = nullptr, *videos = nullptr;
+  VV_CHECK(vv_gallery_create(X(), feat, n, dim, video_ids, &shots));
+  vector<int32_t> item_ids(video_ids, video_ids + n);
+  if (video_level_) {
+    double n_ids = 0;
+    VV_CHECK(vv_gallery_get(shots, "n_ids", &n_ids));
+    const int num_shots_per_video_size = (int)n_ids;
+    CHECK_EQ(num_shots_per_video_size, max_num_videos_);                                              // :187
+    VV_CHECK(vv_gallery_pool_by_id(X(), shots, &videos));
+    std::sort(item_ids.begin(), item_ids.end());
+    item_ids.erase(std::unique(item_ids.begin(), item_ids.end()), item_ids.end());
+  }
+  const size_t items = item_ids.size();
+  const bool file = !stats_output_file_.empty();
+  vector<float> ap, a1, a5; vector<int32_t> t5;
+  if (file) { ap.resize(items); a1.resize(items); a5.resize(items); }
+  if (file && !video_level_) t5.resize(items * 5);
+  vv_class_stats st;
+  VV_CHECK(vv_gallery_class_stats(X(), videos ? videos : shots, map_ids_.data(), map_cls_.data(), (int)map_ids_.size(),
+                                  exclude_same_video_shots() ? 1 : 0, &st, file ? ap.data() : nullptr, file ? a1.data() : nullptr,
+                                  file ? a5.data() : nullptr, t5.empty() ? nullptr : t5.data()));
+  if (videos) VV_CHECK(vv_gallery_destroy(X(), videos));
+  VV_CHECK(vv_gallery_destroy(X(), shots));
+  tops[0] = st.mean_ap; tops[1] = st.hit_at_1; tops[2] = st.hit_at_5;
+  if (!file) return;
+  std::unordered_map<int, int> cls;
+  for (size_t i = 0; i < map_ids_.size(); ++i) cls[map_ids_[i]] = map_cls_[i];
+  auto cls_of = [&](int id) { auto it = cls.find(id); return it == cls.end() ? 0 : it->second; };      // operator[], :110
+  std::ofstream out(stats_output_file_);                                                               // :149-154
+  CHECK(out.good()) << "Failed to open " << stats_output_file_;
+  out << "#video_id,class_id,ap,acc@1,acc@5"
+      << ",ret_id_1,ret_id_2,ret_id_3,ret_id_4,ret_id_5"
+      << ",class_id_1,class_id_2,class_id_3,class_id_4,class_id_5" << std::endl;
+  for (size_t i = 0; i < items; ++i) {                                                                 // :306-338
+    const int label = cls_of(item_ids[i]);
+    if (label < 0) continue;
+    out << item_ids[i] << "," << label << "," << (double)ap[i] << "," << (double)a1[i] << "," << (double)a5[i];
+    if (!video_level_) {
+      // fewer than five items of other videos: -1, class -1 (the reference prints the previous query's entries, top_5_ids
+      // is never cleared)
+      for (int j = 0; j < 5; ++j) out << "," << t5[i * 5 + j];
+      for (int j = 0; j < 5; ++j) out << "," << (t5[i * 5 + j] < 0 ? -1 : cls_of(item_ids[t5[i * 5 + j]]));
+    }
+    out << std::endl;
+  }
 }
 template <typename Dtype>
 void RetrievalStatsLayer<Dtype>::Backward_gpu(const vector<Blob<Dtype>*>&, const vector<bool>&, vector<Blob<Dtype>*>*) {}

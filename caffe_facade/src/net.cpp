@@ -665,10 +665,10 @@ Dtype Net<Dtype>::ForwardTest() {
   }
   if (plan_.stats_layer >= 0) {
     auto* rs = static_cast<RetrievalStatsLayer<Dtype>*>(layers_[plan_.stats_layer].get());
-    float m = 0, h1 = 0, h5 = 0;
-    VV_CHECK(vv_retrieval_stats(ctx_, feat, plan_.B, plan_.D, label_.data(), rs->map_ids().data(), rs->map_cls().data(),
-                                (int)rs->map_ids().size(), rs->exclude_same_video_shots() ? 1 : 0, &m, &h1, &h5));
-    const float v[3] = {m, h1, h5};
+    float v[3] = {0, 0, 0};
+    if (rs->gallery_path()) rs->ForwardGallery(feat, plan_.B, plan_.D, label_.data(), v);
+    else VV_CHECK(vv_retrieval_stats(ctx_, feat, plan_.B, plan_.D, label_.data(), rs->map_ids().data(), rs->map_cls().data(),
+                                     (int)rs->map_ids().size(), rs->exclude_same_video_shots() ? 1 : 0, &v[0], &v[1], &v[2]));
     for (int t = 0; t < 3; ++t) blobs_[blob_names_index_[plan_.stat_blobs[t]]]->mutable_cpu_data()[0] = v[t];
   }
   ++iter_;

@@ -283,7 +283,8 @@ int vv_embed_mean(vv_ctx* ctx, const int32_t* rows, int64_t n, int32_t k, const 
  * the id_to_class_file as two parallel arrays (ids absent from it read as class 0, as the
  * reference's map operator[] does).  Equal distances are ordered by ascending index (std::sort
  * leaves them unspecified; this order reproduces test_retrieval_stats_layer.cpp:82-84).
- * video_level_retrieval and stats_output_file are not built. */
+ * video_level_retrieval and stats_output_file are not built HERE: vv_gallery_pool_by_id and vv_gallery_class_stats below carry
+ * them, for any n and without the n x n download. */
 int vv_retrieval_stats(vv_ctx* ctx, const float* feat, int32_t n, int32_t dim, const int32_t* video_ids,
                        const int32_t* map_ids, const int32_t* map_cls, int32_t n_map,
                        int exclude_same_video_shots, float* mean_ap, float* hit_at_1, float* hit_at_5);
@@ -321,8 +322,34 @@ int vv_gallery_rank_stats(vv_ctx* ctx, vv_gallery* gallery, const float* q, int3
  * loss_layers.hpp:117-124): "n_ref", "dim", "scratch_bytes" (device scratch currently held for query blocks),
  * "scratch_limit_bytes", "query_block" (queries per block), "positive_chunk" (positives of one query ranked per pass; a query
  * with more takes several passes), "last_passes", "last_sim_ms" (device time of the similarity kernels of the last call),
- * "last_device_ms" (device time of the whole last call, uploads of the query blocks included).  Unknown name: VV_ERR_ARG. */
+ * "last_device_ms" (device time of the whole last call, uploads of the query blocks included), "n_ids" (distinct ids; 0 without
+ * ids), "feat_device" / "row_floats" (the device address of the gallery's fp32 rows, for vv_dev_download, and the floats between
+ * two rows: dim rounded up to a multiple of 32, the rest zero).  Unknown name: VV_ERR_ARG. */
 int vv_gallery_get(const vv_gallery* gallery, const char* name, double* value);
+
+/* ---- class-level leave-one-out statistics on a gallery: RetrievalStatsLayer (src/caffe/layers/retrieval_stats_layer.cpp).
+ * vv_gallery_pool_by_id: video_level_retrieval (:165-198).  A new gallery with one item per distinct id of `gallery`, its row the
+ * sum over the id's items, in ascending item index, of (1 / count) x_i in fp32 (the reference's weight matrix, :193, :197-198),
+ * its id that id.  Items are in ASCENDING ID (the reference's order is boost::unordered_map's, unspecified).  Needs a gallery
+ * created with ids; computed on the device from the gallery's own rows.  "n_ids" of vv_gallery_get: the number of distinct ids.
+ *
+ * vv_gallery_class_stats: Forward_cpu (:213-304, :351-353) with ComputeStats (:104-141).  Every item i of the gallery is a query
+ * against all the others; its class is the map's entry for its id, 0 for an id the map does not hold (operator[], :110, :117;
+ * map_ids / map_cls: the id_to_class_file as two parallel host arrays, n_map >= 1, :48; an id listed twice reads as its later
+ * entry).  Distance -2 dot(x_i, x_j) in fp32 (:208-209), order ascending (d, j).  A query of negative class is skipped (:250-252)
+ * but stays an item others are ranked against.  Ranked set: every j != i (:113, :231-232), and with exclude_same_id every j of
+ * another id (:114-115); a positive is a ranked item of the query's class; val / ret of a positive are COUNTED, no row is sorted:
+ * ap = (sum ret / val) / positives, 0 without positives (:125, :131-133); acc1 = positives with val <= 1; acc5 = (positives with
+ * val <= 5) / 5 (:135).  out: the means over the scored queries (:351-353) and their number; no scored query: VV_ERR_ARG.
+ * Optional per-item outputs (NULL to skip): ap / acc1 / acc5 host [n_ref], NaN for a skipped query; top5_idx host [n_ref][5]: the
+ * five nearest items of OTHER ids, whatever exclude_same_id says (what stats_output_file lists, :310-316), -1 where fewer exist
+ * (the reference prints the previous query's entries there) and for a skipped query.  The query rows are read from the gallery's
+ * device features; device scratch stays within "scratch_limit_bytes"; two calls return bit-identical results.
+ * "last_passes", "last_sim_ms", "last_device_ms" of vv_gallery_get describe this call too. */
+typedef struct { float mean_ap, hit_at_1, hit_at_5; int32_t n_scored; } vv_class_stats;
+int vv_gallery_pool_by_id(vv_ctx* ctx, vv_gallery* gallery, vv_gallery** out);
+int vv_gallery_class_stats(vv_ctx* ctx, vv_gallery* gallery, const int32_t* map_ids, const int32_t* map_cls, int32_t n_map,
+                           int exclude_same_id, vv_class_stats* out, float* ap, float* acc1, float* acc5, int32_t* top5_idx);
 
 /* ---- per-layer operators.  The reference's operator interface is Layer<Dtype>::{Forward_gpu, Backward_gpu}
  * (include/caffe/layer.hpp:308-337); its sequential executor (Net::ForwardFromTo / BackwardFromTo, net.cpp:501-578) calls

@@ -8,6 +8,11 @@
   python tools/retrieval_bench.py --versus-within-batch --n 8192 --dim 512 [--reps 5]
       the parent's only retrieval path, vv_retrieval_stats (Gram kernel, download, one host sort per row), against
       vv_gallery_rank_stats with the same n rows as queries and as gallery; host wall time of both calls, alternating.
+  python tools/retrieval_bench.py --class-stats --n 8192 --dim 512 [--classes 15] [--videos 600] [--reps 10] [--no-within-batch]
+      class-level leave-one-out statistics (vv_gallery_class_stats) of n items: host wall time of gallery creation + class_stats
+      against vv_retrieval_stats on the same rows, alternating in one process (skipped with --no-within-batch: n^2 floats no
+      longer fit), and the device time of class_stats alone, its similarity share, passes and scratch bytes.  Input: make_input
+      of tests/class_stats_ref.py (noise 3.0 / 6.0, seed 11).
 
 Inputs are seeded: unit rows around `nid` random centres, ids = the centre's index (the generator of tests/gallery_ref.py, drawn in
 float32 blocks so that a million rows need no float64 copy)."""
@@ -53,9 +58,41 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--versus-within-batch", action="store_true")
     ap.add_argument("--n", type=int, default=8192)
+    ap.add_argument("--class-stats", action="store_true")
+    ap.add_argument("--classes", type=int, default=15)
+    ap.add_argument("--videos", type=int, default=600)
+    ap.add_argument("--no-within-batch", action="store_true")
     a = ap.parse_args()
     eng = vv.Engine(0, "f16")
-    if a.versus_within_batch:
+    if a.class_stats:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        from class_stats_ref import make_input
+        X, ids, id2class = make_input(a.n, a.dim, a.videos, a.classes, 3.0, 6.0, 11)
+        old, new, dev, sim = [], [], [], []
+        res = ref = None
+        for r in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            if not a.no_within_batch:
+                ref = eng.retrieval_stats(X, ids, id2class, exclude_same_video=True)
+            t1 = time.perf_counter()
+            g = eng.gallery(X, ids)
+            res = g.class_stats(id2class, exclude_same_video=True)
+            t2 = time.perf_counter()
+            if r >= a.warmup:
+                old.append((t1 - t0) * 1e3); new.append((t2 - t1) * 1e3)
+                dev.append(g.get("last_device_ms")); sim.append(g.get("last_sim_ms"))
+            passes, scratch, block = int(g.get("last_passes")), g.scratch_bytes, int(g.get("query_block"))
+            g.close()
+        flop = 2.0 * a.n * a.n * a.dim
+        out = dict(bench="class_stats", n=a.n, dim=a.dim, classes=a.classes, videos=a.videos, reps=a.reps, warmup=a.warmup,
+                   gallery_plus_class_stats_ms=stats(new), class_stats_device_ms=stats(dev), similarity_ms=stats(sim),
+                   similarity_tflops=flop / (stats(sim)["median"] * 1e-3) / 1e12, passes=passes, scratch_bytes=scratch,
+                   query_block=block, result={k: float(v) for k, v in res.items()},
+                   timer="host wall clock around the blocking calls; device events for *_device_ms / similarity_ms")
+        if not a.no_within_batch:
+            out.update(retrieval_stats_ms=stats(old), ratio_of_medians=stats(old)["median"] / stats(new)["median"],
+                       retrieval_stats_result=[float(v) for v in ref])
+    elif a.versus_within_batch:
         X, ids, _ = make(a.n, a.dim, max(a.n // 8, 1), a.noise, 7)
         id2class = {int(i): int(i) for i in np.unique(ids)}
         g = eng.gallery(X, ids)

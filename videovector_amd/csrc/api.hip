@@ -9,6 +9,7 @@
 #include <cstring>
 #include <ctime>
 #include <algorithm>
+#include <limits>
 #include <map>
 #include <unordered_map>
 #include <string>
@@ -1809,11 +1810,17 @@ struct vv_gallery {
   int32_t* ref_ids = nullptr;            // [n_ref] or NULL (a gallery for top-k only)
   int32_t* pos_idx = nullptr;            // gallery indices grouped by id (ascending id, ascending index inside one id)
   std::vector<int32_t> uid, ustart;      // host: the distinct ids, ascending, and where each one's group starts in pos_idx
+  std::vector<int32_t> h_ids;            // host: ref_ids
+  // class-level statistics: the lists of the id -> class map last given, kept until another map arrives
+  std::vector<int32_t> cs_map_ids, cs_map_cls;     // that map
+  std::vector<int32_t> h_cls, cvals, cstart;       // class of every item; the distinct classes, ascending; their groups in cpos
+  int32_t *cls = nullptr, *cpos = nullptr;         // device: class of every item; item indices grouped by class (ascending index inside)
   // scratch, grown on demand up to qb_max rows and kept between calls
   int qb_cap = 0;
   float *dist = nullptr, *qdev = nullptr, *out_dist = nullptr;
   uint64_t* part = nullptr; uint32_t* bins = nullptr; int32_t* out_idx = nullptr;
   int32_t *pstart = nullptr, *pcount = nullptr, *qids = nullptr; RankAcc* acc = nullptr;
+  uint64_t* skeys = nullptr; uint32_t* cbins = nullptr;      // class-level statistics only: allocated by its first call
   size_t scratch_bytes = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // call begin / end, similarity begin / end (of the block in flight)
   double last_sim_ms = 0, last_device_ms = 0; int last_passes = 0;
@@ -1821,20 +1828,27 @@ struct vv_gallery {
 
 static void gallery_free_scratch(vv_gallery* g) {
   dfree(g->dist); dfree(g->qdev); dfree(g->out_dist); dfree(g->part); dfree(g->bins); dfree(g->out_idx);
-  dfree(g->pstart); dfree(g->pcount); dfree(g->qids); dfree(g->acc);
+  dfree(g->pstart); dfree(g->pcount); dfree(g->qids); dfree(g->acc); dfree(g->skeys); dfree(g->cbins);
   g->dist = g->qdev = g->out_dist = nullptr; g->part = nullptr; g->bins = nullptr; g->out_idx = nullptr;
-  g->pstart = g->pcount = g->qids = nullptr; g->acc = nullptr;
+  g->pstart = g->pcount = g->qids = nullptr; g->acc = nullptr; g->skeys = nullptr; g->cbins = nullptr;
   g->qb_cap = 0; g->scratch_bytes = 0;
 }
 
-static int gallery_ensure_scratch(vv_gallery* g, int rows) {
-  if (rows <= g->qb_cap) return VV_OK;
+static_assert(sizeof(ClassAcc) == sizeof(RankAcc), "the two statistics share the per-query accumulator buffer");
+static constexpr size_t GALLERY_CLASS_ROW_BYTES = (size_t)RT_CHUNK * 8 + (size_t)3 * RT_CHUNK * 4;   // skeys + cbins of one row
+
+// cls: the call is vv_gallery_class_stats, which needs skeys / cbins as well
+static int gallery_ensure_scratch(vv_gallery* g, int rows, bool cls = false) {
+  if (rows <= g->qb_cap && (!cls || g->skeys)) return VV_OK;
   gallery_free_scratch(g);
   const size_t r = (size_t)rows;
   const size_t b_dist = r * g->pitch * 4, b_q = r * g->Dp * 4, b_part = r * g->S * RT_MAX_K * 8, b_bins = r * 2 * RT_CHUNK * 4,
                b_out = r * RT_MAX_K * 4, b_row = r * 4, b_acc = r * sizeof(RankAcc);
-  const size_t total = b_dist + b_q + b_part + b_bins + 2 * b_out + 3 * b_row + b_acc;
+  const size_t total = b_dist + b_q + b_part + b_bins + 2 * b_out + 3 * b_row + b_acc + (cls ? r * GALLERY_CLASS_ROW_BYTES : 0);
   if (total > GALLERY_SCRATCH_MAX) return fail(VV_ERR_STATE, "gallery scratch of %zu bytes exceeds the limit", total);
+  if (cls) {
+    HIPCHK(hipMalloc((void**)&g->skeys, r * RT_CHUNK * 8)); HIPCHK(hipMalloc((void**)&g->cbins, r * 3 * RT_CHUNK * 4));
+  }
   HIPCHK(hipMalloc((void**)&g->dist, b_dist)); HIPCHK(hipMalloc((void**)&g->qdev, b_q));
   HIPCHK(hipMalloc((void**)&g->part, b_part)); HIPCHK(hipMalloc((void**)&g->bins, b_bins));
   HIPCHK(hipMalloc((void**)&g->out_idx, b_out)); HIPCHK(hipMalloc((void**)&g->out_dist, b_out));
@@ -1865,6 +1879,7 @@ static int gallery_init(vv_ctx* c, vv_gallery* g, int64_t n_ref, int32_t dim, co
   for (int64_t i = 0; i < n_ref; ++i)
     if (i == 0 || ref_ids[order[i]] != ref_ids[order[i - 1]]) { g->uid.push_back(ref_ids[order[i]]); g->ustart.push_back((int32_t)i); }
   g->ustart.push_back((int32_t)n_ref);
+  g->h_ids.assign(ref_ids, ref_ids + n_ref);
   HIPCHK(hipMalloc((void**)&g->ref_ids, (size_t)n_ref * 4)); HIPCHK(hipMalloc((void**)&g->pos_idx, (size_t)n_ref * 4));
   HIPCHK(hipMemcpy(g->ref_ids, ref_ids, (size_t)n_ref * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(g->pos_idx, order.data(), (size_t)n_ref * 4, hipMemcpyHostToDevice));
@@ -1873,7 +1888,7 @@ static int gallery_init(vv_ctx* c, vv_gallery* g, int64_t n_ref, int32_t dim, co
 
 static void gallery_release(vv_gallery* g) {
   gallery_free_scratch(g);
-  dfree(g->feat); dfree(g->ref_ids); dfree(g->pos_idx);
+  dfree(g->feat); dfree(g->ref_ids); dfree(g->pos_idx); dfree(g->cls); dfree(g->cpos);
   for (int i = 0; i < 4; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
   delete g;
 }
@@ -1936,6 +1951,9 @@ int vv_gallery_get(const vv_gallery* g, const char* name, double* value) {
   if (!g || !name || !value) return fail(VV_ERR_ARG, "vv_gallery_get: NULL argument");
   const std::string n(name);
   if (n == "n_ref") *value = (double)g->n_ref;
+  else if (n == "n_ids") *value = (double)g->uid.size();
+  else if (n == "row_floats") *value = g->Dp;
+  else if (n == "feat_device") *value = (double)(uintptr_t)g->feat;      // (a device address: below 2^48, exact in a double)
   else if (n == "dim") *value = g->dim;
   else if (n == "scratch_bytes") *value = (double)g->scratch_bytes;
   else if (n == "scratch_limit_bytes") *value = (double)GALLERY_SCRATCH_MAX;
@@ -2068,6 +2086,137 @@ int vv_gallery_rank_stats(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q,
   out->median_rank = (float)(n_q % 2 == 0 ? (ranks[n_q / 2 - 1] + ranks[n_q / 2]) / 2.0 : (double)ranks[n_q / 2]);
   out->recall_1 = (float)(s1 / n_q); out->recall_5 = (float)(s5 / n_q); out->recall_10 = (float)(s10 / n_q);   // :226-230
   out->mean_ap = (float)(sap / n_q);
+  return gallery_call_end(c, g);
+}
+
+// One item per distinct id, ids ascending: the video-level features of RetrievalStatsLayer (retrieval_stats_layer.cpp:165-198;
+// the reference enumerates the videos in boost::unordered_map order, which is unspecified).
+int vv_gallery_pool_by_id(vv_ctx* c, vv_gallery* g, vv_gallery** out) {
+  if (!c || !g || !out) return fail(VV_ERR_ARG, "vv_gallery_pool_by_id: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_pool_by_id: the gallery belongs to another context");
+  if (!g->ref_ids) return fail(VV_ERR_ARG, "vv_gallery_pool_by_id: the gallery was created without ids");
+  VV_ENTER(c);
+  const int n_ids = (int)g->uid.size();
+  DevTmp<int32_t> dstart;
+  HIPCHK(dstart.alloc((size_t)n_ids + 1));
+  HIPCHK(hipMemcpyAsync(dstart, g->ustart.data(), ((size_t)n_ids + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  vv_gallery* p = new vv_gallery;
+  int rc = gallery_init(c, p, n_ids, g->dim, g->uid.data());
+  if (!rc) {
+    launch_pool_by_id(g->feat, g->Dp, g->pos_idx, dstart, n_ids, p->feat, c->stream);
+    const hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) rc = fail(VV_ERR_HIP, "vv_gallery_pool_by_id: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  if (rc) { gallery_release(p); return rc; }
+  *out = p;
+  return VV_OK;
+}
+
+// The class of every item and the per-class item lists for one id -> class map (an id absent from it: class 0, :110, :117; an id
+// listed twice: the later entry, as vv_retrieval_stats reads the same arrays).  Kept until a different map arrives.
+static int gallery_class_lists(vv_gallery* g, const int32_t* map_ids, const int32_t* map_cls, int32_t n_map) {
+  if (g->cls && (int32_t)g->cs_map_ids.size() == n_map && std::equal(map_ids, map_ids + n_map, g->cs_map_ids.begin()) &&
+      std::equal(map_cls, map_cls + n_map, g->cs_map_cls.begin()))
+    return VV_OK;
+  const int64_t n = g->n_ref;
+  std::unordered_map<int, int> m;
+  for (int i = 0; i < n_map; ++i) m[map_ids[i]] = map_cls[i];
+  std::vector<int32_t> ucls(g->uid.size());
+  for (size_t u = 0; u < g->uid.size(); ++u) { const auto it = m.find(g->uid[u]); ucls[u] = it == m.end() ? 0 : it->second; }
+  g->h_cls.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    g->h_cls[i] = ucls[std::lower_bound(g->uid.begin(), g->uid.end(), g->h_ids[i]) - g->uid.begin()];
+  std::vector<int32_t> order((size_t)n);
+  for (int64_t i = 0; i < n; ++i) order[i] = (int32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return g->h_cls[a] < g->h_cls[b]; });
+  g->cvals.clear(); g->cstart.clear();
+  for (int64_t i = 0; i < n; ++i)
+    if (i == 0 || g->h_cls[order[i]] != g->h_cls[order[i - 1]]) { g->cvals.push_back(g->h_cls[order[i]]); g->cstart.push_back((int32_t)i); }
+  g->cstart.push_back((int32_t)n);
+  g->cs_map_ids.clear();                                                   // (nothing valid until both uploads are queued)
+  if (!g->cls) { HIPCHK(hipMalloc((void**)&g->cls, (size_t)n * 4)); HIPCHK(hipMalloc((void**)&g->cpos, (size_t)n * 4)); }
+  HIPCHK(hipMemcpy(g->cls, g->h_cls.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g->cpos, order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  g->cs_map_ids.assign(map_ids, map_ids + n_map); g->cs_map_cls.assign(map_cls, map_cls + n_map);
+  return VV_OK;
+}
+
+// RetrievalStatsLayer::Forward_cpu (:213-304, :351-353) with ComputeStats (:104-141) over the gallery's own items: every item is a
+// query against all the others.  The counts come from kernels_retrieval.hip; the host divides and averages.
+int vv_gallery_class_stats(vv_ctx* c, vv_gallery* g, const int32_t* map_ids, const int32_t* map_cls, int32_t n_map,
+                           int exclude_same_id, vv_class_stats* out, float* ap, float* acc1, float* acc5, int32_t* top5_idx) {
+  if (!c || !g || !out || (n_map > 0 && (!map_ids || !map_cls))) return fail(VV_ERR_ARG, "vv_gallery_class_stats: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_class_stats: the gallery belongs to another context");
+  if (!g->ref_ids) return fail(VV_ERR_ARG, "vv_gallery_class_stats: the gallery was created without ids");
+  if (n_map < 1) return fail(VV_ERR_ARG, "need atleast one entry in id-to-class map!");              // :48
+  VV_ENTER(c);
+  int rc = gallery_class_lists(g, map_ids, map_cls, n_map);
+  if (rc) return rc;
+  const int n = (int)g->n_ref;
+  int n_scored = 0;
+  for (int i = 0; i < n; ++i) n_scored += g->h_cls[i] >= 0;
+  if (n_scored == 0) return fail(VV_ERR_ARG, "vv_gallery_class_stats: no item with a non-negative class");
+  // rows of a block: the gallery's own, fewer where the two class buffers would pass the scratch limit
+  const size_t row_bytes = (size_t)g->pitch * 4 + (size_t)g->Dp * 4 + (size_t)g->S * RT_MAX_K * 8 + 2 * RT_CHUNK * 4 + 2 * RT_MAX_K * 4 +
+                           3 * 4 + sizeof(RankAcc) + GALLERY_CLASS_ROW_BYTES;
+  const int block = (int)std::min<size_t>(std::min(n, g->qb_max), GALLERY_SCRATCH_MAX / row_bytes);
+  if (block < 1) return fail(VV_ERR_ARG, "vv_gallery_class_stats: %d items do not fit one query row into the scratch limit", n);
+  if ((rc = gallery_ensure_scratch(g, block, true))) return rc;
+  g->last_sim_ms = 0; g->last_device_ms = 0; g->last_passes = 0;
+  HIPCHK(hipEventRecord(g->ev[0], c->stream));
+  // counting segments: long ones, a workgroup's bins are flushed once per segment
+  const int cseg = std::max(g->seg, 65536), cS = (n + cseg - 1) / cseg;
+  ClassAcc* dacc = reinterpret_cast<ClassAcc*>(g->acc);
+  std::vector<int32_t> hstart, hcount, t5; std::vector<ClassAcc> hacc;
+  double s_ap = 0, s_1 = 0, s_5 = 0;                                                                   // :213
+  const float nanv = std::numeric_limits<float>::quiet_NaN();
+  for (int q0 = 0; q0 < n; q0 += g->qb_cap) {
+    const int rows = std::min(g->qb_cap, n - q0);
+    hstart.assign(rows, 0); hcount.assign(rows, 0); hacc.resize(rows);
+    int max_p = 0;
+    for (int i = 0; i < rows; ++i) {
+      const int32_t cl = g->h_cls[q0 + i];
+      if (cl < 0) continue;                                                                            // :250-252
+      const size_t u = std::lower_bound(g->cvals.begin(), g->cvals.end(), cl) - g->cvals.begin();
+      hstart[i] = g->cstart[u]; hcount[i] = g->cstart[u + 1] - g->cstart[u];
+      max_p = std::max(max_p, hcount[i]);
+    }
+    HIPCHK(hipMemcpyAsync(g->pstart, hstart.data(), (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g->pcount, hcount.data(), (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(dacc, 0, (size_t)rows * sizeof(ClassAcc), c->stream));
+    HIPCHK(hipEventRecord(g->ev[2], c->stream));                       // the query rows are the gallery's own device rows
+    launch_sim_f32(g->feat + (size_t)q0 * g->Dp, g->feat, g->dist, rows, n, g->Dp, g->pitch, c->stream);   // :208-209
+    HIPCHK(hipEventRecord(g->ev[3], c->stream));
+    const int passes = (max_p + RT_CHUNK - 1) / RT_CHUNK;
+    g->last_passes = std::max(g->last_passes, passes);
+    for (int pass = 0; pass < passes; ++pass) {
+      HIPCHK(hipMemsetAsync(g->cbins, 0, (size_t)rows * 3 * RT_CHUNK * 4, c->stream));
+      launch_class_pass(g->dist, g->pitch, rows, n, cseg, cS, g->cpos, g->pstart, g->pcount, g->ref_ids, g->cls, q0,
+                        exclude_same_id ? 1 : 0, pass, g->skeys, g->cbins, dacc, c->stream);
+    }
+    if (top5_idx) {                                                                                    // :310-316
+      launch_topk_other_id(g->dist, g->pitch, rows, n, 5, g->seg, g->S, g->ref_ids, q0, g->part, g->out_idx, g->out_dist, c->stream);
+      t5.resize((size_t)rows * 5);
+      HIPCHK(hipMemcpyAsync(t5.data(), g->out_idx, t5.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hacc.data(), dacc, (size_t)rows * sizeof(ClassAcc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = gallery_block_done(c, g))) return rc;
+    for (int i = 0; i < rows; ++i) {
+      const bool scored = g->h_cls[q0 + i] >= 0;
+      const ClassAcc& a = hacc[i];
+      const double qap = a.npos > 0 ? a.ap_sum / a.npos : 0.0, q1 = a.acc1, q5 = a.n5 / 5.0;          // :131-135
+      if (scored) { s_ap += qap; s_1 += q1; s_5 += q5; }                                               // :297-301
+      if (ap) ap[q0 + i] = scored ? (float)qap : nanv;
+      if (acc1) acc1[q0 + i] = scored ? (float)q1 : nanv;
+      if (acc5) acc5[q0 + i] = scored ? (float)q5 : nanv;
+      if (top5_idx)
+        for (int j = 0; j < 5; ++j) top5_idx[(size_t)(q0 + i) * 5 + j] = scored ? t5[(size_t)i * 5 + j] : -1;
+    }
+  }
+  out->mean_ap = (float)(s_ap / n_scored); out->hit_at_1 = (float)(s_1 / n_scored); out->hit_at_5 = (float)(s_5 / n_scored);   // :351-353
+  out->n_scored = n_scored;
   return gallery_call_end(c, g);
 }
 

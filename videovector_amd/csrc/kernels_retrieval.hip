@@ -142,22 +142,31 @@ __device__ inline void rt_offer(uint64_t key, bool cand, uint64_t& mine, uint64_
   kth = __shfl(mine, k - 1);
 }
 
-// grid (S, rows): workgroup (s, row) scans gallery items [s seg, (s+1) seg) of the row, part[row][s][k] = its k smallest keys
+// grid (S, rows): workgroup (s, row) scans gallery items [s seg, (s+1) seg) of the row, part[row][s][k] = its k smallest keys.
+// OTHER_ID: only items whose id differs from the row's own (ids[q0 + row]; the rows are gallery items q0 ..) are offered:
+// "the nearest items of other videos" of RetrievalStatsLayer (retrieval_stats_layer.cpp:310-316).
+template <bool OTHER_ID>
 __global__ __launch_bounds__(256) void k_topk_part(const float* __restrict__ dist, int64_t pitch, int ng, int k, int seg,
-                                                   uint64_t* __restrict__ part) {
+                                                   const int32_t* __restrict__ ids, int q0, uint64_t* __restrict__ part) {
   __shared__ uint64_t sl[4][32];
   const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int begin = s * seg, end = min(ng, begin + seg);
   const float* d = dist + (int64_t)row * pitch;
+  int32_t own = 0;
+  if (OTHER_ID) own = ids[q0 + row];
   uint64_t mine = RT_NOKEY, kth = RT_NOKEY;
   for (int base = begin; base < end; base += 1024) {               // seg is a multiple of 1024, pitch of 4
     const int i = base + tid * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (i < end) v = *(const float4*)(d + i);                      // i + 3 < pitch: the row's pad may be read, never ranked
-    rt_offer(rt_key(v.x, (uint32_t)i), i < end, mine, kth, lane, k);
-    rt_offer(rt_key(v.y, (uint32_t)i + 1), i + 1 < end, mine, kth, lane, k);
-    rt_offer(rt_key(v.z, (uint32_t)i + 2), i + 2 < end, mine, kth, lane, k);
-    rt_offer(rt_key(v.w, (uint32_t)i + 3), i + 3 < end, mine, kth, lane, k);
+    bool c0 = i < end, c1 = i + 1 < end, c2 = i + 2 < end, c3 = i + 3 < end;
+    if (OTHER_ID) {                                                // (ids has ng entries: every read is guarded)
+      c0 = c0 && ids[i] != own; c1 = c1 && ids[i + 1] != own; c2 = c2 && ids[i + 2] != own; c3 = c3 && ids[i + 3] != own;
+    }
+    rt_offer(rt_key(v.x, (uint32_t)i), c0, mine, kth, lane, k);
+    rt_offer(rt_key(v.y, (uint32_t)i + 1), c1, mine, kth, lane, k);
+    rt_offer(rt_key(v.z, (uint32_t)i + 2), c2, mine, kth, lane, k);
+    rt_offer(rt_key(v.w, (uint32_t)i + 3), c3, mine, kth, lane, k);
   }
   if (lane < 32) sl[wave][lane] = mine;
   __syncthreads();
@@ -185,7 +194,12 @@ __global__ __launch_bounds__(64) void k_topk_merge(const uint64_t* __restrict__ 
 }
 void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, uint64_t* part, int32_t* idx,
                  float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_topk_part, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, part);
+  hipLaunchKernelGGL(k_topk_part<false>, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, (const int32_t*)nullptr, 0, part);
+  hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(64), 0, s, part, S, k, idx, dst);
+}
+void launch_topk_other_id(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids, int q0,
+                          uint64_t* part, int32_t* idx, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_topk_part<true>, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, ids, q0, part);
   hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(64), 0, s, part, S, k, idx, dst);
 }
 
@@ -336,6 +350,180 @@ void launch_rank_pass(const float* dist, int64_t pitch, int rows, int ng, int se
   hipLaunchKernelGGL(k_rank_count, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, seg, pos_idx, pstart, pcount, q_ids,
                      ref_ids, pass, bins);
   hipLaunchKernelGGL(k_rank_final, dim3(rows), dim3(256), 0, s, dist, pitch, pos_idx, pstart, pcount, pass, bins, acc);
+}
+
+// ---------------------------------------------------------------------------------------------- class-level statistics
+// RetrievalStatsLayer (retrieval_stats_layer.cpp:104-141, 226-304): every gallery item is a query against all the others, a hit
+// is an item of the query's CLASS.  The rows of a block are the gallery items q0 .. q0 + rows - 1.  Positives of row r: the
+// class list cpos[pstart[r] .. + pcount[r]) (every item of the query's class, the query and the items of its video among them;
+// pcount = 0 for a query of negative class).  Three counts per positive p, all "at or before p in (d, g) order":
+//   all[p]   items                    left[p]  left-out items: the query itself, and with `exclude` the items of its video
+//   cls[p]   items of the class       (same video => same class, so a left-out item is a class-mate)
+// val(p) = all - left, ret(p) = cls - left (:113-125); a positive that is itself left out contributes nothing.
+//
+// A pass ranks RT_CHUNK positives.  Unlike the fixed-reference case the positives are a constant share of the gallery spread
+// over the whole order, so `key > last` discards nothing and every item of the row is searched in every pass; the chunk is
+// therefore sorted ONCE per (row, pass) by k_class_sort into `skeys`, not once per segment workgroup.
+
+// grid (rows): skeys[row][0 .. npad) = the pass's positive keys, ascending, padded with RT_NOKEY to a power of two
+__global__ __launch_bounds__(256) void k_class_sort(const float* __restrict__ dist, int64_t pitch,
+                                                    const int32_t* __restrict__ cpos, const int32_t* __restrict__ pstart,
+                                                    const int32_t* __restrict__ pcount, int pass, uint64_t* __restrict__ skeys) {
+  __shared__ uint64_t sk[RT_CHUNK];
+  const int row = blockIdx.x;
+  int npad = 0;
+  const int n = rt_load_sorted(sk, dist + (int64_t)row * pitch, cpos, pstart[row], pcount[row], pass, &npad);
+  if (n == 0) return;
+  for (int j = threadIdx.x; j < npad; j += 256) skeys[(int64_t)row * RT_CHUNK + j] = sk[j];
+}
+
+// number of this pass's positives of a row and the padded length of its sorted keys (what rt_load_sorted returned to k_class_sort)
+__device__ inline int rt_pass_count(int pcount, int pass, int* npad_out) {
+  const int off = pass * RT_CHUNK;
+  if (off >= pcount) return 0;
+  const int n = min(RT_CHUNK, pcount - off);
+  int npad = 1;
+  while (npad < n) npad <<= 1;
+  *npad_out = npad;
+  return n;
+}
+
+// grid (S, rows).  bins[row][t][slot], t = 0 all / 1 class / 2 left out: the items of the segment whose key lies in
+// (p_{slot-1}, p_slot].  Items beyond the pass's last positive are not counted.
+__global__ __launch_bounds__(256) void k_class_count(const float* __restrict__ dist, int64_t pitch, int ng, int seg,
+                                                     const uint64_t* __restrict__ skeys, const int32_t* __restrict__ pcount,
+                                                     const int32_t* __restrict__ ids, const int32_t* __restrict__ cls, int q0,
+                                                     int exclude, int pass, uint32_t* __restrict__ bins) {
+  __shared__ uint64_t sk[RT_CHUNK];
+  __shared__ uint32_t sb[3][RT_CHUNK];
+  const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  int npad = 0;
+  const int n = rt_pass_count(pcount[row], pass, &npad);             // uniform over the workgroup
+  if (n == 0) return;
+  for (int j = tid; j < npad; j += 256) sk[j] = skeys[(int64_t)row * RT_CHUNK + j];
+  for (int j = tid; j < n; j += 256) { sb[0][j] = 0; sb[1][j] = 0; sb[2][j] = 0; }
+  __syncthreads();
+  const float* d = dist + (int64_t)row * pitch;
+  const int self = q0 + row;
+  const int32_t qid = ids[self], qcls = cls[self];
+  const uint64_t last = sk[n - 1];
+  const int begin = s * seg, end = min(ng, begin + seg);
+  for (int base = begin; base < end; base += 1024) {
+    const int i = base + tid * 4;
+    if (i >= end) continue;
+    const float4 v = *(const float4*)(d + i);
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = i + u;
+      const uint64_t key = rt_key(e[u], (uint32_t)g);
+      if (g >= end || key > last) continue;
+      int slot = 0;
+      for (int step = npad >> 1; step > 0; step >>= 1)
+        if (sk[slot + step - 1] < key) slot += step;                // key <= last, so the answer is at most n - 1 < npad
+      atomicAdd(&sb[0][slot], 1u);
+      if (cls[g] == qcls) {
+        atomicAdd(&sb[1][slot], 1u);
+        if (g == self || (exclude && ids[g] == qid)) atomicAdd(&sb[2][slot], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t* b = bins + (int64_t)row * 3 * RT_CHUNK;
+  for (int j = tid; j < n; j += 256)
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+      if (sb[t][j]) atomicAdd(&b[t * RT_CHUNK + j], sb[t][j]);
+}
+
+// grid (rows).  Inclusive prefix sums of the three bin arrays over the sorted positives = the three counts; ComputeStats
+// (:113-128) from them.  Integer counts; the AP terms are summed in double in a fixed order (per thread ascending slot, then
+// a fixed tree, then pass by pass in stream order).
+__global__ __launch_bounds__(256) void k_class_final(const uint64_t* __restrict__ skeys, const int32_t* __restrict__ pcount,
+                                                     const int32_t* __restrict__ ids, int q0, int exclude, int pass,
+                                                     const uint32_t* __restrict__ bins, ClassAcc* __restrict__ acc) {
+  __shared__ uint32_t ta[256], tc[256], tl[256];
+  __shared__ double rap[256];
+  __shared__ int rn[256], r1[256], r5[256];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  int npad = 0;
+  const int n = rt_pass_count(pcount[row], pass, &npad);
+  if (n == 0) return;
+  const int self = q0 + row;
+  const int32_t qid = ids[self];
+  const uint32_t* b = bins + (int64_t)row * 3 * RT_CHUNK;
+  const uint64_t* sk = skeys + (int64_t)row * RT_CHUNK;
+  constexpr int PER = RT_CHUNK / 256;
+  const int j0 = tid * PER;
+  uint32_t ca[PER], cc[PER], cl[PER], sa = 0, sc = 0, sl = 0;
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int j = j0 + u;
+    ca[u] = j < n ? b[j] : 0; cc[u] = j < n ? b[RT_CHUNK + j] : 0; cl[u] = j < n ? b[2 * RT_CHUNK + j] : 0;
+    sa += ca[u]; sc += cc[u]; sl += cl[u];
+  }
+  ta[tid] = sa; tc[tid] = sc; tl[tid] = sl;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {                                 // inclusive scan of the thread totals
+    const uint32_t x = tid >= o ? ta[tid - o] : 0, y = tid >= o ? tc[tid - o] : 0, z = tid >= o ? tl[tid - o] : 0;
+    __syncthreads();
+    ta[tid] += x; tc[tid] += y; tl[tid] += z;
+    __syncthreads();
+  }
+  uint32_t all = ta[tid] - sa, cmate = tc[tid] - sc, left = tl[tid] - sl;
+  double ap = 0; int np = 0, a1 = 0, a5 = 0;
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int j = j0 + u;
+    all += ca[u]; cmate += cc[u]; left += cl[u];
+    if (j < n) {
+      const int p = (int)(uint32_t)sk[j];
+      if (p != self && !(exclude && ids[p] == qid)) {                 // :113-115
+        const uint32_t val = all - left, ret = cmate - left;          // :116, :124
+        np += 1; a1 += val <= 1; a5 += val <= 5;                      // :118-123
+        ap += (double)ret / (double)val;                              // :125
+      }
+    }
+  }
+  rap[tid] = ap; rn[tid] = np; r1[tid] = a1; r5[tid] = a5;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { rap[tid] += rap[tid + o]; rn[tid] += rn[tid + o]; r1[tid] += r1[tid + o]; r5[tid] += r5[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {                                                      // one workgroup per row and pass, passes in stream order
+    ClassAcc a = acc[row];
+    a.ap_sum += rap[0]; a.npos += rn[0]; a.acc1 += r1[0]; a.n5 += r5[0];
+    acc[row] = a;
+  }
+}
+
+void launch_class_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* cpos,
+                       const int32_t* pstart, const int32_t* pcount, const int32_t* ids, const int32_t* cls, int q0, int exclude,
+                       int pass, uint64_t* skeys, uint32_t* bins, ClassAcc* acc, hipStream_t s) {
+  hipLaunchKernelGGL(k_class_sort, dim3(rows), dim3(256), 0, s, dist, pitch, cpos, pstart, pcount, pass, skeys);
+  hipLaunchKernelGGL(k_class_count, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, seg, skeys, pcount, ids, cls, q0, exclude,
+                     pass, bins);
+  hipLaunchKernelGGL(k_class_final, dim3(rows), dim3(256), 0, s, skeys, pcount, ids, q0, exclude, pass, bins, acc);
+}
+
+// ---------------------------------------------------------------------------------------------- pooling by id
+// Video-level retrieval (retrieval_stats_layer.cpp:189-198): out[u] = sum over the items of id u of (1 / count_u) x_i, the
+// weight multiplied into every term as the reference's weight matrix does, items in ascending index (pos_idx groups them so).
+// grid (n_ids); feat [n][Dp], out [n_ids][Dp] (the zero padding of the columns sums to zero).
+__global__ __launch_bounds__(256) void k_pool_by_id(const float* __restrict__ feat, int Dp, const int32_t* __restrict__ pos_idx,
+                                                    const int32_t* __restrict__ ustart, float* __restrict__ out) {
+  const int u = blockIdx.x, b = ustart[u], e = ustart[u + 1];
+  const float w = 1.0f / (float)(e - b);                                // :193
+  for (int col = threadIdx.x; col < Dp; col += 256) {
+    float acc = 0.f;
+    for (int j = b; j < e; ++j) acc = fmaf(w, feat[(int64_t)pos_idx[j] * Dp + col], acc);
+    out[(int64_t)u * Dp + col] = acc;
+  }
+}
+void launch_pool_by_id(const float* feat, int Dp, const int32_t* pos_idx, const int32_t* ustart, int n_ids, float* out,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(k_pool_by_id, dim3(n_ids), dim3(256), 0, s, feat, Dp, pos_idx, ustart, out);
 }
 
 }  // namespace vv

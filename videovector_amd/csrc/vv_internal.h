@@ -499,6 +499,19 @@ void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int 
 void launch_rank_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* pos_idx,
                       const int32_t* pstart, const int32_t* pcount, const int32_t* q_ids, const int32_t* ref_ids, int pass,
                       uint32_t* bins, RankAcc* acc, hipStream_t s);
+// Class-level statistics (RetrievalStatsLayer): the rows of a block are the gallery items q0 .. q0 + rows - 1.
+struct ClassAcc { double ap_sum; int32_t npos, acc1, n5, pad_; };      // ComputeStats' running values of one query
+// as launch_topk, over the items whose id differs from the row's own
+void launch_topk_other_id(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids, int q0,
+                          uint64_t* part, int32_t* idx, float* dst, hipStream_t s);
+// cpos: item indices grouped by class; ids / cls: id and class of every item; skeys: uint64 [rows][RT_CHUNK];
+// bins: uint32 [rows][3][RT_CHUNK], zero on entry
+void launch_class_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* cpos,
+                       const int32_t* pstart, const int32_t* pcount, const int32_t* ids, const int32_t* cls, int q0, int exclude,
+                       int pass, uint64_t* skeys, uint32_t* bins, ClassAcc* acc, hipStream_t s);
+// ustart: int32 [n_ids + 1], the groups of pos_idx; out: [n_ids][Dp]
+void launch_pool_by_id(const float* feat, int Dp, const int32_t* pos_idx, const int32_t* ustart, int n_ids, float* out,
+                       hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // 16-bit operand types

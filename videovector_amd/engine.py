@@ -49,6 +49,10 @@ class _RankStats(C.Structure):
                 ("mean_ap", C.c_float)]
 
 
+class _ClassStats(C.Structure):
+    _fields_ = [("mean_ap", C.c_float), ("hit_at_1", C.c_float), ("hit_at_5", C.c_float), ("n_scored", C.c_int32)]
+
+
 def load_library():
     """Load libvideovec.so; raises (never falls back) when the HIP library is not built."""
     global _lib
@@ -115,6 +119,8 @@ def load_library():
         "vv_gallery_topk": [vp, vp, vp, i32, i32, vp, vp],
         "vv_gallery_rank_stats": [vp, vp, vp, i32, vp, C.POINTER(_RankStats), vp, vp, vp, vp],
         "vv_gallery_get": [vp, C.c_char_p, C.POINTER(C.c_double)],
+        "vv_gallery_pool_by_id": [vp, vp, C.POINTER(vp)],
+        "vv_gallery_class_stats": [vp, vp, vp, vp, i32, C.c_int, C.POINTER(_ClassStats), vp, vp, vp, vp],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
@@ -135,8 +141,8 @@ def _ptr(a):
 class Gallery:
     """A reference set held on the device by an Engine (RetrievalRankStatsFixedRefLayer's bottom[2] / bottom[3])."""
 
-    def __init__(self, eng, handle):
-        self.eng, self.h = eng, handle
+    def __init__(self, eng, handle, ids=None):
+        self.eng, self.h, self.ids = eng, handle, ids          # ids: the int32 [n_ref] the gallery was created with, or None
 
     def get(self, name):
         v = C.c_double()
@@ -187,6 +193,40 @@ class Gallery:
         out = {f: getattr(st, f) for f, _ in _RankStats._fields_}
         if per_query:
             out.update(best_rank=br, ap=ap, top5_idx=t5i, top5_dist=t5d)
+        return out
+
+    def rows(self):
+        """The gallery's fp32 rows [n_ref][dim], downloaded from the device."""
+        pitch = int(self.get("row_floats"))
+        buf = np.empty((self.n_ref, pitch), np.float32)
+        self.eng._chk(self.eng.L.vv_dev_download(self.eng.h, _ptr(buf), C.c_void_p(int(self.get("feat_device"))), buf.nbytes))
+        return np.ascontiguousarray(buf[:, :self.dim])
+
+    def pool_by_id(self):
+        """A new Gallery with one item per distinct id, ids ascending, each row the mean of the id's rows (RetrievalStatsLayer's
+        video_level_retrieval); its `ids` are those ids."""
+        h = C.c_void_p()
+        self.eng._chk(self.eng.L.vv_gallery_pool_by_id(self.eng.h, self.h, C.byref(h)))
+        ids = None if self.ids is None else np.unique(self.ids).astype(np.int32)
+        return Gallery(self.eng, h, ids)
+
+    def class_stats(self, id2class, exclude_same_video=True, per_query=False):
+        """RetrievalStatsLayer over the gallery's own items, every item a query against all the others: dict(mean_ap, hit_at_1,
+        hit_at_5, n_scored); with per_query also ap / acc1 / acc5 [n_ref] (NaN for a query of negative class) and top5_idx
+        [n_ref][5] (the nearest items of other ids, -1 where fewer exist).  id2class: {id: class}, an absent id reads as class 0."""
+        mi = np.ascontiguousarray(list(id2class.keys()), dtype=np.int32)
+        mc = np.ascontiguousarray(list(id2class.values()), dtype=np.int32)
+        n = self.n_ref
+        st = _ClassStats()
+        ap = np.empty(n, np.float32) if per_query else None
+        a1 = np.empty(n, np.float32) if per_query else None
+        a5 = np.empty(n, np.float32) if per_query else None
+        t5 = np.empty((n, 5), np.int32) if per_query else None
+        self.eng._chk(self.eng.L.vv_gallery_class_stats(self.eng.h, self.h, _ptr(mi), _ptr(mc), len(mi), int(bool(exclude_same_video)),
+                                                        C.byref(st), _ptr(ap), _ptr(a1), _ptr(a5), _ptr(t5)))
+        out = {f: getattr(st, f) for f, _ in _ClassStats._fields_}
+        if per_query:
+            out.update(ap=ap, acc1=a1, acc5=a5, top5_idx=t5)
         return out
 
     def close(self):
@@ -461,7 +501,7 @@ class Engine:
             raise VVError("gallery: ids must be [n_ref]")
         h = C.c_void_p()
         self._chk(self.L.vv_gallery_create(self.h, _ptr(feat), feat.shape[0], feat.shape[1], _ptr(rid), C.byref(h)))
-        return Gallery(self, h)
+        return Gallery(self, h, rid)
 
     def gallery_from_table(self, rows, ids=None, coeff=None, relu=True, l2norm=True):
         """The same from table rows, embedded as embed_mean does ([n][k] rows; [n] rows and no coeff: as embed); the
@@ -476,7 +516,7 @@ class Engine:
             raise VVError("gallery_from_table: ids must be [n]")
         h = C.c_void_p()
         self._chk(self.L.vv_gallery_from_table(self.h, _ptr(r), n, k, _ptr(cf), int(relu), int(l2norm), _ptr(rid), C.byref(h)))
-        return Gallery(self, h)
+        return Gallery(self, h, rid)
 
     # ---- profiling
     def profile_enable(self, on=True):
