@@ -87,6 +87,11 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *                                    rule in that GEMM's epilogue (bit-identical parameters; 0: the update as its own launch)
  *   "comm_chunks" (VV_COMM_CHUNKS, 3)  F-chunks of the overlapped update, 1 .. 4
  *   "comm_test_delay_us" (VV_COMM_TEST_DELAY_US, 0)  TEST HOOK: holds the communication stream this long in front of every chunk
+ * Read-only values (vv_get_option only; vv_set_option: VV_ERR_ARG) -- what the launchers chose for the most recent launch on this context,
+ * recorded where the kernel is launched, for tests that must know which form they exercised:
+ *   "last_fwd_tile_rows"             rows of the forward GEMM's tile, 128, 192 or 256, whoever launched it (a step, vv_embed*, vv_op_inner_product,
+ *                                    vv_gallery_from_table); 0 before the first launch
+ *   "last_wgrad_splits"              splits of K (S) of the weight-gradient GEMM (a step or vv_op_inner_product_bwd); 0 before the first launch
  * Retired options -- "fwd_merge", "score_stream", "comm_first_inline": their alternatives were measured, lost and removed.  They read as 0,
  * the value the library always runs with; setting 0 is accepted, any other value is VV_ERR_ARG.  Their environment variables are not read.
  * Ablated / experimental kernels (timing studies whose results may be wrong) are NOT reachable through this library: they and their

@@ -178,6 +178,7 @@ void launch_wgrad_gemm_ph(int prec, const WgradArgs& a, hipStream_t s);
 // the update in the epilogue (WgradArgs::fuse_upd) exists in the phase-staggered kernel only: api.hip asks before it fills WgradUpd
 bool wgrad_can_fuse_update() { return ko().wgrad_tr != 0 && !ko().ablate && !ko().lab_wg_abl; }
 void launch_wgrad_gemm(int prec, const WgradArgs& a, hipStream_t s) {
+  ko().last_wgrad_splits = a.S;           // ("last_wgrad_splits": both kernels' grids are built from this S)
   if (ko().wgrad_tr != 0) {
     // (lab: VV_LAB_WG_ABL ablates this kernel alone, at whatever size the step runs -- VV_ABLATE switches the de-duplication off)
     WgradArgs b = a; b.abl = ko().ablate ? ko().ablate : ko().lab_wg_abl; launch_wgrad_gemm_ph(prec, b, s); return;

@@ -1019,6 +1019,7 @@ static void launch_fwd_ph_q(const FwdArgs& a, hipStream_t s, long tiles_est) {
   constexpr int BMT = 64 * MQ;
   const dim3 grid(((a.R + BMT - 1) / BMT) * (Dp / BN)), block(GEMM_THREADS);
   (void)tiles_est;
+  ko().last_fwd_tile_rows = BMT;          // ("last_fwd_tile_rows": every product launch of the forward GEMM passes here)
   if constexpr (!DROP && VEC) {
     if (a.h16) {                          // ip2 as f16 (FwdArgs::h16): the same three forms -- sibling lead, gated, plain -- with the narrow epilogue
       constexpr int LDS10 = 10 * PH_SLOT;
