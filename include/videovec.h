@@ -92,6 +92,7 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *   "last_fwd_tile_rows"             rows of the forward GEMM's tile, 128, 192 or 256, whoever launched it (a step, vv_embed*, vv_op_inner_product,
  *                                    vv_gallery_from_table); 0 before the first launch
  *   "last_wgrad_splits"              splits of K (S) of the weight-gradient GEMM (a step or vv_op_inner_product_bwd); 0 before the first launch
+ *   "last_update_form"               what the last vv_apply_update ran for the parameter matrix: 1 k_sgd with 16-byte accesses (the chunked and sharded updates too), 2 k_sgd scalar (F % 4 != 0), 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0 before the first update
  * Retired options -- "fwd_merge", "score_stream", "comm_first_inline": their alternatives were measured, lost and removed.  They read as 0,
  * the value the library always runs with; setting 0 is accepted, any other value is VV_ERR_ARG.  Their environment variables are not read.
  * Ablated / experimental kernels (timing studies whose results may be wrong) are NOT reachable through this library: they and their

@@ -289,7 +289,7 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     if (iv == 0) return VV_OK;
     return fail(VV_ERR_ARG, "vv_set_option: option '%s' is retired; only its fixed value 0 is accepted", name);
   }
-  if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits")
+  if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
@@ -338,6 +338,7 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "comm_test_delay_us") *value = c->comm_test_delay_us;
   else if (n == "last_fwd_tile_rows") *value = c->ko.last_fwd_tile_rows;
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
+  else if (n == "last_update_form") *value = c->ko.last_update_form;
   else return fail(VV_ERR_ARG, "vv_get_option: unknown option '%s'", name);
   return VV_OK;
 }

@@ -1625,6 +1625,7 @@ void launch_delay(int us, hipStream_t s) { hipLaunchKernelGGL(k_delay, dim3(1), 
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s) { hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, flag, seq); }
 void launch_sgd(int prec, const SgdArgs& a, hipStream_t s) {
   const bool vec = a.F % 4 == 0;
+  ko().last_update_form = vec ? 1 : 2;    // ("last_update_form": the chunked and the sharded update pass here too, F % 4 == 0 both)
   const dim3 grid(a.chunked ? a.n_blk : SGD_BLOCKS), block(256);
   if (prec == 0) { if (vec) VV_LAUNCH((k_sgd<F16, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<F16, false>), grid, block, 0, s, a); }
   else { if (vec) VV_LAUNCH((k_sgd<BF16, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<BF16, false>), grid, block, 0, s, a); }
@@ -1772,6 +1773,7 @@ int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s) {
   const int ept = a.r.slab16 ? 8 : 4;                                       // elements per thread (k_reduce_sgd's S16 form: eight)
   const int nblk = a.no_params ? 0 : (int)std::min<int64_t>(((int64_t)a.r.D * (a.r.F / ept) + 255) / 256, WMAX_SLOTS);
   const dim3 grid(nblk + ndb + 1);
+  ko().last_update_form = a.no_params ? 5 : a.r.slab16 ? 4 : 3;     // ("last_update_form"; no_params: the matrix was updated in the weight-gradient GEMM)
   if (a.r.slab16) {
     if (a.prec == 0) VV_LAUNCH((k_reduce_sgd<F16, true>), grid, dim3(256), 0, s, a);
     else VV_LAUNCH((k_reduce_sgd<BF16, true>), grid, dim3(256), 0, s, a);

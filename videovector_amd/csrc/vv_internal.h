@@ -414,10 +414,13 @@ struct KernelOpts {
   int ph_mq = 0;           // (lab) VV_PH_MQ: force the forward tile (2, 3, 4 = 128 / 192 / 256 rows)
   int score_reg = 1;       // (lab) VV_SCORE_REG=0: the LDS-resident score kernel
   int score_rr = 0;        // (lab) VV_SCORE_RR=1: the item-major kernels deal their items round-robin over the XCDs again (kernels_elem.hip: item_of_block)
-  // What the launchers last chose for this context (read-only through vv_get_option: "last_fwd_tile_rows", "last_wgrad_splits"): written where
-  // the kernel is launched (launch_fwd_ph_q / launch_wgrad_gemm), so a test can assert the form it ran without a copy of the pickers' rules.
+  // What the launchers last chose for this context (read-only through vv_get_option: "last_fwd_tile_rows", "last_wgrad_splits",
+  // "last_update_form"): written where the kernel is launched (launch_fwd_ph_q / launch_wgrad_gemm / launch_sgd / launch_reduce_sgd), so a test
+  // can assert the form it ran without a copy of the pickers' rules.
   mutable int last_fwd_tile_rows = 0;   // rows of the forward GEMM's tile (128, 192, 256); 0: no launch yet
   mutable int last_wgrad_splits = 0;    // S (splits of K) of the weight-gradient GEMM; 0: no launch yet
+  mutable int last_update_form = 0;     // what last updated the parameter matrix: 1 k_sgd 16-byte (chunked / sharded launches too), 2 k_sgd scalar,
+                                        // 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0: no update yet
 };
 extern thread_local const KernelOpts* g_ko;
 inline const KernelOpts& ko() { static const KernelOpts dflt; return g_ko ? *g_ko : dflt; }
