@@ -270,6 +270,25 @@ int vv_grads_get(vv_ctx* ctx, float* dW, float* db);
 int vv_blobs_get(vv_ctx* ctx, float* ip2, float* target_score, float* negative_scores,
                  float* ip1_diff);
 
+/* ---- inspection of the row grouping of the last de-duplicated forward/backward pass (vv_set_dedup; no counterpart in the
+ * reference, which copies and multiplies every repeat: video_sampled_shots_data_layer.cpp:836-875).  Read-only, for tests:
+ * nothing a step executes depends on it.  Every output optional (NULL); synchronises.  With R = B*(C+Nn) instances
+ * r = b*(C+Nn) + ch, Rp = R rounded up to 256, U distinct rows (vv_dedup_stats) and n_rows the table's all-zero row:
+ *   rows      int32 [Rp]     table row of every instance (idx outside [0, n_rows) and r >= R: n_rows)
+ *   uniq_rows int32 [Rp]     table row of every slot, slots in order of first appearance; n_rows from U on
+ *   map       int32 [R]      slot of every instance
+ *   ord       int32 [R]      arrival number of the instance inside its slot (a permutation of 0 .. cnt-1 per slot, order unspecified)
+ *   cnt       int32 [Rp]     instances per slot; 0 from U on
+ *   seg_start int32 [U + 1]  exclusive prefix sum of cnt; seg_start[U] = R
+ *   pos       int32 [R]      seg_start[map[r]] + ord[r]: the instance's row in the grouped gradient buffer
+ *   dyu       fp32 [Rp][D]   the per-slot 16-bit gradient sums the weight-gradient GEMM read, divided by *scale
+ *   scale     the power of two those 16-bit values carry (1 for bf16): what vv_blobs_get divides ip1_diff by
+ * Every vv_forward_backward* entry point runs the backward pass too, so dyu and scale always belong to the same step as the grouping
+ * arrays; the debug launches of vv_blobs_get(ip1_diff) leave them untouched.  VV_ERR_STATE before the first forward/backward pass and
+ * after a dense one. */
+int vv_dedup_groups_get(vv_ctx* ctx, int32_t* rows, int32_t* uniq_rows, int32_t* map, int32_t* ord, int32_t* cnt,
+                        int32_t* seg_start, int32_t* pos, float* dyu, float* scale);
+
 /* ---- inference: fc7 (+ReLU) (+L2 normalise) of arbitrary table rows -- the extract_features path
  * (tools/extract_features.cpp:99-198 over videovec_extraction.prototxt:179-205) and the TEST
  * branch's embedding (mednet_embedding_train.prototxt:344-352).  rows host int32 [n] (NULL = 0..n-1),

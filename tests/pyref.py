@@ -229,3 +229,50 @@ def fused_step(table, idx, W, b, C, Nn, margin=2.0, norm=2, loss_weight=1.0, coe
     dY = dH * (Y > 0)
     return dict(loss=loss, violations=viol, s_true=np.repeat(sp[:, None], Nn, 1), s_bogus=sn,
                 Y=Y, H=H, ctx=Ah, posneg=Ph.reshape(-1, D), dY=dY, dW=dY.T @ X, db=dY.sum(0))
+
+
+# ---- the row grouping of one batch (videovector_amd/csrc/kernels_dedup.hip) restated in numpy
+def dedup_groups_expected(idx, n_rows, row_limit=None):
+    """What k_dd_claim .. k_dd_segstart must leave for the [B][C+Nn] index array idx over a table of n_rows rows (its all-zero row is
+    row n_rows; row_limit > n_rows: the scratch rows behind it count as rows, vv_forward_backward_q1).  Instance r = b (C+Nn) + ch; slots in
+    order of first appearance.  `ord` and `pos` depend on the arrival order inside a slot and are not predicted: dedup_groups_check."""
+    flat = np.asarray(idx, np.int64).reshape(-1)
+    R = flat.size
+    Rp = (R + 255) // 256 * 256
+    lim = n_rows if row_limit is None else row_limit
+    rows = np.full(Rp, n_rows, np.int64)
+    rows[:R] = np.where((flat >= 0) & (flat < lim), flat, n_rows)
+    vals, first = np.unique(rows[:R], return_index=True)
+    by_first = np.argsort(first, kind="stable")
+    uniq = vals[by_first]                                   # == rows[:R][np.sort(first)]
+    U = len(uniq)
+    slot_of_val = np.empty(U, np.int64)
+    slot_of_val[by_first] = np.arange(U)
+    m = slot_of_val[np.searchsorted(vals, rows[:R])]
+    uniq_rows = np.full(Rp, n_rows, np.int64)
+    uniq_rows[:U] = uniq
+    cnt = np.zeros(Rp, np.int64)
+    cnt[:U] = np.bincount(m, minlength=U)
+    seg_start = np.concatenate([[0], np.cumsum(cnt[:U])])
+    assert seg_start[U] == R
+    i32 = lambda a: a.astype(np.int32)
+    return dict(R=R, Rp=Rp, U=U, rows=i32(rows), uniq_rows=i32(uniq_rows), map=i32(m), cnt=i32(cnt), seg_start=i32(seg_start))
+
+
+def dedup_groups_check(got, exp):
+    """Raises AssertionError unless `got` (Engine.dedup_groups()) is the grouping `exp` (dedup_groups_expected): every predicted array
+    bit for bit, `ord` a permutation of range(cnt[u]) inside every slot u, pos = seg_start[map] + ord and a permutation of range(R)."""
+    assert (got["R"], got["U"]) == (exp["R"], exp["U"]), ("(R, U)", (got["R"], got["U"]), (exp["R"], exp["U"]))
+    for k in ("rows", "uniq_rows", "map", "cnt", "seg_start"):
+        g, e = np.asarray(got[k]), exp[k]
+        assert g.dtype == np.int32 and g.shape == e.shape, (k, g.dtype, g.shape, e.shape)
+        if not np.array_equal(g, e):
+            bad = np.flatnonzero(g != e)
+            raise AssertionError("%s differs at %d of %d entries, first at %d: got %d, expected %d" % (k, len(bad), len(e), bad[0], g[bad[0]], e[bad[0]]))
+    R, m, seg = exp["R"], exp["map"].astype(np.int64), exp["seg_start"].astype(np.int64)
+    o, p = np.asarray(got["ord"]).astype(np.int64), np.asarray(got["pos"]).astype(np.int64)
+    assert o.shape == (R,) and p.shape == (R,)
+    by_slot = np.lexsort((o, m))                            # instances by slot, by ord inside the slot
+    assert np.array_equal(o[by_slot], np.arange(R) - seg[m[by_slot]]), "ord is not a permutation of range(cnt[u]) inside every slot"
+    assert np.array_equal(p, seg[m] + o), "pos != seg_start[map] + ord"
+    assert np.array_equal(np.sort(p), np.arange(R)), "pos is not a permutation of range(R)"

@@ -80,6 +80,15 @@ def test_dedup_is_deterministic_and_survives_shape_changes(vv):
             key = (B, C, Nn)
             if key in seen:
                 assert np.array_equal(seen[key], dW), key       # f64 segment sums: arrival order cannot matter
+            else:
+                # ... and not merely the same every time: the shape's first result is that of a context which has seen nothing else
+                # (key / aggregate words, rotating sets and the distinct-row hint of the earlier steps must not show)
+                fresh = vv.Engine(0, "f16")
+                fresh.table_set(table); fresh.params_set(W, b)
+                fresh.forward_backward(cfg, idx)
+                assert np.array_equal(fresh.grads()[0], dW), key
+                assert fresh.dedup_stats() == eng.dedup_stats() == (B * (C + Nn), len(np.unique(idx)))
+                fresh.close()
             seen[key] = dW
 
 

@@ -1665,6 +1665,55 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
   return VV_OK;
 }
 
+// debug / test accessor: the grouping of the last de-duplicated step as the kernels left it, from the set that step used (read-only:
+// the one launch is k_dd_pos into the debug buffer, as vv_blobs_get(ip1_diff) does)
+int vv_dedup_groups_get(vv_ctx* c, int32_t* rows, int32_t* uniq_rows, int32_t* map, int32_t* ord, int32_t* cnt, int32_t* seg_start,
+                        int32_t* pos, float* dyu, float* scale) {
+  if (!c) return fail(VV_ERR_ARG, "vv_dedup_groups_get: ctx is NULL");
+  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_dedup_groups_get: no forward pass yet");
+  if (!c->last_dedup) return fail(VV_ERR_STATE, "vv_dedup_groups_get: the last forward pass was dense (vv_set_dedup, dropout)");
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->dd_stream));
+  const size_t R = (size_t)c->R, Rp = (size_t)c->Rp;
+  int32_t U = 0;
+  HIPCHK(hipMemcpy(&U, c->dd_info, sizeof(U), hipMemcpyDeviceToHost));
+  if (U < 0 || (size_t)U > R) return fail(VV_ERR_STATE, "internal error: the grouping reports %d distinct rows of %d", (int)U, c->R);
+  if (rows) HIPCHK(hipMemcpy(rows, c->dd_rows, Rp * 4, hipMemcpyDeviceToHost));
+  if (uniq_rows) HIPCHK(hipMemcpy(uniq_rows, c->dd_uniq, Rp * 4, hipMemcpyDeviceToHost));
+  if (map) HIPCHK(hipMemcpy(map, c->dd_map, R * 4, hipMemcpyDeviceToHost));
+  if (ord) HIPCHK(hipMemcpy(ord, c->dd_ord, R * 4, hipMemcpyDeviceToHost));
+  if (cnt) HIPCHK(hipMemcpy(cnt, c->dd_cnt, Rp * 4, hipMemcpyDeviceToHost));
+  if (seg_start) HIPCHK(hipMemcpy(seg_start, c->dd_seg, ((size_t)U + 1) * 4, hipMemcpyDeviceToHost));
+  if (pos) {
+    DedupArgs da;
+    memset(&da, 0, sizeof(da));
+    da.map = c->dd_map; da.ord = c->dd_ord; da.seg_start = c->dd_seg; da.pos = c->dd_pos; da.R = c->R;
+    launch_dedup_pos(da, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(pos, c->dd_pos, R * 4, hipMemcpyDeviceToHost));
+  }
+  // the scale the step's 16-bit gradients really carry: the host's sg times what the guard's repeats took off
+  float sgf = c->sg;
+  if ((dyu || scale) && c->prec == VV_PREC_F16) {
+    GradGuard gh;
+    HIPCHK(hipMemcpy(&gh, c->gg, sizeof(gh), hipMemcpyDeviceToHost));
+    sgf *= gh.mul;
+  }
+  if (dyu) {
+    DevTmp<float> d;
+    HIPCHK(d.alloc(Rp * c->D));
+    launch_dyh_to_float(c->prec, c->dYu, c->Rp, c->D, c->Dp, 1.f / sgf, d, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(dyu, d, Rp * c->D * 4, hipMemcpyDeviceToHost));
+  }
+  if (scale) *scale = sgf;
+  return VV_OK;
+}
+
 // ------------------------------------------------------------------------------- embed --------
 // The two embedding forms with the result left on the device (dout: fp32 [n][D], the caller's): vv_embed / vv_embed_mean
 // download it, vv_gallery_from_table keeps it.  `who` names the entry point in messages.

@@ -110,6 +110,7 @@ def load_library():
         "vv_grads_device": [vp, C.POINTER(vp), C.POINTER(i64)], "vv_grads_get": [vp, vp, vp],
         "vv_grads_bind": [vp, vp],
         "vv_blobs_get": [vp, vp, vp, vp, vp],
+        "vv_dedup_groups_get": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f32)],
         "vv_embed": [vp, vp, i64, C.c_int, C.c_int, vp],
         "vv_embed_mean": [vp, vp, i64, i32, vp, C.c_int, C.c_int, vp],
         "vv_retrieval_stats": [vp, vp, i32, i32, vp, vp, vp, i32, C.c_int, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)],
@@ -462,6 +463,21 @@ class Engine:
         if ip2: out["ip2"] = a
         if scores: out["target_score"], out["negative_scores"] = st, sn
         if ip1_diff: out["ip1_diff"] = dy
+        return out
+
+    def dedup_groups(self, dyu=True):
+        """The row grouping of the last de-duplicated pass (include/videovec.h: vv_dedup_groups_get) as a dict: R, Rp, U, rows,
+        uniq_rows, map, ord, cnt, seg_start, pos, scale and (dyu=True) the per-slot 16-bit gradient sums dyu [Rp][D]."""
+        R, U = self.dedup_stats()
+        Rp = (R + 255) // 256 * 256
+        i32 = lambda n: np.empty(n, np.int32)
+        out = dict(R=R, Rp=Rp, U=U, rows=i32(Rp), uniq_rows=i32(Rp), map=i32(R), ord=i32(R), cnt=i32(Rp), seg_start=i32(U + 1), pos=i32(R))
+        if dyu:
+            out["dyu"] = np.empty((Rp, self.D), np.float32)
+        sc = C.c_float(0)
+        self._chk(self.L.vv_dedup_groups_get(self.h, *[_ptr(out[k]) for k in ("rows", "uniq_rows", "map", "ord", "cnt", "seg_start", "pos")],
+                                             _ptr(out.get("dyu")), C.byref(sc)))
+        out["scale"] = sc.value
         return out
 
     def embed(self, rows=None, n=None, relu=True, l2norm=False):
