@@ -87,6 +87,8 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *                                    rule in that GEMM's epilogue (bit-identical parameters; 0: the update as its own launch)
  *   "comm_chunks" (VV_COMM_CHUNKS, 3)  F-chunks of the overlapped update, 1 .. 4
  *   "comm_test_delay_us" (VV_COMM_TEST_DELAY_US, 0)  TEST HOOK: holds the communication stream this long in front of every chunk
+ *   "nearest_select_min_k" (VV_NEAREST_SELECT_MIN_K, 33)  vv_gallery_nearest*: the smallest k that runs the selection form; 1 .. 33, anything
+ *                                    else is VV_ERR_ARG.  1 runs the selection form at every k (how the tests hold the two forms against each other)
  * Read-only values (vv_get_option only; vv_set_option: VV_ERR_ARG) -- what the launchers chose for the most recent launch on this context,
  * recorded where the kernel is launched, for tests that must know which form they exercised:
  *   "last_fwd_tile_rows"             rows of the forward GEMM's tile, 128, 192 or 256, whoever launched it (a step, vv_embed*, vv_op_inner_product,
@@ -349,8 +351,31 @@ int vv_gallery_rank_stats(vv_ctx* ctx, vv_gallery* gallery, const float* q, int3
  * with more takes several passes), "last_passes", "last_sim_ms" (device time of the similarity kernels of the last call),
  * "last_device_ms" (device time of the whole last call, uploads of the query blocks included), "n_ids" (distinct ids; 0 without
  * ids), "feat_device" / "row_floats" (the device address of the gallery's fp32 rows, for vv_dev_download, and the floats between
- * two rows: dim rounded up to a multiple of 32, the rest zero).  Unknown name: VV_ERR_ARG. */
+ * two rows: dim rounded up to a multiple of 32, the rest zero), "last_nearest_form" (what the last vv_gallery_nearest* call ran: 1 the
+ * streaming form, 2 the selection form; 0 before the first).  Unknown name: VV_ERR_ARG. */
 int vv_gallery_get(const vv_gallery* gallery, const char* name, double* value);
+
+/* ---- nearest-neighbour lists of up to 2048 items.  The reference's nearest counterparts are the head of sort_ids
+ * (retrieval_rank_stats_fixed_ref_layer.cpp:158-162) and top_5_ids (retrieval_stats_layer.cpp:310-316); k > 5 and the self form
+ * HAVE NO REFERENCE COUNTERPART.  Distance, key and order are vv_gallery_topk's: -2 dot in fp32, ascending (d, g); the
+ * distances returned are the floats the similarity kernel stored for the query block, nothing is evaluated twice.
+ * Two forms, chosen per call: k < "nearest_select_min_k" (vv_set_option; default 33) runs vv_gallery_topk's streaming form with the
+ * eligibility below as one more predicate; any other k selects the k smallest keys of every row without sorting it (digit
+ * histograms of the distance word, a threshold, a collection pass, one sort of the k candidates).  Among equal distances at the
+ * threshold the items of lowest gallery index are taken, whatever order the device ran in.  "last_nearest_form" of vv_gallery_get
+ * tells which form ran; "last_sim_ms" / "last_device_ms" describe these calls too.  Device scratch stays within
+ * "scratch_limit_bytes" (a block takes fewer rows where the selection form's per-row buffers need the room), nothing of size
+ * n_q x n_ref exists on the host, and two calls return bit-identical results.
+ *
+ * vv_gallery_nearest: 1 <= k <= 2048 (= "positive_chunk").  q: host fp32 [n_q][dim].  q_ids: NULL, or host [n_q]: then only gallery
+ * items whose id differs from q_ids[i] are eligible for query i (needs a gallery created with ids).  idx / dist: host [n_q][k],
+ * ascending (d, g); where a query has fewer than k eligible items the remaining slots read idx -1, dist 0. */
+int vv_gallery_nearest(vv_ctx* ctx, vv_gallery* gallery, const float* q, int32_t n_q, const int32_t* q_ids, int32_t k,
+                       int32_t* idx, float* dist);
+/* Every item of the gallery as a query against the gallery; the query rows are read from the gallery's device features
+ * (as vv_gallery_class_stats does).  Eligible for item i: every j != i; with exclude_same_id every j of another id (needs a
+ * gallery created with ids).  idx / dist: host [n_ref][k]. */
+int vv_gallery_nearest_self(vv_ctx* ctx, vv_gallery* gallery, int32_t k, int exclude_same_id, int32_t* idx, float* dist);
 
 /* ---- class-level leave-one-out statistics on a gallery: RetrievalStatsLayer (src/caffe/layers/retrieval_stats_layer.cpp).
  * vv_gallery_pool_by_id: video_level_retrieval (:165-198).  A new gallery with one item per distinct id of `gallery`, its row the

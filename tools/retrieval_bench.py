@@ -13,6 +13,12 @@
       against vv_retrieval_stats on the same rows, alternating in one process (skipped with --no-within-batch: n^2 floats no
       longer fit), and the device time of class_stats alone, its similarity share, passes and scratch bytes.  Input: make_input
       of tests/class_stats_ref.py (noise 3.0 / 6.0, seed 11).
+  python tools/retrieval_bench.py --nearest 33,256,2048 [--nq 4096 --ng 1000000 --dim 512] [--self-n 8192,200000] [--out FILE]
+      nearest-neighbour lists (vv_gallery_nearest): topk(32), the yardstick, and nearest(K) alternate call by call in one process,
+      for every K given; per call the library's device events ("last_device_ms", "last_sim_ms"), and the selection's own share,
+      last_device_ms - last_sim_ms (uploads of the query blocks and downloads of the lists included), next to top-k's.  Then
+      nearest_self(64) on galleries of the --self-n sizes (the class-level benchmark's two).  Writes the JSON it prints to
+      profiles/nearest_<nq>x<ng>x<dim>.json (--out: elsewhere) as well.
 
 Inputs are seeded: unit rows around `nid` random centres, ids = the centre's index (the generator of tests/gallery_ref.py, drawn in
 float32 blocks so that a million rows need no float64 copy)."""
@@ -46,6 +52,64 @@ def stats(v):
     return dict(median=v[len(v) // 2], min=v[0], max=v[-1])
 
 
+def nearest_bench(eng, a):
+    ks = [int(x) for x in a.nearest.split(",")]
+    G, gid, cen = make(a.ng, a.dim, a.nid, a.noise, 5)
+    Q, qid, _ = make(a.nq, a.dim, a.nid, a.noise, 6, cen)
+    g = eng.gallery(G, gid)
+    box = {"before": eng.box_probe()}
+    res = []
+    for k in ks:
+        t = dict(topk=dict(dev=[], sim=[]), nearest=dict(dev=[], sim=[]))
+        form = scratch = None
+        for r in range(a.warmup + a.reps):
+            for name, call in (("topk", lambda: g.topk(Q, 32)), ("nearest", lambda: g.nearest(Q, k))):
+                got = call()
+                if r >= a.warmup:
+                    t[name]["dev"].append(g.get("last_device_ms")); t[name]["sim"].append(g.get("last_sim_ms"))
+                if name == "topk":
+                    head = got
+                else:
+                    form, scratch = int(g.get("last_nearest_form")), g.scratch_bytes
+                    same = bool(np.array_equal(got[0][:, :32], head[0]) and np.array_equal(got[1][:, :32].view(np.uint32), head[1].view(np.uint32)))
+        e = dict(k=k, form=form, scratch_bytes=scratch, first_32_equal_topk_32=same)
+        for name in ("topk", "nearest"):
+            dev, sim = t[name]["dev"], t[name]["sim"]
+            e[name + "_ms"] = stats(dev); e[name + "_similarity_ms"] = stats(sim)
+            e[name + "_other_ms"] = stats([d - s for d, s in zip(dev, sim)])
+        e["nearest_over_topk"] = e["nearest_ms"]["median"] / e["topk_ms"]["median"]
+        res.append(e)
+    blocks = -(-a.nq // int(g.get("query_block")))
+    g.close()
+    del G, Q
+    selfs = []
+    for n in [int(x) for x in a.self_n.split(",") if x]:
+        X, ids, _ = make(n, a.dim, max(n // 8, 1), a.noise, 7)
+        gs = eng.gallery(X, ids)
+        e = dict(n=n, k=64)
+        for name, excl in (("nearest_self", False), ("nearest_self_other_id", True)):
+            dev, sim = [], []
+            for r in range(1 + a.self_reps):
+                gs.nearest_self(64, excl)
+                if r >= 1:
+                    dev.append(gs.get("last_device_ms")); sim.append(gs.get("last_sim_ms"))
+            e[name + "_ms"] = stats(dev); e[name + "_similarity_ms"] = stats(sim)
+            e[name + "_other_ms"] = stats([d - s for d, s in zip(dev, sim)])
+        e.update(form=int(gs.get("last_nearest_form")), scratch_bytes=gs.scratch_bytes)
+        gs.close()
+        selfs.append(e)
+    box["after"] = eng.box_probe()
+    out = dict(bench="nearest", nq=a.nq, ng=a.ng, dim=a.dim, reps=a.reps, warmup=a.warmup, self_reps=a.self_reps, query_blocks=blocks,
+               yardstick="vv_gallery_topk at k = 32, alternating call by call with vv_gallery_nearest in one process",
+               timer="device events inside the library (last_device_ms, last_sim_ms); *_other_ms = device - similarity per call",
+               lists=res, self_lists=selfs, box=box)
+    path = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                 "nearest_%dx%dx%d.json" % (a.nq, a.ng, a.dim))
+    with open(path, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=4096)
@@ -62,9 +126,15 @@ def main():
     ap.add_argument("--classes", type=int, default=15)
     ap.add_argument("--videos", type=int, default=600)
     ap.add_argument("--no-within-batch", action="store_true")
+    ap.add_argument("--nearest", type=str, default=None, metavar="K[,K...]")
+    ap.add_argument("--self-n", type=str, default="8192,200000")
+    ap.add_argument("--self-reps", type=int, default=5)
+    ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     eng = vv.Engine(0, "f16")
-    if a.class_stats:
+    if a.nearest:
+        out = nearest_bench(eng, a)
+    elif a.class_stats:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
         from class_stats_ref import make_input
         X, ids, id2class = make_input(a.n, a.dim, a.videos, a.classes, 3.0, 6.0, 11)

@@ -150,6 +150,7 @@ static int create_init(vv_ctx* c) {
   if (const char* v = opt_env("VV_COMM_GATE")) c->comm_gate = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_INLINE")) c->comm_inline = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_TEST_DELAY_US")) c->comm_test_delay_us = atoi(v);
+  if (const char* v = opt_env("VV_NEAREST_SELECT_MIN_K")) c->nearest_select_min_k = std::max(1, std::min(RT_MAX_K + 1, atoi(v)));
   // lab switches (-DVV_LAB builds only; several of them produce WRONG results by design)
   if (const char* v = lab_env("VV_ABLATE")) c->ko.ablate = atoi(v);
   if (const char* v = lab_env("VV_LAB_FWD_ABL")) c->ko.lab_fwd_abl = atoi(v);
@@ -307,6 +308,11 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
   if (n == "wgrad_update") { c->wgrad_update = iv != 0; return VV_OK; }
   if (n == "comm_chunks") { c->n_chunks = std::max(1, std::min(W_CHUNKS_MAX, iv)); return VV_OK; }
   if (n == "comm_test_delay_us") { c->comm_test_delay_us = iv; return VV_OK; }
+  if (n == "nearest_select_min_k") {
+    if (iv < 1 || iv > RT_MAX_K + 1) return fail(VV_ERR_ARG, "vv_set_option: nearest_select_min_k = %d is outside 1 .. %d", iv, RT_MAX_K + 1);
+    c->nearest_select_min_k = iv;
+    return VV_OK;
+  }
 #ifdef VV_LAB
   if (n == "ablate") { c->ko.ablate = iv; return VV_OK; }
   if (n == "lab_fwd_abl") { c->ko.lab_fwd_abl = iv; return VV_OK; }
@@ -336,6 +342,7 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "wgrad_update") *value = c->wgrad_update;
   else if (n == "comm_chunks") *value = c->n_chunks;
   else if (n == "comm_test_delay_us") *value = c->comm_test_delay_us;
+  else if (n == "nearest_select_min_k") *value = c->nearest_select_min_k;
   else if (n == "last_fwd_tile_rows") *value = c->ko.last_fwd_tile_rows;
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
   else if (n == "last_update_form") *value = c->ko.last_update_form;
@@ -1875,9 +1882,12 @@ struct vv_gallery {
   uint64_t* part = nullptr; uint32_t* bins = nullptr; int32_t* out_idx = nullptr;
   int32_t *pstart = nullptr, *pcount = nullptr, *qids = nullptr; RankAcc* acc = nullptr;
   uint64_t* skeys = nullptr; uint32_t* cbins = nullptr;      // class-level statistics only: allocated by its first call
+  // the selection form of vv_gallery_nearest* only (it shares skeys: its candidate keys): allocated by its first call
+  uint32_t *sel_st = nullptr, *sel_hist = nullptr, *sel_segh = nullptr; int32_t* nn_idx = nullptr; float* nn_dist = nullptr;
   size_t scratch_bytes = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // call begin / end, similarity begin / end (of the block in flight)
   double last_sim_ms = 0, last_device_ms = 0; int last_passes = 0;
+  int last_nearest_form = 0;             // vv_gallery_nearest*: 1 streaming, 2 selection; 0 before the first call
 };
 
 static void gallery_free_scratch(vv_gallery* g) {
@@ -1885,23 +1895,36 @@ static void gallery_free_scratch(vv_gallery* g) {
   dfree(g->pstart); dfree(g->pcount); dfree(g->qids); dfree(g->acc); dfree(g->skeys); dfree(g->cbins);
   g->dist = g->qdev = g->out_dist = nullptr; g->part = nullptr; g->bins = nullptr; g->out_idx = nullptr;
   g->pstart = g->pcount = g->qids = nullptr; g->acc = nullptr; g->skeys = nullptr; g->cbins = nullptr;
+  dfree(g->sel_st); dfree(g->sel_hist); dfree(g->sel_segh); dfree(g->nn_idx); dfree(g->nn_dist);
+  g->sel_st = g->sel_hist = g->sel_segh = nullptr; g->nn_idx = nullptr; g->nn_dist = nullptr;
   g->qb_cap = 0; g->scratch_bytes = 0;
 }
 
 static_assert(sizeof(ClassAcc) == sizeof(RankAcc), "the two statistics share the per-query accumulator buffer");
 static constexpr size_t GALLERY_CLASS_ROW_BYTES = (size_t)RT_CHUNK * 8 + (size_t)3 * RT_CHUNK * 4;   // skeys + cbins of one row
 
-// cls: the call is vv_gallery_class_stats, which needs skeys / cbins as well
-static int gallery_ensure_scratch(vv_gallery* g, int rows, bool cls = false) {
-  if (rows <= g->qb_cap && (!cls || g->skeys)) return VV_OK;
+// the selection form's buffers of one row beside skeys: state, digit histogram, the segments' last-digit histograms, the lists
+static size_t gallery_sel_row_bytes(const vv_gallery* g) {
+  return 4 * 4 + (size_t)RT_SEL_BINS * 4 + (size_t)g->S * RT_SEL_LAST_BINS * 4 + 2 * (size_t)RT_CHUNK * 4;
+}
+
+// cls: the call is vv_gallery_class_stats, which needs skeys / cbins as well; sel: the selection form of vv_gallery_nearest*,
+// which needs skeys and its own buffers
+static int gallery_ensure_scratch(vv_gallery* g, int rows, bool cls = false, bool sel = false) {
+  if (rows <= g->qb_cap && (!cls || g->cbins) && (!sel || g->sel_st)) return VV_OK;
   gallery_free_scratch(g);
   const size_t r = (size_t)rows;
   const size_t b_dist = r * g->pitch * 4, b_q = r * g->Dp * 4, b_part = r * g->S * RT_MAX_K * 8, b_bins = r * 2 * RT_CHUNK * 4,
                b_out = r * RT_MAX_K * 4, b_row = r * 4, b_acc = r * sizeof(RankAcc);
-  const size_t total = b_dist + b_q + b_part + b_bins + 2 * b_out + 3 * b_row + b_acc + (cls ? r * GALLERY_CLASS_ROW_BYTES : 0);
+  const size_t total = b_dist + b_q + b_part + b_bins + 2 * b_out + 3 * b_row + b_acc + (cls ? r * GALLERY_CLASS_ROW_BYTES : 0) +
+                       (sel ? r * (gallery_sel_row_bytes(g) + (cls ? 0 : (size_t)RT_CHUNK * 8)) : 0);
   if (total > GALLERY_SCRATCH_MAX) return fail(VV_ERR_STATE, "gallery scratch of %zu bytes exceeds the limit", total);
-  if (cls) {
-    HIPCHK(hipMalloc((void**)&g->skeys, r * RT_CHUNK * 8)); HIPCHK(hipMalloc((void**)&g->cbins, r * 3 * RT_CHUNK * 4));
+  if (cls || sel) HIPCHK(hipMalloc((void**)&g->skeys, r * RT_CHUNK * 8));
+  if (cls) HIPCHK(hipMalloc((void**)&g->cbins, r * 3 * RT_CHUNK * 4));
+  if (sel) {
+    HIPCHK(hipMalloc((void**)&g->sel_st, r * 4 * 4)); HIPCHK(hipMalloc((void**)&g->sel_hist, r * RT_SEL_BINS * 4));
+    HIPCHK(hipMalloc((void**)&g->sel_segh, r * g->S * RT_SEL_LAST_BINS * 4));
+    HIPCHK(hipMalloc((void**)&g->nn_idx, r * RT_CHUNK * 4)); HIPCHK(hipMalloc((void**)&g->nn_dist, r * RT_CHUNK * 4));
   }
   HIPCHK(hipMalloc((void**)&g->dist, b_dist)); HIPCHK(hipMalloc((void**)&g->qdev, b_q));
   HIPCHK(hipMalloc((void**)&g->part, b_part)); HIPCHK(hipMalloc((void**)&g->bins, b_bins));
@@ -2014,6 +2037,7 @@ int vv_gallery_get(const vv_gallery* g, const char* name, double* value) {
   else if (n == "query_block") *value = g->qb_max;
   else if (n == "positive_chunk") *value = RT_CHUNK;
   else if (n == "last_passes") *value = g->last_passes;
+  else if (n == "last_nearest_form") *value = g->last_nearest_form;
   else if (n == "last_sim_ms") *value = g->last_sim_ms;
   else if (n == "last_device_ms") *value = g->last_device_ms;
   else return fail(VV_ERR_ARG, "vv_gallery_get: unknown name '%s'", name);
@@ -2071,6 +2095,82 @@ int vv_gallery_topk(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, int32
     if ((rc = gallery_block_done(c, g))) return rc;
   }
   return gallery_call_end(c, g);
+}
+
+// vv_gallery_nearest / vv_gallery_nearest_self.  q == NULL: the self form -- the rows of a block are the gallery's own device rows
+// and no item is eligible for itself; q_ids (host queries) / exclude (self form): only items of another id are eligible.
+// k below the context's "nearest_select_min_k": the streaming top-k with that predicate; otherwise the selection form.  Either
+// way the lists are read off the floats k_sim_f32 stored in the block's scratch rows.
+static int gallery_nearest_run(vv_ctx* c, vv_gallery* g, const float* q, int n_q, const int32_t* q_ids, bool exclude, int k,
+                               int32_t* idx, float* dist) {
+  const bool self = q == nullptr, select = k >= c->nearest_select_min_k;
+  // rows of a block: the gallery's own, fewer where the selection form's per-row buffers would pass the scratch limit
+  int block = std::min(n_q, g->qb_max);
+  if (select) {
+    const size_t row_bytes = (size_t)g->pitch * 4 + (size_t)g->Dp * 4 + (size_t)g->S * RT_MAX_K * 8 + 2 * RT_CHUNK * 4 + 2 * RT_MAX_K * 4 +
+                             3 * 4 + sizeof(RankAcc) + (size_t)RT_CHUNK * 8 + gallery_sel_row_bytes(g);
+    block = (int)std::min<size_t>(block, GALLERY_SCRATCH_MAX / row_bytes);
+    if (block < 1) return fail(VV_ERR_ARG, "vv_gallery_nearest: %lld items do not fit one query row into the scratch limit", (long long)g->n_ref);
+  }
+  int rc = gallery_ensure_scratch(g, block, false, select);
+  if (rc) return rc;
+  g->last_sim_ms = 0; g->last_device_ms = 0; g->last_passes = 0;
+  g->last_nearest_form = select ? 2 : 1;
+  HIPCHK(hipEventRecord(g->ev[0], c->stream));
+  const int ng = (int)g->n_ref;
+  for (int q0 = 0; q0 < n_q; q0 += g->qb_cap) {
+    const int rows = std::min(g->qb_cap, n_q - q0);
+    const int32_t* own = nullptr;                                       // device: the id whose items row r may not list
+    if (self) {
+      if (exclude) own = g->ref_ids + q0;
+      HIPCHK(hipEventRecord(g->ev[2], c->stream));
+      launch_sim_f32(g->feat + (size_t)q0 * g->Dp, g->feat, g->dist, rows, ng, g->Dp, g->pitch, c->stream);
+      HIPCHK(hipEventRecord(g->ev[3], c->stream));
+    } else {
+      if (q_ids) {
+        HIPCHK(hipMemcpyAsync(g->qids, q_ids + q0, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+        own = g->qids;
+      }
+      if ((rc = gallery_block_sim(c, g, q, q0, rows))) return rc;
+    }
+    const int32_t* d_idx = g->out_idx; const float* d_dist = g->out_dist;
+    if (select) {
+      HIPCHK(hipMemsetAsync(g->sel_st, 0, (size_t)rows * 4 * 4, c->stream));
+      HIPCHK(hipMemsetAsync(g->sel_hist, 0, (size_t)rows * RT_SEL_BINS * 4, c->stream));
+      launch_select(g->dist, g->pitch, rows, ng, k, g->seg, g->S, g->ref_ids, own, self ? q0 : -1, g->sel_st, g->sel_hist,
+                    g->sel_segh, g->skeys, g->nn_idx, g->nn_dist, c->stream);
+      d_idx = g->nn_idx; d_dist = g->nn_dist;
+    } else {
+      launch_topk_eligible(g->dist, g->pitch, rows, ng, k, g->seg, g->S, g->ref_ids, own, self ? q0 : -1, g->part, g->out_idx,
+                           g->out_dist, c->stream);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(idx + (size_t)q0 * k, d_idx, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(dist + (size_t)q0 * k, d_dist, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = gallery_block_done(c, g))) return rc;
+  }
+  return gallery_call_end(c, g);
+}
+
+int vv_gallery_nearest(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, const int32_t* q_ids, int32_t k, int32_t* idx,
+                       float* dist) {
+  if (!c || !g || !q || !idx || !dist) return fail(VV_ERR_ARG, "vv_gallery_nearest: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_nearest: the gallery belongs to another context");
+  if (n_q < 1) return fail(VV_ERR_ARG, "vv_gallery_nearest: n_q = %d", n_q);
+  if (k < 1 || k > RT_CHUNK) return fail(VV_ERR_ARG, "vv_gallery_nearest: k = %d is outside 1 .. %d", k, RT_CHUNK);
+  if (q_ids && !g->ref_ids) return fail(VV_ERR_ARG, "vv_gallery_nearest: q_ids given, but the gallery was created without ids");
+  VV_ENTER(c);
+  return gallery_nearest_run(c, g, q, n_q, q_ids, false, k, idx, dist);
+}
+
+int vv_gallery_nearest_self(vv_ctx* c, vv_gallery* g, int32_t k, int exclude_same_id, int32_t* idx, float* dist) {
+  if (!c || !g || !idx || !dist) return fail(VV_ERR_ARG, "vv_gallery_nearest_self: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_nearest_self: the gallery belongs to another context");
+  if (k < 1 || k > RT_CHUNK) return fail(VV_ERR_ARG, "vv_gallery_nearest_self: k = %d is outside 1 .. %d", k, RT_CHUNK);
+  if (exclude_same_id && !g->ref_ids) return fail(VV_ERR_ARG, "vv_gallery_nearest_self: exclude_same_id, but the gallery was created without ids");
+  VV_ENTER(c);
+  return gallery_nearest_run(c, g, nullptr, (int)g->n_ref, nullptr, exclude_same_id != 0, k, idx, dist);
 }
 
 int vv_gallery_rank_stats(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, const int32_t* q_ids, vv_rank_stats* out,

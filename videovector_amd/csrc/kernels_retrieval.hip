@@ -1,4 +1,5 @@
-// kernels_retrieval.hip -- gallery retrieval: fp32 similarity, streaming top-k and sort-free rank statistics.
+// kernels_retrieval.hip -- gallery retrieval: fp32 similarity, streaming top-k, sort-free rank statistics and nearest-neighbour
+// lists of up to RT_CHUNK items by radix selection.
 // gfx950 (MI355X, CDNA4) only.  Replaces the hot path of RetrievalRankStatsFixedRefLayer::Forward_cpu
 // (src/caffe/layers/retrieval_rank_stats_fixed_ref_layer.cpp:142-171): the -2 Q R^T product (:142-144), the full
 // std::sort of every query's row (:158-162) and the walk over the sorted row in ComputeApStats (:62-118).
@@ -110,17 +111,32 @@ void launch_sim_f32(const float* Q, const float* G, float* out, int nq, int ng, 
 }
 
 // ---------------------------------------------------------------------------------------------- keys
-__device__ inline uint64_t rt_key(float d, uint32_t g) {
-  uint32_t u = __float_as_uint(d);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | g;
+// the distance's bits as an unsigned integer of the same order: the high word of the key
+__device__ inline uint32_t rt_word(float d) {
+  const uint32_t u = __float_as_uint(d);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+__device__ inline uint64_t rt_key(float d, uint32_t g) { return ((uint64_t)rt_word(d) << 32) | g; }
 __device__ inline float rt_key_dist(uint64_t key) {
   uint32_t u = (uint32_t)(key >> 32);
   u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
   return __uint_as_float(u);
 }
 constexpr uint64_t RT_NOKEY = ~0ull;
+// sk[0 .. npad), npad a power of two, ascending; a 256-thread workgroup, every thread calls it (after a barrier behind the stores)
+__device__ inline void rt_bitonic(uint64_t* sk, int npad) {
+  for (int k2 = 2; k2 <= npad; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < npad; i += 256) {
+        const int x = i ^ j;
+        if (x > i) {
+          const uint64_t a = sk[i], b = sk[x];
+          if ((a > b) == ((i & k2) == 0)) { sk[i] = b; sk[x] = a; }
+        }
+      }
+      __syncthreads();
+    }
+}
 
 // ---------------------------------------------------------------------------------------------- top-k
 // One wave keeps the k smallest keys it has seen, sorted, ONE PER LANE (lanes >= k hold RT_NOKEY), and offers every new key
@@ -143,17 +159,20 @@ __device__ inline void rt_offer(uint64_t key, bool cand, uint64_t& mine, uint64_
 }
 
 // grid (S, rows): workgroup (s, row) scans gallery items [s seg, (s+1) seg) of the row, part[row][s][k] = its k smallest keys.
-// OTHER_ID: only items whose id differs from the row's own (ids[q0 + row]; the rows are gallery items q0 ..) are offered:
-// "the nearest items of other videos" of RetrievalStatsLayer (retrieval_stats_layer.cpp:310-316).
-template <bool OTHER_ID>
+// OTHER_ID: only items whose id differs from the row's own (own[row]; own = ids + q0 where the rows are gallery items q0 ..) are
+// offered: "the nearest items of other videos" of RetrievalStatsLayer (retrieval_stats_layer.cpp:310-316).
+// NOT_SELF: the rows are gallery items q0 .., and item q0 + row is not offered to its own row (vv_gallery_nearest_self).
+template <bool OTHER_ID, bool NOT_SELF = false>
 __global__ __launch_bounds__(256) void k_topk_part(const float* __restrict__ dist, int64_t pitch, int ng, int k, int seg,
-                                                   const int32_t* __restrict__ ids, int q0, uint64_t* __restrict__ part) {
+                                                   const int32_t* __restrict__ ids, const int32_t* __restrict__ own, int q0,
+                                                   uint64_t* __restrict__ part) {
   __shared__ uint64_t sl[4][32];
   const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int begin = s * seg, end = min(ng, begin + seg);
   const float* d = dist + (int64_t)row * pitch;
-  int32_t own = 0;
-  if (OTHER_ID) own = ids[q0 + row];
+  int32_t oid = 0;
+  if (OTHER_ID) oid = own[row];
+  const int self = q0 + row;
   uint64_t mine = RT_NOKEY, kth = RT_NOKEY;
   for (int base = begin; base < end; base += 1024) {               // seg is a multiple of 1024, pitch of 4
     const int i = base + tid * 4;
@@ -161,8 +180,9 @@ __global__ __launch_bounds__(256) void k_topk_part(const float* __restrict__ dis
     if (i < end) v = *(const float4*)(d + i);                      // i + 3 < pitch: the row's pad may be read, never ranked
     bool c0 = i < end, c1 = i + 1 < end, c2 = i + 2 < end, c3 = i + 3 < end;
     if (OTHER_ID) {                                                // (ids has ng entries: every read is guarded)
-      c0 = c0 && ids[i] != own; c1 = c1 && ids[i + 1] != own; c2 = c2 && ids[i + 2] != own; c3 = c3 && ids[i + 3] != own;
+      c0 = c0 && ids[i] != oid; c1 = c1 && ids[i + 1] != oid; c2 = c2 && ids[i + 2] != oid; c3 = c3 && ids[i + 3] != oid;
     }
+    if (NOT_SELF) { c0 = c0 && i != self; c1 = c1 && i + 1 != self; c2 = c2 && i + 2 != self; c3 = c3 && i + 3 != self; }
     rt_offer(rt_key(v.x, (uint32_t)i), c0, mine, kth, lane, k);
     rt_offer(rt_key(v.y, (uint32_t)i + 1), c1, mine, kth, lane, k);
     rt_offer(rt_key(v.z, (uint32_t)i + 2), c2, mine, kth, lane, k);
@@ -194,12 +214,25 @@ __global__ __launch_bounds__(64) void k_topk_merge(const uint64_t* __restrict__ 
 }
 void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, uint64_t* part, int32_t* idx,
                  float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_topk_part<false>, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, (const int32_t*)nullptr, 0, part);
+  hipLaunchKernelGGL(k_topk_part<false>, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, (const int32_t*)nullptr,
+                     (const int32_t*)nullptr, 0, part);
   hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(64), 0, s, part, S, k, idx, dst);
 }
 void launch_topk_other_id(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids, int q0,
                           uint64_t* part, int32_t* idx, float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_topk_part<true>, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, ids, q0, part);
+  hipLaunchKernelGGL(k_topk_part<true>, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, k, seg, ids, ids + q0, q0, part);
+  hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(64), 0, s, part, S, k, idx, dst);
+}
+// The streaming form of vv_gallery_nearest*: own != NULL: row r is offered only the items whose id differs from own[r];
+// self0 >= 0: the rows are gallery items self0 .., none is offered to itself.
+void launch_topk_eligible(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids,
+                          const int32_t* own, int self0, uint64_t* part, int32_t* idx, float* dst, hipStream_t s) {
+  const dim3 grid(S, rows), wg(256);
+  const int q0 = self0 < 0 ? 0 : self0;
+  if (own && self0 >= 0) hipLaunchKernelGGL((k_topk_part<true, true>), grid, wg, 0, s, dist, pitch, ng, k, seg, ids, own, q0, part);
+  else if (own) hipLaunchKernelGGL((k_topk_part<true, false>), grid, wg, 0, s, dist, pitch, ng, k, seg, ids, own, q0, part);
+  else if (self0 >= 0) hipLaunchKernelGGL((k_topk_part<false, true>), grid, wg, 0, s, dist, pitch, ng, k, seg, ids, own, q0, part);
+  else hipLaunchKernelGGL((k_topk_part<false, false>), grid, wg, 0, s, dist, pitch, ng, k, seg, ids, own, q0, part);
   hipLaunchKernelGGL(k_topk_merge, dim3(rows), dim3(64), 0, s, part, S, k, idx, dst);
 }
 
@@ -220,17 +253,7 @@ __device__ inline int rt_load_sorted(uint64_t* sk, const float* d, const int32_t
     sk[j] = key;
   }
   __syncthreads();
-  for (int k2 = 2; k2 <= npad; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += 256) {
-        const int x = i ^ j;
-        if (x > i) {
-          const uint64_t a = sk[i], b = sk[x];
-          if ((a > b) == ((i & k2) == 0)) { sk[i] = b; sk[x] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  rt_bitonic(sk, npad);
   *npad_out = npad;
   return n;
 }
@@ -505,6 +528,189 @@ void launch_class_pass(const float* dist, int64_t pitch, int rows, int ng, int s
   hipLaunchKernelGGL(k_class_count, dim3(S, rows), dim3(256), 0, s, dist, pitch, ng, seg, skeys, pcount, ids, cls, q0, exclude,
                      pass, bins);
   hipLaunchKernelGGL(k_class_final, dim3(rows), dim3(256), 0, s, skeys, pcount, ids, q0, exclude, pass, bins, acc);
+}
+
+// ---------------------------------------------------------------------------------------------- nearest-neighbour lists
+// vv_gallery_nearest*, selection form: the k smallest eligible keys of every scratch row for k up to RT_CHUNK, the row never
+// sorted.  Radix select on the key's high word (rt_word), most significant digit first, digits of 12, 12 and 8 bits:
+//   k_sel_hist<P>   grid (S, rows): the histogram of digit P over the segment's eligible items whose higher digits equal the
+//                   threshold's, in LDS, its non-zero bins added to hist[row][4096]
+//   k_sel_scan<P>   grid (rows), one wave: the bin in which the running count reaches the count still wanted becomes digit P of
+//                   the threshold T; the wanted count drops by the items in the bins below it; the bins are cleared for P + 1
+// After digit 2, T is the word of the k-th eligible key and st[1] = k - #{eligible words < T}: how many of the keys with word
+// == T are taken.  Those are the ones of LOWEST GALLERY INDEX, whatever order the workgroups run in: k_sel_hist<2> keeps every
+// segment's own histogram (segh[row][s][256]), so k_sel_collect knows how many equal words the segments before its own hold and
+// numbers its own by an in-workgroup scan in index order.  Words below T go to the row's candidates at positions drawn from an
+// atomic counter -- k_sel_sort orders the at most RT_CHUNK candidates in LDS and writes the lists.
+// A row with fewer than k eligible items (st[2] = 1, found by k_sel_scan<0>) skips digits 1 and 2 and takes every eligible item.
+// st: uint32 [rows][4] = {T, wanted, take-all, candidates below T}, zero on entry; hist: zero on entry.
+// Eligible for row r: every item; with own != NULL those whose id differs from own[r]; with self0 >= 0 not item self0 + r.
+constexpr int SEL_BINS = RT_SEL_BINS, SEL_LAST_BINS = RT_SEL_LAST_BINS;        // 12-bit digits 0 and 1, 8-bit digit 2
+
+__device__ inline bool rt_eligible(int g, const int32_t* __restrict__ ids, bool other, int32_t oid, int self) {
+  return g != self && (!other || ids[g] != oid);
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ dist, int64_t pitch, int ng, int seg,
+                                                  const int32_t* __restrict__ ids, const int32_t* __restrict__ own, int self0,
+                                                  const uint32_t* __restrict__ st, uint32_t* __restrict__ hist,
+                                                  uint32_t* __restrict__ segh) {
+  constexpr int SHIFT = P == 0 ? 20 : P == 1 ? 8 : 0, NB = P == 2 ? SEL_LAST_BINS : SEL_BINS, HI = P == 1 ? 20 : 8;
+  __shared__ uint32_t sh[NB];
+  const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  if (P > 0 && st[row * 4 + 2]) return;                              // (uniform) fewer than k eligible items: all are taken
+  const uint32_t T = P > 0 ? st[row * 4] : 0;
+  for (int j = tid; j < NB; j += 256) sh[j] = 0;
+  __syncthreads();
+  const float* d = dist + (int64_t)row * pitch;
+  const bool other = own != nullptr;
+  const int32_t oid = other ? own[row] : 0;
+  const int self = self0 < 0 ? -1 : self0 + row;
+  const int begin = s * seg, end = min(ng, begin + seg);
+  for (int base = begin; base < end; base += 1024) {                 // seg is a multiple of 1024, pitch of 4
+    const int i = base + tid * 4;
+    if (i >= end) continue;
+    const float4 v = *(const float4*)(d + i);                        // i + 3 < pitch: the row's pad may be read, never counted
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = i + u;
+      if (g >= end || !rt_eligible(g, ids, other, oid, self)) continue;
+      const uint32_t w = rt_word(e[u]);
+      if (P == 0 || (w >> HI) == (T >> HI)) atomicAdd(&sh[(w >> SHIFT) & (NB - 1)], 1u);
+    }
+  }
+  __syncthreads();
+  for (int j = tid; j < NB; j += 256)
+    if (sh[j]) atomicAdd(&hist[(int64_t)row * SEL_BINS + j], sh[j]);
+  if (P == 2) segh[((int64_t)row * gridDim.x + s) * SEL_LAST_BINS + tid] = sh[tid];
+}
+
+template <int P>
+__global__ __launch_bounds__(64) void k_sel_scan(uint32_t* __restrict__ hist, uint32_t* __restrict__ st, int k) {
+  constexpr int SHIFT = P == 0 ? 20 : P == 1 ? 8 : 0, NB = P == 2 ? SEL_LAST_BINS : SEL_BINS, PER = NB / 64;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  uint32_t* sr = st + row * 4;
+  if (P > 0 && sr[2]) return;
+  uint32_t* h = hist + (int64_t)row * SEL_BINS + lane * PER;          // this lane's PER consecutive bins
+  const uint32_t want = P == 0 ? (uint32_t)k : sr[1];
+  uint32_t sum = 0;
+  for (int j = 0; j < PER; j += 4) { const uint4 v = *(const uint4*)(h + j); sum += v.x + v.y + v.z + v.w; }
+  uint32_t incl = sum;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t a = __shfl_up(incl, o); if (lane >= o) incl += a; }
+  const uint32_t total = __shfl(incl, 63), excl = incl - sum;
+  if (total < want) {                                                  // only at P = 0: later digits count >= `want` items
+    if (lane == 0) { sr[0] = 0xffffffffu; sr[1] = 0; sr[2] = 1; }
+  } else if (excl < want && want <= incl) {                            // exactly one lane
+    uint32_t below = excl;
+    int bin = 0;
+    for (; bin < PER - 1; ++bin) { const uint32_t c = h[bin]; if (below + c >= want) break; below += c; }
+    sr[0] = (P == 0 ? 0u : sr[0]) | ((uint32_t)(lane * PER + bin) << SHIFT);
+    sr[1] = want - below;
+  }
+  for (int j = 0; j < PER; j += 4) *(uint4*)(h + j) = make_uint4(0, 0, 0, 0);
+}
+
+// grid (S, rows).  cand: uint64 [rows][RT_CHUNK].
+__global__ __launch_bounds__(256) void k_sel_collect(const float* __restrict__ dist, int64_t pitch, int ng, int seg, int k,
+                                                     const int32_t* __restrict__ ids, const int32_t* __restrict__ own, int self0,
+                                                     uint32_t* __restrict__ st, const uint32_t* __restrict__ segh,
+                                                     uint64_t* __restrict__ cand) {
+  __shared__ uint32_t wtot[4];
+  const int row = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t T = st[row * 4], want_eq = st[row * 4 + 1];
+  const bool all = st[row * 4 + 2] != 0;
+  const uint32_t below = (uint32_t)k - want_eq;                        // (unused with `all`) the candidates' slots for words == T
+  uint64_t* c = cand + (int64_t)row * RT_CHUNK;
+  // equal words in the segments before this one, and whether this segment has any that are taken
+  uint32_t eqbase = 0;
+  bool ties = false;
+  if (!all) {
+    const uint32_t* sg = segh + (int64_t)row * gridDim.x * SEL_LAST_BINS + (T & (SEL_LAST_BINS - 1));
+    for (int t = 0; t < s; ++t) eqbase += sg[t * SEL_LAST_BINS];
+    ties = eqbase < want_eq && sg[s * SEL_LAST_BINS] != 0;
+  }
+  const float* d = dist + (int64_t)row * pitch;
+  const bool other = own != nullptr;
+  const int32_t oid = other ? own[row] : 0;
+  const int self = self0 < 0 ? -1 : self0 + row;
+  const int begin = s * seg, end = min(ng, begin + seg);
+  for (int base = begin; base < end; base += 1024) {
+    const int i = base + tid * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < end) v = *(const float4*)(d + i);
+    const float e[4] = {v.x, v.y, v.z, v.w};
+    uint32_t w[4];
+    bool el[4], eq[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = i + u;
+      el[u] = g < end && rt_eligible(g, ids, other, oid, self);
+      w[u] = rt_word(e[u]);
+      eq[u] = el[u] && !all && w[u] == T;
+      if (el[u] && (all || w[u] < T)) {
+        const uint32_t pos = atomicAdd(&st[row * 4 + 3], 1u);          // fewer than k of them
+        if (pos < (uint32_t)RT_CHUNK) c[pos] = ((uint64_t)w[u] << 32) | (uint32_t)g;
+      }
+    }
+    if (!ties) continue;                                               // (uniform over the workgroup)
+    // ordinal of an equal word among the row's equal words in index order: thread t holds items base + 4 t .. + 3
+    const uint64_t lower = ((uint64_t)1 << lane) - 1;
+    uint32_t before = 0, wsum = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t m = __ballot(eq[u]);
+      before += (uint32_t)__popcll(m & lower);
+      wsum += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) wtot[wave] = wsum;
+    __syncthreads();
+    uint32_t chunk = 0;
+    for (int t = 0; t < 4; ++t) { if (t < wave) before += wtot[t]; chunk += wtot[t]; }
+    __syncthreads();                                                   // wtot is written again in the next round
+    uint32_t ord = eqbase + before;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (eq[u]) {
+        if (ord < want_eq && below + ord < (uint32_t)RT_CHUNK) c[below + ord] = ((uint64_t)T << 32) | (uint32_t)(i + u);
+        ++ord;
+      }
+    eqbase += chunk;
+    ties = eqbase < want_eq;
+  }
+}
+
+// grid (rows).  idx / dst: [rows][k]; slots past the eligible count read -1 / 0.
+__global__ __launch_bounds__(256) void k_sel_sort(const uint64_t* __restrict__ cand, const uint32_t* __restrict__ st, int k,
+                                                  int32_t* __restrict__ idx, float* __restrict__ dst) {
+  __shared__ uint64_t sk[RT_CHUNK];
+  const int row = blockIdx.x;
+  const int n = st[row * 4 + 2] ? (int)min(st[row * 4 + 3], (uint32_t)k) : k;
+  int npad = 1;
+  while (npad < n) npad <<= 1;
+  for (int j = threadIdx.x; j < npad; j += 256) sk[j] = j < n ? cand[(int64_t)row * RT_CHUNK + j] : RT_NOKEY;
+  __syncthreads();
+  rt_bitonic(sk, npad);
+  for (int j = threadIdx.x; j < k; j += 256) {
+    const uint64_t key = j < n ? sk[j] : RT_NOKEY;
+    idx[(int64_t)row * k + j] = j < n ? (int32_t)(uint32_t)key : -1;
+    dst[(int64_t)row * k + j] = j < n ? rt_key_dist(key) : 0.f;
+  }
+}
+
+void launch_select(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids,
+                   const int32_t* own, int self0, uint32_t* st, uint32_t* hist, uint32_t* segh, uint64_t* cand, int32_t* idx,
+                   float* dst, hipStream_t s) {
+  const dim3 grid(S, rows), wg(256);
+  hipLaunchKernelGGL(k_sel_hist<0>, grid, wg, 0, s, dist, pitch, ng, seg, ids, own, self0, st, hist, segh);
+  hipLaunchKernelGGL(k_sel_scan<0>, dim3(rows), dim3(64), 0, s, hist, st, k);
+  hipLaunchKernelGGL(k_sel_hist<1>, grid, wg, 0, s, dist, pitch, ng, seg, ids, own, self0, st, hist, segh);
+  hipLaunchKernelGGL(k_sel_scan<1>, dim3(rows), dim3(64), 0, s, hist, st, k);
+  hipLaunchKernelGGL(k_sel_hist<2>, grid, wg, 0, s, dist, pitch, ng, seg, ids, own, self0, st, hist, segh);
+  hipLaunchKernelGGL(k_sel_scan<2>, dim3(rows), dim3(64), 0, s, hist, st, k);
+  hipLaunchKernelGGL(k_sel_collect, grid, wg, 0, s, dist, pitch, ng, seg, k, ids, own, self0, st, segh, cand);
+  hipLaunchKernelGGL(k_sel_sort, dim3(rows), dim3(64 * 4), 0, s, cand, st, k, idx, dst);
 }
 
 // ---------------------------------------------------------------------------------------------- pooling by id

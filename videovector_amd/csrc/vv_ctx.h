@@ -157,6 +157,7 @@ struct vv_ctx {
   bool grads_lost = false;                  // the last step's dW was consumed in registers (vv_grads_* refuse until the next backward pass)
   uint32_t* lab_score_ts = nullptr;         // (lab builds) device buffer of k_score_fwd's phase stamps, api.hip
   bool comm_inline = true;                  // option "comm_inline" (VV_COMM_INLINE): the sharded update queued on the compute stream itself (no second stream, no gate)
+  int nearest_select_min_k = 33;    // "nearest_select_min_k" / VV_NEAREST_SELECT_MIN_K: vv_gallery_nearest* use the selection form from this k on (1 .. 33)
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

@@ -511,6 +511,17 @@ struct ClassAcc { double ap_sum; int32_t npos, acc1, n5, pad_; };      // Comput
 // as launch_topk, over the items whose id differs from the row's own
 void launch_topk_other_id(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids, int q0,
                           uint64_t* part, int32_t* idx, float* dst, hipStream_t s);
+// Nearest-neighbour lists (vv_gallery_nearest*).  Eligible for row r: every item; own != NULL: those whose id (ids[]) differs from
+// own[r]; self0 >= 0: the rows are gallery items self0 .., item self0 + r is not eligible for row r.
+// Streaming form, k <= RT_MAX_K: launch_topk with that predicate.
+void launch_topk_eligible(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids,
+                          const int32_t* own, int self0, uint64_t* part, int32_t* idx, float* dst, hipStream_t s);
+// Selection form, k <= RT_CHUNK.  st: uint32 [rows][4] and hist: uint32 [rows][RT_SEL_BINS], both zero on entry;
+// segh: uint32 [rows][S][RT_SEL_LAST_BINS]; cand: uint64 [rows][RT_CHUNK]; idx / dst: [rows][k]
+constexpr int RT_SEL_BINS = 4096, RT_SEL_LAST_BINS = 256;
+void launch_select(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids,
+                   const int32_t* own, int self0, uint32_t* st, uint32_t* hist, uint32_t* segh, uint64_t* cand, int32_t* idx,
+                   float* dst, hipStream_t s);
 // cpos: item indices grouped by class; ids / cls: id and class of every item; skeys: uint64 [rows][RT_CHUNK];
 // bins: uint32 [rows][3][RT_CHUNK], zero on entry
 void launch_class_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* cpos,

@@ -122,6 +122,8 @@ def load_library():
         "vv_gallery_get": [vp, C.c_char_p, C.POINTER(C.c_double)],
         "vv_gallery_pool_by_id": [vp, vp, C.POINTER(vp)],
         "vv_gallery_class_stats": [vp, vp, vp, vp, i32, C.c_int, C.POINTER(_ClassStats), vp, vp, vp, vp],
+        "vv_gallery_nearest": [vp, vp, vp, i32, vp, i32, vp, vp],
+        "vv_gallery_nearest_self": [vp, vp, i32, C.c_int, vp, vp],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
@@ -174,6 +176,28 @@ class Gallery:
         idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
         dist = np.empty(idx.shape, np.float32)
         self.eng._chk(self.eng.L.vv_gallery_topk(self.eng.h, self.h, _ptr(q), q.shape[0], int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def nearest(self, q, k, q_ids=None):
+        """(idx int32 [n_q][k], dist fp32 [n_q][k]): the k <= 2048 nearest reference items, ascending (distance, index); with q_ids
+        [n_q] only items whose id differs from the query's.  Slots past a query's eligible items read -1 / 0."""
+        q = self._queries(q)
+        qid = None
+        if q_ids is not None:
+            qid = np.ascontiguousarray(q_ids, dtype=np.int32)
+            if qid.shape != (q.shape[0],):
+                raise VVError("nearest: q_ids must be [n_q]")
+        idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
+        dist = np.empty(idx.shape, np.float32)
+        self.eng._chk(self.eng.L.vv_gallery_nearest(self.eng.h, self.h, _ptr(q), q.shape[0], _ptr(qid), int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def nearest_self(self, k, exclude_same_id=False):
+        """(idx int32 [n_ref][k], dist fp32 [n_ref][k]): every item's k <= 2048 nearest OTHER items of the gallery; with
+        exclude_same_id only items of another id.  Slots past an item's eligible items read -1 / 0."""
+        idx = np.empty((self.n_ref, max(int(k), 0)), np.int32)
+        dist = np.empty(idx.shape, np.float32)
+        self.eng._chk(self.eng.L.vv_gallery_nearest_self(self.eng.h, self.h, int(k), int(bool(exclude_same_id)), _ptr(idx), _ptr(dist)))
         return idx, dist
 
     def rank_stats(self, q, q_ids, per_query=False):
