@@ -61,7 +61,12 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  * per-object configuration, not globals.
  *   "dedup" (VV_DEDUP, 1)            row de-duplication, as vv_set_dedup
  *   "seg_bwd" (VV_SEG_BWD, 1)        segment-wise backward of de-duplicated batches (0: per-instance gradient rows + their sums)
- *   "drop_dedup" (VV_DROP_DEDUP, 1)  dropout on the de-duplicated path where the kernels carry per-instance masks (D = 512); 0: dense
+ *   "drop_dedup" (VV_DROP_DEDUP, 1)  on which shapes a dropout step stays de-duplicated (the score and segment kernels carry per-instance masks over the
+ *                                    shared pre-dropout rows): 0 none -- dense, the mask in the forward GEMM's epilogue; 1 the shapes of the
+ *                                    register-resident score kernel (D = 512, up to 55 negatives and 6 context rows); 2 every shape of the
+ *                                    segment-wise path (D = 512 or 1024; the one-sweep score kernel and the two-chunk segment backward; dropout
+ *                                    steps then run with "v16" off).  All three drop the same elements.  Any other value: VV_ERR_ARG (an invalid
+ *                                    VV_DROP_DEDUP leaves the default)
  *   "h16" (VV_H16, 1)                ip2 stored as f16 between the forward GEMM and the segment-wise score / backward kernels (de-duplicated batches
  *                                    of D = 512 / 1024): half the bytes of the GEMM's epilogue and of every later read of a row; adds one f16 rounding
  *                                    (2^-12 relative per element; values past 65504 saturate) to the embeddings the loss is computed from --
@@ -95,6 +100,8 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *                                    vv_gallery_from_table); 0 before the first launch
  *   "last_wgrad_splits"              splits of K (S) of the weight-gradient GEMM (a step or vv_op_inner_product_bwd); 0 before the first launch
  *   "last_update_form"               what the last vv_apply_update ran for the parameter matrix: 1 k_sgd with 16-byte accesses (the chunked and sharded updates too), 2 k_sgd scalar (F % 4 != 0), 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0 before the first update
+ *   "last_score_form"                what the last forward pass launched for scores and loss: 1 k_score_fwd (register-resident), 2 k_score_stream at
+ *                                    D = 512, 3 k_score_stream at D = 1024, 4 the per-instance kernels (dense or row-writing execution); 0 before the first step
  * Retired options -- "fwd_merge", "score_stream", "comm_first_inline": their alternatives were measured, lost and removed.  They read as 0,
  * the value the library always runs with; setting 0 is accepted, any other value is VV_ERR_ARG.  Their environment variables are not read.
  * Ablated / experimental kernels (timing studies whose results may be wrong) are NOT reachable through this library: they and their

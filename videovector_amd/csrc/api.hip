@@ -146,7 +146,11 @@ static int create_init(vv_ctx* c) {
   if (const char* v = opt_env("VV_V16")) c->v16 = atoi(v) != 0;
   if (const char* v = opt_env("VV_DEDUP")) c->dedup = atoi(v) != 0;
   if (const char* v = opt_env("VV_FUSE_UPDATE")) c->fuse_update = atoi(v) != 0;
-  if (const char* v = opt_env("VV_DROP_DEDUP")) c->drop_dedup = atoi(v) != 0;
+  if (const char* v = opt_env("VV_DROP_DEDUP")) {                 // 0, 1 or 2; anything else leaves the default
+    char* end = nullptr;
+    const double dv = strtod(v, &end);
+    if (end != v && *end == 0 && (dv == 0.0 || dv == 1.0 || dv == 2.0)) c->drop_dedup = (int)dv;
+  }
   if (const char* v = opt_env("VV_COMM_GATE")) c->comm_gate = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_INLINE")) c->comm_inline = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_TEST_DELAY_US")) c->comm_test_delay_us = atoi(v);
@@ -290,11 +294,15 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     if (iv == 0) return VV_OK;
     return fail(VV_ERR_ARG, "vv_set_option: option '%s' is retired; only its fixed value 0 is accepted", name);
   }
-  if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form")
+  if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form" || n == "last_score_form")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
-  if (n == "drop_dedup") { c->drop_dedup = iv != 0; return VV_OK; }
+  if (n == "drop_dedup") {
+    if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(VV_ERR_ARG, "vv_set_option: drop_dedup = %g is none of 0 (dense), 1 (the register-resident shapes), 2 (every segment-path shape)", value);
+    c->drop_dedup = iv;
+    return VV_OK;
+  }
   if (n == "h16") { c->h16 = iv != 0; return VV_OK; }
   if (n == "slab16") { c->slab16 = iv != 0; return VV_OK; }
   if (n == "v16") { c->v16 = iv != 0; return VV_OK; }
@@ -346,6 +354,7 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "last_fwd_tile_rows") *value = c->ko.last_fwd_tile_rows;
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
   else if (n == "last_update_form") *value = c->ko.last_update_form;
+  else if (n == "last_score_form") *value = c->ko.last_score_form;
   else return fail(VV_ERR_ARG, "vv_get_option: unknown option '%s'", name);
   return VV_OK;
 }
@@ -967,12 +976,13 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   }
 
   // De-duplicate the batch rows.  Dropout sits BEHIND the projection (fc7 -> ReLU -> drop2, mednet_embedding_train.prototxt:190-230): the
-  // projection of equal rows is equal, only the mask differs per instance.  Where the segment-wise pair carries the masks (k_score_fwd +
-  // k_seg_bwd at D = 512: every instance masks its row as it reads it, the backward sums m_i-weighted terms per distinct row) dropout
-  // rides the de-duplicated path; on the other shapes it stays dense (the mask in the forward GEMM's epilogue).  The two executions
-  // evaluate the same mask function (vv_internal.h: DropSpec).
+  // projection of equal rows is equal, only the mask differs per instance.  The segment-wise pair carries the masks (k_score_fwd /
+  // k_score_stream + k_seg_bwd at D = 512 and 1024: every instance masks its row as it reads it, the backward sums m_i-weighted terms per
+  // distinct row), and option "drop_dedup" says on which of its shapes dropout rides the de-duplicated path: 1, the default, the shapes of
+  // the register-resident k_score_fwd; 2 every shape of the pair; 0 none.  Elsewhere it stays dense (the mask in the forward GEMM's
+  // epilogue).  The two executions evaluate the same mask function (vv_internal.h: DropSpec).
   const bool drop_on = cfg->dropout_ratio > 0.f;
-  const bool drop_dd = drop_on && c->drop_dedup && c->seg_bwd && score_fwd_dropout_supported(D, C, Nn);
+  const bool drop_dd = drop_on && c->drop_dedup && c->seg_bwd && score_fwd_dropout_supported(c->drop_dedup, D, C, Nn);
   const bool dd = c->dedup && (!drop_on || drop_dd) && !ablate_on();
   DropSpec dsp;
   if (drop_on) {
@@ -1626,6 +1636,7 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
     }
     DevTmp<float> yrows; DevTmp<uint16_t> dyrows;
     bool expanded = false;
+    const int score_form = c->ko.last_score_form;     // ("last_score_form" names the forward pass's kernel, not this accessor's)
     if (c->last_seg_bwd && (c->last_drop.mode || c->last_h16)) {
       // ... with dropout: the instances' masked rows are materialised (item-major) and the per-instance kernel runs on them as on a
       // dense batch whose forward pass applied the mask -- its gradient rows come out per instance, nothing to ungroup
@@ -1639,6 +1650,7 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
       la.drop = DropSpec(); la.bound_out = nullptr; la.h16 = 0;
       la.sg = sgf; la.guard = GuardArgs();
       launch_score_loss(c->prec, la, c->stream);
+      c->ko.last_score_form = score_form;
       expanded = true;
     } else if (c->last_seg_bwd) {
       // the step kept its backward factored: produce the per-instance rows now (same forward values; the loss partials
@@ -1646,6 +1658,7 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
       ScoreArgs la = c->last_score;
       la.sg = sgf; la.guard = GuardArgs();
       launch_score_loss(c->prec, la, c->stream);
+      c->ko.last_score_form = score_form;
     }
     if (expanded) {
       launch_dyh_to_float(c->prec, dyrows, c->R, D, c->Dp, 1.f / sgf, d, c->stream);

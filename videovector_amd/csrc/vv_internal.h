@@ -415,12 +415,15 @@ struct KernelOpts {
   int score_reg = 1;       // (lab) VV_SCORE_REG=0: the LDS-resident score kernel
   int score_rr = 0;        // (lab) VV_SCORE_RR=1: the item-major kernels deal their items round-robin over the XCDs again (kernels_elem.hip: item_of_block)
   // What the launchers last chose for this context (read-only through vv_get_option: "last_fwd_tile_rows", "last_wgrad_splits",
-  // "last_update_form"): written where the kernel is launched (launch_fwd_ph_q / launch_wgrad_gemm / launch_sgd / launch_reduce_sgd), so a test
+  // "last_update_form", "last_score_form"): written where the kernel is launched (launch_fwd_ph_q / launch_wgrad_gemm / launch_sgd /
+  // launch_reduce_sgd / launch_score_fwd / launch_score_loss), so a test
   // can assert the form it ran without a copy of the pickers' rules.
   mutable int last_fwd_tile_rows = 0;   // rows of the forward GEMM's tile (128, 192, 256); 0: no launch yet
   mutable int last_wgrad_splits = 0;    // S (splits of K) of the weight-gradient GEMM; 0: no launch yet
   mutable int last_update_form = 0;     // what last updated the parameter matrix: 1 k_sgd 16-byte (chunked / sharded launches too), 2 k_sgd scalar,
                                         // 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0: no update yet
+  mutable int last_score_form = 0;      // what last computed scores and loss: 1 k_score_fwd, 2 k_score_stream at D = 512, 3 k_score_stream at D = 1024,
+                                        // 4 the per-instance kernels (launch_score_loss); 0: no forward pass yet
 };
 extern thread_local const KernelOpts* g_ko;
 inline const KernelOpts& ko() { static const KernelOpts dflt; return g_ko ? *g_ko : dflt; }
@@ -455,7 +458,7 @@ void launch_dedup(const DedupArgs& a, hipStream_t s);
 void launch_dedup_groups(const DedupArgs& a, hipStream_t s);
 void launch_dedup_pos(const DedupArgs& a, hipStream_t s);   // pos[] for the debug accessors only
 void launch_segsum(int prec, const SegsumArgs& a, hipStream_t s);
-bool score_fwd_dropout_supported(int D, int C, int Nn);
+bool score_fwd_dropout_supported(int drop_dedup, int D, int C, int Nn);   // drop_dedup: the option's value (0, 1, 2)
 bool score_fwd_supported(const ScoreArgs& a);               // shapes the segment-wise pair is built for
 void launch_score_fwd(const ScoreArgs& a, hipStream_t s);   // forward + factored backward records (dedup mode)
 void launch_seg_bwd(int prec, const SegBwdArgs& a, hipStream_t s);
