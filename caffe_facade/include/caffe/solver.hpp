@@ -49,6 +49,7 @@ class Solver {
 
   SolverParameter param_;
   int iter_;
+  bool h16_warned_ = false;            // the one warning line of the f16 rows' fallback has been written (Step)
   shared_ptr<Net<Dtype> > net_;
   vector<shared_ptr<Net<Dtype> > > test_nets_;
 };

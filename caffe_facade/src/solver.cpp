@@ -5,6 +5,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <sstream>
 #include <string>
 
@@ -99,6 +100,11 @@ void Solver<Dtype>::Init(const SolverParameter& param) {
   if (param_.get_int("random_seed") >= 0) Caffe::set_random_seed((unsigned)param_.get_int("random_seed"));   // solver.cpp:37-39
   InitTrainNet();
   InitTestNets();
+  // A training job must never go on, unnoticed, on embeddings that f16's range has clipped: the solver runs its engine with "h16_guard" 2
+  // (include/videovec.h: once a step's report shows saturated elements or faint rows of ip2, every later step stores fp32 rows) unless
+  // VV_H16_GUARD names another value, which the context took when it was created.
+  const char* hg = getenv("VV_H16_GUARD");
+  if (!hg || !*hg) VV_CHECK(vv_set_option(Caffe::ctx(), "h16_guard", 2));
   LOG(INFO) << "Solver scaffolding done.";
 }
 
@@ -156,6 +162,17 @@ void Solver<Dtype>::Step(bool display) {
   // weight-gradient GEMM's epilogue and the gradient never exists outside its registers)
   if (!param_.get_bool("snapshot_diff")) net_->HintUpdate();
   const Dtype loss = net_->ForwardBackward(no_bottom);
+  if (!h16_warned_) {                               // (a flag of the context: nothing is read from the device)
+    double fb = 0, sat = 0, faint = 0;
+    VV_CHECK(vv_get_option(Caffe::ctx(), "h16_fallback", &fb));
+    if (fb != 0) {
+      VV_CHECK(vv_get_option(Caffe::ctx(), "h16_flagged_saturated", &sat));
+      VV_CHECK(vv_get_option(Caffe::ctx(), "h16_flagged_faint_rows", &faint));
+      LOG(WARNING) << "Iteration " << iter_ << ", ip2 left f16's range: " << (long long)sat << " saturated elements, " << (long long)faint
+                   << " faint rows in the step reported now (four iterations back); fp32 rows from this iteration on";
+      h16_warned_ = true;
+    }
+  }
   if (display) {
     LOG(INFO) << "Iteration " << iter_ << ", loss = " << loss;                          // solver.cpp:196
     vector<Dtype> values;

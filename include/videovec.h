@@ -72,6 +72,12 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *                                    (2^-12 relative per element; values past 65504 saturate) to the embeddings the loss is computed from --
  *                                    measured against the fp32 oracle on whole batches: rows 2.7e-4 -> 3.5e-4, scores 3.8e-5 -> 5.3e-5, loss
  *                                    unchanged to 1e-6 (inside the 1e-3 the path is held to); 0: fp32 rows (the rounds 1-5 form)
+ *   "h16_guard" (VV_H16_GUARD, 1)    what watches those f16 rows' range (vv_h16_stats below): 0 nothing -- the kernels of the step are the ones without
+ *                                    the option; 1 the segment-wise backward counts, per step, the saturated elements and the faint rows of the
+ *                                    distinct rows it holds and the step reports them (no value of the step changes: dW, db, loss and W are
+ *                                    bit-identical to 0); 2 also falls back: once the report of a step shows either count non-zero, every later
+ *                                    step stores fp32 rows, exactly the execution of "h16" 0 (and "v16" with it), until "h16" is set to 1 again.
+ *                                    Steps on fp32 rows (dense, other D, "h16" 0) count nothing.  Any other value: VV_ERR_ARG
  *   "slab16" (VV_SLAB16, 1)          the weight gradient's split-K partial products as f16 x one power of two per (split, 256 x 256 tile) instead of
  *                                    fp32 (half of the 134 MB they cost per step at the benchmark's shape; a second rounding, 2^-12 relative per
  *                                    partial product, in the gradient path -- every split still accumulates in fp32 and the sum over the splits is
@@ -102,6 +108,10 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *   "last_update_form"               what the last vv_apply_update ran for the parameter matrix: 1 k_sgd with 16-byte accesses (the chunked and sharded updates too), 2 k_sgd scalar (F % 4 != 0), 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0 before the first update
  *   "last_score_form"                what the last forward pass launched for scores and loss: 1 k_score_fwd (register-resident), 2 k_score_stream at
  *                                    D = 512, 3 k_score_stream at D = 1024, 4 the per-instance kernels (dense or row-writing execution); 0 before the first step
+ *   "last_h16"                       1: the last forward pass stored ip2 as f16 rows, 0: fp32 rows (or no step yet)
+ *   "h16_fallback"                   1: "h16_guard" 2 has switched this context to fp32 rows (vv_h16_report::fallback, without synchronising);
+ *   "h16_flagged_step", "h16_flagged_saturated", "h16_flagged_faint_rows"   the step whose report started that fallback -- with none, the first
+ *                                    flagged step -- and its two counts (-1, 0, 0: none flagged so far)
  * Retired options -- "fwd_merge", "score_stream", "comm_first_inline": their alternatives were measured, lost and removed.  They read as 0,
  * the value the library always runs with; setting 0 is accepted, any other value is VV_ERR_ARG.  Their environment variables are not read.
  * Ablated / experimental kernels (timing studies whose results may be wrong) are NOT reachable through this library: they and their
@@ -109,6 +119,23 @@ int vv_set_dedup(vv_ctx* ctx, int on);
 int vv_set_option(vv_ctx* ctx, const char* name, double value);
 int vv_get_option(vv_ctx* ctx, const char* name, double* value);      /* ... and their current values */
 int vv_dedup_stats(vv_ctx* ctx, int64_t* rows, int64_t* unique_rows);
+/* Range loss of the f16 ip2 rows (option "h16": rows stored at scale 1, values past 65504 saturated by the forward GEMM's epilogue).  With
+ * "h16_guard" >= 1 the segment-wise backward counts, over the distinct rows of the step (each once, however often the batch repeats it):
+ *   saturated   elements whose stored f16 value is 65504, the largest finite one.  ip2 is post-ReLU, so >= 0; a true value in
+ *               [65488, 65504) rounds to 65504 and is counted too (conservative).
+ *   faint_rows  rows whose largest element is > 0 and < 2^-14, the smallest normal f16: every element is subnormal and the normalised
+ *               embedding keeps fewer than 11 significant bits.  An all-zero row (index -1 with zero bias, a row dead behind the ReLU) is not faint.
+ * The counts ride in the step's report to the host, which reads the report of step s when it issues step s + 4 (a fixed lag: what the
+ * reports steer is bit-reproducible, and a host running ahead is never stalled).  flagged_steps / first_flagged_step (steps count from 0,
+ * one per vv_forward_backward*) are therefore up to four steps behind, and under "h16_guard" 2 the four steps from the flagged one on have
+ * still trained on f16 rows before the fallback holds: nothing is redone.  With f16 and with bf16 operands alike (the rows are f16 in both).
+ * "h16_guard" 0, or a step on fp32 rows: both counts 0.  Library default 1; the Solver of the Caffe facade runs its engine with 2. */
+typedef struct { int64_t saturated, faint_rows;     /* of the LAST completed step (synchronises, like vv_dedup_stats) */
+                 int64_t flagged_steps;             /* steps with either count non-zero since vv_create, as read from the ring */
+                 int64_t first_flagged_step;        /* its step number, -1: none */
+                 int32_t fallback;                  /* 1: guard 2 has switched this engine to fp32 rows */
+                 int32_t rows_f16; } vv_h16_report; /* 1: the last forward pass stored f16 rows */
+int vv_h16_stats(vv_ctx* ctx, vv_h16_report* out);
 /* f16 operands: the 16-bit gradient operand of the weight-gradient product (InnerProductLayer::Backward,
  * inner_product_layer.cpp:80-97) carries one power-of-two scale per step.  A gradient value outside f16's range is never
  * applied clipped: the kernels that round gradients record their maxima, and a step whose values did not fit produces

@@ -151,6 +151,11 @@ static int create_init(vv_ctx* c) {
     const double dv = strtod(v, &end);
     if (end != v && *end == 0 && (dv == 0.0 || dv == 1.0 || dv == 2.0)) c->drop_dedup = (int)dv;
   }
+  if (const char* v = opt_env("VV_H16_GUARD")) {
+    char* end = nullptr;
+    const double dv = strtod(v, &end);
+    if (end != v && *end == 0 && (dv == 0.0 || dv == 1.0 || dv == 2.0)) c->h16_guard = (int)dv;
+  }
   if (const char* v = opt_env("VV_COMM_GATE")) c->comm_gate = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_INLINE")) c->comm_inline = atoi(v) != 0;
   if (const char* v = opt_env("VV_COMM_TEST_DELAY_US")) c->comm_test_delay_us = atoi(v);
@@ -197,8 +202,9 @@ static int create_init(vv_ctx* c) {
   HIPCHK(hipMemset(c->gg_bound, 0, GG_BOUND_SLOTS * GG_BOUND_STRIDE * sizeof(unsigned long long)));
   HIPCHK(hipMalloc(&c->gg, sizeof(GradGuard)));
   { GradGuard g0; memset(&g0, 0, sizeof(g0)); g0.mul = 1.f; HIPCHK(hipMemcpy(c->gg, &g0, sizeof(g0), hipMemcpyHostToDevice)); }
-  HIPCHK(hipHostMalloc((void**)&c->gmax_host, 32 * sizeof(unsigned long long), hipHostMallocMapped));
-  memset(c->gmax_host, 0, 32 * sizeof(unsigned long long));
+  HIPCHK(hipHostMalloc((void**)&c->gmax_host, GMAX_ENTRIES * GMAX_ENTRY_WORDS * sizeof(unsigned long long), hipHostMallocMapped));
+  memset(c->gmax_host, 0, GMAX_ENTRIES * GMAX_ENTRY_WORDS * sizeof(unsigned long long));
+  for (int i = 0; i < GMAX_ENTRIES; ++i) c->h16_counted[i] = INT32_MIN;
   HIPCHK(hipHostGetDevicePointer((void**)&c->gmax_host_dev, c->gmax_host, 0));
   HIPCHK(hipHostMalloc((void**)&c->seq_host, 2 * sizeof(int32_t), hipHostMallocMapped));
   c->seq_host[0] = c->seq_host[1] = 0;
@@ -239,8 +245,9 @@ static void free_batch(vv_ctx* c) {
     d.rows = d.slot_of = d.uniq = d.map = d.ord = d.cnt = d.seg = nullptr; d.used_seq = 0;
   }
   c->dd_rows = nullptr;
-  dfree(c->segV); dfree(c->seg_rec); dfree(c->seg_dbp); dfree(c->gg_slots);
-  c->segV = nullptr; c->seg_rec = nullptr; c->seg_dbp = nullptr; c->gg_slots = nullptr; c->gg_nslot = 0;
+  dfree(c->segV); dfree(c->seg_rec); dfree(c->seg_dbp); dfree(c->gg_slots); dfree(c->h16_cnt);
+  c->segV = nullptr; c->seg_rec = nullptr; c->seg_dbp = nullptr; c->gg_slots = nullptr; c->gg_nslot = 0; c->h16_cnt = nullptr;
+  c->last_h16 = c->last_h16_counted = false;
   c->sg_adj = 0; c->gg_seq0 = 0;
   c->dd_agg = nullptr; c->dd_slot_of = c->dd_uniq = c->dd_map = c->dd_ord = c->dd_cnt = c->dd_seg = c->dd_pos = nullptr;
   c->dYu = nullptr;
@@ -294,7 +301,8 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     if (iv == 0) return VV_OK;
     return fail(VV_ERR_ARG, "vv_set_option: option '%s' is retired; only its fixed value 0 is accepted", name);
   }
-  if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form" || n == "last_score_form")
+  if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form" || n == "last_score_form" || n == "last_h16" ||
+      n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
@@ -303,7 +311,17 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     c->drop_dedup = iv;
     return VV_OK;
   }
-  if (n == "h16") { c->h16 = iv != 0; return VV_OK; }
+  if (n == "h16") {
+    c->h16 = iv != 0;
+    // setting it on re-arms the guard: a fallback (h16_guard 2) ends, and no report of a step issued before this call starts another
+    if (c->h16) { c->h16_fallback = false; c->h16_arm_seq = c->step_seq; }
+    return VV_OK;
+  }
+  if (n == "h16_guard") {
+    if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(VV_ERR_ARG, "vv_set_option: h16_guard = %g is none of 0 (off), 1 (count and report), 2 (count, report and fall back to fp32 rows)", value);
+    c->h16_guard = iv;
+    return VV_OK;
+  }
   if (n == "slab16") { c->slab16 = iv != 0; return VV_OK; }
   if (n == "v16") { c->v16 = iv != 0; return VV_OK; }
   if (n == "fuse_update") { c->fuse_update = iv != 0; return VV_OK; }
@@ -338,6 +356,12 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "seg_bwd") *value = c->seg_bwd;
   else if (n == "drop_dedup") *value = c->drop_dedup;
   else if (n == "h16") *value = c->h16;
+  else if (n == "h16_guard") *value = c->h16_guard;
+  else if (n == "last_h16") *value = c->last_h16;
+  else if (n == "h16_fallback") *value = c->h16_fallback;
+  else if (n == "h16_flagged_step") *value = (double)c->h16_flag_step;
+  else if (n == "h16_flagged_saturated") *value = (double)c->h16_flag_sat;
+  else if (n == "h16_flagged_faint_rows") *value = (double)c->h16_flag_faint;
   else if (n == "slab16") *value = c->slab16;
   else if (n == "v16") *value = c->v16;
   else if (n == "fuse_update") *value = c->fuse_update;
@@ -375,6 +399,24 @@ int vv_dedup_stats(vv_ctx* c, int64_t* rows, int64_t* unique_rows) {
   if (c->last_dedup) HIPCHK(hipMemcpy(&U, c->dd_info, sizeof(U), hipMemcpyDeviceToHost));
   if (rows) *rows = c->R;
   if (unique_rows) *unique_rows = U;
+  return VV_OK;
+}
+
+int vv_h16_stats(vv_ctx* c, vv_h16_report* out) {
+  if (!c || !out) return fail(VV_ERR_ARG, "vv_h16_stats: ctx / out is NULL");
+  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_h16_stats: no forward pass yet");
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out->saturated = out->faint_rows = 0;
+  if (c->last_h16_counted) {          // the last step's per-workgroup partials, as its kernel left them (whether or not its report has been folded yet)
+    std::vector<uint32_t> part((size_t)2 * SEGB_BLOCKS);
+    HIPCHK(hipMemcpy(part.data(), c->h16_cnt, part.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int i = 0; i < SEGB_BLOCKS; ++i) { out->saturated += part[2 * i]; out->faint_rows += part[2 * i + 1]; }
+  }
+  out->flagged_steps = c->h16_flagged_steps;
+  out->first_flagged_step = c->h16_first_flagged;
+  out->fallback = c->h16_fallback ? 1 : 0;
+  out->rows_f16 = c->last_h16 ? 1 : 0;
   return VV_OK;
 }
 
@@ -657,6 +699,8 @@ static int ensure_batch(vv_ctx* c, int B, int C, int Nn) {
   HIPCHK(hipMalloc(&c->segV, (size_t)2 * B * D * 4));
   HIPCHK(hipMalloc(&c->seg_rec, (size_t)c->Rp * sizeof(SegRec)));
   HIPCHK(hipMalloc(&c->seg_dbp, (size_t)SEGB_BLOCKS * D * 4));
+  HIPCHK(hipMalloc(&c->h16_cnt, (size_t)2 * SEGB_BLOCKS * sizeof(uint32_t)));
+  HIPCHK(hipMemset(c->h16_cnt, 0, (size_t)2 * SEGB_BLOCKS * sizeof(uint32_t)));
   c->gg_nslot = std::max(std::max(B, SEGB_BLOCKS), (c->Rp + 3) / 4);
   HIPCHK(hipMalloc(&c->gg_slots, (size_t)3 * 2 * c->gg_nslot * 4));
   HIPCHK(hipMemset(c->gg_slots, 0, (size_t)3 * 2 * c->gg_nslot * 4));
@@ -703,6 +747,22 @@ static int stage_acquire(vv_ctx* c, size_t bytes, int* slot) {
   c->wait_ms[3] += host_now_ms() - tw0;
   *slot = sl;
   return VV_OK;
+}
+
+// The report entry of step `want` in the host-visible ring (vv_internal.h: GMAX_ENTRY_WORDS; reduce_loss writes it): waits until it is there.
+// false: the stream ran empty without it (a step whose reduction never ran).  kLag: how many steps behind the host reads -- fixed, so that
+// whatever the reports steer (the gradient scale, the f16 rows' fallback) does not depend on host timing and runs stay bit-reproducible.
+constexpr int kLag = 4;
+static bool report_wait(vv_ctx* c, int32_t want, hipStream_t s) {
+  volatile unsigned long long* en = c->gmax_host + GMAX_ENTRY_WORDS * (want & (GMAX_ENTRIES - 1));
+  bool have = false;
+  const double tw0 = host_now_ms();
+  for (unsigned spins = 0; !(have = (int32_t)(uint32_t)__atomic_load_n(en, __ATOMIC_ACQUIRE) == want); ++spins) {
+    if (spins > 4096) { timespec ts = {0, 20000}; nanosleep(&ts, nullptr); }
+    if (hipStreamQuery(s) == hipSuccess) { have = (int32_t)(uint32_t)__atomic_load_n(en, __ATOMIC_ACQUIRE) == want; break; }
+  }
+  c->wait_ms[0] += host_now_ms() - tw0;
+  return have;
 }
 
 // The solver's parameters of a step as the update kernels read them (k_sgd, k_reduce_sgd, the weight-gradient GEMM's epilogue)
@@ -1030,9 +1090,31 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // ip2 as f16 (option "h16"): only where the segment-wise pair reads it -- de-duplicated batches of D = 512 / 1024 (k_score_fwd / k_score_stream /
   // k_seg_bwd carry the f16 row loads; the dense and the generic kernels keep fp32 rows), D % 8 == 0, the phase-staggered forward kernel
   const bool seg_path = dd && c->seg_bwd && (D == 512 || D == 1024);
-  const bool h16 = c->h16 && seg_path && !ablate_on();
+  // ... and their range loss (option "h16_guard"): a step that stored f16 rows had them counted (k_seg_bwd_cnt), its counts ride in its report
+  // entry, and the entry of step seq - kLag is read HERE, at a fixed lag like the gradient scale's, so that whatever it steers -- value 2: this
+  // and every later step store fp32 rows, exactly the execution of h16 = 0, until the caller sets h16 again -- does not depend on host timing.
+  // Up to kLag steps have trained on the flagged rows by then: the price of never stalling a host that runs ahead; it is reported.
+  if (c->h16_guard >= 1 && c->h16_counted[(seq - kLag) & (GMAX_ENTRIES - 1)] == seq - kLag) {
+    const int32_t want = seq - kLag;
+    if (report_wait(c, want, s)) {
+      const volatile unsigned long long* en = c->gmax_host + GMAX_ENTRY_WORDS * (want & (GMAX_ENTRIES - 1));
+      const long long sat = (long long)en[2], faint = (long long)en[3];
+      if (sat | faint) {
+        ++c->h16_flagged_steps;
+        if (c->h16_first_flagged < 0) c->h16_first_flagged = want - 1;      // (steps count from 0, sequence numbers from 1)
+        const bool sw = c->h16_guard == 2 && !c->h16_fallback && want > c->h16_arm_seq;
+        if (sw) c->h16_fallback = true;
+        if (sw || c->h16_flag_step < 0) { c->h16_flag_step = want - 1; c->h16_flag_sat = sat; c->h16_flag_faint = faint; }
+      }
+    }
+    c->h16_counted[(seq - kLag) & (GMAX_ENTRIES - 1)] = INT32_MIN;
+  }
+  const bool h16 = c->h16 && !c->h16_fallback && seg_path && !ablate_on();
+  const bool h16_count = h16 && c->h16_guard >= 1;
   fa.h16 = h16 ? 1 : 0;
   c->last_h16 = h16;
+  c->last_h16_counted = h16_count;
+  if (h16_count) c->h16_counted[seq & (GMAX_ENTRIES - 1)] = seq;
   fa.drop_ratio = (dd && drop_on) ? 0.f : cfg->dropout_ratio;      // (de-duplicated: H holds the shared pre-dropout rows, the instances mask them)
   fa.mask = (!(dd && drop_on) && cfg->dropout_ratio > 0.f && cfg->dropout_mask) ? c->mask : nullptr;
   fa.drop_seed = cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter;
@@ -1065,18 +1147,11 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // the scale moves so that it lies in [2^9, 2^10).  That only keeps the guard's repeats rare: a value past f16's range never
   // reaches the weight-gradient GEMM either way (GradGuard).
   if (c->prec == VV_PREC_F16) {
-    constexpr int kLag = 4;
     if (c->gg_seq0 == 0) c->gg_seq0 = seq;
     if (seq - c->gg_seq0 >= kLag) {
       const int32_t want = seq - kLag;
-      volatile unsigned long long* en = c->gmax_host + 2 * (want & 15);
-      bool have = false;
-      const double tw0 = host_now_ms();
-      for (unsigned spins = 0; !(have = (int32_t)(uint32_t)__atomic_load_n(en, __ATOMIC_ACQUIRE) == want); ++spins) {
-        if (spins > 4096) { timespec ts = {0, 20000}; nanosleep(&ts, nullptr); }
-        if (hipStreamQuery(s) == hipSuccess) { have = (int32_t)(uint32_t)__atomic_load_n(en, __ATOMIC_ACQUIRE) == want; break; }
-      }
-      c->wait_ms[0] += host_now_ms() - tw0;
+      volatile unsigned long long* en = c->gmax_host + GMAX_ENTRY_WORDS * (want & (GMAX_ENTRIES - 1));
+      const bool have = report_wait(c, want, s);
       if (c->trace_waits && ++c->wait_calls % 100 == 0) {
         fprintf(stderr, "[vv waits] per step over the last 100: gradient-scale report %.3f, grouping-set gate %.3f, grouping event %.3f, staging slot %.3f ms\n",
                 c->wait_ms[0] / 100, c->wait_ms[1] / 100, c->wait_ms[2] / 100, c->wait_ms[3] / 100);
@@ -1155,6 +1230,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     if (gd.gg && proactive) { sa.bound_out = c->gg_bound; sa.bound_seq = seq; }
     ba.H = c->H; ba.V = c->segV; ba.rec = c->seg_rec; ba.seg_start = c->dd_seg; ba.info = c->dd_info; ba.dYu = c->dYu;
     ba.dbp = c->seg_dbp; ba.Rp = c->Rp; ba.D = D; ba.Dp = c->Dp; ba.inv_sg = 1.f / c->sg; ba.h16 = h16 ? 1 : 0; ba.v16 = v16 ? 1 : 0;
+    if (h16_count) ba.h16_cnt = c->h16_cnt;
     if (drop_on) ba.drop = dsp;
   } else if (dd) {
     ga.dYh = c->dYh; ga.seg_start = c->dd_seg; ga.info = c->dd_info; ga.dYu = c->dYu; ga.Rp = c->Rp; ga.Dp = c->Dp;
@@ -1195,6 +1271,10 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     ra.gg = c->gg; ra.gmax_slots = c->gg_slots; ra.gmax_n0 = gd.n_of[0]; ra.gmax_n1 = gd.n_of[1]; ra.gmax_stride = c->gg_nslot;
     ra.gmax_host = c->gmax_host_dev; ra.seq = seq; ra.guard_last_round = n_rounds;
     if (proactive) { ra.gbound = c->gg_bound; ra.gcnt = c->dd_info + 1; }
+  }
+  if (h16_count) {       // (bf16 operands publish a report entry for these steps only: the rows of H are f16 there too)
+    ra.gmax_host = c->gmax_host_dev; ra.seq = seq;
+    ra.h16_cnt = c->h16_cnt; ra.h16_cnt_n = SEGB_BLOCKS;
   }
   ra.ip_scale = cfg->ip_regularization > 0.f ? 1.f + cfg->ip_regularization * 0.5f : 1.f;     // inner_product_layer.cpp:80-90
   ra.loss_part = c->loss_part; ra.viol_part = c->viol_part; ra.loss_scale = cfg->loss_weight / (float)count; ra.loss_out = c->loss2;

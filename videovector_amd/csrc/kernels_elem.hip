@@ -1135,9 +1135,17 @@ template <bool H16> __device__ __forceinline__ void seg_row8(const float* H, int
 //   dx_u = [x_u > 0] (sum_i m_i alpha_i V_i - x_u scale sum_i m_i beta_i)        (alpha, beta already carry one factor scale)
 // -- the mask regenerated per instance from its reference row (b = vec / 2, ch = pad - b CN) and per chunk (columns 512 c + c0 .. + 7), the
 // beta sum per column of every chunk.  The DROP forms read fp32 vectors only: dropout steps run with v16 off (api.hip, option "drop_dedup").
-template <typename T, int CH, bool DROP = false, bool H16 = false, bool V16 = false>
-__global__ __launch_bounds__(256) void k_seg_bwd(SegBwdArgs a) {
+// CNT (option "h16_guard", the k_seg_bwd_cnt kernels below; f16 rows only): the wave also counts what f16's range cost the rows it holds --
+// elements stored as 65504, the largest finite f16 (the forward GEMM's epilogue saturates there; a true value in [65488, 65504) rounds to
+// it and is counted too: conservative), and rows whose largest element is > 0 and < 2^-14 (every element subnormal; an all-zero row is
+// not faint).  Taken from the row values where the wave consumes them (so both placements of the row load and both segment paths are
+// covered), behind two wave-uniform ballots: a row that neither saturates nor is faint costs a running maximum and three compares.  One
+// pair of 32-bit partials per workgroup goes to SegBwdArgs::h16_cnt -- every workgroup of the grid writes its pair every step, so nothing
+// has to be reset -- and the loss workgroup folds them into the step's report entry (reduce_loss).  No value of the step depends on them.
+template <typename T, int CH, bool DROP, bool H16, bool V16, bool CNT>
+__device__ __forceinline__ void seg_bwd_body(const SegBwdArgs& a) {
   static_assert(!DROP || !V16, "dropout steps run with v16 off");
+  static_assert(!CNT || H16, "only f16 rows are counted");
   constexpr int BC = DROP ? CH - 1 : 0, BJ = DROP ? 7 : 0;      // index masks of the per-column beta sums (one dummy element without DROP)
   __shared__ float cs[4][512 * CH];
   __shared__ SegRec strip[4][64];
@@ -1165,6 +1173,7 @@ __global__ __launch_bounds__(256) void k_seg_bwd(SegBwdArgs a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) col[c][j] = 0.f;
   float gmx = 0.f;
+  uint32_t n_sat = 0, n_faint = 0;                    // CNT: this lane's saturated elements, this wave's faint rows
   // A wave's rows are a chain of dependent reads each: segment bounds, records, the vectors the records name, and the row
   // itself.  The row's own values (needed last) and the NEXT row's segment bounds are requested right behind the records,
   // so that only records -> vectors is exposed: 18.7 -> 17.9 us.  (More waves do not help: 89 registers and five blocks per
@@ -1325,11 +1334,20 @@ __global__ __launch_bounds__(256) void k_seg_bwd(SegBwdArgs a) {
           for (int j = 0; j < 8; ++j) bsv[c & BC][j & BJ] = (float)dbsv[c & BC][j & BJ];
       }
     }
+    float rmx = 0.f;                                  // CNT: the largest of this lane's elements of the row
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       if (CH != 1) seg_row8<H16>(a.H, (int64_t)u * D + 512 * c + c0, xr0[c], xr1[c]);
       const float4 x0 = xr0[c], x1 = xr1[c];
       const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+      if constexpr (CNT) {
+        const float cmx = fmaxf(fmaxf(fmaxf(xv[0], xv[1]), fmaxf(xv[2], xv[3])), fmaxf(fmaxf(xv[4], xv[5]), fmaxf(xv[6], xv[7])));
+        if (__ballot(cmx >= 65504.f)) {               // (wave-uniform, rare)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) n_sat += xv[j] >= 65504.f;
+        }
+        rmx = fmaxf(rmx, cmx);
+      }
       float g[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -1342,6 +1360,18 @@ __global__ __launch_bounds__(256) void k_seg_bwd(SegBwdArgs a) {
       for (int j = 0; j < 4; ++j) o[j] = T::from_float(g[2 * j]) | ((uint32_t)T::from_float(g[2 * j + 1]) << 16);
       *(uint4*)(a.dYu + (int64_t)u * a.Dp + 512 * c + c0) = make_uint4(o[0], o[1], o[2], o[3]);
     }
+    if constexpr (CNT) {
+      if (!__ballot(rmx >= 6.103515625e-05f) && __ballot(rmx > 0.f)) ++n_faint;      // 2^-14: the smallest normal f16
+    }
+  }
+  if constexpr (CNT) {
+    __shared__ uint32_t hc[4][2];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n_sat += __shfl_xor(n_sat, o, 64);
+    if (lane == 0) { hc[wave][0] = n_sat; hc[wave][1] = n_faint; }
+    __syncthreads();
+    if (first && threadIdx.x == 0)
+      *(uint2*)(a.h16_cnt + 2 * blockIdx.x) = make_uint2(hc[0][0] + hc[1][0] + hc[2][0] + hc[3][0], hc[0][1] + hc[1][1] + hc[2][1] + hc[3][1]);
   }
 #pragma unroll
   for (int c = 0; c < CH; ++c)
@@ -1358,12 +1388,28 @@ __global__ __launch_bounds__(256) void k_seg_bwd(SegBwdArgs a) {
   }
 }
 
+template <typename T, int CH, bool DROP = false, bool H16 = false, bool V16 = false>
+__global__ __launch_bounds__(256) void k_seg_bwd(SegBwdArgs a) { seg_bwd_body<T, CH, DROP, H16, V16, false>(a); }
+// ... the same over f16 rows, counting their range loss (SegBwdArgs::h16_cnt set: option "h16_guard" >= 1, guard round 0)
+template <typename T, int CH, bool DROP = false, bool V16 = false>
+__global__ __launch_bounds__(256) void k_seg_bwd_cnt(SegBwdArgs a) { seg_bwd_body<T, CH, DROP, true, V16, true>(a); }
+
 void launch_seg_bwd(int prec, const SegBwdArgs& a, hipStream_t s) {
   const int ch = a.D / 512;
   // (a conditional repeat of the gradient-scale guard normally returns at once: a quarter of the grid starts faster)
   const int nb = a.guard.round == 0 ? SEGB_BLOCKS : SEGB_BLOCKS / 4;
 #define VV_SB(T, CH, DROP) do { if (a.h16) VV_LAUNCH((k_seg_bwd<T, CH, DROP, true>), dim3(nb), dim3(256), 0, s, a); \
                                  else VV_LAUNCH((k_seg_bwd<T, CH, DROP, false>), dim3(nb), dim3(256), 0, s, a); } while (0)
+  if (a.h16_cnt && a.h16 && a.guard.round == 0) {          // the counting twins: one per H16 = true instantiation below
+#define VV_SBC(T) do { if (a.drop.mode) { if (ch == 1) VV_LAUNCH((k_seg_bwd_cnt<T, 1, true>), dim3(nb), dim3(256), 0, s, a); \
+                                         else VV_LAUNCH((k_seg_bwd_cnt<T, 2, true>), dim3(nb), dim3(256), 0, s, a); } \
+                     else if (ch == 2 && a.v16) VV_LAUNCH((k_seg_bwd_cnt<T, 2, false, true>), dim3(nb), dim3(256), 0, s, a); \
+                     else if (ch == 1) VV_LAUNCH((k_seg_bwd_cnt<T, 1>), dim3(nb), dim3(256), 0, s, a); \
+                     else VV_LAUNCH((k_seg_bwd_cnt<T, 2>), dim3(nb), dim3(256), 0, s, a); } while (0)
+    if (prec == 0) VV_SBC(F16); else VV_SBC(BF16);
+#undef VV_SBC
+    return;
+  }
   if (a.drop.mode) {                             // (fp32 vectors: dropout steps run with v16 off)
     if (prec == 0) { if (ch == 1) VV_SB(F16, 1, true); else VV_SB(F16, 2, true); }
     else { if (ch == 1) VV_SB(BF16, 1, true); else VV_SB(BF16, 2, true); }
@@ -1468,6 +1514,17 @@ __device__ __forceinline__ void reduce_loss(const ReduceArgs& a) {
   v = block_sum(v, red + 4);
   if (threadIdx.x == 0) { a.loss_out[0] = l * a.loss_scale; a.loss_out[1] = v; }
   if (a.gmax_host) {
+    // f16 rows of ip2 (option "h16_guard"): k_seg_bwd_cnt's per-workgroup partials, folded in a fixed order (integers: exact anyway)
+    unsigned long long hsat = 0, hfaint = 0;
+    if (a.h16_cnt) {
+      __shared__ unsigned long long hred[4][2];
+      for (int i = threadIdx.x; i < a.h16_cnt_n; i += 256) { const uint2 p = *(const uint2*)(a.h16_cnt + 2 * i); hsat += p.x; hfaint += p.y; }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { hsat += __shfl_xor(hsat, o, 64); hfaint += __shfl_xor(hfaint, o, 64); }
+      if ((threadIdx.x & 63) == 0) { hred[threadIdx.x >> 6][0] = hsat; hred[threadIdx.x >> 6][1] = hfaint; }
+      __syncthreads();
+      hsat = hred[0][0] + hred[1][0] + hred[2][0] + hred[3][0]; hfaint = hred[0][1] + hred[1][1] + hred[2][1] + hred[3][1];
+    }
     // f16 gradient-scale guard: the step's largest |dY| (unscaled: the normal pass's per-block maxima over the host's sg)
     // and the shift the repeats applied go to a host-visible ring; the host reads entry seq - 4 when it issues step seq
     __shared__ float gsm[16];
@@ -1486,7 +1543,9 @@ __device__ __forceinline__ void reduce_loss(const ReduceArgs& a) {
              (a.gg->flag[a.guard_last_round] == a.seq ? (1u << 30) : 0u);
         if (a.gbound) G = gbm * (float)(*a.gcnt) / a.sg;
       }
-      unsigned long long* e = a.gmax_host + 2 * (a.seq & 15);
+      unsigned long long* e = a.gmax_host + GMAX_ENTRY_WORDS * (a.seq & 15);
+      __hip_atomic_store(e + 2, hsat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // words 2, 3: the f16 rows' saturated elements and faint rows (0 where nothing counted)
+      __hip_atomic_store(e + 3, hfaint, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(e + 1, ((unsigned long long)__float_as_uint(G) << 32) | fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(e, ((unsigned long long)__float_as_uint(m / a.sg) << 32) | (unsigned)a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }

@@ -83,7 +83,7 @@ struct vv_ctx {
   // f16 gradient-scale guard (vv_internal.h: GradGuard)
   vv::GradGuard* gg = nullptr; float* gg_slots = nullptr; int gg_nslot = 0;
   unsigned long long* gg_bound = nullptr;      // GuardArgs::bound: the score kernel's (seq, largest per-instance element bound)
-  unsigned long long* gmax_host = nullptr;     // pinned + mapped: 16 entries of {seq | bits(max |dY|) << 32, final shift}
+  unsigned long long* gmax_host = nullptr;     // pinned + mapped: GMAX_ENTRIES report entries of GMAX_ENTRY_WORDS words (vv_internal.h)
   unsigned long long* gmax_host_dev = nullptr;
   int sg_adj = 0;                   // powers of two on top of the count-based default scale (follows the reported maxima)
   int32_t gg_seq0 = 0;              // first step since the guard's state was reset (no reports older than that)
@@ -103,6 +103,15 @@ struct vv_ctx {
   bool v16 = true;                 // option "v16" (VV_V16=0: fp32): the per-item vectors of the one-sweep score kernel (D = 1024) as f16, with h16
   bool h16 = true;                 // option "h16" (VV_H16=0: fp32 rows): ip2 as f16 between the forward GEMM and the segment-wise pair (FwdArgs::h16)
   bool last_h16 = false;           // ... and whether the last forward pass stored it that way (the accessors read H accordingly)
+  // option "h16_guard" (VV_H16_GUARD): the f16 rows' range loss -- 0 off, 1 counted and reported (vv_h16_stats), 2 also falls back to fp32 rows
+  int h16_guard = 1;
+  uint32_t* h16_cnt = nullptr;     // [SEGB_BLOCKS][2] k_seg_bwd_cnt's per-workgroup {saturated elements, faint rows} of the last counted step
+  bool last_h16_counted = false;   // the last forward/backward pass counted
+  int32_t h16_counted[vv::GMAX_ENTRIES];     // [seq & 15] == seq: step seq counted, its report entry is due kLag steps later (INT32_MIN: none)
+  int64_t h16_flagged_steps = 0, h16_first_flagged = -1;   // as read from the ring; the first flagged step's number
+  int64_t h16_flag_step = -1, h16_flag_sat = 0, h16_flag_faint = 0;   // the step whose report started the fallback (with none: the first flagged one) and its two counts
+  bool h16_fallback = false;       // guard 2 switched this context to fp32 rows (until option "h16" is set again)
+  int32_t h16_arm_seq = 0;         // reports of steps up to this sequence number start no fallback (the guard was re-armed after them)
   vv::ScoreArgs last_score;            // to rebuild the per-instance gradient rows for vv_blobs_get(ip1_diff)
   int32_t* U_host = nullptr;        // pinned + mapped: k_dd_leaders stores U here every step, the launcher reads it late
   int32_t* U_host_dev = nullptr;    // device alias of U_host

@@ -63,6 +63,10 @@ struct GradGuard {
   int32_t pad[2];
 };
 constexpr float GG_LIMIT = 32768.f;
+// The step's report entry in the host-visible ring (vv_ctx::gmax_host: GMAX_ENTRIES of them, written by reduce_loss, read by the host at a
+// fixed lag): word 0 the sequence number | bits(max |dY|) << 32 (stored last, release), word 1 the guard's shifts and flags, words 2 and 3
+// the f16 ip2 rows' saturated elements and faint rows (option "h16_guard").  Internal.
+constexpr int GMAX_ENTRY_WORDS = 4, GMAX_ENTRIES = 16;
 struct GuardArgs {
   GradGuard* gg = nullptr;   // null: no guard (bf16 operands: fp32's exponent range)
   float* slots = nullptr;    // [3 rounds][2 producers][nslot] per-block max |g| in the units of that round's scale
@@ -253,6 +257,8 @@ struct SegBwdArgs {
   DropSpec drop;                 // as ScoreArgs::drop: dx_u = [x_u > 0] (sum_i m_i alpha_i V_i - x_u scale sum_i m_i beta_i), m_i the instance's mask
   int h16 = 0;                   // H holds f16 rows (FwdArgs::h16)
   int v16 = 0;                   // V holds f16 rows (ScoreArgs::v16: the one-sweep score kernel wrote them so)
+  uint32_t* h16_cnt = nullptr;   // non-null (option "h16_guard" >= 1; f16 rows, guard round 0): [SEGB_BLOCKS][2] per-workgroup counts of the rows'
+                                 //   {saturated elements, faint rows} (k_seg_bwd_cnt, kernels_elem.hip); every workgroup writes its pair
 };
 
 struct SegsumArgs {
@@ -338,6 +344,7 @@ struct ReduceArgs {
   const float* gmax_slots = nullptr; int gmax_n0 = 0, gmax_n1 = 0, gmax_stride = 0;
   unsigned long long* gmax_host = nullptr; int32_t seq = 0;
   int guard_last_round = 0;        // the step's final guard round (its flag must not be up)
+  const uint32_t* h16_cnt = nullptr; int h16_cnt_n = 0;   // SegBwdArgs::h16_cnt and its pairs: folded into words 2 and 3 of the report entry (null: zeros)
   const unsigned long long* gbound = nullptr; const int32_t* gcnt = nullptr;   // proactive path: GuardArgs::bound / cnt_max (reported too)
   float* grads;            // [D*F + D]
   int D, F;

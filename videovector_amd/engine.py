@@ -49,6 +49,11 @@ class _RankStats(C.Structure):
                 ("mean_ap", C.c_float)]
 
 
+class _H16Report(C.Structure):
+    _fields_ = [("saturated", C.c_int64), ("faint_rows", C.c_int64), ("flagged_steps", C.c_int64),
+                ("first_flagged_step", C.c_int64), ("fallback", C.c_int32), ("rows_f16", C.c_int32)]
+
+
 class _ClassStats(C.Structure):
     _fields_ = [("mean_ap", C.c_float), ("hit_at_1", C.c_float), ("hit_at_5", C.c_float), ("n_scored", C.c_int32)]
 
@@ -82,6 +87,7 @@ def load_library():
         "vv_set_option": [vp, C.c_char_p, C.c_double], "vv_get_option": [vp, C.c_char_p, C.POINTER(C.c_double)],
         "vv_set_dedup": [vp, C.c_int], "vv_dedup_stats": [vp, C.POINTER(i64), C.POINTER(i64)],
         "vv_grad_scale_stats": [vp, C.POINTER(i64), C.POINTER(C.c_float)],
+        "vv_h16_stats": [vp, C.POINTER(_H16Report)],
         "vv_table_set": [vp, vp, i64, i32], "vv_table_synth": [vp, C.c_uint64, i64, i32],
         "vv_table_get": [vp, vp, i64, vp],
         "vv_params_set": [vp, i32, vp, vp, vp, vp], "vv_params_get": [vp, vp, vp, vp, vp],
@@ -357,6 +363,14 @@ class Engine:
         r, u = C.c_int64(0), C.c_int64(0)
         self._chk(self.L.vv_dedup_stats(self.h, C.byref(r), C.byref(u)))
         return r.value, u.value
+
+    def h16_stats(self):
+        """Range loss of the f16 ip2 rows (include/videovec.h: vv_h16_stats; option "h16_guard"): a dict of saturated and
+        faint_rows of the last completed step (synchronises), flagged_steps and first_flagged_step as the host has read them
+        from the steps' reports (four steps late), fallback and rows_f16."""
+        r = _H16Report()
+        self._chk(self.L.vv_h16_stats(self.h, C.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in _H16Report._fields_}
 
     def grad_scale_stats(self):
         """(steps whose 16-bit gradients had to be produced again at a smaller scale, current scale); videovec.h."""
