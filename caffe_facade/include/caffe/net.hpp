@@ -36,6 +36,11 @@ class Net {
   void Update();
   void SetUpdateHyperParams(float rate, float momentum, float weight_decay, const string& reg, int solver_type = 0,
                             float delta = 1e-8f);
+  // RMSProp / Adam (BVLC Caffe's SolverParameter.momentum2 / rms_decay; vv_solver_ext_set), Adam's second history (v of W, v of b) and
+  // its update count (vv_history2_*, vv_solver_iter_set)
+  void SetSolverExt(float momentum2, float rms_decay);
+  void GetHistory2(vector<shared_ptr<Blob<Dtype> > >* history2);
+  void SetHistory2(const vector<shared_ptr<Blob<Dtype> > >& history2, int iter);
 
   // net.cpp:638-667: a TEST net takes the weights of the train net (device-to-device through the host)
   void ShareTrainedLayersWith(Net* other);

@@ -87,10 +87,22 @@ class UpdateRuleSolver : public SGDSolver<Dtype> {
   void CheckHyperParams() {
     if (RULE == VV_SOLVER_ADAGRAD)                           // the reference's constructor_sanity_check, solver.hpp:121-122
       CHECK_EQ(0, this->param_.get_num("momentum")) << "Momentum cannot be used with AdaGrad.";
+    if (RULE == VV_SOLVER_RMSPROP) {                         // BVLC RMSPropSolver::constructor_sanity_check
+      CHECK_EQ(0, this->param_.get_num("momentum")) << "Momentum cannot be used with RMSProp.";
+      CHECK_GE(this->param_.get_num("rms_decay"), 0) << "rms_decay should lie between 0 and 1.";
+      CHECK_LT(this->param_.get_num("rms_decay"), 1) << "rms_decay should lie between 0 and 1.";
+    }
   }
+  // Adam keeps two histories: the solverstate holds FOUR blobs in BVLC AdamSolver's order (m of W, m of b, v of W, v of b), and a
+  // restored run continues the bias correction at t = iter + 1.  The other rules keep SGDSolver's two-blob state.
+  virtual void SnapshotSolverState(SolverState* out);
+  virtual void RestoreSolverState(const SolverState& in);
 };
 template <typename Dtype> using NesterovSolver = UpdateRuleSolver<Dtype, VV_SOLVER_NESTEROV>;
 template <typename Dtype> using AdaGradSolver = UpdateRuleSolver<Dtype, VV_SOLVER_ADAGRAD>;
+// BVLC Caffe's RMSPropSolver and AdamSolver (sgd_solvers.hpp; the reference tree has neither): the same class, two more rules
+template <typename Dtype> using RMSPropSolver = UpdateRuleSolver<Dtype, VV_SOLVER_RMSPROP>;
+template <typename Dtype> using AdamSolver = UpdateRuleSolver<Dtype, VV_SOLVER_ADAM>;
 
 // SolverParameter.solver_type -> solver object (solver.hpp:128-143)
 template <typename Dtype>

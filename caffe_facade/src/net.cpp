@@ -557,6 +557,22 @@ void Net<Dtype>::SetUpdateHyperParams(float rate, float momentum, float weight_d
   else LOG(FATAL) << "Unknown regularization type: " << reg;                          // solver.cpp:523
 }
 template <typename Dtype>
+void Net<Dtype>::SetSolverExt(float momentum2, float rms_decay) { VV_CHECK(vv_solver_ext_set(ctx_, momentum2, rms_decay)); }
+template <typename Dtype>
+void Net<Dtype>::GetHistory2(vector<shared_ptr<Blob<Dtype> > >* history) {
+  history->resize(2);
+  (*history)[0].reset(new Blob<Dtype>(1, 1, plan_.D, plan_.F));
+  (*history)[1].reset(new Blob<Dtype>(1, 1, 1, plan_.D));
+  VV_CHECK(vv_history2_get(ctx_, (*history)[0]->mutable_cpu_data(), (*history)[1]->mutable_cpu_data()));
+}
+template <typename Dtype>
+void Net<Dtype>::SetHistory2(const vector<shared_ptr<Blob<Dtype> > >& history, int iter) {
+  CHECK_EQ((int)history.size(), 2) << "Incorrect length of history blobs.";
+  CHECK_EQ(history[0]->count(), plan_.D * plan_.F); CHECK_EQ(history[1]->count(), plan_.D);
+  VV_CHECK(vv_history2_set(ctx_, history[0]->cpu_data(), history[1]->cpu_data()));
+  VV_CHECK(vv_solver_iter_set(ctx_, iter));
+}
+template <typename Dtype>
 void Net<Dtype>::ShareTrainedLayersWith(Net* other) {
   CHECK_EQ(plan_.D, other->plan_.D); CHECK_EQ(plan_.F, other->plan_.F);
   other->PullParamsFromDevice();
@@ -822,8 +838,14 @@ void Net<Dtype>::CopyTrainedLayersFrom(const NetParameter& param) {
   GetHistory(&hist);
   params_stale_ = false;
   Layer<Dtype>* ip = layers_[plan_.ip_layer].get();
+  // ... and, in an Adam run, the second history and the update count (vv_params_set starts both over)
+  int64_t adam_t = 0;
+  VV_CHECK(vv_solver_iter_get(ctx_, &adam_t));
+  vector<shared_ptr<Blob<Dtype> > > hist2;
+  if (adam_t > 0) GetHistory2(&hist2);
   VV_CHECK(vv_params_set(ctx_, plan_.D, ip->blobs()[0]->cpu_data(), ip->blobs()[1]->cpu_data(),
                          hist[0]->cpu_data(), hist[1]->cpu_data()));
+  if (adam_t > 0) SetHistory2(hist2, (int)adam_t);
 }
 template <typename Dtype>
 void Net<Dtype>::CopyTrainedLayersFrom(const string trained_filename) {

@@ -28,7 +28,8 @@ static const std::vector<EnumDef>& Enums() {
   static const std::vector<EnumDef> e = {
       {"Phase", {{"TRAIN", 0}, {"TEST", 1}}},                                       // :182-185
       {"SolverMode", {{"CPU", 0}, {"GPU", 1}}},                                     // :141-144
-      {"SolverType", {{"SGD", 0}, {"NESTEROV", 1}, {"ADAGRAD", 2}}},                // :155-159
+      {"SolverType", {{"SGD", 0}, {"NESTEROV", 1}, {"ADAGRAD", 2},                  // :155-159
+                      {"RMSPROP", 3}, {"ADADELTA", 4}, {"ADAM", 5}}},              // (BVLC Caffe's numbers; not in the fork)
       {"DimCheckMode", {{"STRICT", 0}, {"PERMISSIVE", 1}}},
       {"DB", {{"LEVELDB", 0}, {"LMDB", 1}}},
       {"CONTEXT", {{"PAIRWISE", 0}, {"WINDOW", 1}, {"PAST", 2}, {"PAST_CONTINUOUS", 3},
@@ -96,7 +97,9 @@ static const std::vector<MsgDef>& Msgs() {
         OENUM(30, "solver_type", "SolverType", "SGD"), OPTD(31, "delta", T_FLOAT, "1e-8"),
         OPTD(23, "debug_info", T_BOOL, "false"), OPTD(28, "snapshot_after_train", T_BOOL, "true"),
         OPT(33, "snapshot_vis", T_INT32), OPT(34, "snapshot_vis_blobs", T_STRING),
-        OPT(35, "snapshot_vis_truncate_len", T_INT32), OPT(36, "snapshot_vis_dir", T_STRING)}},
+        OPT(35, "snapshot_vis_truncate_len", T_INT32), OPT(36, "snapshot_vis_dir", T_STRING),
+        // BVLC Caffe's SolverParameter.rms_decay = 38 and momentum2 = 39 (the fork's message ends at 36: both numbers are free)
+        OPTD(38, "rms_decay", T_FLOAT, "0.99"), OPTD(39, "momentum2", T_FLOAT, "0.999")}},
       {"SolverState",                                                               // :176-180
        {OPT(1, "iter", T_INT32), OPT(2, "learned_net", T_STRING), RMSG(3, "history", "BlobProto")}},
       {"LayerParameter",                                                            // :215-389

@@ -306,6 +306,8 @@ void SGDSolver<Dtype>::ComputeUpdateValue() {
 }
 template <typename Dtype>
 void SGDSolver<Dtype>::PrepareUpdate() {
+  if (solver_type() == VV_SOLVER_RMSPROP || solver_type() == VV_SOLVER_ADAM)
+    this->net_->SetSolverExt((float)this->param_.get_num("momentum2"), (float)this->param_.get_num("rms_decay"));
   this->net_->SetUpdateHyperParams(GetLearningRate(), (float)this->param_.get_num("momentum"), (float)this->param_.get_num("weight_decay"),
                                    this->param_.get_str("regularization_type"), solver_type(), (float)this->param_.get_num("delta"));
 }
@@ -326,12 +328,34 @@ void SGDSolver<Dtype>::RestoreSolverState(const SolverState& state) {
   this->net_->SetHistory(h);
 }
 
+template <typename Dtype, int RULE>
+void UpdateRuleSolver<Dtype, RULE>::SnapshotSolverState(SolverState* state) {
+  SGDSolver<Dtype>::SnapshotSolverState(state);              // m of W, m of b (the other rules: their one history)
+  if (RULE != VV_SOLVER_ADAM) return;
+  vector<shared_ptr<Blob<Dtype> > > v;
+  this->net_->GetHistory2(&v);
+  for (size_t i = 0; i < v.size(); ++i) v[i]->ToProto(state->add_msg("history"));     // then v of W, v of b
+}
+template <typename Dtype, int RULE>
+void UpdateRuleSolver<Dtype, RULE>::RestoreSolverState(const SolverState& state) {
+  if (RULE != VV_SOLVER_ADAM) { SGDSolver<Dtype>::RestoreSolverState(state); return; }
+  CHECK_EQ(state.size("history"), 4) << "Incorrect length of history blobs: an Adam solverstate holds 4 (m of W, m of b, v of W, v of b).";
+  LOG(INFO) << "AdamSolver: restoring history";
+  vector<shared_ptr<Blob<Dtype> > > h(4);
+  for (int i = 0; i < 4; ++i) { h[i].reset(new Blob<Dtype>()); h[i]->FromProto(state.get_msg("history", i)); }
+  this->net_->SetHistory(vector<shared_ptr<Blob<Dtype> > >(h.begin(), h.begin() + 2));
+  this->net_->SetHistory2(vector<shared_ptr<Blob<Dtype> > >(h.begin() + 2, h.end()), this->iter_);      // t continues at iter + 1
+}
+
 template <typename Dtype>
 Solver<Dtype>* GetSolver(const SolverParameter& param) {
   const string type = param.get_enum("solver_type");
   if (type == "SGD") return new SGDSolver<Dtype>(param);
   if (type == "NESTEROV") return new NesterovSolver<Dtype>(param);
   if (type == "ADAGRAD") return new AdaGradSolver<Dtype>(param);
+  if (type == "RMSPROP") return new RMSPropSolver<Dtype>(param);
+  if (type == "ADAM") return new AdamSolver<Dtype>(param);
+  if (type == "ADADELTA") LOG(FATAL) << "SolverType ADADELTA is not implemented (SGD, NESTEROV, ADAGRAD, RMSPROP, ADAM are)";
   LOG(FATAL) << "Unknown SolverType: " << type;                                        // solver.hpp:141
   return nullptr;
 }
@@ -340,6 +364,8 @@ template class Solver<float>;
 template class SGDSolver<float>;
 template class UpdateRuleSolver<float, VV_SOLVER_NESTEROV>;
 template class UpdateRuleSolver<float, VV_SOLVER_ADAGRAD>;
+template class UpdateRuleSolver<float, VV_SOLVER_RMSPROP>;
+template class UpdateRuleSolver<float, VV_SOLVER_ADAM>;
 template Solver<float>* GetSolver(const SolverParameter& param);
 
 }  // namespace caffe

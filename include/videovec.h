@@ -31,8 +31,9 @@ enum { VV_PREC_F16 = 0, VV_PREC_BF16 = 1 };
 enum { VV_NORM_L1 = 1, VV_NORM_L2 = 2 };
 /* SolverParameter.regularization_type (caffe.proto:130-132). */
 enum { VV_REG_L1 = 1, VV_REG_L2 = 2 };
-/* SolverParameter.solver_type (caffe.proto SolverType). */
-enum { VV_SOLVER_SGD = 0, VV_SOLVER_NESTEROV = 1, VV_SOLVER_ADAGRAD = 2 };
+/* SolverParameter.solver_type (caffe.proto SolverType: SGD, NESTEROV, ADAGRAD).  RMSPROP and ADAM carry BVLC Caffe's numbers
+ * (its caffe.proto SolverType: RMSPROP = 3, ADADELTA = 4, ADAM = 5); the reference tree has neither solver.  4 is not implemented. */
+enum { VV_SOLVER_SGD = 0, VV_SOLVER_NESTEROV = 1, VV_SOLVER_ADAGRAD = 2, VV_SOLVER_RMSPROP = 3, VV_SOLVER_ADAM = 5 };
 
 /* One context per process / GPU.  Replaces Caffe::SetDevice + Caffe::set_mode(GPU)
  * (src/caffe/common.cpp:127-145, tools/caffe.cpp:92-104). */
@@ -161,6 +162,23 @@ int vv_params_set(vv_ctx* ctx, int32_t D, const float* W, const float* b, const 
                   const float* hb);
 int vv_params_get(vv_ctx* ctx, float* W, float* b, float* hW, float* hb);
 
+/* ---- RMSProp and Adam: the parameters vv_step_cfg has no field for, the update count and the second history.  BVLC Caffe's
+ * SolverParameter.momentum2 (field 39, default 0.999: Adam's beta2) and rms_decay (field 38, default 0.99); the reference tree's solver
+ * (solver.cpp:485-781) knows neither.  Sticky on the context until set again; each range ([0, 1)) is checked by the calls that take a
+ * vv_step_cfg of the solver that uses the value.  vv_update_hint's "exactly these solver parameters" includes them. */
+int vv_solver_ext_set(vv_ctx* ctx, float momentum2, float rms_decay);
+int vv_solver_ext_get(vv_ctx* ctx, float* momentum2, float* rms_decay);
+/* The number of Adam updates applied so far: the next one is update t = count + 1 of AdamSolver::ComputeUpdateValue's
+ * correction sqrt(1 - beta2^t) / (1 - beta1^t) (BVLC adam_solver.cpp: t = iter + 1).  Counts Adam updates only; vv_params_set puts it
+ * back to 0; a restored run sets it to the snapshot's iteration. */
+int vv_solver_iter_set(vv_ctx* ctx, int64_t count);
+int vv_solver_iter_get(vv_ctx* ctx, int64_t* count);
+/* Adam's second history (v; vv_params_set / _get's history holds m), shapes of W and b: BVLC AdamSolver keeps it in the second half of
+ * SGDSolver::history_ (adam_solver.cpp: val_v = history_[i + update_history_offset]).  NULL = zeros; before the first Adam update it reads
+ * as zeros.  vv_params_set clears it.  Host fp32; with the sharded update vv_history2_get gathers like vv_params_get (a collective). */
+int vv_history2_set(vv_ctx* ctx, const float* vW, const float* vb);
+int vv_history2_get(vv_ctx* ctx, float* vW, float* vb);
+
 /* ---- one training iteration */
 typedef struct {
   /* shapes: VideoSampledShotsDataParameter batch_size / context_size / num_negative_samples
@@ -190,7 +208,10 @@ typedef struct {
   int32_t reg;
   /* SolverParameter.solver_type (caffe.proto: SGD = 0, NESTEROV = 1, ADAGRAD = 2; GetSolver, solver.hpp:128-143):
    * NesterovSolver / AdaGradSolver::ComputeUpdateValue (solver.cpp:599-655, 714-781).  delta = AdaGrad's
-   * stability constant (SolverParameter.delta, default 1e-8); AdaGrad requires momentum == 0 (solver.hpp:121). */
+   * stability constant (SolverParameter.delta, default 1e-8); AdaGrad requires momentum == 0 (solver.hpp:121).
+   * RMSPROP = 3 and ADAM = 5 follow BVLC Caffe's RMSPropSolver / AdamSolver::ComputeUpdateValue (sgd_solvers: rmsprop_solver.cpp,
+   * adam_solver.cpp; not in the reference tree): RMSProp needs momentum == 0, Adam reads momentum as beta1; delta is their stability
+   * constant too, and what this struct has no field for arrives through vv_solver_ext_set. */
   int32_t solver_type;
   float delta;
   /* InnerProductParameter.regularization (inner_product_layer.cpp:80-90): the weight gradient is scaled by
@@ -237,13 +258,13 @@ int vv_apply_update(vv_ctx* ctx, const vv_step_cfg* cfg);
 int vv_step(vv_ctx* ctx, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device);
 /* Solver::Step as ONE unit (solver.cpp:177-221: ForwardBackward, ComputeUpdateValue, Update back to back): announces that the NEXT
  * vv_forward_backward* call will be followed by vv_apply_update with exactly these solver parameters (lr, momentum, weight_decay, lr_mult,
- * decay_mult, reg, solver_type, delta) and that nothing reads the gradient in between.  The library may then apply the update where the
+ * decay_mult, reg, solver_type, delta, and vv_solver_ext_set's values) and that nothing reads the gradient in between.  The library may then apply the update where the
  * gradient is produced (option "wgrad_update", on by default): when the weight-gradient GEMM runs with one split of K (large D x F, small batches -- the shipped
  * mednet_embedding_train.prototxt: 4096 x 4096, batch 128) its epilogue applies the solver's rule to the tile it holds, and the 4 D F bytes
  * of dW are neither written nor read back; vv_apply_update then only finishes the step (bias, loss, scale bookkeeping).  Parameters, history
  * and losses are bit for bit those of the un-hinted calls.  Between such a vv_forward_backward* and its vv_apply_update only vv_loss_get
  * is allowed (vv_grads_*, vv_params_get, another forward pass: VV_ERR_STATE -- the gradient of such a step is not kept, the parameters are
- * half-way).  Where the fusion does not apply (several splits of K, a communicator, a bound gradient buffer) the hint changes nothing.
+ * half-way).  Where the fusion does not apply (several splits of K, a communicator, a bound gradient buffer, Adam's two histories) the hint changes nothing.
  * vv_step announces itself.  One hint covers one step. */
 int vv_update_hint(vv_ctx* ctx, const vv_step_cfg* cfg);
 

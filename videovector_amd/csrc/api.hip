@@ -32,6 +32,7 @@ static inline const char* lab_env(const char*) { return nullptr; }
 using namespace vv;
 
 static int upd_pending_guard(vv_ctx* c, const char* who);      // (vv_update_hint, below)
+static int ensure_history2(vv_ctx* c);                         // (the second history of a two-history solver, below)
 thread_local char vv_g_err[512] = "";
 int vv_fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -266,7 +267,7 @@ int vv_destroy(vv_ctx* c) {
   if (c->comm) { vv::comm_destroy(c->comm); c->comm = nullptr; }    // drains the communication stream: before any buffer it uses goes
   vv_ops_release(c);
   free_batch(c);
-  dfree(c->table); dfree(c->patch_desc); dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->Wh);
+  dfree(c->table); dfree(c->patch_desc); dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh);
   dfree(c->scales); dfree(c->wmax_blocks); dfree(c->grads_own); dfree(c->mask); dfree(c->loss2);
   dfree(c->dd_key); dfree(c->dd_info_all); dfree(c->gg); dfree(c->gg_bound); dfree(c->w_gate);
   if (c->gate_err) (void)hipHostFree(c->gate_err);
@@ -555,8 +556,8 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   const size_t nW = (size_t)D * F;
   if (D != c->D && c->comm) return fail(VV_ERR_STATE, "vv_params_set: the communicator was sized for D = %d (vv_comm_destroy first)", c->D);
   if (D != c->D) {
-    dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->Wh); dfree(c->grads_own);
-    c->W = c->b = c->hW = c->hb = nullptr; c->Wh = nullptr; c->grads = c->grads_own = nullptr;
+    dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh); dfree(c->grads_own);
+    c->W = c->b = c->hW = c->hb = c->hW2 = c->hb2 = nullptr; c->Wh = nullptr; c->grads = c->grads_own = nullptr;
     c->D = D; c->Dp = (int)round_up(D, D_ALIGN);
 #ifdef VV_LAB
     // (lab: VV_LAB_PARAM_ARENA="skew_hW,skew_Wh" bytes -- W, its history and the 16-bit copy in ONE allocation, the second and third a
@@ -590,6 +591,9 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   if (b) HIPCHK(hipMemcpy(c->b, b, D * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(c->b, 0, D * 4));
   if (hW) HIPCHK(hipMemcpy(c->hW, hW, nW * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(c->hW, 0, nW * 4));
   if (hb) HIPCHK(hipMemcpy(c->hb, hb, D * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(c->hb, 0, D * 4));
+  // new parameters start a new run of the two-history solver: its second history and its update count go back to zero
+  if (c->hW2) { HIPCHK(hipMemset(c->hW2, 0, nW * 4)); HIPCHK(hipMemset(c->hb2, 0, D * 4)); }
+  c->adam_t = 0; c->hist2_partial = false;
   // scale for the half copy from max|W|, then convert (a scale update still pending from an earlier SGD step is void)
   c->scale_pending = false;
   c->red_lazy = false; c->grads_stale = false;   // (a gradient nobody asked for goes with the parameters it belonged to)
@@ -622,6 +626,11 @@ static int gather_params(vv_ctx* c) {
   HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
   HIPCHK(hipStreamWaitEvent(vv::comm_stream(c->comm), c->ev_chunk, 0));
   if (vv::comm_allgather(c->comm, bufs, sbytes, 3, 1)) return fail(VV_ERR_HIP, "all-gather of the parameters: %s", vv::comm_error(c->comm));
+  if (c->hist2_partial && c->hW2) {          // (a sharded Adam update: every rank took it, so every rank gathers the second history too)
+    void* bufs2[2] = {c->hW2, c->hb2};
+    if (vv::comm_allgather(c->comm, bufs2, sbytes + 1, 2, 1)) return fail(VV_ERR_HIP, "all-gather of the second history: %s", vv::comm_error(c->comm));
+  }
+  c->hist2_partial = false;
   if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-gather of the parameters: %s", vv::comm_error(c->comm));
   HIPCHK(hipStreamWaitEvent(c->stream, vv::comm_done_event(c->comm), 0));
   c->params_partial = false;
@@ -642,6 +651,63 @@ int vv_params_get(vv_ctx* c, float* W, float* b, float* hW, float* hb) {
   if (b) HIPCHK(hipMemcpy(b, c->b, c->D * 4, hipMemcpyDeviceToHost));
   if (hW) HIPCHK(hipMemcpy(hW, c->hW, nW * 4, hipMemcpyDeviceToHost));
   if (hb) HIPCHK(hipMemcpy(hb, c->hb, c->D * 4, hipMemcpyDeviceToHost));
+  return VV_OK;
+}
+
+// ---- the solvers beyond the reference's three (BVLC Caffe's RMSPropSolver / AdamSolver): what vv_step_cfg has no field for
+int vv_solver_ext_set(vv_ctx* c, float momentum2, float rms_decay) {
+  if (!c) return fail(VV_ERR_ARG, "vv_solver_ext_set: ctx is NULL");
+  if (!(momentum2 == momentum2) || !(rms_decay == rms_decay)) return fail(VV_ERR_ARG, "vv_solver_ext_set: NaN");
+  c->momentum2 = momentum2; c->rms_decay = rms_decay;      // (their ranges are checked with the rule that uses them: check_cfg)
+  return VV_OK;
+}
+int vv_solver_ext_get(vv_ctx* c, float* momentum2, float* rms_decay) {
+  if (!c) return fail(VV_ERR_ARG, "vv_solver_ext_get: ctx is NULL");
+  if (momentum2) *momentum2 = c->momentum2;
+  if (rms_decay) *rms_decay = c->rms_decay;
+  return VV_OK;
+}
+int vv_solver_iter_set(vv_ctx* c, int64_t t) {
+  if (!c || t < 0) return fail(VV_ERR_ARG, "vv_solver_iter_set: bad argument");
+  c->adam_t = t;
+  return VV_OK;
+}
+int vv_solver_iter_get(vv_ctx* c, int64_t* t) {
+  if (!c || !t) return fail(VV_ERR_ARG, "vv_solver_iter_get: NULL argument");
+  *t = c->adam_t;
+  return VV_OK;
+}
+int vv_history2_set(vv_ctx* c, const float* vW, const float* vb) {
+  if (!c) return fail(VV_ERR_ARG, "vv_history2_set: ctx is NULL");
+  { const int rcg = upd_pending_guard(c, "vv_history2_set"); if (rcg) return rcg; }
+  if (!c->W) return fail(VV_ERR_STATE, "vv_history2_set: no parameters");
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  { const int rce = ensure_history2(c); if (rce) return rce; }
+  const size_t nW = (size_t)c->D * c->F;
+  if (vW) HIPCHK(hipMemcpy(c->hW2, vW, nW * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(c->hW2, 0, nW * 4));
+  if (vb) HIPCHK(hipMemcpy(c->hb2, vb, (size_t)c->D * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(c->hb2, 0, (size_t)c->D * 4));
+  HIPCHK(hipDeviceSynchronize());
+  c->hist2_partial = false;                  // (every rank is given the whole history)
+  return VV_OK;
+}
+int vv_history2_get(vv_ctx* c, float* vW, float* vb) {
+  if (!c) return fail(VV_ERR_ARG, "vv_history2_get: ctx is NULL");
+  { const int rcg = upd_pending_guard(c, "vv_history2_get"); if (rcg) return rcg; }
+  if (!c->W) return fail(VV_ERR_STATE, "vv_history2_get: no parameters");
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  { const int rcg = gather_params(c); if (rcg) return rcg; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t nW = (size_t)c->D * c->F;
+  if (!c->hW2) {                             // no two-history update yet: the history is zero
+    if (vW) memset(vW, 0, nW * 4);
+    if (vb) memset(vb, 0, (size_t)c->D * 4);
+    return VV_OK;
+  }
+  if (vW) HIPCHK(hipMemcpy(vW, c->hW2, nW * 4, hipMemcpyDeviceToHost));
+  if (vb) HIPCHK(hipMemcpy(vb, c->hb2, (size_t)c->D * 4, hipMemcpyDeviceToHost));
   return VV_OK;
 }
 
@@ -717,8 +783,17 @@ static int check_cfg(vv_ctx* c, const vv_step_cfg* cfg) {
   if (cfg->norm != VV_NORM_L1 && cfg->norm != VV_NORM_L2) return fail(VV_ERR_ARG, "Unknown Norm (max_margin_loss_layer.cpp:120)");
   if (cfg->dropout_ratio < 0.f || cfg->dropout_ratio >= 1.f) return fail(VV_ERR_ARG, "dropout_ratio must be in [0,1)");
   if (cfg->reg != VV_REG_L1 && cfg->reg != VV_REG_L2) return fail(VV_ERR_ARG, "Unknown regularization type (solver.cpp:523)");
-  if (cfg->solver_type < VV_SOLVER_SGD || cfg->solver_type > VV_SOLVER_ADAGRAD) return fail(VV_ERR_ARG, "Unknown SolverType (solver.hpp:141)");
+  if (cfg->solver_type == 4) return fail(VV_ERR_ARG, "SolverType 4 (BVLC Caffe's ADADELTA) is not implemented");
+  if (cfg->solver_type < VV_SOLVER_SGD || cfg->solver_type > VV_SOLVER_ADAM) return fail(VV_ERR_ARG, "Unknown SolverType (solver.hpp:141)");
   if (cfg->solver_type == VV_SOLVER_ADAGRAD && cfg->momentum != 0.f) return fail(VV_ERR_ARG, "Momentum cannot be used with AdaGrad. (solver.hpp:121-122)");
+  if (cfg->solver_type == VV_SOLVER_RMSPROP) {
+    if (cfg->momentum != 0.f) return fail(VV_ERR_ARG, "Momentum cannot be used with RMSProp. (BVLC Caffe sgd_solvers.hpp, RMSPropSolver::constructor_sanity_check)");
+    if (!(c->rms_decay >= 0.f && c->rms_decay < 1.f)) return fail(VV_ERR_ARG, "rms_decay should lie between 0 and 1. (BVLC Caffe sgd_solvers.hpp, RMSPropSolver::constructor_sanity_check; vv_solver_ext_set)");
+  }
+  if (cfg->solver_type == VV_SOLVER_ADAM) {
+    if (!(cfg->momentum >= 0.f && cfg->momentum < 1.f)) return fail(VV_ERR_ARG, "Adam: momentum (beta1) must be in [0, 1)");
+    if (!(c->momentum2 >= 0.f && c->momentum2 < 1.f)) return fail(VV_ERR_ARG, "Adam: momentum2 (beta2) must be in [0, 1) (vv_solver_ext_set)");
+  }
   if (cfg->ip_regularization < 0.f) return fail(VV_ERR_ARG, "ip_regularization must be >= 0");
   return VV_OK;
 }
@@ -766,13 +841,30 @@ static bool report_wait(vv_ctx* c, int32_t want, hipStream_t s) {
 }
 
 // The solver's parameters of a step as the update kernels read them (k_sgd, k_reduce_sgd, the weight-gradient GEMM's epilogue)
-static SolverRule solver_rule(const vv_step_cfg& cfg) {
+// momentum2 / rms_decay: the context's vv_solver_ext_set values (as they stood at vv_update_hint for an announced rule); t: the 1-based
+// count of the Adam update this rule is for (0: none -- corr stays 1).  The 1 - x coefficients are formed here, once, in fp32.
+static SolverRule solver_rule(const vv_step_cfg& cfg, float momentum2, float rms_decay, int64_t t = 0) {
   SolverRule r;
   r.rate = cfg.lr; r.momentum = cfg.momentum; r.weight_decay = cfg.weight_decay;
   r.lr_mult_w = cfg.lr_mult[0]; r.lr_mult_b = cfg.lr_mult[1];
   r.decay_mult_w = cfg.decay_mult[0]; r.decay_mult_b = cfg.decay_mult[1];
   r.reg = cfg.reg; r.solver_type = cfg.solver_type; r.delta = cfg.delta;
+  if (cfg.solver_type == VV_SOLVER_RMSPROP) { r.decay2 = rms_decay; r.om2 = 1.f - rms_decay; }
+  if (cfg.solver_type == VV_SOLVER_ADAM) {
+    r.decay2 = momentum2; r.om1 = 1.f - cfg.momentum; r.om2 = 1.f - momentum2;
+    // BVLC AdamSolver::ComputeUpdateValue: correction = sqrt(1 - beta2^t) / (1 - beta1^t), t = iter + 1; in double, rounded once
+    if (t > 0) r.corr = (float)(std::sqrt(1.0 - std::pow((double)momentum2, (double)t)) / (1.0 - std::pow((double)cfg.momentum, (double)t)));
+  }
   return r;
+}
+// the second history, zero-filled, on the first use of a two-history solver (or vv_history2_set): the only allocation a step may make
+static int ensure_history2(vv_ctx* c) {
+  if (c->hW2) return VV_OK;
+  const size_t nW = (size_t)c->D * c->F;
+  HIPCHK(hipMalloc(&c->hW2, nW * 4)); HIPCHK(hipMalloc(&c->hb2, (size_t)c->D * 4));
+  HIPCHK(hipMemset(c->hW2, 0, nW * 4)); HIPCHK(hipMemset(c->hb2, 0, (size_t)c->D * 4));
+  HIPCHK(hipDeviceSynchronize());            // (the fills are complete before a kernel of any stream reads them)
+  return VV_OK;
 }
 
 // A launch just queued on s recomputed the W -> half scale (consumed: FusedUpdArgs / WgradUpd::recompute_scale) and so folded
@@ -789,6 +881,7 @@ static hipError_t clear_wmax_seed(vv_ctx* c, bool consumed, hipStream_t s) {
 static int finish_update(vv_ctx* c, int n_slots) {
   c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = n_slots;
   c->scale_pending = true;
+  if (c->adam_pending) { c->adam_t++; c->adam_pending = false; }      // the Adam update is queued: its t is taken
   HIPCHK(hipGetLastError());
   c->iter++;
   c->prof_calls++;
@@ -984,6 +1077,7 @@ int vv_update_hint(vv_ctx* c, const vv_step_cfg* cfg) {
   if (rc) return rc;
   c->upd_hint = true;
   c->upd_cfg = *cfg;
+  c->upd_momentum2 = c->momentum2; c->upd_rms_decay = c->rms_decay;
   return VV_OK;
 }
 
@@ -1302,8 +1396,9 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // vv_update_hint + one split of K: the tile in the weight-gradient GEMM's accumulators IS the gradient -- the solver's rule is applied
   // there (WgradUpd) and the 4 D F bytes of dW are neither written nor read back (the shipped configuration: D = F = 4096, 134 MB of the
   // update's 370).  vv_apply_update then runs only the bias / loss workgroups.
+  // (Adam keeps two histories: the epilogue declines it, the step takes k_reduce_sgd -- the hint changes nothing, as for several splits)
   const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
-                      (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS;
+                      (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM;
   if (fuse_w) {
     WgradUpd& u = wa.upd;
     wa.fuse_upd = 1;
@@ -1312,7 +1407,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     u.wmax_prev = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; u.wmax_prev_n = c->wmax_n;
     u.recompute_scale = c->scale_pending ? 1 : 0; u.prec = c->prec;
     u.D = c->D; u.F = c->F;
-    u.rule = solver_rule(c->upd_cfg);
+    u.rule = solver_rule(c->upd_cfg, c->upd_momentum2, c->upd_rms_decay);
     u.sg = ra.sg; u.gg = ra.gg; u.ip_scale = ra.ip_scale;
   }
   // f16 split-K partial products (option "slab16"): the phase-staggered kernel with several splits only (one split: the update rides in the
@@ -1478,16 +1573,23 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   float* const wmax_new = c->wmax_blocks + (1 - c->wmax_cur) * WMAX_SLOTS;     // the buffer the previous update did not write
   a.W = c->W; a.b = c->b; a.hW = c->hW; a.hb = c->hb; a.grads = c->grads; a.Wh = c->Wh; a.scales = c->scales; a.wmax_blocks = wmax_new;
   a.D = c->D; a.F = c->F; a.Dp = c->Dp; a.Fp = c->Fp;
-  a.rule = solver_rule(*cfg);
+  // Adam: the second history (allocated by the first such update) and this update's own bias correction -- t is the library's counter of
+  // Adam updates, every queued update carries its corr_t as a kernel argument and nothing synchronises
+  const bool adam = cfg->solver_type == VV_SOLVER_ADAM;
+  if (adam && c->upd_in_wgrad) return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
+  if (adam && (rc = ensure_history2(c))) return rc;
+  a.rule = solver_rule(*cfg, c->momentum2, c->rms_decay, adam ? c->adam_t + 1 : 0);     // (t is committed where the update is queued: finish_update)
+  c->adam_pending = adam;
+  float* const vW = adam ? c->hW2 : nullptr; float* const vb = adam ? c->hb2 : nullptr;
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
   if (c->upd_in_wgrad) {
     // the parameter matrix was updated in the weight-gradient GEMM (vv_update_hint): bias, loss, the guard's report -- k_reduce_sgd's
     // special workgroups alone -- and the bookkeeping of the scale
     // (what the weight-gradient GEMM applied: WgradUpd::rule -- the bias multipliers may differ, the bias is updated here)
-    const SolverRule h = solver_rule(c->upd_cfg);
+    const SolverRule h = solver_rule(c->upd_cfg, c->upd_momentum2, c->upd_rms_decay);
     const SolverRule& r = a.rule;
     if (r.rate != h.rate || r.momentum != h.momentum || r.weight_decay != h.weight_decay || r.lr_mult_w != h.lr_mult_w ||
-        r.decay_mult_w != h.decay_mult_w || r.reg != h.reg || r.solver_type != h.solver_type || r.delta != h.delta)
+        r.decay_mult_w != h.decay_mult_w || r.reg != h.reg || r.solver_type != h.solver_type || r.delta != h.delta || r.decay2 != h.decay2)
       return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
     FusedUpdArgs fa;
     fa.r = c->red_args; fa.g = a; fa.prec = c->prec; fa.no_params = 1; fa.recompute_scale = 0; fa.store_grads = 0;
@@ -1506,7 +1608,7 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
     fa.store_grads = keep_grads;
     c->red_lazy = false; c->grads_stale = !keep_grads;
     int n_new = 0;
-    PROFILED(c, "reduce_sgd", (n_new = launch_reduce_sgd(fa, c->stream)));
+    PROFILED(c, "reduce_sgd", (n_new = launch_reduce_sgd(fa, c->stream, vW, vb)));
     HIPCHK(clear_wmax_seed(c, fa.recompute_scale, c->stream));
     return finish_update(c, n_new);
   }
@@ -1539,10 +1641,11 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
     g.W = c->W + (size_t)rank * rps * c->F; g.hW = c->hW + (size_t)rank * rps * c->F;
     g.b = c->b + (size_t)rank * rps; g.hb = c->hb + (size_t)rank * rps;
     g.grads = c->grads + (size_t)rank * shard_f;
+    float* const svW = adam ? vW + (size_t)rank * rps * c->F : nullptr; float* const svb = adam ? vb + (size_t)rank * rps : nullptr;     // the shard owns its rows of v
     g.Wh = c->Wh + (size_t)rank * rps * c->Fp;
     g.chunked = 1; g.f_begin = 0; g.f_count = c->F; g.do_bias = 1; g.set_scale = 1;      // (chunked = 1 with the whole width: this launch's own grid and slots)
     g.blk_off = rank * nb; g.n_blk = nb;
-    PROFILED(c, "sgd", launch_sgd(c->prec, g, cs));
+    PROFILED(c, "sgd", launch_sgd(c->prec, g, cs, svW, svb));
     void* bufs[3] = {c->Wh, c->b, wmax_new};
     const size_t sbytes[3] = {(size_t)rps * c->Fp * 2, (size_t)rps * 4, (size_t)nb * 4};
     if (vv::comm_allgather(c->comm, bufs, sbytes, 3)) return fail(VV_ERR_HIP, "all-gather: %s", vv::comm_error(c->comm));
@@ -1552,6 +1655,7 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
     }
     c->grads_pending = false; c->upd_inflight = !inl; c->upd_unjoined = false;
     c->params_partial = world > 1;
+    if (adam) c->hist2_partial = world > 1;
     return finish_update(c, nb * world);
   }
   if (overlapped) {
@@ -1579,12 +1683,12 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
       a.chunked = 1; a.f_begin = c0; a.f_count = c1 - c0; a.do_bias = last; a.set_scale = k == 0;
       a.blk_off = k * (SGD_BLOCKS / nch); a.n_blk = last ? SGD_BLOCKS - a.blk_off : SGD_BLOCKS / nch;      // together: every slot of wmax_blocks
       a.pub_flag = c->w_gate + k * W_GATE_STRIDE;          // the kernel's last workgroup publishes the chunk (SgdArgs::pub_flag)
-      if (k == 0) PROFILED(c, "sgd", launch_sgd(c->prec, a, cs)); else launch_sgd(c->prec, a, cs);     // (an empty chunk: its wmax slots become 0, the bias if it is the last)
+      if (k == 0) PROFILED(c, "sgd", launch_sgd(c->prec, a, cs, vW, vb)); else launch_sgd(c->prec, a, cs, vW, vb);     // (an empty chunk: its wmax slots become 0, the bias if it is the last)
     }
     if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
     c->grads_pending = false; c->upd_inflight = true; c->upd_unjoined = false;    // (comm_done_event now marks the end of THIS update, behind the old one)
   } else
-  PROFILED(c, "sgd", launch_sgd(c->prec, a, c->stream));
+  PROFILED(c, "sgd", launch_sgd(c->prec, a, c->stream, vW, vb));
   // The next W -> half scale (k_scale_update: folds this kernel's per-block max |w|) is needed by the NEXT k_sgd only.  It
   // is left pending and performed by one extra workgroup of the next step's k_reduce; anything else that touches the
   // scales or the parameters first flushes it as its own launch.

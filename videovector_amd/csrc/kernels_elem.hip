@@ -14,6 +14,10 @@
 //                  (solver.cpp:502-531, blob.cpp:112-136), also refreshes the half copy of W.
 //   table / conversion helpers.
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <type_traits>
+#include "../../include/videovec.h"
 #include "vv_internal.h"
 
 namespace vv {
@@ -1666,8 +1670,12 @@ void launch_reduce(const ReduceArgs& a, hipStream_t s) {
 // solver.cpp:502-531: g += local_decay * w (L2) | sign(w) (L1); h = local_rate * g + momentum * h;
 // blob.cpp:118-120: w -= h.  Also writes the scaled half copy used by the next forward and tracks
 // max |w| for the f16 range guard.
-template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
+// A = SgdArgs2: the two-history form (Adam, SolverRule::step2) -- instantiations of their own with the sibling's access widths, so that
+// the one-history kernels carry neither the second pointer nor its loads; v is read and written once: non-temporal like W and the history.
+// RMS: the instantiation that also knows RMSProp (SolverRule::step<RMS>); the others are the parent's code for the three older rules.
+template <typename T, bool VEC, typename A = SgdArgs, bool RMS = false>
+__global__ __launch_bounds__(256) void k_sgd(A a) {
+  constexpr bool H2 = std::is_same<A, SgdArgs2>::value;
   if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // (a failed exchange in front: SgdArgs::skip_if)
   const float sw = a.scales->sw_next;
   const int64_t nW = (int64_t)a.D * a.F;
@@ -1675,7 +1683,12 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
   const float lr_w = rule.rate * rule.lr_mult_w, dc_w = rule.weight_decay * rule.decay_mult_w;
   float wmax = 0.f;
   auto upd = [&](float w, float g, float& h) {
-    w = rule.step(w, g, h, lr_w, dc_w);
+    w = rule.template step<RMS>(w, g, h, lr_w, dc_w);
+    wmax = fmaxf(wmax, fabsf(w));
+    return w;
+  };
+  auto upd2 = [&](float w, float g, float& h, float& v) {
+    w = rule.step2(w, g, h, v, lr_w, dc_w);
     wmax = fmaxf(wmax, fabsf(w));
     return w;
   };
@@ -1689,7 +1702,13 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
       const int64_t og = a.chunked ? (int64_t)a.D * a.f_begin + (int64_t)d * fc + fl : o;     // chunk-major gradient buffer
       float4 w = nt_load4(a.W + o), h = nt_load4(a.hW + o);
       const float4 g = nt_load4(a.grads + og);
+      if constexpr (H2) {
+        float4 v = nt_load4(a.vW + o);
+        w.x = upd2(w.x, g.x, h.x, v.x); w.y = upd2(w.y, g.y, h.y, v.y); w.z = upd2(w.z, g.z, h.z, v.z); w.w = upd2(w.w, g.w, h.w, v.w);
+        nt_store4(a.vW + o, v);
+      } else {
       w.x = upd(w.x, g.x, h.x); w.y = upd(w.y, g.y, h.y); w.z = upd(w.z, g.z, h.z); w.w = upd(w.w, g.w, h.w);
+      }
       nt_store4(a.W + o, w);
       nt_store4(a.hW + o, h);
       const uint2 q = pack_half4<T>(w.x, w.y, w.z, w.w, sw);
@@ -1699,7 +1718,9 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
   } else {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nW; i += (int64_t)gridDim.x * 256) {
       float h = a.hW[i];
-      const float w = upd(a.W[i], a.grads[i], h);
+      float w;
+      if constexpr (H2) { float v = a.vW[i]; w = upd2(a.W[i], a.grads[i], h, v); a.vW[i] = v; }
+      else w = upd(a.W[i], a.grads[i], h);
       a.hW[i] = h;
       a.W[i] = w;
       const int d = (int)(i / a.F), f = (int)(i % a.F);
@@ -1709,7 +1730,9 @@ __global__ __launch_bounds__(256) void k_sgd(SgdArgs a) {
   const float lr_b = rule.rate * rule.lr_mult_b, dc_b = rule.weight_decay * rule.decay_mult_b;
   for (int d = blockIdx.x * 256 + threadIdx.x; a.do_bias && d < a.D; d += gridDim.x * 256) {
     float h = a.hb[d];
-    const float bn = rule.step(a.b[d], a.grads[nW + d], h, lr_b, dc_b);
+    float bn;
+    if constexpr (H2) { float v = a.vb[d]; bn = rule.step2(a.b[d], a.grads[nW + d], h, v, lr_b, dc_b); a.vb[d] = v; }
+    else bn = rule.template step<RMS>(a.b[d], a.grads[nW + d], h, lr_b, dc_b);
     if (a.pub_flag) __hip_atomic_store(a.b + d, bn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else a.b[d] = bn;
     a.hb[d] = h;
   }
@@ -1748,10 +1771,22 @@ __global__ void k_delay(int us) {
 }
 void launch_delay(int us, hipStream_t s) { hipLaunchKernelGGL(k_delay, dim3(1), dim3(1), 0, s, us); }
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s) { hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, s, flag, seq); }
-void launch_sgd(int prec, const SgdArgs& a, hipStream_t s) {
+void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW, float* vb) {
   const bool vec = a.F % 4 == 0;
   ko().last_update_form = vec ? 1 : 2;    // ("last_update_form": the chunked and the sharded update pass here too, F % 4 == 0 both)
   const dim3 grid(a.chunked ? a.n_blk : SGD_BLOCKS), block(256);
+  if (a.rule.solver_type == VV_SOLVER_ADAM) {          // the two-history instantiations (api.hip provides the second history)
+    if (!vW || !vb) { fprintf(stderr, "launch_sgd: an Adam rule without its second history\n"); abort(); }      // (a caller's bug: never a null store on the device)
+    SgdArgs2 a2; (SgdArgs&)a2 = a; a2.vW = vW; a2.vb = vb;
+    if (prec == 0) { if (vec) VV_LAUNCH((k_sgd<F16, true, SgdArgs2>), grid, block, 0, s, a2); else VV_LAUNCH((k_sgd<F16, false, SgdArgs2>), grid, block, 0, s, a2); }
+    else { if (vec) VV_LAUNCH((k_sgd<BF16, true, SgdArgs2>), grid, block, 0, s, a2); else VV_LAUNCH((k_sgd<BF16, false, SgdArgs2>), grid, block, 0, s, a2); }
+    return;
+  }
+  if (a.rule.solver_type == VV_SOLVER_RMSPROP) {       // the instantiations that know RMSProp
+    if (prec == 0) { if (vec) VV_LAUNCH((k_sgd<F16, true, SgdArgs, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<F16, false, SgdArgs, true>), grid, block, 0, s, a); }
+    else { if (vec) VV_LAUNCH((k_sgd<BF16, true, SgdArgs, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<BF16, false, SgdArgs, true>), grid, block, 0, s, a); }
+    return;
+  }
   if (prec == 0) { if (vec) VV_LAUNCH((k_sgd<F16, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<F16, false>), grid, block, 0, s, a); }
   else { if (vec) VV_LAUNCH((k_sgd<BF16, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<BF16, false>), grid, block, 0, s, a); }
 }
@@ -1771,8 +1806,11 @@ void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_b
 // (Round 4, residency: 76 registers = six workgroups per CU resident, the eight of a CU in two uneven rounds.  A one-element form at 57
 // registers with all eight resident is SLOWER (23.7 against 21.8 us), so is every cap below six (LDS-limited 5 / 4 / 3 per CU: 23.8-25 /
 // 24.7 / 29.5 us); half or a quarter of the workgroups with two / four elements per thread: the same 21.3-22.6 us.)
-template <typename T, bool S16 = false>
-__global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
+// FA = FusedUpdArgs2: the two-history form (Adam), as k_sgd's -- 16-byte accesses of v beside those of the history, two per eight elements
+// on f16 slabs, non-temporal.
+template <typename T, bool S16 = false, typename FA = FusedUpdArgs, bool RMS = false>
+__global__ __launch_bounds__(256) void k_reduce_sgd(FA fa) {
+  constexpr bool H2 = std::is_same<FA, FusedUpdArgs2>::value;
   const ReduceArgs& a = fa.r;
   const SgdArgs& g = fa.g;
   const int ndb = (a.D + 15) / 16;
@@ -1787,7 +1825,8 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
     db_colsum(a, bid - (G - 1 - ndb), part, [&](int d, float t) {
       a.grads[(int64_t)a.D * a.F + d] = t;
       float h = g.hb[d];
-      g.b[d] = rule.step(g.b[d], t, h, rule.rate * rule.lr_mult_b, rule.weight_decay * rule.decay_mult_b);
+      if constexpr (H2) { float v = fa.vb[d]; g.b[d] = rule.step2(g.b[d], t, h, v, rule.rate * rule.lr_mult_b, rule.weight_decay * rule.decay_mult_b); fa.vb[d] = v; }
+      else g.b[d] = rule.template step<RMS>(g.b[d], t, h, rule.rate * rule.lr_mult_b, rule.weight_decay * rule.decay_mult_b);
       g.hb[d] = h;
     });
     return;
@@ -1799,7 +1838,7 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
   const int64_t slab_sz = slab_pitch(a.Dp, a.Fp);
   int64_t i = (int64_t)bid * 256 + threadIdx.x;
   // the first element's loads fly while the scale is worked out
-  float4 t[8], w = make_float4(0.f, 0.f, 0.f, 0.f), h = w;
+  float4 t[8], w = make_float4(0.f, 0.f, 0.f, 0.f), h = w, v = w, v1 = w;     // (v, v1: the second history, H2 only)
   auto load = [&](int64_t ii) {
     const int d = (int)(ii / f4), f = (int)(ii % f4) * 4;
     const int64_t po = (int64_t)d * a.Fp + f;
@@ -1813,6 +1852,7 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
     }
     const int64_t o = (int64_t)d * a.F + f;
     w = nt_load4(g.W + o); h = nt_load4(g.hW + o);
+    if constexpr (H2) v = nt_load4(fa.vW + o);
   };
   // S16 (f16 partial products): EIGHT elements per thread -- 16-byte loads of the eight slabs (8-byte accesses run at ~0.6 of the 16-byte rate
   // per byte), two 16-byte accesses each for W and the history, one 16-byte store of the half copy; the same per-element arithmetic in the same
@@ -1835,6 +1875,7 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
     }
     const int64_t o = (int64_t)d * a.F + f;
     w = nt_load4(g.W + o); w1 = nt_load4(g.W + o + 4); h = nt_load4(g.hW + o); h1 = nt_load4(g.hW + o + 4);
+    if constexpr (H2) { v = nt_load4(fa.vW + o); v1 = nt_load4(fa.vW + o + 4); }
   };
   if constexpr (S16) { if (i < n8) load8(i); }
   else { if (i < n4) load(i); }
@@ -1851,6 +1892,7 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
       const int64_t o = (int64_t)d * a.F + f;
       float gr[8], wn[8], hn[8];
       const float w8[8] = {w.x, w.y, w.z, w.w, w1.x, w1.y, w1.z, w1.w}, hh8[8] = {h.x, h.y, h.z, h.w, h1.x, h1.y, h1.z, h1.w};
+      float vn[8] = {v.x, v.y, v.z, v.w, v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float sj = (float)t8[0][j] * sc8[0];
@@ -1859,7 +1901,8 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
           if (u < a.S) sj += (float)t8[u][j] * sc8[u];
         gr[j] = __fmul_rn(sj, inv);
         hn[j] = hh8[j];
-        wn[j] = rule.step(w8[j], gr[j], hn[j], lr_w, dc_w);
+        if constexpr (H2) wn[j] = rule.step2(w8[j], gr[j], hn[j], vn[j], lr_w, dc_w);
+        else wn[j] = rule.template step<RMS>(w8[j], gr[j], hn[j], lr_w, dc_w);
         wmax = fmaxf(wmax, fabsf(wn[j]));
       }
       if (fa.store_grads) { nt_store4(a.grads + o, make_float4(gr[0], gr[1], gr[2], gr[3])); nt_store4(a.grads + o + 4, make_float4(gr[4], gr[5], gr[6], gr[7])); }
@@ -1867,6 +1910,7 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
       if (i < n8) load8(i);                      // the next element's loads before this one's stores
       nt_store4(g.W + o, make_float4(wn[0], wn[1], wn[2], wn[3])); nt_store4(g.W + o + 4, make_float4(wn[4], wn[5], wn[6], wn[7]));
       nt_store4(g.hW + o, make_float4(hn[0], hn[1], hn[2], hn[3])); nt_store4(g.hW + o + 4, make_float4(hn[4], hn[5], hn[6], hn[7]));
+      if constexpr (H2) { nt_store4(fa.vW + o, make_float4(vn[0], vn[1], vn[2], vn[3])); nt_store4(fa.vW + o + 4, make_float4(vn[4], vn[5], vn[6], vn[7])); }
       const uint2 q0 = pack_half4<T>(wn[0], wn[1], wn[2], wn[3], sw), q1 = pack_half4<T>(wn[4], wn[5], wn[6], wn[7], sw);
       *(uint4*)(g.Wh + (int64_t)d * g.Fp + f) = make_uint4(q0.x, q0.y, q1.x, q1.y);
     }
@@ -1880,25 +1924,49 @@ __global__ __launch_bounds__(256) void k_reduce_sgd(FusedUpdArgs fa) {
     // (rounded products, as the two-launch form stores them: no contraction into the rule's first multiply-add)
     const float4 gr = make_float4(__fmul_rn(s.x, inv), __fmul_rn(s.y, inv), __fmul_rn(s.z, inv), __fmul_rn(s.w, inv));
     if (fa.store_grads) nt_store4(a.grads + o, gr);
-    float4 wn = w, hn = h;
-    wn.x = rule.step(wn.x, gr.x, hn.x, lr_w, dc_w); wn.y = rule.step(wn.y, gr.y, hn.y, lr_w, dc_w);
-    wn.z = rule.step(wn.z, gr.z, hn.z, lr_w, dc_w); wn.w = rule.step(wn.w, gr.w, hn.w, lr_w, dc_w);
+    float4 wn = w, hn = h, vn = v;
+    if constexpr (H2) {
+      wn.x = rule.step2(wn.x, gr.x, hn.x, vn.x, lr_w, dc_w); wn.y = rule.step2(wn.y, gr.y, hn.y, vn.y, lr_w, dc_w);
+      wn.z = rule.step2(wn.z, gr.z, hn.z, vn.z, lr_w, dc_w); wn.w = rule.step2(wn.w, gr.w, hn.w, vn.w, lr_w, dc_w);
+    } else {
+    wn.x = rule.template step<RMS>(wn.x, gr.x, hn.x, lr_w, dc_w); wn.y = rule.template step<RMS>(wn.y, gr.y, hn.y, lr_w, dc_w);
+    wn.z = rule.template step<RMS>(wn.z, gr.z, hn.z, lr_w, dc_w); wn.w = rule.template step<RMS>(wn.w, gr.w, hn.w, lr_w, dc_w);
+    }
     wmax = fmaxf(wmax, fmaxf(fmaxf(fabsf(wn.x), fabsf(wn.y)), fmaxf(fabsf(wn.z), fabsf(wn.w))));
     i += (int64_t)nblk * 256;
     if (i < n4) load(i);                       // the next element's loads before this one's stores
     nt_store4(g.W + o, wn);
     nt_store4(g.hW + o, hn);
+    if constexpr (H2) nt_store4(fa.vW + o, vn);
     *(uint2*)(g.Wh + (int64_t)d * g.Fp + f) = pack_half4<T>(wn.x, wn.y, wn.z, wn.w, sw);
   }
   __shared__ float wm[4];
   update_end<4>(wmax, wm, threadIdx.x >> 6, g.wmax_blocks + bid, bid == 0, g.scales, sw, fa.recompute_scale);
 }
-int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s) {
+int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s, float* vW, float* vb) {
   const int ndb = (a.r.D + 15) / 16;
   const int ept = a.r.slab16 ? 8 : 4;                                       // elements per thread (k_reduce_sgd's S16 form: eight)
   const int nblk = a.no_params ? 0 : (int)std::min<int64_t>(((int64_t)a.r.D * (a.r.F / ept) + 255) / 256, WMAX_SLOTS);
   const dim3 grid(nblk + ndb + 1);
   ko().last_update_form = a.no_params ? 5 : a.r.slab16 ? 4 : 3;     // ("last_update_form"; no_params: the matrix was updated in the weight-gradient GEMM)
+  if (a.g.rule.solver_type == VV_SOLVER_ADAM) {        // the two-history instantiations (never with no_params: the epilogue declines Adam, api.hip)
+    if (!vW || !vb) { fprintf(stderr, "launch_reduce_sgd: an Adam rule without its second history\n"); abort(); }
+    FusedUpdArgs2 a2; (FusedUpdArgs&)a2 = a; a2.vW = vW; a2.vb = vb;
+    if (a.r.slab16) {
+      if (a.prec == 0) VV_LAUNCH((k_reduce_sgd<F16, true, FusedUpdArgs2>), grid, dim3(256), 0, s, a2);
+      else VV_LAUNCH((k_reduce_sgd<BF16, true, FusedUpdArgs2>), grid, dim3(256), 0, s, a2);
+    } else if (a.prec == 0) VV_LAUNCH((k_reduce_sgd<F16, false, FusedUpdArgs2>), grid, dim3(256), 0, s, a2);
+    else VV_LAUNCH((k_reduce_sgd<BF16, false, FusedUpdArgs2>), grid, dim3(256), 0, s, a2);
+    return nblk;
+  }
+  if (a.g.rule.solver_type == VV_SOLVER_RMSPROP) {     // the instantiations that know RMSProp
+    if (a.r.slab16) {
+      if (a.prec == 0) VV_LAUNCH((k_reduce_sgd<F16, true, FusedUpdArgs, true>), grid, dim3(256), 0, s, a);
+      else VV_LAUNCH((k_reduce_sgd<BF16, true, FusedUpdArgs, true>), grid, dim3(256), 0, s, a);
+    } else if (a.prec == 0) VV_LAUNCH((k_reduce_sgd<F16, false, FusedUpdArgs, true>), grid, dim3(256), 0, s, a);
+    else VV_LAUNCH((k_reduce_sgd<BF16, false, FusedUpdArgs, true>), grid, dim3(256), 0, s, a);
+    return nblk;
+  }
   if (a.r.slab16) {
     if (a.prec == 0) VV_LAUNCH((k_reduce_sgd<F16, true>), grid, dim3(256), 0, s, a);
     else VV_LAUNCH((k_reduce_sgd<BF16, true>), grid, dim3(256), 0, s, a);

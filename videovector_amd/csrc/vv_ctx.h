@@ -48,6 +48,14 @@ struct vv_ctx {
   // parameters
   int D = 0, Dp = 0;
   float *W = nullptr, *b = nullptr, *hW = nullptr, *hb = nullptr;
+  // the second history (Adam's v; hW / hb hold m): allocated zero-filled by the first two-history update or by vv_history2_set, never on
+  // the step path after that; vv_params_set clears it
+  float *hW2 = nullptr, *hb2 = nullptr;
+  float momentum2 = 0.999f, rms_decay = 0.99f;   // vv_solver_ext_set: sticky (BVLC SolverParameter's defaults)
+  int64_t adam_t = 0;                       // Adam updates applied so far (the next one uses t = adam_t + 1); vv_solver_iter_set, reset by vv_params_set
+  bool adam_pending = false;                // the vv_apply_update in progress is an Adam update: finish_update commits adam_t (a failed call leaves t alone)
+  float upd_momentum2 = 0.f, upd_rms_decay = 0.f;   // ... as they stood when vv_update_hint announced upd_cfg
+  bool hist2_partial = false;               // as params_partial, for hW2 / hb2 (a sharded Adam update ran since the last gather)
   uint16_t* Wh = nullptr; vv::Scales* scales = nullptr; float* wmax_blocks = nullptr;
   int n_cu = 256;                           // compute units of the device
   bool scale_pending = false;               // k_sgd ran, its scale update has not (it rides in the next k_reduce)

@@ -271,23 +271,59 @@ struct SegsumArgs {
 };
 
 // The solver's parameters as the three update kernels read them -- k_sgd, k_reduce_sgd and the weight-gradient GEMM's UPD epilogue, which
-// must give bit-identical parameters -- and the rule itself (api.hip: solver_rule fills it from a vv_step_cfg).
+// must give bit-identical parameters -- and the rule itself (api.hip: solver_rule fills it from a vv_step_cfg and the context's
+// vv_solver_ext_set values).
 struct SolverRule {
   float rate, momentum, weight_decay;
   float lr_mult_w, lr_mult_b, decay_mult_w, decay_mult_b;
   int reg;                 // 1 L1, 2 L2
-  int solver_type;         // 0 SGD, 1 Nesterov, 2 AdaGrad
-  float delta;             // AdaGrad stability constant
+  int solver_type;         // 0 SGD, 1 Nesterov, 2 AdaGrad, 3 RMSProp, 5 Adam
+  float delta;             // stability constant of AdaGrad, RMSProp and Adam
+  // RMSProp and Adam (BVLC Caffe's RMSPropSolver / AdamSolver; the reference tree has neither).  Every 1 - x is formed ONCE, on the host, in
+  // fp32: decay2 = rms_decay (RMSProp) or beta2 (Adam; beta1 is `momentum`), om1 = 1 - beta1, om2 = 1 - decay2;
+  // corr = sqrt(1 - beta2^t) / (1 - beta1^t) of THIS update (computed in double, rounded once): a queued step carries its own
+  float decay2 = 0.f, om1 = 0.f, om2 = 0.f, corr = 1.f;
 #ifdef __HIPCC__
-  // one parameter element: regulariser, then SGD (solver.cpp:502-531), Nesterov (:599-655) or AdaGrad (:714-781); h: its history.
-  // lr / dc: the local rate and decay (rate and weight_decay times the blob's multipliers)
-  __device__ __forceinline__ float step(float w, float g, float& h, float lr, float dc) const {
+  // the regulariser (solver.cpp:502-531): g' = g + dc r
+  __device__ __forceinline__ float regularise(float w, float g, float dc) const {
     if (dc != 0.f) g += dc * (reg == 2 ? w : (float)((w > 0.f) - (w < 0.f)));
+    return g;
+  }
+  // one parameter element: regulariser, then SGD (solver.cpp:502-531), Nesterov (:599-655), AdaGrad (:714-781) or RMSProp (BVLC
+  // RMSPropSolver::ComputeUpdateValue: h' = rms_decay h + (1 - rms_decay) g'^2, u = lr (g' / (sqrt(h') + delta))); h: its history.
+  // lr / dc: the local rate and decay (rate and weight_decay times the blob's multipliers).
+  // RMSProp shares the regulariser's statement with the three older rules -- g' formed exactly as today, contraction left to the
+  // compiler -- and rounds its OWN products and sums in the order written (contraction off inside its branch).  A form of `step` that
+  // took RMSProp out in front of the regulariser, to un-fuse that too, cost the weight-gradient epilogue 84-100 bytes of scratch per
+  // lane: rejected.
+  // RMS = false: the three older rules alone, instruction for instruction what they always were -- k_sgd and k_reduce_sgd give RMSProp
+  // instantiations of its own (with the runtime branch in every instantiation k_reduce_sgd over f16 slabs ran 18.7 -> 19.2 us for SGD
+  // at cfg 2 and the step missed the condition of DESIGN.md 3.5); the weight-gradient GEMM's epilogue keeps the branch (RMS = true).
+  template <bool RMS = true>
+  __device__ __forceinline__ float step(float w, float g, float& h, float lr, float dc) const {
+    g = regularise(w, g, dc);
     float u;
     if (solver_type == 1) { const float h0 = h; h = lr * g + momentum * h0; u = (1.f + momentum) * h - momentum * h0; }
     else if (solver_type == 2) { h += g * g; u = lr * (g / (sqrtf(h) + delta)); }
+    else if (RMS && solver_type == 3) {
+#pragma clang fp contract(off)
+      h = decay2 * h + om2 * (g * g); u = lr * (g / (sqrtf(h) + delta));
+      return w - u;
+    }
     else { h = lr * g + momentum * h; u = h; }
     return w - u;
+  }
+  // Adam lives in instantiations of its own, so it rounds EVERYTHING in the order written, the regulariser's product and sum included
+  // (contraction off): left to the compiler, the scalar bias loops of k_sgd and k_reduce_sgd fused differently and the last bit of m and
+  // v of a few bias elements depended on the form.  (So Adam's g' may differ in the last bit from the g' the other rules form.)
+  // Adam (BVLC AdamSolver::ComputeUpdateValue), two histories: m' = beta1 m + (1 - beta1) g', v' = beta2 v + (1 - beta2) g'^2,
+  // u = (lr corr_t) (m' / (sqrt(v') + delta)).  Only the two-history instantiations of k_sgd and k_reduce_sgd call it.
+  __device__ __forceinline__ float step2(float w, float g, float& m, float& v, float lr, float dc) const {
+#pragma clang fp contract(off)
+    if (dc != 0.f) g = g + dc * (reg == 2 ? w : (float)((w > 0.f) - (w < 0.f)));
+    m = momentum * m + om1 * g;
+    v = decay2 * v + om2 * (g * g);
+    return w - (lr * corr) * (m / (sqrtf(v) + delta));
   }
 #endif
 };
@@ -402,6 +438,10 @@ struct FusedUpdArgs {
   const float* wmax_prev = nullptr; int wmax_prev_n = 0; int recompute_scale = 0; int prec = 0;
   int store_grads = 0;       // also write dW to the gradient buffer (0: it stays in the slabs, api.hip materialises it on request)
 };
+// The two-history forms (Adam): the second history of W and b rides in an argument struct of its own, so that the one-history kernels
+// carry no extra pointer.  v of the same shapes and at the same offsets as hW / hb.
+struct SgdArgs2 : SgdArgs { float* vW = nullptr; float* vb = nullptr; };
+struct FusedUpdArgs2 : FusedUpdArgs { float* vW = nullptr; float* vb = nullptr; };
 constexpr int WMAX_SLOTS = 2048;      // slots of one per-block-maxima buffer (k_sgd writes SGD_BLOCKS of them, k_reduce_sgd RED_DW_BLOCKS)
 
 // Which kernels a context runs (vv_ctx::ko).  The launchers read the options of the context whose entry point is running on this
@@ -474,11 +514,12 @@ void launch_gather_rows_dropout(const float* src, const int32_t* map, int R, int
 void launch_gather_rows_f32(const float* src, const int32_t* map, int R, int D, float* dst, hipStream_t s, int h16 = 0);
 void launch_gather_rows_u16(const uint16_t* src, const int32_t* pos, int R, int Dp, uint16_t* dst, hipStream_t s);
 void launch_reduce(const ReduceArgs& a, hipStream_t s);
-void launch_sgd(int prec, const SgdArgs& a, hipStream_t s);
+// (vW / vb: the second history, rule.solver_type == 5 only -- the two-history instantiations)
+void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW = nullptr, float* vb = nullptr);
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s);
 void launch_delay(int us, hipStream_t s);                             // test hook: occupies s for `us` microseconds       // flag <- seq (agent scope), behind everything queued on s
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s);
-int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s);   // -> the number of per-block maxima it writes
+int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s, float* vW = nullptr, float* vb = nullptr);   // -> the number of per-block maxima it writes
 void launch_table_convert(int prec, const float* src, uint16_t* dst, int64_t n_rows, int F, int Fp,
                           float sx, hipStream_t s);
 void launch_table_synth(int prec, uint16_t* dst, uint64_t seed, int64_t n_rows, int F, int Fp,

@@ -134,6 +134,9 @@ def load_library():
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
         "vv_box_probe": [vp, C.POINTER(_BoxProbe)],
+        "vv_solver_ext_set": [vp, f32, f32], "vv_solver_ext_get": [vp, C.POINTER(f32), C.POINTER(f32)],
+        "vv_solver_iter_set": [vp, i64], "vv_solver_iter_get": [vp, C.POINTER(i64)],
+        "vv_history2_set": [vp, vp, vp], "vv_history2_get": [vp, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -273,10 +276,16 @@ class Gallery:
             pass
 
 
+SOLVER_TYPES = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADAM": 5}     # (4, BVLC's ADADELTA: not implemented)
+
+
 class StepConfig:
-    """vv_step_cfg with the shipped project defaults (vv_step_cfg_default)."""
+    """vv_step_cfg with the shipped project defaults (vv_step_cfg_default).  momentum2 (Adam's beta2) and rms_decay have no field in the
+    struct: given here, the Engine forwards them through vv_solver_ext_set in front of every call that takes this configuration (the one
+    not given keeps the context's value)."""
 
     def __init__(self, B, C_, Nn, **kw):
+        self.momentum2 = self.rms_decay = None
         self.c = _StepCfg()
         load_library().vv_step_cfg_default(C.byref(self.c))
         self.c.B, self.c.C, self.c.Nn = B, C_, Nn
@@ -302,7 +311,9 @@ class StepConfig:
         elif k == "reg":
             self.c.reg = {"L1": 1, "L2": 2}.get(v, v)
         elif k == "solver_type":
-            self.c.solver_type = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2}.get(v, v)
+            self.c.solver_type = SOLVER_TYPES.get(v, v)
+        elif k in ("momentum2", "rms_decay"):
+            setattr(self, k, None if v is None else float(v))
         elif k == "norm":
             self.c.norm = {"L1": 1, "L2": 2}.get(v, v)
         else:
@@ -322,6 +333,7 @@ class Engine:
         self._chk(self.L.vv_create(device, PREC[prec], C.byref(self.h)))
         self.F = self.D = 0
         self.n_rows = 0
+        self._ext_sent = None                      # the (momentum2, rms_decay) of a StepConfig last forwarded by _ext
 
     def _chk(self, rc):
         if rc != 0:
@@ -408,10 +420,54 @@ class Engine:
         self._chk(self.L.vv_params_get(self.h, _ptr(W), _ptr(b), _ptr(hW), _ptr(hb)))
         return W, b, hW, hb
 
+    # ---- RMSProp / Adam (vv_solver_ext_*, vv_solver_iter_*, vv_history2_*)
+    def solver_ext_set(self, momentum2, rms_decay):
+        self._ext_sent = None
+        self._chk(self.L.vv_solver_ext_set(self.h, float(momentum2), float(rms_decay)))
+
+    def solver_ext_get(self):
+        """(momentum2, rms_decay) of the context."""
+        m, r = C.c_float(), C.c_float()
+        self._chk(self.L.vv_solver_ext_get(self.h, C.byref(m), C.byref(r)))
+        return m.value, r.value
+
+    @property
+    def solver_iter(self):
+        """Adam updates applied so far (the next one is t = solver_iter + 1)."""
+        t = C.c_int64()
+        self._chk(self.L.vv_solver_iter_get(self.h, C.byref(t)))
+        return t.value
+
+    @solver_iter.setter
+    def solver_iter(self, t):
+        self._chk(self.L.vv_solver_iter_set(self.h, int(t)))
+
+    def history2_set(self, vW=None, vb=None):
+        cv = lambda a, shape: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        vW, vb = cv(vW, (self.D, self.F)), cv(vb, (self.D,))
+        self._chk(self.L.vv_history2_set(self.h, _ptr(vW), _ptr(vb)))
+
+    def history2_get(self):
+        vW = np.empty((self.D, self.F), np.float32); vb = np.empty(self.D, np.float32)
+        self._chk(self.L.vv_history2_get(self.h, _ptr(vW), _ptr(vb)))
+        return vW, vb
+
+    def _ext(self, cfg):
+        """StepConfig's momentum2 / rms_decay -> the context, in front of a call that takes cfg."""
+        if cfg.momentum2 is None and cfg.rms_decay is None:
+            return
+        want = (cfg.momentum2, cfg.rms_decay)
+        if want == self._ext_sent:                 # (this engine already holds them: no call at all in a training loop)
+            return
+        m, r = self.solver_ext_get()
+        self.solver_ext_set(m if cfg.momentum2 is None else cfg.momentum2, r if cfg.rms_decay is None else cfg.rms_decay)
+        self._ext_sent = want
+
     # ---- iteration
     def forward_backward(self, cfg, idx=None, idx_dev_ptr=None, idx_ready=False):
         """idx: host array [B][C+Nn]; or idx_dev_ptr: device indices produced on the context's stream (ordered behind it),
         idx_ready=True when they are complete already (static batches: no ordering added)."""
+        self._ext(cfg)
         if idx_dev_ptr is not None:
             self._chk(self.L.vv_forward_backward(self.h, C.byref(cfg.c), C.c_void_p(int(idx_dev_ptr)), 2 if idx_ready else 1))
         else:
@@ -423,10 +479,12 @@ class Engine:
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         last_src = np.ascontiguousarray(last_src, dtype=np.int32)
         assert idx.shape == last_src.shape == (cfg.c.B, cfg.c.C + cfg.c.Nn)
+        self._ext(cfg)
         self._chk(self.L.vv_forward_backward_q1(self.h, C.byref(cfg.c), _ptr(idx), _ptr(last_src)))
 
     def forward_backward_ring(self, cfg, ring, consumer=0, item_begin=0, label_out=None, timeout_s=60.0):
         """Next batch of the sampler's prefetch ring -> pinned staging -> async H2D -> forward/backward."""
+        self._ext(cfg)
         self._chk(self.L.vv_forward_backward_ring(self.h, C.byref(cfg.c), ring.h, consumer, item_begin, _ptr(label_out),
                                                   float(timeout_s)))
 
@@ -462,9 +520,11 @@ class Engine:
 
     def update_hint(self, cfg):
         """The next forward_backward* is followed by apply_update(cfg) and nothing reads the gradient in between (vv_update_hint)."""
+        self._ext(cfg)
         self._chk(self.L.vv_update_hint(self.h, C.byref(cfg.c)))
 
     def apply_update(self, cfg):
+        self._ext(cfg)
         self._chk(self.L.vv_apply_update(self.h, C.byref(cfg.c)))
 
     def step(self, cfg, idx=None, idx_dev_ptr=None):
