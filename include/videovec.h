@@ -263,8 +263,9 @@ int vv_step(vv_ctx* ctx, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_
  * mednet_embedding_train.prototxt: 4096 x 4096, batch 128) its epilogue applies the solver's rule to the tile it holds, and the 4 D F bytes
  * of dW are neither written nor read back; vv_apply_update then only finishes the step (bias, loss, scale bookkeeping).  Parameters, history
  * and losses are bit for bit those of the un-hinted calls.  Between such a vv_forward_backward* and its vv_apply_update only vv_loss_get
- * is allowed (vv_grads_*, vv_params_get, another forward pass: VV_ERR_STATE -- the gradient of such a step is not kept, the parameters are
- * half-way).  Where the fusion does not apply (several splits of K, a communicator, a bound gradient buffer, Adam's two histories) the hint changes nothing.
+ * is allowed (vv_grads_*, vv_params_get, vv_op_inner_product_bwd, another forward pass: VV_ERR_STATE -- the gradient of such a step is not
+ * kept, the parameters are half-way); after that vv_apply_update, until the next backward pass, vv_grads_* and a second vv_apply_update
+ * are refused the same way (the gradient was never stored).  Where the fusion does not apply (several splits of K, a communicator, a bound gradient buffer, Adam's two histories) the hint changes nothing.
  * vv_step announces itself.  One hint covers one step. */
 int vv_update_hint(vv_ctx* ctx, const vv_step_cfg* cfg);
 

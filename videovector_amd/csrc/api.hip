@@ -31,7 +31,7 @@ static inline const char* lab_env(const char*) { return nullptr; }
 #endif
 using namespace vv;
 
-static int upd_pending_guard(vv_ctx* c, const char* who);      // (vv_update_hint, below)
+static inline int upd_pending_guard(vv_ctx* c, const char* who) { return vv_upd_pending_guard(c, who); }      // (vv_update_hint, below)
 static int ensure_history2(vv_ctx* c);                         // (the second history of a two-history solver, below)
 thread_local char vv_g_err[512] = "";
 int vv_fail(int code, const char* fmt, ...) {
@@ -102,6 +102,7 @@ void vv_step_cfg_default(vv_step_cfg* cfg) {
 
 static int create_init(vv_ctx* c);
 static inline int comm_join(vv_ctx* c) { return vv_comm_join(c); }
+static inline int reduce_now(vv_ctx* c) { return vv_reduce_now(c); }
 
 int vv_create(int device, int prec, vv_ctx** out) {
   if (!out) return fail(VV_ERR_ARG, "vv_create: out is NULL");
@@ -255,8 +256,7 @@ static void free_batch(vv_ctx* c) {
   c->idx_dev = c->rows = nullptr; c->H = nullptr; c->dYh = nullptr; c->dbp = nullptr;
   c->loss_part = c->viol_part = c->s_true = c->s_bogus = c->coeff = nullptr; c->slabs = nullptr;
   c->slab_bytes = 0; c->B = c->C = c->Nn = c->R = c->Rp = 0; c->coeff_host.clear();
-  c->have_fwd = false;
-  c->red_lazy = c->grads_stale = false;       // a reduction that was still due named the buffers just freed (red_args)
+  grad_discard(c->grad);                      // (a reduction that was still due named the buffers just freed: red_args)
 }
 
 int vv_destroy(vv_ctx* c) {
@@ -393,7 +393,7 @@ int vv_set_dedup(vv_ctx* c, int on) {
 
 int vv_dedup_stats(vv_ctx* c, int64_t* rows, int64_t* unique_rows) {
   if (!c) return fail(VV_ERR_ARG, "vv_dedup_stats: ctx is NULL");
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_dedup_stats: no forward pass yet");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_dedup_stats: no forward pass yet");
   VV_ENTER(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   int32_t U = c->R;
@@ -405,7 +405,7 @@ int vv_dedup_stats(vv_ctx* c, int64_t* rows, int64_t* unique_rows) {
 
 int vv_h16_stats(vv_ctx* c, vv_h16_report* out) {
   if (!c || !out) return fail(VV_ERR_ARG, "vv_h16_stats: ctx / out is NULL");
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_h16_stats: no forward pass yet");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_h16_stats: no forward pass yet");
   VV_ENTER(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   out->saturated = out->faint_rows = 0;
@@ -596,10 +596,10 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   c->adam_t = 0; c->hist2_partial = false;
   // scale for the half copy from max|W|, then convert (a scale update still pending from an earlier SGD step is void)
   c->scale_pending = false;
-  c->red_lazy = false; c->grads_stale = false;   // (a gradient nobody asked for goes with the parameters it belonged to)
+  // (a gradient nobody asked for goes with the parameters it belonged to, when the call has succeeded: grad_discard below)
   // ... and so does a hinted step that was waiting for its vv_apply_update (its half-applied update is overwritten here) and a hint not yet
-  // consumed (the context was stuck -- every later vv_forward_backward refused, vv_apply_update failing on !have_fwd)
-  c->upd_in_wgrad = false; c->upd_hint = false; c->grads_lost = false;
+  // consumed (the context was stuck -- every later vv_forward_backward refused, vv_apply_update failing on "no gradients")
+  c->upd_hint = false;
   HIPCHK(hipMemsetAsync(&c->scales->wmax_bits, 0, sizeof(unsigned), c->stream));
   launch_absmax(c->W, (int64_t)nW, &c->scales->wmax_bits, c->stream);
   launch_scale_update(c->prec, c->scales, nullptr, 0, c->stream);
@@ -610,7 +610,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   c->wmax_seed_live = true;
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->have_fwd = false;
+  grad_discard(c->grad);
   return VV_OK;
 }
 
@@ -895,35 +895,33 @@ static void flush_scale_update(vv_ctx* c) {
   c->wmax_seed_live = false;               // (the scale update folds and clears Scales::wmax_bits)
 }
 
-// The reduction vv_forward_backward left undone (vv_ctx::red_lazy): run it now, as the plain k_reduce -- somebody reads the
+// The reduction vv_forward_backward left undone (GradAt::Slabs): run it now, as the plain k_reduce -- somebody reads the
 // gradient or the loss before an update.
-static int reduce_now(vv_ctx* c) {
-  if (c->upd_in_wgrad) {
-    // (vv_loss_get between the backward pass and vv_apply_update of a step announced by vv_update_hint: the loss scalars now, from the
-    // partials; the bias update and the bookkeeping stay with vv_apply_update)
-    ReduceArgs ra = c->red_args;
-    ra.parts = 2; ra.scale_sc = nullptr; ra.gmax_host = nullptr;
-    launch_reduce(ra, c->stream);
-    HIPCHK(hipGetLastError());
-    return VV_OK;
-  }
-  if (c->grads_stale) {
-    // the fused update consumed the slabs without writing dW out; they are untouched since: reduce them now (dW only --
-    // db, the loss and the guard's report were produced by the fused launch)
-    c->grads_stale = false;
-    ReduceArgs ra = c->red_args;
-    ra.parts = 1; ra.scale_sc = nullptr; ra.gmax_host = nullptr;
-    launch_reduce(ra, c->stream);
-    HIPCHK(hipGetLastError());
-  }
-  if (!c->red_lazy) return VV_OK;
-  c->red_lazy = false;
+extern "C++" int vv_reduce_now(vv_ctx* c) {
   ReduceArgs ra = c->red_args;
-  if (c->scale_pending) {
-    ra.scale_sc = c->scales; ra.scale_wmax = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; ra.scale_n = c->wmax_n; ra.scale_prec = c->prec;
-    c->scale_pending = false; c->wmax_seed_live = false;
+  switch (c->grad.at) {
+    case GradAt::SlabsWUpdated:
+      // (vv_loss_get between the backward pass and vv_apply_update of a step announced by vv_update_hint: the loss scalars now, from the
+      // partials; the bias update and the bookkeeping stay with vv_apply_update)
+      ra.parts = 2; ra.scale_sc = nullptr; ra.gmax_host = nullptr;
+      launch_reduce(ra, c->stream);
+      break;
+    case GradAt::SlabsStale:
+      // the fused update consumed the slabs without writing dW out; they are untouched since: reduce them now (dW only --
+      // db, the loss and the guard's report were produced by the fused launch)
+      ra.parts = 1; ra.scale_sc = nullptr; ra.gmax_host = nullptr;
+      launch_reduce(ra, c->stream);
+      break;
+    case GradAt::Slabs:
+      if (c->scale_pending) {
+        ra.scale_sc = c->scales; ra.scale_wmax = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; ra.scale_n = c->wmax_n; ra.scale_prec = c->prec;
+        c->scale_pending = false; c->wmax_seed_live = false;
+      }
+      PROFILED(c, "reduce", launch_reduce(ra, c->stream));
+      break;
+    default: return VV_OK;           // nothing kept in the slabs
   }
-  PROFILED(c, "reduce", launch_reduce(ra, c->stream));
+  grad_reduced(c->grad);
   HIPCHK(hipGetLastError());
   return VV_OK;
 }
@@ -959,11 +957,11 @@ static int chunk_plan(vv_ctx* c) {
 // that reads or writes the parameters, their half copy, the momentum or the gradient buffer goes through here first;
 // the one reader that does not is the next step's forward GEMM, which waits chunk by chunk inside the kernel instead.
 extern "C++" int vv_comm_join(vv_ctx* c) {
-  // upd_unjoined: the gated forward GEMM has consumed the update chunk by chunk, but nothing on the compute stream waits for
+  // UpdSync::Gated: the gated forward GEMM has consumed the update chunk by chunk, but nothing on the compute stream waits for
   // the END of the update's kernels (their plain stores -- W, the history -- are released at that end, not at the gate)
-  if (c->comm && (c->upd_inflight || c->upd_unjoined)) {
+  if (c->comm && c->upd_sync != UpdSync::Joined) {
     HIPCHK(hipStreamWaitEvent(c->stream, vv::comm_done_event(c->comm), 0));
-    c->upd_inflight = c->upd_unjoined = false;
+    upd_joined(c->upd_sync);
   }
   if (c->gate_err && *(volatile int32_t*)c->gate_err) {
     *c->gate_err = 0;
@@ -1053,13 +1051,17 @@ static int dd_issue(vv_ctx* c, const int32_t* didx, int idx_on_device, int64_t r
 // there); 2 device indices that are complete already (no ordering needed: the ring's staging slots, static batches)
 // vv_update_hint: the parameter matrix of this step was updated inside the weight-gradient GEMM; until vv_apply_update has finished the step
 // (bias, loss, the scale bookkeeping) the parameters are half-way -- only vv_apply_update and vv_loss_get may come next
-static int upd_pending_guard(vv_ctx* c, const char* who) {
-  if (c && c->grads_lost && !strncmp(who, "vv_grads", 8))
-    return fail(VV_ERR_STATE, "%s: the last step was announced by vv_update_hint and applied its update where the gradient was produced: "
-                              "that gradient was never stored (run the step without the hint to read it)", who);
-  if (c && c->upd_in_wgrad)
-    return fail(VV_ERR_STATE, "%s: the step announced by vv_update_hint has applied its update where the gradient was produced -- call vv_apply_update "
-                              "first (the gradient of such a step is not kept; without the hint every call is allowed as before)", who);
+extern "C++" int vv_upd_pending_guard(vv_ctx* c, const char* who) {
+  if (!c) return VV_OK;
+  switch (grad_guard(c->grad, who)) {
+    case GradRefusal::NeverStored:
+      return fail(VV_ERR_STATE, "%s: the last step was announced by vv_update_hint and applied its update where the gradient was produced: "
+                                "that gradient was never stored (run the step without the hint to read it)", who);
+    case GradRefusal::UpdateFirst:
+      return fail(VV_ERR_STATE, "%s: the step announced by vv_update_hint has applied its update where the gradient was produced -- call vv_apply_update "
+                                "first (the gradient of such a step is not kept; without the hint every call is allowed as before)", who);
+    case GradRefusal::No: break;
+  }
   return VV_OK;
 }
 
@@ -1081,6 +1083,85 @@ int vv_update_hint(vv_ctx* c, const vv_step_cfg* cfg) {
   return VV_OK;
 }
 
+// The end of a backward pass: the weight-gradient GEMM, and where its gradient goes -- it stays in the slabs (lazy; with vv_update_hint and
+// one split of K the GEMM updates W as well), or k_reduce writes it to the gradient buffer, flat, chunk-major or shard-major.  wa and ra
+// arrive filled in for the step; the destination is recorded in c->grad.
+static int wgrad_to_destination(vv_ctx* c, WgradArgs& wa, ReduceArgs& ra, bool upd_hint) {
+  hipStream_t s = c->stream;
+  // Data-parallel overlap: the gradient buffer is laid out chunk-major (a few column blocks, each one contiguous
+  // all-reduce message) and vv_apply_update runs the update chunk by chunk on the communication stream.
+  const int shard_rows = c->comm ? c->D / vv::comm_world(c->comm) : 0;
+  const bool sharded = c->comm && c->comm_sharded && c->F % 4 == 0 && c->grads == c->grads_own && !c->grads_exposed &&
+                       shard_rows * vv::comm_world(c->comm) == c->D && shard_rows % 4 == 0 && vv::comm_world(c->comm) * (SGD_BLOCKS / vv::comm_world(c->comm)) <= WMAX_SLOTS;
+  if (sharded) ra.shard_rows = shard_rows;
+  const bool chunked = !sharded && c->comm && c->comm_overlap && c->F % 4 == 0 && c->grads == c->grads_own && !c->grads_exposed;   // (a holder of vv_grads_device's pointer reads the documented flat layout)
+  if (chunked) {
+    ra.n_chunks = chunk_plan(c);
+    for (int i = 0; i <= ra.n_chunks; ++i) ra.chunk_c0[i] = std::min(c->F, c->chunk_kt[i] * BK);
+  }
+  // Lazy reduction (GradAt::Slabs): with no communicator in the way, dW stays in the slabs until somebody wants it --
+  // normally vv_apply_update, which reduces and updates in one launch.  VV_FUSE_UPDATE=0: reduce here, as ever.
+  const bool fuse_on = c->fuse_update;
+  const bool lazy = fuse_on && !c->comm && !c->grads_exposed && c->grads == c->grads_own && c->F % 4 == 0 && c->S <= 8;
+  // the W -> half scale update the previous vv_apply_update left pending rides in this step's reduction launch
+  if (!lazy && c->scale_pending) {
+    ra.scale_sc = c->scales; ra.scale_wmax = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; ra.scale_n = c->wmax_n; ra.scale_prec = c->prec;
+    c->scale_pending = false; c->wmax_seed_live = false;
+  }
+  // vv_update_hint + one split of K: the tile in the weight-gradient GEMM's accumulators IS the gradient -- the solver's rule is applied
+  // there (WgradUpd) and the 4 D F bytes of dW are neither written nor read back (the shipped configuration: D = F = 4096, 134 MB of the
+  // update's 370).  vv_apply_update then runs only the bias / loss workgroups.
+  // (Adam keeps two histories: the epilogue declines it, the step takes k_reduce_sgd -- the hint changes nothing, as for several splits)
+  const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
+                      (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM;
+  if (fuse_w) {
+    WgradUpd& u = wa.upd;
+    wa.fuse_upd = 1;
+    u.W = c->W; u.hW = c->hW; u.Wh = c->Wh; u.scales = c->scales;
+    u.wmax_blocks = c->wmax_blocks + (1 - c->wmax_cur) * WMAX_SLOTS;
+    u.wmax_prev = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; u.wmax_prev_n = c->wmax_n;
+    u.recompute_scale = c->scale_pending ? 1 : 0; u.prec = c->prec;
+    u.D = c->D; u.F = c->F;
+    u.rule = solver_rule(c->upd_cfg, c->upd_momentum2, c->upd_rms_decay);
+    u.sg = ra.sg; u.gg = ra.gg; u.ip_scale = ra.ip_scale;
+  }
+  // f16 split-K partial products (option "slab16"): the phase-staggered kernel with several splits only (one split: the update rides in the
+  // epilogue or the slab is the gradient); whoever reduces the slabs -- k_reduce, k_reduce_sgd, now or lazily -- reads the same flag
+  if (c->slab16 && !fuse_w && c->S > 1 && c->S <= 8 && c->F % 8 == 0 && wgrad_can_fuse_update()) {
+    wa.slab16 = 1; wa.slab_sc = c->slab_sc;
+    ra.slab16 = 1; ra.slab_sc = c->slab_sc;
+  }
+  PROFILED(c, "wgrad_gemm", launch_wgrad_gemm(c->prec, wa, s));     // (the slabs now hold this step's gradient)
+  if (lazy) {
+    if (fuse_w) {
+      HIPCHK(clear_wmax_seed(c, wa.upd.recompute_scale, s));
+      c->upd_wgrad_blocks = (c->Dp / BM) * (c->Fp / BN);
+    }
+    c->red_args = ra;
+    HIPCHK(hipGetLastError());
+    grad_to_slabs(c->grad, fuse_w);
+    return VV_OK;
+  }
+  const bool chunk0 = chunked && ra.n_chunks > 1 && ra.chunk_c0[1] < c->F;
+  if (chunk0) {
+    // the first F-chunk is reduced by a launch of its own and an event marks it: the communication stream starts on
+    // chunk 0 (all-reduce, SGD) while the other chunks, db and the loss are still being reduced here
+    ReduceArgs r0 = ra;
+    r0.f_begin = 0; r0.f_count = ra.chunk_c0[1]; r0.parts = 1; r0.gmax_host = nullptr;
+    PROFILED(c, "reduce", launch_reduce(r0, s));
+    HIPCHK(hipEventRecord(c->ev_chunk0, s));
+    ra.scale_sc = nullptr;
+    ra.f_begin = ra.chunk_c0[1]; ra.f_count = c->F - ra.f_begin;
+    launch_reduce(ra, s);
+  } else {
+    PROFILED(c, "reduce", launch_reduce(ra, s));
+  }
+  HIPCHK(hipGetLastError());
+  // (the sum over the ranks is due with a communicator -- a one-rank communicator still runs its collective: same code path)
+  grad_to_buffer(c->grad, sharded ? GradLayout::Sharded : chunked ? GradLayout::Chunked : GradLayout::Flat, !c->comm, chunk0);
+  return VV_OK;
+}
+
 static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device, int64_t row_limit, int32_t seq = 0) {
   { const int rcg = upd_pending_guard(c, "vv_forward_backward"); if (rcg) return rcg; }
   const bool upd_hint = c && c->upd_hint;       // (consumed by this call whatever path it takes)
@@ -1090,7 +1171,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   if (!idx) return fail(VV_ERR_ARG, "vv_forward_backward: idx is NULL");
   VV_ENTER(c);
   // (an overlapped update of the previous step may still be arriving: see the forward GEMM below)
-  if (c->upd_inflight && (cfg->B != c->B || cfg->C != c->C || cfg->Nn != c->Nn || !c->H) && (rc = comm_join(c))) return rc;
+  if (c->upd_sync == UpdSync::InFlight && (cfg->B != c->B || cfg->C != c->C || cfg->Nn != c->Nn || !c->H) && (rc = comm_join(c))) return rc;
   if ((rc = ensure_batch(c, cfg->B, cfg->C, cfg->Nn))) return rc;
   const int B = c->B, C = c->C, Nn = c->Nn, CN = C + Nn, D = c->D;
   hipStream_t s = c->stream;
@@ -1213,7 +1294,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   fa.mask = (!(dd && drop_on) && cfg->dropout_ratio > 0.f && cfg->dropout_mask) ? c->mask : nullptr;
   fa.drop_seed = cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter;
   fa.B = B; fa.CN = CN;
-  if (c->upd_inflight) {
+  if (c->upd_sync == UpdSync::InFlight) {
     // Data-parallel overlap: the previous step's update is still arriving on the communication stream, F-chunk by
     // F-chunk.  The forward GEMM starts anyway and waits per chunk inside the kernel -- provided its persistent
     // workgroups leave compute units free for the update's own kernels (all-reduce, SGD: they must be able to run
@@ -1222,10 +1303,11 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     const bool no_gate = !c->comm_gate;
     if (!no_gate && !ablate_on() && fwd_gemm_can_gate(fa) && (!dd || fa.R_hint > 0) && tiles <= c->n_cu - 16) {
       fa.gate = c->w_gate; fa.gate_seq = c->upd_seq; fa.gate_err = c->gate_err_dev;
-      if (c->grads_sharded) { fa.gate_n = 1; fa.gate_kt[0] = 0; fa.gate_kt[1] = c->Fp / BK; }        // the sharded update publishes once
+      if (c->grad.buf.layout == GradLayout::Sharded) { fa.gate_n = 1; fa.gate_kt[0] = 0; fa.gate_kt[1] = c->Fp / BK; }        // the sharded update publishes once
       else { fa.gate_n = chunk_plan(c); for (int i = 0; i <= fa.gate_n; ++i) fa.gate_kt[i] = c->chunk_kt[i]; }
-      c->upd_inflight = false;              // whatever follows the forward GEMM on this stream follows every PUBLISHED store of the update
-      c->upd_unjoined = true;               // ... its plain stores (W, the history) only behind the event: vv_comm_join for whoever reads those
+      // whatever follows the forward GEMM on this stream follows every PUBLISHED store of the update; its plain stores (W, the history) only
+      // behind the event: vv_comm_join for whoever reads those
+      upd_gated(c->upd_sync);
     } else if ((rc = comm_join(c))) return rc;
   }
   PROFILED(c, "fwd_gemm", launch_fwd_gemm(c->prec, fa, s));
@@ -1373,85 +1455,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   ra.ip_scale = cfg->ip_regularization > 0.f ? 1.f + cfg->ip_regularization * 0.5f : 1.f;     // inner_product_layer.cpp:80-90
   ra.loss_part = c->loss_part; ra.viol_part = c->viol_part; ra.loss_scale = cfg->loss_weight / (float)count; ra.loss_out = c->loss2;
 
-  // Data-parallel overlap: the gradient buffer is laid out chunk-major (a few column blocks, each one contiguous
-  // all-reduce message) and vv_apply_update runs the update chunk by chunk on the communication stream.
-  const int shard_rows = c->comm ? c->D / vv::comm_world(c->comm) : 0;
-  const bool sharded = c->comm && c->comm_sharded && c->F % 4 == 0 && c->grads == c->grads_own && !c->grads_exposed &&
-                       shard_rows * vv::comm_world(c->comm) == c->D && shard_rows % 4 == 0 && vv::comm_world(c->comm) * (SGD_BLOCKS / vv::comm_world(c->comm)) <= WMAX_SLOTS;
-  if (sharded) ra.shard_rows = shard_rows;
-  const bool chunked = !sharded && c->comm && c->comm_overlap && c->F % 4 == 0 && c->grads == c->grads_own && !c->grads_exposed;   // (a holder of vv_grads_device's pointer reads the documented flat layout)
-  if (chunked) {
-    ra.n_chunks = chunk_plan(c);
-    for (int i = 0; i <= ra.n_chunks; ++i) ra.chunk_c0[i] = std::min(c->F, c->chunk_kt[i] * BK);
-  }
-  // Lazy reduction (vv_ctx::red_lazy): with no communicator in the way, dW stays in the slabs until somebody wants it --
-  // normally vv_apply_update, which reduces and updates in one launch.  VV_FUSE_UPDATE=0: reduce here, as ever.
-  const bool fuse_on = c->fuse_update;
-  const bool lazy = fuse_on && !c->comm && !c->grads_exposed && c->grads == c->grads_own && c->F % 4 == 0 && c->S <= 8;
-  // the W -> half scale update the previous vv_apply_update left pending rides in this step's reduction launch
-  if (!lazy && c->scale_pending) {
-    ra.scale_sc = c->scales; ra.scale_wmax = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; ra.scale_n = c->wmax_n; ra.scale_prec = c->prec;
-    c->scale_pending = false; c->wmax_seed_live = false;
-  }
-  // vv_update_hint + one split of K: the tile in the weight-gradient GEMM's accumulators IS the gradient -- the solver's rule is applied
-  // there (WgradUpd) and the 4 D F bytes of dW are neither written nor read back (the shipped configuration: D = F = 4096, 134 MB of the
-  // update's 370).  vv_apply_update then runs only the bias / loss workgroups.
-  // (Adam keeps two histories: the epilogue declines it, the step takes k_reduce_sgd -- the hint changes nothing, as for several splits)
-  const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
-                      (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM;
-  if (fuse_w) {
-    WgradUpd& u = wa.upd;
-    wa.fuse_upd = 1;
-    u.W = c->W; u.hW = c->hW; u.Wh = c->Wh; u.scales = c->scales;
-    u.wmax_blocks = c->wmax_blocks + (1 - c->wmax_cur) * WMAX_SLOTS;
-    u.wmax_prev = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; u.wmax_prev_n = c->wmax_n;
-    u.recompute_scale = c->scale_pending ? 1 : 0; u.prec = c->prec;
-    u.D = c->D; u.F = c->F;
-    u.rule = solver_rule(c->upd_cfg, c->upd_momentum2, c->upd_rms_decay);
-    u.sg = ra.sg; u.gg = ra.gg; u.ip_scale = ra.ip_scale;
-  }
-  // f16 split-K partial products (option "slab16"): the phase-staggered kernel with several splits only (one split: the update rides in the
-  // epilogue or the slab is the gradient); whoever reduces the slabs -- k_reduce, k_reduce_sgd, now or lazily -- reads the same flag
-  if (c->slab16 && !fuse_w && c->S > 1 && c->S <= 8 && c->F % 8 == 0 && wgrad_can_fuse_update()) {
-    wa.slab16 = 1; wa.slab_sc = c->slab_sc;
-    ra.slab16 = 1; ra.slab_sc = c->slab_sc;
-  }
-  PROFILED(c, "wgrad_gemm", launch_wgrad_gemm(c->prec, wa, s));
-  c->red_lazy = false; c->grads_stale = false;        // (the slabs now hold this step's gradient)
-  c->grads_lost = false;
-  if (fuse_w) {
-    HIPCHK(clear_wmax_seed(c, wa.upd.recompute_scale, s));
-    c->upd_in_wgrad = true; c->upd_wgrad_blocks = (c->Dp / BM) * (c->Fp / BN);
-  }
-  if (lazy) {
-    c->red_args = ra; c->red_lazy = true;
-    c->grads_pending = false; c->grads_chunked = false; c->chunk0_event = false;
-    HIPCHK(hipGetLastError());
-    c->have_fwd = true;
-    return VV_OK;
-  }
-  if (chunked && ra.n_chunks > 1 && ra.chunk_c0[1] < c->F) {
-    // the first F-chunk is reduced by a launch of its own and an event marks it: the communication stream starts on
-    // chunk 0 (all-reduce, SGD) while the other chunks, db and the loss are still being reduced here
-    ReduceArgs r0 = ra;
-    r0.f_begin = 0; r0.f_count = ra.chunk_c0[1]; r0.parts = 1; r0.gmax_host = nullptr;
-    PROFILED(c, "reduce", launch_reduce(r0, s));
-    HIPCHK(hipEventRecord(c->ev_chunk0, s));
-    ra.scale_sc = nullptr;
-    ra.f_begin = ra.chunk_c0[1]; ra.f_count = c->F - ra.f_begin;
-    launch_reduce(ra, s);
-    c->chunk0_event = true;
-  } else {
-    PROFILED(c, "reduce", launch_reduce(ra, s));
-    c->chunk0_event = false;
-  }
-  c->grads_pending = c->comm != nullptr;       // (a one-rank communicator still runs its collective: same code path)
-  c->grads_chunked = chunked;
-  c->grads_sharded = sharded;
-
-  HIPCHK(hipGetLastError());
-  c->have_fwd = true;
-  return VV_OK;
+  return wgrad_to_destination(c, wa, ra, upd_hint);
 }
 
 int vv_forward_backward(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device) {
@@ -1549,26 +1553,154 @@ int vv_forward_backward_q1(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx
   return fb_impl(c, cfg, c->stage_dev[sl], 2, c->n_rows + 1 + P, seq);
 }
 
+// The five forms of the update.  Each is handed the common SgdArgs (vv_apply_update's prologue), Adam's second history (vW / vb, or NULL)
+// and ends in finish_update.
+
+// 1: finish a step whose parameter matrix the weight-gradient GEMM has updated (GradAt::SlabsWUpdated)
+static int update_finish_wgrad(vv_ctx* c, const SgdArgs& a) {
+  // the parameter matrix was updated in the weight-gradient GEMM (vv_update_hint): bias, loss, the guard's report -- k_reduce_sgd's
+  // special workgroups alone -- and the bookkeeping of the scale
+  // (what the weight-gradient GEMM applied: WgradUpd::rule -- the bias multipliers may differ, the bias is updated here)
+  const SolverRule h = solver_rule(c->upd_cfg, c->upd_momentum2, c->upd_rms_decay);
+  const SolverRule& r = a.rule;
+  if (r.rate != h.rate || r.momentum != h.momentum || r.weight_decay != h.weight_decay || r.lr_mult_w != h.lr_mult_w ||
+      r.decay_mult_w != h.decay_mult_w || r.reg != h.reg || r.solver_type != h.solver_type || r.delta != h.delta || r.decay2 != h.decay2)
+    return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
+  FusedUpdArgs fa;
+  fa.r = c->red_args; fa.g = a; fa.prec = c->prec; fa.no_params = 1; fa.recompute_scale = 0; fa.store_grads = 0;
+  grad_update_consumed(c->grad);              // (-> Lost: dW of this step never existed outside the GEMM's registers)
+  PROFILED(c, "reduce_sgd", (void)launch_reduce_sgd(fa, c->stream));
+  return finish_update(c, c->upd_wgrad_blocks);
+}
+
+// 2: the reduction is still due (GradAt::Slabs): reduce and update in one launch (k_reduce_sgd)
+static int update_fused(vv_ctx* c, const SgdArgs& a, float* vW, float* vb) {
+  FusedUpdArgs fa;
+  fa.r = c->red_args; fa.g = a; fa.prec = c->prec;
+  fa.recompute_scale = c->scale_pending ? 1 : 0;
+  fa.wmax_prev = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; fa.wmax_prev_n = c->wmax_n;
+  fa.store_grads = c->fuse_keep_grads;
+  if (fa.store_grads) grad_reduced(c->grad); else grad_update_consumed(c->grad);      // (-> Buffer, or SlabsStale: dW stays in the slabs)
+  int n_new = 0;
+  PROFILED(c, "reduce_sgd", (n_new = launch_reduce_sgd(fa, c->stream, vW, vb)));
+  HIPCHK(clear_wmax_seed(c, fa.recompute_scale, c->stream));
+  return finish_update(c, n_new);
+}
+
+// 3: the sharded schedule (GradLayout::Sharded, the sum over the ranks due)
+static int update_sharded(vv_ctx* c, const SgdArgs& a, float* vW, float* vb) {
+  // Exact synchronous SGD, the update SHARDED over the ranks (Multi-GPU): on the communication stream, behind one event of
+  // the compute stream,   reduce-scatter (fp32, shard-major buffer: 7/8 of it on the wire at N = 8, once)  ->  k_sgd on THIS rank's
+  // D / N rows (1/N of the update's 46 MB)  ->  ONE grouped all-gather of what every rank's next forward pass reads: the 16-bit copy
+  // of W (4 MB instead of the all-reduce's second 8.4 MB), the bias, the per-block maxima the next W -> half scale comes from  ->
+  // publish.  3/4 of the all-reduce's wire bytes.  The next forward GEMM is gated on the one flag (it starts, and waits in front of
+  // its first W tile); the fp32 master W and the history stay sharded until vv_params_get gathers them.
+  // comm_inline (default): this schedule has ONE gate, in front of the GEMM's first W tile -- nothing of the exchange hides behind the
+  // GEMM, and the second stream costs its hand-off chain (event -> wake -> ... -> publish: + 17 us on one rank).  So the
+  // three steps are queued on the COMPUTE stream itself, in order, and the next forward GEMM is the plain kernel (with its sibling lead).
+  const bool adam = vW != nullptr;
+  const bool inl = c->comm_inline;
+  hipStream_t cs = inl ? c->stream : vv::comm_stream(c->comm);
+  const int world = vv::comm_world(c->comm), rank = vv::comm_rank(c->comm);
+  const int rps = c->D / world;
+  const size_t shard_f = (size_t)rps * c->F + rps;
+  int32_t useq = c->upd_seq;
+  if (!inl) { HIPCHK(hipEventRecord(c->ev_chunk, c->stream)); useq = ++c->upd_seq; }
+  if (c->comm_test_delay_us > 0) { if (!inl) HIPCHK(hipStreamWaitEvent(cs, c->ev_chunk, 0)); launch_delay(c->comm_test_delay_us, cs); }
+  struct StreamScope { vv::Comm* k; ~StreamScope() { vv::comm_use_stream(k, nullptr); } } scope{c->comm};
+  vv::comm_use_stream(c->comm, inl ? c->stream : nullptr);
+  if (vv::comm_reduce_scatter(c->comm, c->grads, shard_f, inl ? nullptr : c->ev_chunk)) return fail(VV_ERR_HIP, "reduce-scatter: %s", vv::comm_error(c->comm));
+  const int nb = SGD_BLOCKS / world;
+  SgdArgs g = a;                                    // the shard as a parameter matrix of its own: rps rows, its gradient buffer [dW rows | db entries]
+  g.D = rps;
+  g.W = c->W + (size_t)rank * rps * c->F; g.hW = c->hW + (size_t)rank * rps * c->F;
+  g.b = c->b + (size_t)rank * rps; g.hb = c->hb + (size_t)rank * rps;
+  g.grads = c->grads + (size_t)rank * shard_f;
+  float* const svW = adam ? vW + (size_t)rank * rps * c->F : nullptr; float* const svb = adam ? vb + (size_t)rank * rps : nullptr;     // the shard owns its rows of v
+  g.Wh = c->Wh + (size_t)rank * rps * c->Fp;
+  g.chunked = 1; g.f_begin = 0; g.f_count = c->F; g.do_bias = 1; g.set_scale = 1;      // (chunked = 1 with the whole width: this launch's own grid and slots)
+  g.blk_off = rank * nb; g.n_blk = nb;
+  PROFILED(c, "sgd", launch_sgd(c->prec, g, cs, svW, svb));
+  void* bufs[3] = {c->Wh, c->b, a.wmax_blocks};
+  const size_t sbytes[3] = {(size_t)rps * c->Fp * 2, (size_t)rps * 4, (size_t)nb * 4};
+  if (vv::comm_allgather(c->comm, bufs, sbytes, 3)) return fail(VV_ERR_HIP, "all-gather: %s", vv::comm_error(c->comm));
+  if (!inl) {
+    launch_publish(c->w_gate, useq, cs);
+    if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-gather: %s", vv::comm_error(c->comm));
+  }
+  grad_update_consumed(c->grad);
+  if (!inl) upd_queued(c->upd_sync);          // (in-stream: vv_apply_update joined whatever was in flight)
+  c->params_partial = world > 1;
+  if (adam) c->hist2_partial = world > 1;
+  return finish_update(c, nb * world);
+}
+
+// 4: the overlapped schedule (GradLayout::Chunked, the sum over the ranks due)
+static int update_overlapped(vv_ctx* c, SgdArgs a, float* vW, float* vb) {
+  // Exact synchronous SGD with the exchange hidden behind the NEXT step's forward GEMM: behind one event of the compute
+  // stream, the communication stream runs per F-chunk  all-reduce -> SGD on the chunk's columns -> publish w_gate[chunk];
+  // the next forward GEMM (fb_impl) starts right away and waits for each chunk where its K loop reaches it.  db rides
+  // with the last chunk; the bias is updated there.
+  hipStream_t cs = vv::comm_stream(c->comm);
+  const int32_t useq = ++c->upd_seq;
+  const int nch = chunk_plan(c);               // (the layout k_reduce wrote: same Fp, same plan)
+  const bool chunk0 = c->grad.buf.chunk0_event;
+  a.pub_count = c->pub_count; a.pub_seq = useq;
+  HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
+  for (int k = 0; k < nch; ++k) {
+    // chunk 0 may start as soon as ITS reduction is done (ev_chunk0, fb_impl); the others follow the whole backward pass
+    hipEvent_t after = k == 0 ? (chunk0 ? c->ev_chunk0 : c->ev_chunk) : (k == 1 && chunk0 ? c->ev_chunk : nullptr);
+    const int c0 = std::min(c->F, c->chunk_kt[k] * BK), c1 = std::min(c->F, c->chunk_kt[k + 1] * BK);
+    const bool last = k == nch - 1;
+    const size_t off = (size_t)c->D * c0, n = (size_t)c->D * (c1 - c0) + (last ? (size_t)c->D : 0);
+    const int delay_us = c->comm_test_delay_us;
+    if (after) HIPCHK(hipStreamWaitEvent(cs, after, 0));
+    if (delay_us > 0) launch_delay(delay_us, cs);      // test hook: a slow exchange, so that the next forward GEMM really waits at its gates
+    const bool skip_ar1 = c->comm_skip_ar1;   // (lab) diagnosis: no collective call at world 1
+    if (!(skip_ar1 && vv::comm_world(c->comm) == 1) && n > 0 && vv::comm_allreduce(c->comm, c->grads, off, n, nullptr))
+      return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
+    a.chunked = 1; a.f_begin = c0; a.f_count = c1 - c0; a.do_bias = last; a.set_scale = k == 0;
+    a.blk_off = k * (SGD_BLOCKS / nch); a.n_blk = last ? SGD_BLOCKS - a.blk_off : SGD_BLOCKS / nch;      // together: every slot of wmax_blocks
+    a.pub_flag = c->w_gate + k * W_GATE_STRIDE;          // the kernel's last workgroup publishes the chunk (SgdArgs::pub_flag)
+    if (k == 0) PROFILED(c, "sgd", launch_sgd(c->prec, a, cs, vW, vb)); else launch_sgd(c->prec, a, cs, vW, vb);     // (an empty chunk: its wmax slots become 0, the bias if it is the last)
+  }
+  if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
+  grad_update_consumed(c->grad);
+  upd_queued(c->upd_sync);                    // (comm_done_event now marks the end of THIS update, behind the old one)
+  return finish_update(c, SGD_BLOCKS);
+}
+
+// 5: the gradient is in the buffer, summed: plain k_sgd
+static int update_plain(vv_ctx* c, const SgdArgs& a, float* vW, float* vb) {
+  PROFILED(c, "sgd", launch_sgd(c->prec, a, c->stream, vW, vb));
+  grad_update_consumed(c->grad);
+  // The next W -> half scale (k_scale_update: folds this kernel's per-block max |w|) is needed by the NEXT k_sgd only.  It
+  // is left pending and performed by one extra workgroup of the next step's k_reduce; anything else that touches the
+  // scales or the parameters first flushes it as its own launch.
+  return finish_update(c, SGD_BLOCKS);
+}
+
 int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   int rc = check_cfg(c, cfg);
   if (rc) return rc;
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_apply_update: no gradients (call vv_forward_backward)");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_apply_update: no gradients (call vv_forward_backward)");
+  if ((rc = upd_pending_guard(c, "vv_apply_update"))) return rc;     // (GradAt::Lost: a second update on a gradient that was never stored)
   VV_ENTER(c);
-  // two updates in a row: the first one completes first.  (After a gated forward GEMM -- upd_unjoined -- nothing is due here: the
+  // two updates in a row: the first one completes first.  (After a gated forward GEMM -- UpdSync::Gated -- nothing is due here: the
   // new update is queued on the communication stream behind the old one, and what this step's kernels on the compute stream read
   // of the old one -- the half copy, its scale, the bias, the per-block maxima -- was stored at agent scope before the gates opened.)
   // That holds only while the new update goes to the communication stream too.  One that runs on the COMPUTE stream -- the schedule was
   // switched to `sync`, the gradient buffer was handed out or bound after an overlapped step, the sharded update runs in-stream -- reads
   // W and the history, which the previous update wrote with plain stores released only at its end: it joins first.
-  const bool overlapped = c->comm && c->grads_pending && c->grads_chunked;
-  const bool sharded = c->comm && c->grads_pending && c->grads_sharded;
+  const bool overlapped = c->comm && grad_sum_due(c->grad) && c->grad.buf.layout == GradLayout::Chunked;
+  const bool sharded = c->comm && grad_sum_due(c->grad) && c->grad.buf.layout == GradLayout::Sharded;
   const bool on_comm_stream = overlapped || (sharded && !c->comm_inline);
-  if ((c->upd_inflight || (c->upd_unjoined && !on_comm_stream)) && (rc = comm_join(c))) return rc;
+  if ((c->upd_sync == UpdSync::InFlight || (c->upd_sync == UpdSync::Gated && !on_comm_stream)) && (rc = comm_join(c))) return rc;
   // A sharded update left the other ranks' rows of the fp32 master W and of the history stale here; an update of the WHOLE matrix needs
   // them (the step left the sharded path -- gradients exposed or bound, the schedule changed -- without a gather).  A
   // collective, like the update itself: every rank takes this branch in the same iteration.
   if (!sharded && c->params_partial && (rc = gather_params(c))) return rc;
-  if (!overlapped && !sharded && c->grads_pending && (rc = vv_allreduce_grads(c))) return rc;     // data-parallel: the update consumes the SUM over the ranks
+  if (!overlapped && !sharded && grad_sum_due(c->grad) && (rc = vv_allreduce_grads(c))) return rc;     // data-parallel: the update consumes the SUM over the ranks
   SgdArgs a;
   float* const wmax_new = c->wmax_blocks + (1 - c->wmax_cur) * WMAX_SLOTS;     // the buffer the previous update did not write
   a.W = c->W; a.b = c->b; a.hW = c->hW; a.hb = c->hb; a.grads = c->grads; a.Wh = c->Wh; a.scales = c->scales; a.wmax_blocks = wmax_new;
@@ -1576,123 +1708,19 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   // Adam: the second history (allocated by the first such update) and this update's own bias correction -- t is the library's counter of
   // Adam updates, every queued update carries its corr_t as a kernel argument and nothing synchronises
   const bool adam = cfg->solver_type == VV_SOLVER_ADAM;
-  if (adam && c->upd_in_wgrad) return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
+  if (adam && c->grad.at == GradAt::SlabsWUpdated) return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
   if (adam && (rc = ensure_history2(c))) return rc;
   a.rule = solver_rule(*cfg, c->momentum2, c->rms_decay, adam ? c->adam_t + 1 : 0);     // (t is committed where the update is queued: finish_update)
   c->adam_pending = adam;
   float* const vW = adam ? c->hW2 : nullptr; float* const vb = adam ? c->hb2 : nullptr;
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
-  if (c->upd_in_wgrad) {
-    // the parameter matrix was updated in the weight-gradient GEMM (vv_update_hint): bias, loss, the guard's report -- k_reduce_sgd's
-    // special workgroups alone -- and the bookkeeping of the scale
-    // (what the weight-gradient GEMM applied: WgradUpd::rule -- the bias multipliers may differ, the bias is updated here)
-    const SolverRule h = solver_rule(c->upd_cfg, c->upd_momentum2, c->upd_rms_decay);
-    const SolverRule& r = a.rule;
-    if (r.rate != h.rate || r.momentum != h.momentum || r.weight_decay != h.weight_decay || r.lr_mult_w != h.lr_mult_w ||
-        r.decay_mult_w != h.decay_mult_w || r.reg != h.reg || r.solver_type != h.solver_type || r.delta != h.delta || r.decay2 != h.decay2)
-      return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (the weights were updated with the announced ones)");
-    FusedUpdArgs fa;
-    fa.r = c->red_args; fa.g = a; fa.prec = c->prec; fa.no_params = 1; fa.recompute_scale = 0; fa.store_grads = 0;
-    c->red_lazy = false; c->grads_stale = false; c->upd_in_wgrad = false;
-    c->grads_lost = true;                       // (dW of this step never existed outside the GEMM's registers)
-    PROFILED(c, "reduce_sgd", (void)launch_reduce_sgd(fa, c->stream));
-    return finish_update(c, c->upd_wgrad_blocks);
-  }
-  if (c->red_lazy && !overlapped) {
-    // the reduction is still due: reduce and update in one launch (k_reduce_sgd)
-    FusedUpdArgs fa;
-    fa.r = c->red_args; fa.g = a; fa.prec = c->prec;
-    fa.recompute_scale = c->scale_pending ? 1 : 0;
-    fa.wmax_prev = c->wmax_blocks + c->wmax_cur * WMAX_SLOTS; fa.wmax_prev_n = c->wmax_n;
-    const bool keep_grads = c->fuse_keep_grads;
-    fa.store_grads = keep_grads;
-    c->red_lazy = false; c->grads_stale = !keep_grads;
-    int n_new = 0;
-    PROFILED(c, "reduce_sgd", (n_new = launch_reduce_sgd(fa, c->stream, vW, vb)));
-    HIPCHK(clear_wmax_seed(c, fa.recompute_scale, c->stream));
-    return finish_update(c, n_new);
-  }
-  if ((rc = reduce_now(c))) return rc;
+  if (c->grad.at == GradAt::SlabsWUpdated) return update_finish_wgrad(c, a);
+  if (c->grad.at == GradAt::Slabs) return update_fused(c, a, vW, vb);
+  if ((rc = reduce_now(c))) return rc;       // (GradAt::SlabsStale: a second update on the same gradient reads it from the buffer)
   flush_scale_update(c);               // two updates in a row without a step between them
-  if (sharded) {
-    // Exact synchronous SGD, the update SHARDED over the ranks (Multi-GPU): on the communication stream, behind one event of
-    // the compute stream,   reduce-scatter (fp32, shard-major buffer: 7/8 of it on the wire at N = 8, once)  ->  k_sgd on THIS rank's
-    // D / N rows (1/N of the update's 46 MB)  ->  ONE grouped all-gather of what every rank's next forward pass reads: the 16-bit copy
-    // of W (4 MB instead of the all-reduce's second 8.4 MB), the bias, the per-block maxima the next W -> half scale comes from  ->
-    // publish.  3/4 of the all-reduce's wire bytes.  The next forward GEMM is gated on the one flag (it starts, and waits in front of
-    // its first W tile); the fp32 master W and the history stay sharded until vv_params_get gathers them.
-    // comm_inline (default): this schedule has ONE gate, in front of the GEMM's first W tile -- nothing of the exchange hides behind the
-    // GEMM, and the second stream costs its hand-off chain (event -> wake -> ... -> publish: + 17 us on one rank).  So the
-    // three steps are queued on the COMPUTE stream itself, in order, and the next forward GEMM is the plain kernel (with its sibling lead).
-    const bool inl = c->comm_inline;
-    hipStream_t cs = inl ? c->stream : vv::comm_stream(c->comm);
-    const int world = vv::comm_world(c->comm), rank = vv::comm_rank(c->comm);
-    const int rps = c->D / world;
-    const size_t shard_f = (size_t)rps * c->F + rps;
-    int32_t useq = c->upd_seq;
-    if (!inl) { HIPCHK(hipEventRecord(c->ev_chunk, c->stream)); useq = ++c->upd_seq; }
-    if (c->comm_test_delay_us > 0) { if (!inl) HIPCHK(hipStreamWaitEvent(cs, c->ev_chunk, 0)); launch_delay(c->comm_test_delay_us, cs); }
-    struct StreamScope { vv::Comm* k; ~StreamScope() { vv::comm_use_stream(k, nullptr); } } scope{c->comm};
-    vv::comm_use_stream(c->comm, inl ? c->stream : nullptr);
-    if (vv::comm_reduce_scatter(c->comm, c->grads, shard_f, inl ? nullptr : c->ev_chunk)) return fail(VV_ERR_HIP, "reduce-scatter: %s", vv::comm_error(c->comm));
-    const int nb = SGD_BLOCKS / world;
-    SgdArgs g = a;                                    // the shard as a parameter matrix of its own: rps rows, its gradient buffer [dW rows | db entries]
-    g.D = rps;
-    g.W = c->W + (size_t)rank * rps * c->F; g.hW = c->hW + (size_t)rank * rps * c->F;
-    g.b = c->b + (size_t)rank * rps; g.hb = c->hb + (size_t)rank * rps;
-    g.grads = c->grads + (size_t)rank * shard_f;
-    float* const svW = adam ? vW + (size_t)rank * rps * c->F : nullptr; float* const svb = adam ? vb + (size_t)rank * rps : nullptr;     // the shard owns its rows of v
-    g.Wh = c->Wh + (size_t)rank * rps * c->Fp;
-    g.chunked = 1; g.f_begin = 0; g.f_count = c->F; g.do_bias = 1; g.set_scale = 1;      // (chunked = 1 with the whole width: this launch's own grid and slots)
-    g.blk_off = rank * nb; g.n_blk = nb;
-    PROFILED(c, "sgd", launch_sgd(c->prec, g, cs, svW, svb));
-    void* bufs[3] = {c->Wh, c->b, wmax_new};
-    const size_t sbytes[3] = {(size_t)rps * c->Fp * 2, (size_t)rps * 4, (size_t)nb * 4};
-    if (vv::comm_allgather(c->comm, bufs, sbytes, 3)) return fail(VV_ERR_HIP, "all-gather: %s", vv::comm_error(c->comm));
-    if (!inl) {
-      launch_publish(c->w_gate, useq, cs);
-      if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-gather: %s", vv::comm_error(c->comm));
-    }
-    c->grads_pending = false; c->upd_inflight = !inl; c->upd_unjoined = false;
-    c->params_partial = world > 1;
-    if (adam) c->hist2_partial = world > 1;
-    return finish_update(c, nb * world);
-  }
-  if (overlapped) {
-    // Exact synchronous SGD with the exchange hidden behind the NEXT step's forward GEMM: behind one event of the compute
-    // stream, the communication stream runs per F-chunk  all-reduce -> SGD on the chunk's columns -> publish w_gate[chunk];
-    // the next forward GEMM (fb_impl) starts right away and waits for each chunk where its K loop reaches it.  db rides
-    // with the last chunk; the bias is updated there.
-    hipStream_t cs = vv::comm_stream(c->comm);
-    const int32_t useq = ++c->upd_seq;
-    const int nch = chunk_plan(c);               // (the layout k_reduce wrote: same Fp, same plan)
-    a.pub_count = c->pub_count; a.pub_seq = useq;
-    HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
-    for (int k = 0; k < nch; ++k) {
-      // chunk 0 may start as soon as ITS reduction is done (ev_chunk0, fb_impl); the others follow the whole backward pass
-      hipEvent_t after = k == 0 ? (c->chunk0_event ? c->ev_chunk0 : c->ev_chunk) : (k == 1 && c->chunk0_event ? c->ev_chunk : nullptr);
-      const int c0 = std::min(c->F, c->chunk_kt[k] * BK), c1 = std::min(c->F, c->chunk_kt[k + 1] * BK);
-      const bool last = k == nch - 1;
-      const size_t off = (size_t)c->D * c0, n = (size_t)c->D * (c1 - c0) + (last ? (size_t)c->D : 0);
-      const int delay_us = c->comm_test_delay_us;
-      if (after) HIPCHK(hipStreamWaitEvent(cs, after, 0));
-      if (delay_us > 0) launch_delay(delay_us, cs);      // test hook: a slow exchange, so that the next forward GEMM really waits at its gates
-      const bool skip_ar1 = c->comm_skip_ar1;   // (lab) diagnosis: no collective call at world 1
-      if (!(skip_ar1 && vv::comm_world(c->comm) == 1) && n > 0 && vv::comm_allreduce(c->comm, c->grads, off, n, nullptr))
-        return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
-      a.chunked = 1; a.f_begin = c0; a.f_count = c1 - c0; a.do_bias = last; a.set_scale = k == 0;
-      a.blk_off = k * (SGD_BLOCKS / nch); a.n_blk = last ? SGD_BLOCKS - a.blk_off : SGD_BLOCKS / nch;      // together: every slot of wmax_blocks
-      a.pub_flag = c->w_gate + k * W_GATE_STRIDE;          // the kernel's last workgroup publishes the chunk (SgdArgs::pub_flag)
-      if (k == 0) PROFILED(c, "sgd", launch_sgd(c->prec, a, cs, vW, vb)); else launch_sgd(c->prec, a, cs, vW, vb);     // (an empty chunk: its wmax slots become 0, the bias if it is the last)
-    }
-    if (vv::comm_record_done(c->comm)) return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
-    c->grads_pending = false; c->upd_inflight = true; c->upd_unjoined = false;    // (comm_done_event now marks the end of THIS update, behind the old one)
-  } else
-  PROFILED(c, "sgd", launch_sgd(c->prec, a, c->stream, vW, vb));
-  // The next W -> half scale (k_scale_update: folds this kernel's per-block max |w|) is needed by the NEXT k_sgd only.  It
-  // is left pending and performed by one extra workgroup of the next step's k_reduce; anything else that touches the
-  // scales or the parameters first flushes it as its own launch.
-  return finish_update(c, SGD_BLOCKS);
+  if (sharded) return update_sharded(c, a, vW, vb);
+  if (overlapped) return update_overlapped(c, a, vW, vb);
+  return update_plain(c, a, vW, vb);
 }
 
 int vv_step(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device) {
@@ -1705,7 +1733,7 @@ int vv_step(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_de
 
 int vv_loss_get(vv_ctx* c, float* loss, float* violations) {
   if (!c) return fail(VV_ERR_ARG, "vv_loss_get: ctx is NULL");
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_loss_get: no forward pass yet");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_loss_get: no forward pass yet");
   VV_ENTER(c);
   if (c->gate_err && *(volatile int32_t*)c->gate_err) { const int rcj = comm_join(c); if (rcj) return rcj; }
   { const int rcr = reduce_now(c); if (rcr) return rcr; }
@@ -1742,13 +1770,14 @@ int vv_grads_bind(vv_ctx* c, void* dev_ptr) {
 int vv_grads_get(vv_ctx* c, float* dW, float* db) {
   { const int rcg = upd_pending_guard(c, "vv_grads_get"); if (rcg) return rcg; }
   if (!c) return fail(VV_ERR_ARG, "vv_grads_get: ctx is NULL");
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_grads_get: no backward pass yet");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_grads_get: no backward pass yet");
   VV_ENTER(c);
   { const int rcj = comm_join(c); if (rcj) return rcj; }       // block-wise all-reduces in flight: the buffer is read whole
   { const int rcr = reduce_now(c); if (rcr) return rcr; }
   HIPCHK(hipStreamSynchronize(c->stream));
   const size_t nW = (size_t)c->D * c->F;
-  if (c->grads_sharded) {              // shard-major buffer (ReduceArgs::shard_rows) -> the blob's [dW | db]
+  const GradLayout layout = c->grad.buf.layout;
+  if (layout == GradLayout::Sharded) {              // shard-major buffer (ReduceArgs::shard_rows) -> the blob's [dW | db]
     const int rps = c->D / vv::comm_world(c->comm);
     const size_t sf = (size_t)rps * c->F + rps;
     std::vector<float> tmp(nW + c->D);
@@ -1759,8 +1788,8 @@ int vv_grads_get(vv_ctx* c, float* dW, float* db) {
     }
     return VV_OK;
   }
-  if (dW && !c->grads_chunked) HIPCHK(hipMemcpy(dW, c->grads, nW * 4, hipMemcpyDeviceToHost));
-  if (dW && c->grads_chunked) {        // chunk-major buffer (ReduceArgs::n_chunks) -> the blob's row-major D x F
+  if (dW && layout != GradLayout::Chunked) HIPCHK(hipMemcpy(dW, c->grads, nW * 4, hipMemcpyDeviceToHost));
+  if (dW && layout == GradLayout::Chunked) {        // chunk-major buffer (ReduceArgs::n_chunks) -> the blob's row-major D x F
     std::vector<float> tmp(nW);
     HIPCHK(hipMemcpy(tmp.data(), c->grads, nW * 4, hipMemcpyDeviceToHost));
     const int nch = chunk_plan(c);
@@ -1776,7 +1805,7 @@ int vv_grads_get(vv_ctx* c, float* dW, float* db) {
 
 int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_scores, float* ip1_diff) {
   if (!c) return fail(VV_ERR_ARG, "vv_blobs_get: ctx is NULL");
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_blobs_get: no forward pass yet");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_blobs_get: no forward pass yet");
   VV_ENTER(c);
   { const int rcj = comm_join(c); if (rcj) return rcj; }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1874,7 +1903,7 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
 int vv_dedup_groups_get(vv_ctx* c, int32_t* rows, int32_t* uniq_rows, int32_t* map, int32_t* ord, int32_t* cnt, int32_t* seg_start,
                         int32_t* pos, float* dyu, float* scale) {
   if (!c) return fail(VV_ERR_ARG, "vv_dedup_groups_get: ctx is NULL");
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_dedup_groups_get: no forward pass yet");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_dedup_groups_get: no forward pass yet");
   if (!c->last_dedup) return fail(VV_ERR_STATE, "vv_dedup_groups_get: the last forward pass was dense (vv_set_dedup, dropout)");
   VV_ENTER(c);
   { const int rcj = comm_join(c); if (rcj) return rcj; }
@@ -2609,20 +2638,20 @@ int vv_comm_schedule(vv_ctx* c, int schedule) {
 int vv_allreduce_grads(vv_ctx* c) {
   { const int rcg = upd_pending_guard(c, "vv_allreduce_grads"); if (rcg) return rcg; }
   if (!c) return fail(VV_ERR_ARG, "vv_allreduce_grads: ctx is NULL");
-  if (!c->comm) { c->grads_pending = false; return VV_OK; }
-  if (!c->have_fwd) return fail(VV_ERR_STATE, "vv_allreduce_grads: no gradients (call vv_forward_backward)");
-  if (!c->grads_pending) return VV_OK;                         // already summed
-  if (c->grads_chunked || c->grads_sharded) return VV_OK;      // overlapped / sharded schedule: vv_apply_update runs the exchange
+  if (!c->comm) { grad_summed(c->grad); return VV_OK; }
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_allreduce_grads: no gradients (call vv_forward_backward)");
+  if (!grad_sum_due(c->grad)) return VV_OK;                    // already summed
+  if (c->grad.buf.layout != GradLayout::Flat) return VV_OK;    // overlapped / sharded schedule: vv_apply_update runs the exchange
   VV_ENTER(c);
   // synchronous schedule over RCCL: the collective goes straight into the compute stream (nothing would run beside it)
   const int rc = vv::comm_allreduce_inline(c->comm, c->grads, (size_t)c->D * c->F + c->D, c->stream);
   if (rc < 0) return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
-  if (rc == 0) { c->grads_pending = false; return VV_OK; }
+  if (rc == 0) { grad_summed(c->grad); return VV_OK; }
   HIPCHK(hipEventRecord(c->ev_chunk, c->stream));
   if (vv::comm_allreduce(c->comm, c->grads, 0, (size_t)c->D * c->F + c->D, c->ev_chunk))
     return fail(VV_ERR_HIP, "all-reduce: %s", vv::comm_error(c->comm));
   HIPCHK(hipStreamWaitEvent(c->stream, vv::comm_done_event(c->comm), 0));   // the update waits for the sum; the host does not
-  c->grads_pending = false;
+  grad_summed(c->grad);
   return VV_OK;
 }
 
@@ -2633,7 +2662,7 @@ int vv_comm_destroy(vv_ctx* c) {
     (void)gather_params(c);                    // (collective: a sharded update leaves the master parameters whole again)
     (void)comm_join(c); (void)hipStreamSynchronize(c->stream); vv::comm_destroy(c->comm); c->comm = nullptr;
   }
-  c->grads_pending = c->grads_chunked = c->grads_sharded = c->upd_inflight = c->upd_unjoined = c->params_partial = false;
+  grad_comm_destroyed(c->grad); upd_joined(c->upd_sync); c->params_partial = false;
   return VV_OK;
 }
 

@@ -384,6 +384,9 @@ int vv_op_inner_product(vv_ctx* c, const float* X, int64_t R, float* Y) {
 // Propagation to the bottom (dX = dY W, :51-57) is not built: the fc layer of this path sits on the data layer.
 int vv_op_inner_product_bwd(vv_ctx* c, const float* dY, int64_t R, float ip_regularization) {
   NEED(c);
+  { const int rcg = vv_upd_pending_guard(c, "vv_op_inner_product_bwd"); if (rcg) return rcg; }     // (a hinted step half-way: its vv_apply_update is due first)
+  // a fused step whose reduction is still due keeps its loss: reduced now, then this gradient supersedes that step's in the buffer
+  if (c->grad.at == vv::GradAt::Slabs) { const int rcr = vv_reduce_now(c); if (rcr) return rcr; }
   OpScratch& s = scratch_of(c);
   const int64_t Rp = round_up(R, R_ALIGN);
   if (!dY || R <= 0 || !s.x16 || Rp > s.x_rows || s.Fp != c->Fp || s.Dp != c->Dp) return vv_fail(VV_ERR_STATE, "vv_op_inner_product_bwd: call vv_op_inner_product on the same rows first");
@@ -413,7 +416,6 @@ int vv_op_inner_product_bwd(vv_ctx* c, const float* dY, int64_t R, float ip_regu
   wa.Rp = (int)Rp; wa.Dp = Dp; wa.Fp = c->Fp; wa.S = S; wa.ksteps_per_split = (total_steps + S - 1) / S;
   wa.n_dev = nullptr; wa.zero_row = (int32_t)Rp;
   launch_wgrad_gemm(c->prec, wa, c->stream);
-  c->red_lazy = false; c->grads_stale = false;     // (a lazily kept gradient of the fused step is superseded by this one)
   ReduceArgs ra;
   ra.slabs = s.slabs; ra.S = S; ra.Dp = Dp; ra.Fp = c->Fp; ra.dbp = nullptr; ra.B = 0;
   ra.scales = c->scales; ra.sg = 1.f; ra.sg_dev = s.sgs + 1; ra.grads = c->grads; ra.D = D; ra.F = c->F;
@@ -423,9 +425,8 @@ int vv_op_inner_product_bwd(vv_ctx* c, const float* dY, int64_t R, float ip_regu
   launch_reduce(ra, c->stream);
   hipLaunchKernelGGL(k_colsum, dim3((unsigned)((D + 63) / 64)), dim3(EB), 0, c->stream, dY, R, D, c->grads + (size_t)D * c->F);
   HIPCHK(hipGetLastError());
-  c->have_fwd = true;                      // gradients exist: vv_apply_update / vv_grads_get may follow
-  c->grads_pending = c->comm != nullptr;
-  c->grads_chunked = false;
+  // gradients exist, flat: vv_apply_update / vv_grads_get may follow (a lazily kept gradient of the fused step is superseded by this one)
+  vv::grad_to_buffer(c->grad, vv::GradLayout::Flat, !c->comm, false);
   return VV_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "../../include/videovec.h"
 #include "vv_internal.h"
 #include "vv_comm.h"
+#include "vv_step_state.h"
 
 extern thread_local char vv_g_err[512];
 int vv_fail(int code, const char* fmt, ...);
@@ -62,12 +63,12 @@ struct vv_ctx {
   // wmax_blocks holds two buffers of WMAX_SLOTS per-block maxima: an update writes the one the previous update did not
   int wmax_cur = 0, wmax_n = 0;             // the buffer the latest update wrote, and how many slots of it
   bool wmax_seed_live = false;              // Scales::wmax_bits still carries vv_params_set's seed (the next scale update consumes it)
-  // Lazy reduction: vv_forward_backward leaves dW in the split-K slabs (and db / the loss in their partials) when nothing
-  // but an update is likely to want them; vv_apply_update then reduces and updates in ONE launch (k_reduce_sgd), and
-  // anything that reads the gradient or the loss first runs the plain k_reduce (reduce_now in api.hip).
-  bool red_lazy = false; vv::ReduceArgs red_args;
+  // Where the last backward pass left its gradient, and whether an overlapped update has been joined (vv_step_state.h: written through
+  // its transitions only).  red_args: the reduction of a gradient kept in the slabs; upd_wgrad_blocks: the per-block max |w| slots the
+  // weight-gradient GEMM wrote when it applied the update itself.
+  vv::GradState grad; vv::UpdSync upd_sync = vv::UpdSync::Joined;
+  vv::ReduceArgs red_args; int upd_wgrad_blocks = 0;
   bool grads_exposed = false;               // vv_grads_device handed the buffer out: its holder may read it any time, so the reduction is eager from then on
-  bool grads_stale = false;                 // the fused update ran without writing dW to the gradient buffer: it is still in the slabs
   float* grads = nullptr;           // [D*F + D] (own buffer, or the bound external one)
   float* grads_own = nullptr;
   // per-batch buffers
@@ -84,7 +85,6 @@ struct vv_ctx {
   float* loss2 = nullptr;           // {loss, violations}
   float sg = 1.f; float last_loss_weight = 1.f;
   uint64_t iter = 0;
-  bool have_fwd = false;
   // row de-duplication (kernels_dedup.hip)
   int dedup = 1;                    // 1 = on whenever dropout is off (VV_DEDUP / vv_set_dedup)
   bool last_dedup = false;          // what the last forward/backward pass used
@@ -154,8 +154,6 @@ struct vv_ctx {
   vv::Comm* comm = nullptr;
   bool comm_overlap = false;        // the update runs F-chunk by F-chunk on the communication stream (all-reduce, SGD, publish) and
                                     // the NEXT step's forward GEMM waits per chunk inside the kernel (FwdArgs::gate)
-  bool grads_pending = false;       // a backward pass has produced gradients that have not been all-reduced yet
-  bool grads_chunked = false;       // the gradient buffer of the last backward pass is laid out chunk-major (ReduceArgs::n_chunks)
   // per-context switches (vv_set_option; environment read once, in vv_create).  Nothing of this is process-global.
   vv::KernelOpts ko;                // which kernels the launchers pick (vv_internal.h)
   bool fuse_update = true;          // "fuse_update" / VV_FUSE_UPDATE=0: reduce at the end of every backward pass, update apart
@@ -169,9 +167,6 @@ struct vv_ctx {
                                             // happened to lie in physical memory; with it forty processes in forty at 95-107 us: 0.211-0.224 ms per iteration at the
                                             // shipped shape against 0.229-0.236 with the update as its own launch (profiles/r05_shipped_update.txt).
   vv_step_cfg upd_cfg;
-  bool upd_in_wgrad = false;                // this step's parameter matrix is already updated; vv_apply_update finishes the step
-  int upd_wgrad_blocks = 0;                 // per-block max |w| slots that launch wrote
-  bool grads_lost = false;                  // the last step's dW was consumed in registers (vv_grads_* refuse until the next backward pass)
   uint32_t* lab_score_ts = nullptr;         // (lab builds) device buffer of k_score_fwd's phase stamps, api.hip
   bool comm_inline = true;                  // option "comm_inline" (VV_COMM_INLINE): the sharded update queued on the compute stream itself (no second stream, no gate)
   int nearest_select_min_k = 33;    // "nearest_select_min_k" / VV_NEAREST_SELECT_MIN_K: vv_gallery_nearest* use the selection form from this k on (1 .. 33)
@@ -189,16 +184,13 @@ struct vv_ctx {
   // rank's D / world rows of W / history / bias, all-gather of the 16-bit copy + the bias + the per-block maxima that every rank's next
   // forward pass reads.  The fp32 master W and the history are complete only on their owner until vv_params_get gathers them.
   bool comm_sharded = false;
-  bool grads_sharded = false;       // the gradient buffer of the last backward pass is laid out shard-major (ReduceArgs::shard_rows)
   bool params_partial = false;      // W / hW / hb rows of the other ranks' shards are stale (a sharded update ran since the last gather)
-  bool upd_inflight = false;        // an overlapped update is on the communication stream and the compute stream has not joined it
-  bool upd_unjoined = false;        // ... the gated forward GEMM has consumed it, the compute stream has still not waited for its end
   int32_t upd_seq = 0;              // sequence number of the last overlapped update (what w_gate[c] reaches when chunk c is done)
   int32_t* w_gate = nullptr;        // device [W_CHUNKS_MAX * W_GATE_STRIDE]: one flag per 128-B line
   int n_chunks = 3;                 // F-chunks of the overlapped update (env VV_COMM_CHUNKS, 1 .. 4)
   int chunk_kt[5] = {0, 0, 0, 0, 0};    // first K-tile of each chunk for the current Fp (chunk_plan)
   int32_t* pub_count = nullptr;     // device: arrival counter of the publishing SGD kernels (behind the flags)
-  hipEvent_t ev_chunk0 = nullptr; bool chunk0_event = false;     // the first F-chunk's reduction is done (recorded by fb_impl)
+  hipEvent_t ev_chunk0 = nullptr;   // the first F-chunk's reduction is done (recorded by fb_impl: GradBuffer::chunk0_event)
   int32_t* gate_err = nullptr; int32_t* gate_err_dev = nullptr;     // pinned + mapped: a gated forward gave up waiting
   hipEvent_t ev_chunk = nullptr;
   hipEvent_t ev_idx = nullptr;      // orders the grouping stream behind caller-produced device indices (idx_on_device = 1)
@@ -216,3 +208,7 @@ struct vv_ctx {
 void vv_ops_release(vv_ctx* c);
 // api.hip: orders the compute stream behind an overlapped parameter update still on the communication stream
 int vv_comm_join(vv_ctx* c);
+// api.hip: the reduction a backward pass left undone (GradAt::Slabs), now -- the gradient to the buffer, the loss to its scalars
+int vv_reduce_now(vv_ctx* c);
+// api.hip: VV_ERR_STATE where the gradient's state refuses the entry point `who` (vv_step_state.h: grad_guard)
+int vv_upd_pending_guard(vv_ctx* c, const char* who);
