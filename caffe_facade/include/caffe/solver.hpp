@@ -49,7 +49,8 @@ class Solver {
 
   SolverParameter param_;
   int iter_;
-  bool h16_warned_ = false;            // the one warning line of the f16 rows' fallback has been written (Step)
+  float clip_gradients_ = -1.f;        // SolverParameter.clip_gradients (BVLC; < 0: off), handed to the engine by Init
+  bool h16_warned_ = false;           // the one warning line of the f16 rows' fallback has been written (Step)
   shared_ptr<Net<Dtype> > net_;
   vector<shared_ptr<Net<Dtype> > > test_nets_;
 };

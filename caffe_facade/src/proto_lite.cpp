@@ -99,7 +99,10 @@ static const std::vector<MsgDef>& Msgs() {
         OPT(33, "snapshot_vis", T_INT32), OPT(34, "snapshot_vis_blobs", T_STRING),
         OPT(35, "snapshot_vis_truncate_len", T_INT32), OPT(36, "snapshot_vis_dir", T_STRING),
         // BVLC Caffe's SolverParameter.rms_decay = 38 and momentum2 = 39 (the fork's message ends at 36: both numbers are free)
-        OPTD(38, "rms_decay", T_FLOAT, "0.99"), OPTD(39, "momentum2", T_FLOAT, "0.999")}},
+        OPTD(38, "rms_decay", T_FLOAT, "0.99"), OPTD(39, "momentum2", T_FLOAT, "0.999"),
+        // BVLC Caffe's SolverParameter.clip_gradients is field 35, which the fork gave to snapshot_vis_truncate_len (36 is taken too):
+        // here it is 135, outside both projects' ranges.  Text solver files read by name, so BVLC's work as they are.
+        OPTD(135, "clip_gradients", T_FLOAT, "-1")}},
       {"SolverState",                                                               // :176-180
        {OPT(1, "iter", T_INT32), OPT(2, "learned_net", T_STRING), RMSG(3, "history", "BlobProto")}},
       {"LayerParameter",                                                            // :215-389

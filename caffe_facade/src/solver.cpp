@@ -105,6 +105,16 @@ void Solver<Dtype>::Init(const SolverParameter& param) {
   // VV_H16_GUARD names another value, which the context took when it was created.
   const char* hg = getenv("VV_H16_GUARD");
   if (!hg || !*hg) VV_CHECK(vv_set_option(Caffe::ctx(), "h16_guard", 2));
+  // BVLC SolverParameter.clip_gradients (SGDSolver::ClipGradients; vv_clip_gradients_set): the norm needs the whole summed gradient, so a
+  // data-parallel job that clips runs the sync exchange schedule
+  clip_gradients_ = (float)param_.get_num("clip_gradients");
+  if (clip_gradients_ >= 0) {
+    if (Caffe::world() > 1) {
+      VV_CHECK(vv_comm_schedule(Caffe::ctx(), 0));
+      LOG(INFO) << "clip_gradients: " << clip_gradients_ << " -- the gradient exchange runs on the sync schedule (the norm is taken of the summed gradient)";
+    }
+    VV_CHECK(vv_clip_gradients_set(Caffe::ctx(), clip_gradients_));
+  }
   LOG(INFO) << "Solver scaffolding done.";
 }
 
@@ -181,6 +191,12 @@ void Solver<Dtype>::Step(bool display) {
   }
   ComputeUpdateValue();
   net_->Update();
+  if (display && clip_gradients_ >= 0) {            // (a display iteration has read the loss anyway; no synchronisation on the others)
+    vv_clip_report r;
+    VV_CHECK(vv_clip_stats(Caffe::ctx(), &r));
+    if (r.clipped)                                  // BVLC SGDSolver::ClipGradients' line
+      LOG(INFO) << "Gradient clipping: scaling down gradients (L2 norm " << r.norm << " > " << clip_gradients_ << ") by scale factor " << r.scale;
+  }
 }
 
 template <typename Dtype>
@@ -209,6 +225,11 @@ void Solver<Dtype>::Solve(const char* resume_file) {
     LOG(INFO) << "Iteration " << iter_ << ", loss = " << loss;
   }
   if (Every(test, iter_)) TestAll();
+  if (clip_gradients_ >= 0) {
+    vv_clip_report r;
+    VV_CHECK(vv_clip_stats(Caffe::ctx(), &r));
+    LOG(INFO) << "Gradient clipping: " << (long long)r.clipped_updates << " of " << (long long)r.updates << " updates were scaled down (clip_gradients " << clip_gradients_ << ")";
+  }
   LOG(INFO) << "Optimization Done.";
 }
 

@@ -106,7 +106,8 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *   "last_fwd_tile_rows"             rows of the forward GEMM's tile, 128, 192 or 256, whoever launched it (a step, vv_embed*, vv_op_inner_product,
  *                                    vv_gallery_from_table); 0 before the first launch
  *   "last_wgrad_splits"              splits of K (S) of the weight-gradient GEMM (a step or vv_op_inner_product_bwd); 0 before the first launch
- *   "last_update_form"               what the last vv_apply_update ran for the parameter matrix: 1 k_sgd with 16-byte accesses (the chunked and sharded updates too), 2 k_sgd scalar (F % 4 != 0), 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0 before the first update
+ *   "last_update_form"               what the last vv_apply_update ran for the parameter matrix: 1 k_sgd with 16-byte accesses (the chunked and sharded updates too), 2 k_sgd scalar (F % 4 != 0), 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0 before the first update.
+ *                                    While gradient clipping is active (vv_clip_gradients_set >= 0) every update is 1 or 2: the fused forms 3 - 5 are not used
  *   "last_score_form"                what the last forward pass launched for scores and loss: 1 k_score_fwd (register-resident), 2 k_score_stream at
  *                                    D = 512, 3 k_score_stream at D = 1024, 4 the per-instance kernels (dense or row-writing execution); 0 before the first step
  *   "last_h16"                       1: the last forward pass stored ip2 as f16 rows, 0: fp32 rows (or no step yet)
@@ -178,6 +179,33 @@ int vv_solver_iter_get(vv_ctx* ctx, int64_t* count);
  * as zeros.  vv_params_set clears it.  Host fp32; with the sharded update vv_history2_get gathers like vv_params_get (a collective). */
 int vv_history2_set(vv_ctx* ctx, const float* vW, const float* vb);
 int vv_history2_get(vv_ctx* ctx, float* vW, float* vb);
+
+/* ---- gradient clipping by the global L2 norm: BVLC Caffe's SolverParameter.clip_gradients and SGDSolver::ClipGradients (sgd_solver.cpp);
+ * the reference tree has no such function, so the semantics are BVLC's.  clip < 0 (the default, -1) disables it and a step is in every
+ * respect what it was; clip >= 0 makes it active; NaN is VV_ERR_ARG.  Sticky on the context until set again.  In an active
+ * vv_apply_update, before the regulariser and before any rule: sumsq = the sum of g^2 over the whole flat gradient buffer [dW (D F) | db (D)]
+ * -- the values vv_grads_get would return at that moment: ip_regularization's factor included, summed over the ranks of a communicator --
+ * accumulated in double in a fixed order (the same buffer gives the same bits on every run and every rank); norm = sqrt(sumsq); if
+ * norm > clip (strictly; norm == clip and norm == 0 scale nothing, there is no division by zero) every element is multiplied in place
+ * by scale = clip / norm (one fp32 multiply), else nothing is written.  vv_grads_get after the update returns the clipped gradient, as
+ * BVLC's diff would.  Two kernels on the step's stream (k_grad_sumsq, k_grad_scale), no host synchronisation.
+ * An active update brings the gradient into the buffer as a reader of the gradient would, and runs the plain k_sgd: "last_update_form" 1
+ * or 2.  The fused forms 3 - 5 are not used, and vv_update_hint / vv_step do not announce the epilogue update for such a step ("where the
+ * fusion does not apply the hint changes nothing"); vv_update_hint's "exactly these solver parameters" includes the threshold: a
+ * vv_apply_update under another one than its hint announced is VV_ERR_ARG.  All five solver rules work.
+ * Data parallel: on the sync schedule only -- the all-reduce finishes, then every rank runs the same two kernels on identical buffers.
+ * VV_ERR_STATE: vv_clip_gradients_set(>= 0) while schedule 1 or 2 is selected, and vv_comm_schedule(1 or 2) / vv_comm_overlap(1) while
+ * clipping is active. */
+int vv_clip_gradients_set(vv_ctx* ctx, float clip);
+int vv_clip_gradients_get(vv_ctx* ctx, float* clip);
+/* What SGDSolver::ClipGradients would have logged (BVLC: "Gradient clipping: scaling down gradients (L2 norm X > Y) by scale factor Z"). */
+typedef struct { float norm, scale;                 /* of the LAST completed clipping update (synchronises, like vv_dedup_stats): norm and scale each
+                                                       formed in double and rounded once; scale is 1 where the step was not clipped.  0, 1 before the first */
+                 int32_t clipped;                   /* 1: that update scaled its gradient */
+                 int32_t reserved_;
+                 int64_t updates;                   /* updates that computed a norm (clipping active) since vv_create */
+                 int64_t clipped_updates; } vv_clip_report;     /* ... of which scaled their gradient */
+int vv_clip_stats(vv_ctx* ctx, vv_clip_report* out);
 
 /* ---- one training iteration */
 typedef struct {
@@ -258,14 +286,14 @@ int vv_apply_update(vv_ctx* ctx, const vv_step_cfg* cfg);
 int vv_step(vv_ctx* ctx, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device);
 /* Solver::Step as ONE unit (solver.cpp:177-221: ForwardBackward, ComputeUpdateValue, Update back to back): announces that the NEXT
  * vv_forward_backward* call will be followed by vv_apply_update with exactly these solver parameters (lr, momentum, weight_decay, lr_mult,
- * decay_mult, reg, solver_type, delta, and vv_solver_ext_set's values) and that nothing reads the gradient in between.  The library may then apply the update where the
+ * decay_mult, reg, solver_type, delta, and vv_solver_ext_set's and vv_clip_gradients_set's values) and that nothing reads the gradient in between.  The library may then apply the update where the
  * gradient is produced (option "wgrad_update", on by default): when the weight-gradient GEMM runs with one split of K (large D x F, small batches -- the shipped
  * mednet_embedding_train.prototxt: 4096 x 4096, batch 128) its epilogue applies the solver's rule to the tile it holds, and the 4 D F bytes
  * of dW are neither written nor read back; vv_apply_update then only finishes the step (bias, loss, scale bookkeeping).  Parameters, history
  * and losses are bit for bit those of the un-hinted calls.  Between such a vv_forward_backward* and its vv_apply_update only vv_loss_get
  * is allowed (vv_grads_*, vv_params_get, vv_op_inner_product_bwd, another forward pass: VV_ERR_STATE -- the gradient of such a step is not
  * kept, the parameters are half-way); after that vv_apply_update, until the next backward pass, vv_grads_* and a second vv_apply_update
- * are refused the same way (the gradient was never stored).  Where the fusion does not apply (several splits of K, a communicator, a bound gradient buffer, Adam's two histories) the hint changes nothing.
+ * are refused the same way (the gradient was never stored).  Where the fusion does not apply (several splits of K, a communicator, a bound gradient buffer, Adam's two histories, active gradient clipping) the hint changes nothing.
  * vv_step announces itself.  One hint covers one step. */
 int vv_update_hint(vv_ctx* ctx, const vv_step_cfg* cfg);
 

@@ -268,6 +268,7 @@ int vv_destroy(vv_ctx* c) {
   vv_ops_release(c);
   free_batch(c);
   dfree(c->table); dfree(c->patch_desc); dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh);
+  dfree(c->clip_rec);
   dfree(c->scales); dfree(c->wmax_blocks); dfree(c->grads_own); dfree(c->mask); dfree(c->loss2);
   dfree(c->dd_key); dfree(c->dd_info_all); dfree(c->gg); dfree(c->gg_bound); dfree(c->w_gate);
   if (c->gate_err) (void)hipHostFree(c->gate_err);
@@ -711,6 +712,48 @@ int vv_history2_get(vv_ctx* c, float* vW, float* vb) {
   return VV_OK;
 }
 
+// ---- gradient clipping by the global L2 norm (BVLC Caffe's SGDSolver::ClipGradients, sgd_solver.cpp; the reference tree has none)
+static const char* const kClipSchedule = "gradient clipping runs on the sync exchange schedule only (it needs the summed gradient's norm before the first "
+                                         "chunk or shard is updated): vv_clip_gradients_set(< 0) or vv_comm_schedule(0)";
+int vv_clip_gradients_set(vv_ctx* c, float clip) {
+  if (!c) return fail(VV_ERR_ARG, "vv_clip_gradients_set: ctx is NULL");
+  if (!(clip == clip)) return fail(VV_ERR_ARG, "vv_clip_gradients_set: NaN");
+  if (clip >= 0.f && (c->comm_overlap || c->comm_sharded)) return fail(VV_ERR_STATE, "vv_clip_gradients_set: %s", kClipSchedule);
+  if (clip >= 0.f && !c->clip_rec) {         // the record, the partial sums, the arrival counter: here, never on the step path
+    VV_ENTER(c);
+    const size_t bytes = sizeof(ClipRec) + (size_t)CLIP_BLOCKS * sizeof(double) + 16;
+    HIPCHK(hipMalloc((void**)&c->clip_rec, bytes));
+    HIPCHK(hipMemset(c->clip_rec, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());            // (the fill is complete before a kernel of any stream reads it)
+  }
+  c->clip = clip;
+  return VV_OK;
+}
+int vv_clip_gradients_get(vv_ctx* c, float* clip) {
+  if (!c || !clip) return fail(VV_ERR_ARG, "vv_clip_gradients_get: NULL argument");
+  *clip = c->clip;
+  return VV_OK;
+}
+int vv_clip_stats(vv_ctx* c, vv_clip_report* out) {
+  if (!c || !out) return fail(VV_ERR_ARG, "vv_clip_stats: ctx / out is NULL");
+  out->norm = 0.f; out->scale = 1.f; out->clipped = 0; out->updates = out->clipped_updates = 0;
+  if (!c->clip_rec) return VV_OK;              // clipping was never active
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  ClipRec r;
+  HIPCHK(hipMemcpy(&r, c->clip_rec, sizeof(r), hipMemcpyDeviceToHost));
+  if (r.updates > 0) { out->norm = r.norm; out->scale = r.scale; out->clipped = r.clipped; }
+  out->updates = r.updates; out->clipped_updates = r.clipped_updates;
+  return VV_OK;
+}
+static ClipArgs clip_args(vv_ctx* c) {
+  ClipArgs a;
+  a.g = c->grads; a.n = (int64_t)c->D * c->F + c->D; a.clip = c->clip;
+  a.rec = c->clip_rec; a.part = (double*)(c->clip_rec + 1); a.arrived = (uint32_t*)(a.part + CLIP_BLOCKS);
+  a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
+  return a;
+}
+
 // ------------------------------------------------------------------------------- step ---------
 static int ensure_batch(vv_ctx* c, int B, int C, int Nn) {
   if (B == c->B && C == c->C && Nn == c->Nn && c->H) return VV_OK;
@@ -882,6 +925,7 @@ static int finish_update(vv_ctx* c, int n_slots) {
   c->wmax_cur = 1 - c->wmax_cur; c->wmax_n = n_slots;
   c->scale_pending = true;
   if (c->adam_pending) { c->adam_t++; c->adam_pending = false; }      // the Adam update is queued: its t is taken
+  c->upd_announced = false;
   HIPCHK(hipGetLastError());
   c->iter++;
   c->prof_calls++;
@@ -1079,7 +1123,7 @@ int vv_update_hint(vv_ctx* c, const vv_step_cfg* cfg) {
   if (rc) return rc;
   c->upd_hint = true;
   c->upd_cfg = *cfg;
-  c->upd_momentum2 = c->momentum2; c->upd_rms_decay = c->rms_decay;
+  c->upd_momentum2 = c->momentum2; c->upd_rms_decay = c->rms_decay; c->upd_clip = c->clip;
   return VV_OK;
 }
 
@@ -1111,9 +1155,11 @@ static int wgrad_to_destination(vv_ctx* c, WgradArgs& wa, ReduceArgs& ra, bool u
   // vv_update_hint + one split of K: the tile in the weight-gradient GEMM's accumulators IS the gradient -- the solver's rule is applied
   // there (WgradUpd) and the 4 D F bytes of dW are neither written nor read back (the shipped configuration: D = F = 4096, 134 MB of the
   // update's 370).  vv_apply_update then runs only the bias / loss workgroups.
-  // (Adam keeps two histories: the epilogue declines it, the step takes k_reduce_sgd -- the hint changes nothing, as for several splits)
+  // (Adam keeps two histories: the epilogue declines it, the step takes k_reduce_sgd -- the hint changes nothing, as for several splits.
+  // Gradient clipping announced with the hint: the update needs the whole gradient's norm first -- the hint changes nothing either.)
+  c->upd_announced = upd_hint;
   const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
-                      (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM;
+                      (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM && !(c->upd_clip >= 0.f);
   if (fuse_w) {
     WgradUpd& u = wa.upd;
     wa.fuse_upd = 1;
@@ -1694,6 +1740,13 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   // W and the history, which the previous update wrote with plain stores released only at its end: it joins first.
   const bool overlapped = c->comm && grad_sum_due(c->grad) && c->grad.buf.layout == GradLayout::Chunked;
   const bool sharded = c->comm && grad_sum_due(c->grad) && c->grad.buf.layout == GradLayout::Sharded;
+  // Gradient clipping (vv_clip_gradients_set >= 0): the step's gradient goes to the buffer by the transition a reader takes (the plain
+  // k_reduce), k_grad_sumsq and k_grad_scale run on it, then the plain k_sgd -- form 1 or 2; the fused forms are not used.  "Exactly
+  // these solver parameters" of vv_update_hint includes the threshold.
+  const bool clip_on = c->clip >= 0.f;
+  if (c->upd_announced && c->clip != c->upd_clip)
+    return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (vv_clip_gradients_set's threshold)");
+  if (clip_on && (overlapped || sharded)) return fail(VV_ERR_STATE, "vv_apply_update: this step's gradient was laid out for another schedule -- %s", kClipSchedule);
   const bool on_comm_stream = overlapped || (sharded && !c->comm_inline);
   if ((c->upd_sync == UpdSync::InFlight || (c->upd_sync == UpdSync::Gated && !on_comm_stream)) && (rc = comm_join(c))) return rc;
   // A sharded update left the other ranks' rows of the fp32 master W and of the history stale here; an update of the WHOLE matrix needs
@@ -1715,9 +1768,14 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   float* const vW = adam ? c->hW2 : nullptr; float* const vb = adam ? c->hb2 : nullptr;
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
   if (c->grad.at == GradAt::SlabsWUpdated) return update_finish_wgrad(c, a);
-  if (c->grad.at == GradAt::Slabs) return update_fused(c, a, vW, vb);
+  if (c->grad.at == GradAt::Slabs && !clip_on) return update_fused(c, a, vW, vb);
   if ((rc = reduce_now(c))) return rc;       // (GradAt::SlabsStale: a second update on the same gradient reads it from the buffer)
   flush_scale_update(c);               // two updates in a row without a step between them
+  if (clip_on) {                       // (the sum over the ranks, where one is due, is queued in front: every rank reads identical buffers)
+    const ClipArgs ca = clip_args(c);
+    PROFILED(c, "grad_sumsq", launch_grad_sumsq(ca, c->stream));
+    PROFILED(c, "grad_scale", launch_grad_scale(ca, c->stream));
+  }
   if (sharded) return update_sharded(c, a, vW, vb);
   if (overlapped) return update_overlapped(c, a, vW, vb);
   return update_plain(c, a, vW, vb);
@@ -2619,6 +2677,7 @@ int vv_comm_init(vv_ctx* c, int32_t world, int32_t rank, const char* id_path, in
 
 int vv_comm_overlap(vv_ctx* c, int on) {
   if (!c) return fail(VV_ERR_ARG, "vv_comm_overlap: ctx is NULL");
+  if (on && c->clip >= 0.f) return fail(VV_ERR_STATE, "vv_comm_overlap: %s", kClipSchedule);
   if (on && c->comm_sharded && c->params_partial) { VV_ENTER(c); const int rcg = gather_params(c); if (rcg) return rcg; }   // (collective, as in vv_comm_schedule: leaving the sharded schedule)
   c->comm_overlap = on != 0;
   if (on) c->comm_sharded = false;
@@ -2628,6 +2687,7 @@ int vv_comm_overlap(vv_ctx* c, int on) {
 int vv_comm_schedule(vv_ctx* c, int schedule) {
   if (!c) return fail(VV_ERR_ARG, "vv_comm_schedule: ctx is NULL");
   if (schedule < 0 || schedule > 2) return fail(VV_ERR_ARG, "vv_comm_schedule: 0 sync, 1 overlap, 2 sharded");
+  if (schedule != 0 && c->clip >= 0.f) return fail(VV_ERR_STATE, "vv_comm_schedule: %s", kClipSchedule);
   { const int rcg = upd_pending_guard(c, "vv_comm_schedule"); if (rcg) return rcg; }
   if (schedule != 2 && c->params_partial) { VV_ENTER(c); const int rcg = gather_params(c); if (rcg) return rcg; }     // (collective: the other schedules update the whole matrix)
   c->comm_overlap = schedule == 1;

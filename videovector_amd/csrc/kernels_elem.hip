@@ -1791,6 +1791,87 @@ void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW, float* vb)
   else { if (vec) VV_LAUNCH((k_sgd<BF16, true>), grid, block, 0, s, a); else VV_LAUNCH((k_sgd<BF16, false>), grid, block, 0, s, a); }
 }
 
+// ------------------------------------------------------------------------------- gradient clipping ----
+// BVLC Caffe's SGDSolver::ClipGradients (sgd_solver.cpp; the reference tree has no such function): the L2 norm of ALL parameter gradients
+// -- the flat buffer [dW | db] -- and, where it exceeds the threshold, g *= threshold / norm, before the regulariser and the rule.
+// The buffer splits the same way in both kernels: the floats in front of the first 16-byte boundary (none in the library's own buffer;
+// a bound one may start at any float), 16-byte items, the floats behind the last whole item.
+struct ClipSplit { int64_t head, n4, tail0, rest; };
+__device__ __forceinline__ ClipSplit clip_split(const float* g, int64_t n) {
+  ClipSplit p;
+  p.head = std::min<int64_t>(n, (int64_t)(((16 - ((uintptr_t)g & 15)) & 15) / 4));
+  p.n4 = (n - p.head) / 4;
+  p.tail0 = p.head + p.n4 * 4;
+  p.rest = p.head + (n - p.tail0);      // the scalar elements: at most 3 + 3, thread j of the grid takes the j-th
+  return p;
+}
+// k_grad_sumsq: a FIXED grid of CLIP_BLOCKS x 256 threads; thread t squares items t, t + grid, ... in that order into four double sums
+// (one per lane of the item; a float's square is exact in double), folds them as (x + y) + (z + w), adds its scalar element; the wave
+// folds by halves (lane l += lane l + 32, 16, ... 1), the workgroup adds its four waves in order, and the workgroup that arrives last
+// adds the CLIP_BLOCKS partials in index order.  No atomics on the sum: the same buffer gives the same bits on every run and on every
+// rank.  That last workgroup forms norm and scale in double, rounds each once, and writes the record.
+__global__ __launch_bounds__(256) void k_grad_sumsq(ClipArgs a) {
+  if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  const ClipSplit p = clip_split(a.g, a.n);
+  const float4* g4 = (const float4*)(a.g + p.head);
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)CLIP_BLOCKS * 256;
+  double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
+  for (int64_t i = tid; i < p.n4; i += nth) {
+    const float4 v = g4[i];
+    sx += (double)v.x * (double)v.x; sy += (double)v.y * (double)v.y; sz += (double)v.z * (double)v.z; sw += (double)v.w * (double)v.w;
+  }
+  double s = (sx + sy) + (sz + sw);
+  if (tid < p.rest) {
+    const double v = (double)a.g[tid < p.head ? tid : p.tail0 + (tid - p.head)];
+    s += v * v;
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  __shared__ double ws[CLIP_BLOCKS > 4 ? CLIP_BLOCKS : 4];
+  __shared__ int last;
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double b = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    __hip_atomic_store(a.part + blockIdx.x, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (release: the partial is visible at agent scope before the count; acquire: the last arrival sees every other partial)
+    last = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)CLIP_BLOCKS - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  for (int i = threadIdx.x; i < CLIP_BLOCKS; i += 256) ws[i] = __hip_atomic_load(a.part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double sumsq = 0.0;
+#pragma unroll 8
+  for (int i = 0; i < CLIP_BLOCKS; ++i) sumsq += ws[i];
+  const double norm = sqrt(sumsq);
+  const float norm_f = (float)norm;
+  const bool clipped = norm_f > a.clip;             // strictly, in fp32 as BVLC compares (norm == clip and norm == 0 scale nothing)
+  ClipRec& r = *a.rec;
+  r.sumsq = sumsq; r.norm = norm_f;
+  r.scale = clipped ? (float)((double)a.clip / norm) : 1.f;     // (clipped: norm > clip >= 0, no division by zero)
+  r.clipped = clipped ? 1 : 0;
+  r.updates += 1; r.clipped_updates += clipped ? 1 : 0;
+  __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the next launch
+}
+// k_grad_scale: g[i] = g[i] * scale -- one fp32 multiply per element -- where the record says the step is clipped
+__global__ __launch_bounds__(256) void k_grad_scale(ClipArgs a) {
+  if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  if (!a.rec->clipped) return;
+  const float sc = a.rec->scale;
+  const ClipSplit p = clip_split(a.g, a.n);
+  float4* g4 = (float4*)(a.g + p.head);
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+  for (int64_t i = tid; i < p.n4; i += nth) {
+    float4 v = g4[i];
+    v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc;
+    g4[i] = v;
+  }
+  if (tid < p.rest) a.g[tid < p.head ? tid : p.tail0 + (tid - p.head)] *= sc;
+}
+void launch_grad_sumsq(const ClipArgs& a, hipStream_t s) { VV_LAUNCH(k_grad_sumsq, dim3(CLIP_BLOCKS), dim3(256), 0, s, a); }
+void launch_grad_scale(const ClipArgs& a, hipStream_t s) { VV_LAUNCH(k_grad_scale, dim3(SGD_BLOCKS), dim3(256), 0, s, a); }
+
 __global__ void k_scale_update(Scales* sc, const float* wmax_blocks, int nblocks, int prec) { scale_update_body(sc, wmax_blocks, nblocks, prec); }
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s) {
   hipLaunchKernelGGL(k_scale_update, dim3(1), dim3(256), 0, s, sc, wmax_blocks, n_blocks, prec);

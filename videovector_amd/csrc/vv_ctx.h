@@ -57,6 +57,12 @@ struct vv_ctx {
   bool adam_pending = false;                // the vv_apply_update in progress is an Adam update: finish_update commits adam_t (a failed call leaves t alone)
   float upd_momentum2 = 0.f, upd_rms_decay = 0.f;   // ... as they stood when vv_update_hint announced upd_cfg
   bool hist2_partial = false;               // as params_partial, for hW2 / hb2 (a sharded Adam update ran since the last gather)
+  // vv_clip_gradients_set (BVLC SolverParameter.clip_gradients): < 0 off; sticky.  While >= 0 vv_apply_update brings the gradient into the
+  // buffer, runs k_grad_sumsq + k_grad_scale and then the plain k_sgd; the fused forms and the overlapped / sharded schedules are not used.
+  float clip = -1.f;
+  float upd_clip = -1.f;                    // ... as it stood when vv_update_hint announced upd_cfg
+  bool upd_announced = false;               // the last backward pass was announced by vv_update_hint and its vv_apply_update has not run yet
+  vv::ClipRec* clip_rec = nullptr;          // device: the record, then CLIP_BLOCKS partial sums and the arrival counter (one allocation, made by vv_clip_gradients_set)
   uint16_t* Wh = nullptr; vv::Scales* scales = nullptr; float* wmax_blocks = nullptr;
   int n_cu = 256;                           // compute units of the device
   bool scale_pending = false;               // k_sgd ran, its scale update has not (it rides in the next k_reduce)

@@ -444,6 +444,23 @@ struct SgdArgs2 : SgdArgs { float* vW = nullptr; float* vb = nullptr; };
 struct FusedUpdArgs2 : FusedUpdArgs { float* vW = nullptr; float* vb = nullptr; };
 constexpr int WMAX_SLOTS = 2048;      // slots of one per-block-maxima buffer (k_sgd writes SGD_BLOCKS of them, k_reduce_sgd RED_DW_BLOCKS)
 
+// Gradient clipping by the global L2 norm (BVLC Caffe's SGDSolver::ClipGradients; vv_clip_gradients_set): k_grad_sumsq leaves this
+// record, k_grad_scale and vv_clip_stats read it.  sumsq: the sum of g^2 over the flat buffer [dW | db] in double; norm = sqrt(sumsq)
+// and scale = clip / norm are formed in double and rounded once each; clipped = norm (the fp32 value, as BVLC compares) > clip, else
+// scale is 1 and k_grad_scale writes nothing.  updates / clipped_updates: counted by the kernel itself, so nothing synchronises per step.
+struct ClipRec {
+  double sumsq; float norm; float scale; int32_t clipped; int32_t pad_;
+  int64_t updates, clipped_updates;
+};
+constexpr int CLIP_BLOCKS = 256;      // k_grad_sumsq's fixed grid = the per-block partial sums its last stage adds in index order
+struct ClipArgs {
+  float* g; int64_t n;                // the flat gradient buffer
+  float clip;
+  ClipRec* rec; double* part;         // [CLIP_BLOCKS]
+  uint32_t* arrived;                  // arrival counter of k_grad_sumsq's workgroups (0 between launches)
+  const uint32_t* skip_if = nullptr;  // as SgdArgs::skip_if: a failed exchange in front, the launch changes nothing
+};
+
 // Which kernels a context runs (vv_ctx::ko).  The launchers read the options of the context whose entry point is running on this
 // thread (g_ko, set by every ABI entry point next to hipSetDevice); nothing here is process-global, so two contexts of one process
 // do not inherit each other's choices.  Product options are set by vv_set_option (their environment variables are read ONCE per
@@ -516,6 +533,8 @@ void launch_gather_rows_u16(const uint16_t* src, const int32_t* pos, int R, int 
 void launch_reduce(const ReduceArgs& a, hipStream_t s);
 // (vW / vb: the second history, rule.solver_type == 5 only -- the two-history instantiations)
 void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW = nullptr, float* vb = nullptr);
+void launch_grad_sumsq(const ClipArgs& a, hipStream_t s);            // -> ClipArgs::rec (no host synchronisation)
+void launch_grad_scale(const ClipArgs& a, hipStream_t s);            // g *= rec->scale where rec->clipped, else every workgroup returns at once
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s);
 void launch_delay(int us, hipStream_t s);                             // test hook: occupies s for `us` microseconds       // flag <- seq (agent scope), behind everything queued on s
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s);

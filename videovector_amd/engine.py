@@ -54,6 +54,11 @@ class _H16Report(C.Structure):
                 ("first_flagged_step", C.c_int64), ("fallback", C.c_int32), ("rows_f16", C.c_int32)]
 
 
+class _ClipReport(C.Structure):
+    _fields_ = [("norm", C.c_float), ("scale", C.c_float), ("clipped", C.c_int32), ("reserved_", C.c_int32),
+                ("updates", C.c_int64), ("clipped_updates", C.c_int64)]
+
+
 class _ClassStats(C.Structure):
     _fields_ = [("mean_ap", C.c_float), ("hit_at_1", C.c_float), ("hit_at_5", C.c_float), ("n_scored", C.c_int32)]
 
@@ -137,6 +142,8 @@ def load_library():
         "vv_solver_ext_set": [vp, f32, f32], "vv_solver_ext_get": [vp, C.POINTER(f32), C.POINTER(f32)],
         "vv_solver_iter_set": [vp, i64], "vv_solver_iter_get": [vp, C.POINTER(i64)],
         "vv_history2_set": [vp, vp, vp], "vv_history2_get": [vp, vp, vp],
+        "vv_clip_gradients_set": [vp, f32], "vv_clip_gradients_get": [vp, C.POINTER(f32)],
+        "vv_clip_stats": [vp, C.POINTER(_ClipReport)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -282,10 +289,11 @@ SOLVER_TYPES = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADAM": 5} 
 class StepConfig:
     """vv_step_cfg with the shipped project defaults (vv_step_cfg_default).  momentum2 (Adam's beta2) and rms_decay have no field in the
     struct: given here, the Engine forwards them through vv_solver_ext_set in front of every call that takes this configuration (the one
-    not given keeps the context's value)."""
+    not given keeps the context's value).  clip_gradients (BVLC SolverParameter.clip_gradients; vv_clip_gradients_set) is forwarded the
+    same way: None keeps the context's threshold, a negative value disables clipping."""
 
     def __init__(self, B, C_, Nn, **kw):
-        self.momentum2 = self.rms_decay = None
+        self.momentum2 = self.rms_decay = self.clip_gradients = None
         self.c = _StepCfg()
         load_library().vv_step_cfg_default(C.byref(self.c))
         self.c.B, self.c.C, self.c.Nn = B, C_, Nn
@@ -312,7 +320,7 @@ class StepConfig:
             self.c.reg = {"L1": 1, "L2": 2}.get(v, v)
         elif k == "solver_type":
             self.c.solver_type = SOLVER_TYPES.get(v, v)
-        elif k in ("momentum2", "rms_decay"):
+        elif k in ("momentum2", "rms_decay", "clip_gradients"):
             setattr(self, k, None if v is None else float(v))
         elif k == "norm":
             self.c.norm = {"L1": 1, "L2": 2}.get(v, v)
@@ -334,6 +342,7 @@ class Engine:
         self.F = self.D = 0
         self.n_rows = 0
         self._ext_sent = None                      # the (momentum2, rms_decay) of a StepConfig last forwarded by _ext
+        self._clip_sent = None                     # ... and its clip_gradients
 
     def _chk(self, rc):
         if rc != 0:
@@ -452,8 +461,29 @@ class Engine:
         self._chk(self.L.vv_history2_get(self.h, _ptr(vW), _ptr(vb)))
         return vW, vb
 
+    # ---- gradient clipping by the global L2 norm (vv_clip_gradients_*, vv_clip_stats)
+    def clip_gradients_set(self, clip):
+        """clip < 0 disables, clip >= 0 is the threshold of the gradient's L2 norm (BVLC SGDSolver::ClipGradients)."""
+        self._clip_sent = None
+        self._chk(self.L.vv_clip_gradients_set(self.h, float(clip)))
+
+    def clip_gradients_get(self):
+        v = C.c_float()
+        self._chk(self.L.vv_clip_gradients_get(self.h, C.byref(v)))
+        return v.value
+
+    def clip_stats(self):
+        """norm / scale / clipped of the last completed clipping update (synchronises) and the updates / clipped_updates totals."""
+        r = _ClipReport()
+        self._chk(self.L.vv_clip_stats(self.h, C.byref(r)))
+        return {"norm": np.float32(r.norm), "scale": np.float32(r.scale), "clipped": int(r.clipped), "updates": int(r.updates),
+                "clipped_updates": int(r.clipped_updates)}
+
     def _ext(self, cfg):
-        """StepConfig's momentum2 / rms_decay -> the context, in front of a call that takes cfg."""
+        """StepConfig's momentum2 / rms_decay / clip_gradients -> the context, in front of a call that takes cfg."""
+        if cfg.clip_gradients is not None and cfg.clip_gradients != self._clip_sent:
+            self.clip_gradients_set(cfg.clip_gradients)
+            self._clip_sent = cfg.clip_gradients
         if cfg.momentum2 is None and cfg.rms_decay is None:
             return
         want = (cfg.momentum2, cfg.rms_decay)
