@@ -1030,7 +1030,9 @@ __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(Score
 #pragma unroll
     for (int w = 1; w < NW; ++w) m = fmaxf(m, red[w]);
     float sc = 1.f;
-    if (m > 0.f && m < 3.0e38f) { int e; (void)frexpf(m, &e); sc = ldexpf(1.f, 14 - e); }      // m sc in [2^13, 2^14)
+    // m sc in [2^13, 2^14); the exponent stops at 126 so that sc and 1 / sc stay normal floats (m below about 2^-113: 14 - e passed 127, sc was inf and
+    // 1 / sc zero -- reachable with bf16 operands, whose gradient scale is 1, and a tiny loss_weight): below that dA_b keeps fewer bits
+    if (m > 0.f && m < 3.0e38f) { int e; (void)frexpf(m, &e); sc = ldexpf(1.f, min(14 - e, 126)); }
 #pragma unroll
     for (int v = 0; v < CV; ++v) Vh[D + tid + v * THREADS] = (_Float16)(da[v] * sc);
     const float isc = 1.f / sc;                     // (a power of two: alpha_j / sc times the stored row is alpha_j dA_b)

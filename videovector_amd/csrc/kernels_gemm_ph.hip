@@ -943,7 +943,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void k_wgrad_gemm_ph(WgradArgs a) {
 #pragma unroll
     for (int w8 = 1; w8 < 8; ++w8) mx = fmaxf(mx, red8[w8]);
     float sc = 1.f;
-    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); sc = ldexpf(1.f, 15 - e); }      // mx sc in [2^14, 2^15); inf / nan: passed through at scale 1
+    // mx sc in [2^14, 2^15); inf / nan: passed through at scale 1.  The exponent stops at 126: sc and 1 / sc stay normal floats (mx below about 2^-112 made
+    // sc inf and 1 / sc zero: inf partial products, 0 x inf in the reducer)
+    if (mx > 0.f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); sc = ldexpf(1.f, min(15 - e, 126)); }
     if (tid == 0) a.slab_sc[(int64_t)sp * (tilesM * tilesN) + tm * tilesN + tn] = 1.f / sc;        // (a power of two: exact)
     uint16_t* slab = (uint16_t*)a.slabs + (int64_t)sp * slab_pitch(a.Dp, a.Fp);
 #pragma unroll
