@@ -102,7 +102,10 @@ static const std::vector<MsgDef>& Msgs() {
         OPTD(38, "rms_decay", T_FLOAT, "0.99"), OPTD(39, "momentum2", T_FLOAT, "0.999"),
         // BVLC Caffe's SolverParameter.clip_gradients is field 35, which the fork gave to snapshot_vis_truncate_len (36 is taken too):
         // here it is 135, outside both projects' ranges.  Text solver files read by name, so BVLC's work as they are.
-        OPTD(135, "clip_gradients", T_FLOAT, "-1")}},
+        OPTD(135, "clip_gradients", T_FLOAT, "-1"),
+        // BVLC Caffe's SolverParameter.iter_size is field 36, which the fork gave to snapshot_vis_dir: here it is 136, by the same rule
+        // (Solver::Init holds it to CHECK_GE(iter_size, 1))
+        OPTD(136, "iter_size", T_INT32, "1")}},
       {"SolverState",                                                               // :176-180
        {OPT(1, "iter", T_INT32), OPT(2, "learned_net", T_STRING), RMSG(3, "history", "BlobProto")}},
       {"LayerParameter",                                                            // :215-389

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <sstream>
 #include <string>
 
@@ -115,6 +116,20 @@ void Solver<Dtype>::Init(const SolverParameter& param) {
     }
     VV_CHECK(vv_clip_gradients_set(Caffe::ctx(), clip_gradients_));
   }
+  // BVLC SolverParameter.iter_size (Solver::Step, SGDSolver::Normalize; vv_grads_bank): iter_size forward/backward passes per update.  The
+  // bank is exchanged whole, once per update: a data-parallel job that accumulates runs the sync exchange schedule
+  iter_size_ = (int)param_.get_int("iter_size");
+  CHECK_GE(iter_size_, 1) << "iter_size must be at least 1";
+  if (iter_size_ > 1) {
+    CHECK(!net_->sequential()) << "iter_size: " << iter_size_ << " needs the fused training step (this net runs layer by layer)";
+    if (Caffe::world() > 1 && !(clip_gradients_ >= 0)) {     // (as Net::Init chose it; clip_gradients has selected the sync schedule above)
+      const char* sch = getenv("VV_COMM_SCHEDULE");
+      const char* ov = getenv("VV_COMM_OVERLAP");
+      const bool sync = sch ? !strcmp(sch, "sync") : (ov && atoi(ov) == 0);
+      CHECK(sync) << "iter_size: " << iter_size_ << " accumulates gradients on the sync exchange schedule only (one exchange per update): set VV_COMM_SCHEDULE=sync";
+    }
+    LOG(INFO) << "iter_size: " << iter_size_ << " -- " << iter_size_ << " forward/backward passes are banked per update; iterations, the learning-rate policy and snapshots count updates";
+  }
   LOG(INFO) << "Solver scaffolding done.";
 }
 
@@ -170,8 +185,22 @@ void Solver<Dtype>::Step(bool display) {
   // (snapshot_diff, caffe.proto SolverParameter field 16; Net::ToProto, net.cpp:784-800, then reads them back): such a job keeps its
   // gradient, i.e. the update stays its own launch (with the hint the shipped 4096 x 4096 shape applies the rule in the
   // weight-gradient GEMM's epilogue and the gradient never exists outside its registers)
-  if (!param_.get_bool("snapshot_diff")) net_->HintUpdate();
-  const Dtype loss = net_->ForwardBackward(no_bottom);
+  Dtype loss;
+  if (iter_size_ == 1) {
+    if (!param_.get_bool("snapshot_diff")) net_->HintUpdate();
+    loss = net_->ForwardBackward(no_bottom);
+  } else {
+    // BVLC Solver::Step: ClearParamDiffs, iter_size x ForwardBackward adding into the diffs, loss /= iter_size.  No hint: every pass's
+    // gradient is kept and banked.  The mean as the library forms it (vv_accum_stats): fp32 sum in pass order times 1.0f / iter_size
+    VV_CHECK(vv_grads_bank_reset(Caffe::ctx()));
+    Dtype sum = 0;
+    for (int k = 0; k < iter_size_; ++k) {
+      const Dtype l = net_->ForwardBackward(no_bottom);
+      sum = k ? sum + l : l;
+      VV_CHECK(vv_grads_bank(Caffe::ctx()));
+    }
+    loss = sum * (1.0f / (float)iter_size_);           // (without display the passes return the last value read: not shown)
+  }
   if (!h16_warned_) {                               // (a flag of the context: nothing is read from the device)
     double fb = 0, sat = 0, faint = 0;
     VV_CHECK(vv_get_option(Caffe::ctx(), "h16_fallback", &fb));

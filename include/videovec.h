@@ -107,7 +107,8 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *                                    vv_gallery_from_table); 0 before the first launch
  *   "last_wgrad_splits"              splits of K (S) of the weight-gradient GEMM (a step or vv_op_inner_product_bwd); 0 before the first launch
  *   "last_update_form"               what the last vv_apply_update ran for the parameter matrix: 1 k_sgd with 16-byte accesses (the chunked and sharded updates too), 2 k_sgd scalar (F % 4 != 0), 3 k_reduce_sgd, 4 k_reduce_sgd over f16 slabs, 5 the weight-gradient GEMM's epilogue; 0 before the first update.
- *                                    While gradient clipping is active (vv_clip_gradients_set >= 0) every update is 1 or 2: the fused forms 3 - 5 are not used
+ *                                    While gradient clipping is active (vv_clip_gradients_set >= 0) every update is 1 or 2: the fused forms 3 - 5 are not used;
+ *                                    so is every update of banked gradients (vv_grads_bank)
  *   "last_score_form"                what the last forward pass launched for scores and loss: 1 k_score_fwd (register-resident), 2 k_score_stream at
  *                                    D = 512, 3 k_score_stream at D = 1024, 4 the per-instance kernels (dense or row-writing execution); 0 before the first step
  *   "last_h16"                       1: the last forward pass stored ip2 as f16 rows, 0: fp32 rows (or no step yet)
@@ -206,6 +207,40 @@ typedef struct { float norm, scale;                 /* of the LAST completed cli
                  int64_t updates;                   /* updates that computed a norm (clipping active) since vv_create */
                  int64_t clipped_updates; } vv_clip_report;     /* ... of which scaled their gradient */
 int vv_clip_stats(vv_ctx* ctx, vv_clip_report* out);
+
+/* ---- gradient accumulation: BVLC Caffe's SolverParameter.iter_size, Solver::Step (solver.cpp) and SGDSolver::Normalize (sgd_solver.cpp);
+ * the reference tree has no iter_size, so the semantics are BVLC's.  BVLC's Step clears the diffs (Net::ClearParamDiffs), runs iter_size x
+ * ForwardBackward with the layers adding into the diffs, divides the loss by iter_size and calls ApplyUpdate: ClipGradients on the SUM,
+ * Normalize (diff *= Dtype(1) / iter_size), Regularize, the rule.  Here the sum is kept in a BANK: a second flat fp32 buffer
+ * [dW (D F) | db (D)], allocated zero-filled by the first vv_grads_bank (the one allocation a step may make, never on the step path
+ * afterwards).
+ * vv_grads_bank: the layers' "add into the diff" (BVLC Solver::Step's accumulating Net::ForwardBackward).  Adds the gradient of the last
+ * vv_forward_backward* -- the values vv_grads_get would return at that moment: ip_regularization's factor included, this rank's own
+ * gradient, read from a bound buffer (vv_grads_bind) where one is bound -- into the bank.  The first bank of a cycle STORES (the bank is
+ * not read: -0 stays -0), every later one computes bank = bank + g, one fp32 add per element, in banking order.  It also folds the last
+ * forward pass's loss and violations into two fp32 sums on the device (the first bank stores, later ones add).  One kernel (k_grad_bank)
+ * on the step's stream, no atomics, no host synchronisation; no parameter changes.
+ * vv_grads_bank_reset: Net::ClearParamDiffs -- discards the bank and the two sums; vv_params_set does the same.
+ * vv_apply_update with m >= 1 gradients banked (BVLC SGDSolver::ApplyUpdate), in this order: the bank is written into the flat gradient
+ * buffer; with a communicator its all-reduce runs (ONE exchange per cycle); where clipping is active k_grad_sumsq / k_grad_scale run on
+ * it (the norm is the SUM's); every element is multiplied by inv = 1.0f / (float)m, one fp32 multiply (SGDSolver::Normalize; without a
+ * communicator and without clipping the write and the multiply are one pass); the regulariser and the rule run in the plain k_sgd:
+ * "last_update_form" 1 or 2.  Afterwards vv_grads_get returns the normalised (and clipped) buffer, the bank is empty and a new cycle
+ * starts; Adam's t has advanced by one.  With nothing banked vv_apply_update is in every respect what it was.
+ * VV_ERR_STATE: vv_grads_bank before any backward pass, twice for one backward pass, after a step announced by vv_update_hint (its
+ * gradient is not kept), after vv_allreduce_grads (the bank is exchanged once per cycle), or while schedule 1 or 2 is selected;
+ * vv_comm_schedule(1 or 2) / vv_comm_overlap(1) while the bank is non-empty; vv_apply_update or vv_step while the bank is non-empty
+ * and the last backward pass's gradient has not been banked.  vv_update_hint announces nothing while the bank is non-empty.  A second
+ * vv_forward_backward* without banking simply replaces the gradient. */
+int vv_grads_bank(vv_ctx* ctx);
+int vv_grads_bank_reset(vv_ctx* ctx);
+/* What BVLC's Solver::Step would display for an accumulated iteration (loss /= iter_size). */
+typedef struct { int32_t banked;                    /* gradients in the bank now */
+                 int32_t last_count;                /* the m of the LAST completed accumulated update (synchronises, like vv_clip_stats); 0 before the first */
+                 float last_mean_loss;              /* that cycle's sums x inv = 1.0f / (float)m, one fp32 multiply each */
+                 float last_mean_violations;
+                 int64_t updates; } vv_accum_report;    /* accumulated updates since vv_create */
+int vv_accum_stats(vv_ctx* ctx, vv_accum_report* out);
 
 /* ---- one training iteration */
 typedef struct {

@@ -1,0 +1,79 @@
+"""Non-GPU checks of the gradient-accumulation plumbing: include/videovec.h declares the three entry points and cites the BVLC functions
+they stand for, the built library exports them, the ctypes binding declares them; the facade's SolverParameter parses iter_size from
+text (by name, as a BVLC solver file writes it), round-trips it on the wire with its documented number (136: BVLC's 36 is
+snapshot_vis_dir in this fork, as 35 was taken for clip_gradients), defaults to 1 and is held to CHECK_GE(iter_size, 1) by the solver;
+the prototxt writer emits it only when asked."""
+import os
+import re
+import subprocess
+
+import ctypes as C
+
+import videovector_amd as vv
+from tests.test_facade_proto import tool  # noqa: F401  (fixture)
+from tests.test_solver_ext_host import fields
+from videovector_amd import engine
+from videovector_amd.prototxt import solver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = {"vv_grads_bank": 1, "vv_grads_bank_reset": 1, "vv_accum_stats": 2}
+FIELD = 136
+
+
+def test_header_binding_and_exports_agree(tool):  # noqa: F811  (the fixture builds the library)
+    hdr = open(os.path.join(ROOT, "include", "videovec.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    out = subprocess.run(["nm", "-D", "--defined-only", vv.lib_path()], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
+    L = vv.load_library()
+    for name, nargs in NEW.items():
+        m = re.search(r"int\s+%s\s*\(([^)]*)\)\s*;" % name, code)
+        assert m, name + " is not declared"
+        assert len(m.group(1).split(",")) == nargs, name
+        assert name in exported, name + " is not exported"
+        assert len(getattr(L, name).argtypes) == nargs and getattr(L, name).restype is C.c_int
+    for phrase in ("SolverParameter.iter_size", "Solver::Step", "SGDSolver::Normalize", "Net::ClearParamDiffs", "SGDSolver::ApplyUpdate", "BVLC",
+                   "the reference tree has no iter_size", "1.0f / (float)m", "VV_ERR_STATE", "vv_update_hint announces nothing"):
+        assert phrase in hdr, phrase
+    m = re.search(r"typedef struct \{([^{}]*)\}\s*vv_accum_report;", code)
+    want = ["banked", "last_count", "last_mean_loss", "last_mean_violations", "updates"]
+    assert m and re.findall(r"\b(%s)\b" % "|".join(want), m.group(1)) == want
+    assert C.sizeof(engine._AccumReport) == 24 and [f[0] for f in engine._AccumReport._fields_] == want
+    for meth in ("grads_bank", "grads_bank_reset", "accum_stats"):
+        assert hasattr(vv.Engine, meth), meth
+    src = open(os.path.join(ROOT, "videovector_amd", "csrc", "api.hip")).read()
+    for name in NEW:                                       # every new entry point cites the BVLC function it stands for
+        at = src.index("int %s(" % name)
+        assert "BVLC" in src[src.rfind("\n//", 0, at):at], name
+
+
+def test_solver_parameter_iter_size(tool, tmp_path):  # noqa: F811
+    txt = tmp_path / "s.prototxt"
+    txt.write_text(solver("net.prototxt", iter_size=4))
+    assert "iter_size: 4" in txt.read_text()
+    subprocess.run([tool, "text2bin", "SolverParameter", str(txt), str(tmp_path / "s.bin")], check=True)
+    f = fields((tmp_path / "s.bin").read_bytes())
+    assert (FIELD, 0, 4) in f, f
+    assert not [x for x in f if x[0] == 36], "36 is snapshot_vis_dir in this fork"
+    subprocess.run([tool, "bin2text", "SolverParameter", str(tmp_path / "s.bin"), str(tmp_path / "s.txt")], check=True)
+    assert re.search(r"iter_size:\s*4\b", (tmp_path / "s.txt").read_text())
+    subprocess.run([tool, "text2bin", "SolverParameter", str(tmp_path / "s.txt"), str(tmp_path / "s2.bin")], check=True)
+    assert (tmp_path / "s2.bin").read_bytes() == (tmp_path / "s.bin").read_bytes()
+    # a BVLC solver file as it is: the field by name beside the fork's own field 36
+    both = tmp_path / "both.prototxt"
+    both.write_text(solver("net.prototxt") + 'iter_size: 2\nsnapshot_vis_dir: "vis"\n')
+    subprocess.run([tool, "text2bin", "SolverParameter", str(both), str(tmp_path / "both.bin")], check=True)
+    f = fields((tmp_path / "both.bin").read_bytes())
+    assert (FIELD, 0, 2) in f and [x for x in f if x[0] == 36 and x[1] == 2]
+    # absent: not written, and the default is 1
+    plain = solver("net.prototxt")
+    assert "iter_size" not in plain, "the field is written only when asked"
+    (tmp_path / "p.prototxt").write_text(plain)
+    subprocess.run([tool, "text2bin", "SolverParameter", str(tmp_path / "p.prototxt"), str(tmp_path / "p.bin")], check=True)
+    assert not [x for x in fields((tmp_path / "p.bin").read_bytes()) if x[0] == FIELD]
+    src = open(os.path.join(ROOT, "caffe_facade", "src", "proto_lite.cpp")).read()
+    assert re.search(r'OPTD\(%d,\s*"iter_size",\s*T_INT32,\s*"1"\)' % FIELD, src), "the default is 1"
+    sol = open(os.path.join(ROOT, "caffe_facade", "src", "solver.cpp")).read()
+    assert re.search(r"CHECK_GE\(iter_size_,\s*1\)", sol)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert "iter_size" in doc and str(FIELD) in doc

@@ -268,7 +268,7 @@ int vv_destroy(vv_ctx* c) {
   vv_ops_release(c);
   free_batch(c);
   dfree(c->table); dfree(c->patch_desc); dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh);
-  dfree(c->clip_rec);
+  dfree(c->clip_rec); dfree(c->bank_rec);
   dfree(c->scales); dfree(c->wmax_blocks); dfree(c->grads_own); dfree(c->mask); dfree(c->loss2);
   dfree(c->dd_key); dfree(c->dd_info_all); dfree(c->gg); dfree(c->gg_bound); dfree(c->w_gate);
   if (c->gate_err) (void)hipHostFree(c->gate_err);
@@ -558,6 +558,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   if (D != c->D && c->comm) return fail(VV_ERR_STATE, "vv_params_set: the communicator was sized for D = %d (vv_comm_destroy first)", c->D);
   if (D != c->D) {
     dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh); dfree(c->grads_own);
+    dfree(c->bank_rec); c->bank_rec = nullptr; c->bank = nullptr;      // (the bank has the gradient buffer's size: the next vv_grads_bank allocates it anew)
     c->W = c->b = c->hW = c->hb = c->hW2 = c->hb2 = nullptr; c->Wh = nullptr; c->grads = c->grads_own = nullptr;
     c->D = D; c->Dp = (int)round_up(D, D_ALIGN);
 #ifdef VV_LAB
@@ -595,6 +596,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   // new parameters start a new run of the two-history solver: its second history and its update count go back to zero
   if (c->hW2) { HIPCHK(hipMemset(c->hW2, 0, nW * 4)); HIPCHK(hipMemset(c->hb2, 0, D * 4)); }
   c->adam_t = 0; c->hist2_partial = false;
+  c->bank_count = 0; c->grad_banked = false; c->fb_hinted = false;      // banked gradients belonged to the old parameters (vv_grads_bank_reset)
   // scale for the half copy from max|W|, then convert (a scale update still pending from an earlier SGD step is void)
   c->scale_pending = false;
   // (a gradient nobody asked for goes with the parameters it belonged to, when the call has succeeded: grad_discard below)
@@ -752,6 +754,90 @@ static ClipArgs clip_args(vv_ctx* c) {
   a.rec = c->clip_rec; a.part = (double*)(c->clip_rec + 1); a.arrived = (uint32_t*)(a.part + CLIP_BLOCKS);
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
   return a;
+}
+
+// ---- gradient accumulation (BVLC Caffe's SolverParameter.iter_size: Solver::Step and SGDSolver::Normalize; the reference tree has none)
+static const char* const kBankSchedule = "gradients are banked on the sync exchange schedule only (the bank is exchanged whole, once per cycle, before the first "
+                                         "chunk or shard is updated): vv_grads_bank_reset or vv_comm_schedule(0)";
+static inline size_t bank_floats(const vv_ctx* c) { return (size_t)c->D * c->F + c->D; }
+// BVLC Solver::Step's accumulating Net::ForwardBackward: the layers add into the parameter diffs
+int vv_grads_bank(vv_ctx* c) {
+  if (!c) return fail(VV_ERR_ARG, "vv_grads_bank: ctx is NULL");
+  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_grads_bank: no backward pass yet");
+  { const int rcg = upd_pending_guard(c, "vv_grads_bank"); if (rcg) return rcg; }
+  if (c->fb_hinted) return fail(VV_ERR_STATE, "vv_grads_bank: the last backward pass was announced by vv_update_hint: its gradient is not kept (run the pass without the hint to bank it)");
+  if (c->grad_banked) return fail(VV_ERR_STATE, "vv_grads_bank: the gradient of the last backward pass has been banked already (one bank per vv_forward_backward)");
+  if (c->comm_overlap || c->comm_sharded) return fail(VV_ERR_STATE, "vv_grads_bank: %s", kBankSchedule);
+  if (c->grad.at == GradAt::Buffer && c->grad.buf.layout != GradLayout::Flat) return fail(VV_ERR_STATE, "vv_grads_bank: this step's gradient was laid out for another schedule -- %s", kBankSchedule);
+  if (c->comm && c->grad.at == GradAt::Buffer && !grad_sum_due(c->grad))
+    return fail(VV_ERR_STATE, "vv_grads_bank: this gradient has been summed over the ranks already (vv_allreduce_grads); the bank is exchanged once per cycle, by vv_apply_update");
+  VV_ENTER(c);
+  int rc = comm_join(c);                     // (an overlapped update of an earlier schedule may still be writing)
+  if (rc) return rc;
+  if (!c->bank_rec) {                        // the one allocation: here, never on the step path afterwards
+    static_assert(sizeof(AccumRec) % 16 == 0, "the bank starts on a 16-byte boundary behind its record");
+    const size_t bytes = sizeof(AccumRec) + (bank_floats(c) + 4) * sizeof(float);
+    HIPCHK(hipMalloc((void**)&c->bank_rec, bytes));
+    HIPCHK(hipMemset(c->bank_rec, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());          // (the fill is complete before a kernel of any stream reads it)
+  }
+  if ((rc = reduce_now(c))) return rc;       // the gradient into the buffer and the loss into its scalars, as any reader brings them
+  const bool first = c->bank_count == 0;
+  if (first) c->bank = (float*)(c->bank_rec + 1) + (((uintptr_t)c->grads & 15) / 4);     // one 16-byte grid in both buffers
+  BankArgs a;
+  a.src = c->grads; a.dst = c->bank; a.n = (int64_t)bank_floats(c);
+  a.fold = 1; a.loss2 = c->loss2; a.rec = c->bank_rec;
+  PROFILED(c, "grad_bank", launch_grad_bank(first ? BankOp::Store : BankOp::Add, a, c->stream));
+  HIPCHK(hipGetLastError());
+  c->bank_count++;
+  c->grad_banked = true;
+  return VV_OK;
+}
+// BVLC Net::ClearParamDiffs (Solver::Step's first statement)
+int vv_grads_bank_reset(vv_ctx* c) {
+  if (!c) return fail(VV_ERR_ARG, "vv_grads_bank_reset: ctx is NULL");
+  c->bank_count = 0;                         // (the next bank stores: neither the bank nor the two sums are read again)
+  return VV_OK;
+}
+// BVLC Solver::Step's "loss /= iter_size"
+int vv_accum_stats(vv_ctx* c, vv_accum_report* out) {
+  if (!c || !out) return fail(VV_ERR_ARG, "vv_accum_stats: ctx / out is NULL");
+  out->banked = c->bank_count; out->last_count = 0; out->last_mean_loss = out->last_mean_violations = 0.f; out->updates = 0;
+  if (!c->bank_rec) return VV_OK;              // nothing was ever banked
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  AccumRec r;
+  HIPCHK(hipMemcpy(&r, c->bank_rec, sizeof(r), hipMemcpyDeviceToHost));
+  out->last_count = r.last_count; out->last_mean_loss = r.last_mean_loss; out->last_mean_violations = r.last_mean_viol; out->updates = r.updates;
+  return VV_OK;
+}
+// BVLC SGDSolver::ApplyUpdate's first half for m banked gradients: the sum into the flat gradient buffer, its exchange, ClipGradients on
+// the sum, Normalize.  Steps are one pass where the bits cannot differ: without a communicator and without clipping, the write and the
+// multiply.  The regulariser and the rule follow in the plain k_sgd.
+static int bank_to_buffer(vv_ctx* c, bool clip_on) {
+  int rc;
+  const int m = c->bank_count;
+  BankArgs a;
+  a.n = (int64_t)bank_floats(c); a.inv = 1.0f / (float)m; a.m = m; a.rec = c->bank_rec;
+  a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
+  const bool two_pass = c->comm || clip_on;
+  if (two_pass) {
+    a.src = c->bank; a.dst = c->grads;
+    PROFILED(c, "grad_bank", launch_grad_bank(BankOp::Store, a, c->stream));
+    grad_to_buffer(c->grad, GradLayout::Flat, !c->comm, false);     // the buffer holds this rank's sum; with a communicator the sum over the ranks is due
+    if ((rc = vv_allreduce_grads(c))) return rc;                     // ONE exchange per cycle
+    if (clip_on) {                                                   // (every rank reads identical buffers)
+      const ClipArgs ca = clip_args(c);
+      PROFILED(c, "grad_sumsq", launch_grad_sumsq(ca, c->stream));
+      PROFILED(c, "grad_scale", launch_grad_scale(ca, c->stream));
+    }
+  }
+  a.src = two_pass ? c->grads : c->bank; a.dst = c->grads; a.fold = 2;
+  PROFILED(c, "grad_bank", launch_grad_bank(BankOp::Scale, a, c->stream));
+  grad_to_buffer(c->grad, GradLayout::Flat, true, false);
+  HIPCHK(hipGetLastError());
+  c->bank_count = 0;                         // a new cycle; the buffer holds the normalised sum, not a backward pass's gradient: grad_banked stays
+  return VV_OK;
 }
 
 // ------------------------------------------------------------------------------- step ---------
@@ -1121,6 +1207,7 @@ struct HintScope {
 int vv_update_hint(vv_ctx* c, const vv_step_cfg* cfg) {
   int rc = check_cfg(c, cfg);
   if (rc) return rc;
+  if (c->bank_count > 0) return VV_OK;       // a cycle of banked gradients is open: the next pass's gradient is kept, nothing is announced
   c->upd_hint = true;
   c->upd_cfg = *cfg;
   c->upd_momentum2 = c->momentum2; c->upd_rms_decay = c->rms_decay; c->upd_clip = c->clip;
@@ -1158,6 +1245,7 @@ static int wgrad_to_destination(vv_ctx* c, WgradArgs& wa, ReduceArgs& ra, bool u
   // (Adam keeps two histories: the epilogue declines it, the step takes k_reduce_sgd -- the hint changes nothing, as for several splits.
   // Gradient clipping announced with the hint: the update needs the whole gradient's norm first -- the hint changes nothing either.)
   c->upd_announced = upd_hint;
+  c->fb_hinted = upd_hint; c->grad_banked = false;       // (vv_grads_bank: a new gradient, bankable once unless it was announced)
   const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
                       (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM && !(c->upd_clip >= 0.f);
   if (fuse_w) {
@@ -1731,6 +1819,10 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   if (rc) return rc;
   if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_apply_update: no gradients (call vv_forward_backward)");
   if ((rc = upd_pending_guard(c, "vv_apply_update"))) return rc;     // (GradAt::Lost: a second update on a gradient that was never stored)
+  // Banked gradients (vv_grads_bank, m >= 1): the update consumes the bank -- BVLC SGDSolver::ApplyUpdate on the accumulated diffs
+  const bool banked = c->bank_count > 0;
+  if (banked && !c->grad_banked)
+    return fail(VV_ERR_STATE, "vv_apply_update: %d gradients are banked and the last backward pass's is not among them (vv_grads_bank it, or vv_grads_bank_reset)", c->bank_count);
   VV_ENTER(c);
   // two updates in a row: the first one completes first.  (After a gated forward GEMM -- UpdSync::Gated -- nothing is due here: the
   // new update is queued on the communication stream behind the old one, and what this step's kernels on the compute stream read
@@ -1753,7 +1845,8 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   // them (the step left the sharded path -- gradients exposed or bound, the schedule changed -- without a gather).  A
   // collective, like the update itself: every rank takes this branch in the same iteration.
   if (!sharded && c->params_partial && (rc = gather_params(c))) return rc;
-  if (!overlapped && !sharded && grad_sum_due(c->grad) && (rc = vv_allreduce_grads(c))) return rc;     // data-parallel: the update consumes the SUM over the ranks
+  // data-parallel: the update consumes the SUM over the ranks (of banked gradients: the bank's, exchanged by bank_to_buffer)
+  if (!banked && !overlapped && !sharded && grad_sum_due(c->grad) && (rc = vv_allreduce_grads(c))) return rc;
   SgdArgs a;
   float* const wmax_new = c->wmax_blocks + (1 - c->wmax_cur) * WMAX_SLOTS;     // the buffer the previous update did not write
   a.W = c->W; a.b = c->b; a.hW = c->hW; a.hb = c->hb; a.grads = c->grads; a.Wh = c->Wh; a.scales = c->scales; a.wmax_blocks = wmax_new;
@@ -1767,6 +1860,11 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   c->adam_pending = adam;
   float* const vW = adam ? c->hW2 : nullptr; float* const vb = adam ? c->hb2 : nullptr;
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
+  if (banked) {                        // (the banks brought every gradient into the buffer: nothing is left in the slabs; form 1 or 2)
+    flush_scale_update(c);
+    if ((rc = bank_to_buffer(c, clip_on))) return rc;
+    return update_plain(c, a, vW, vb);
+  }
   if (c->grad.at == GradAt::SlabsWUpdated) return update_finish_wgrad(c, a);
   if (c->grad.at == GradAt::Slabs && !clip_on) return update_fused(c, a, vW, vb);
   if ((rc = reduce_now(c))) return rc;       // (GradAt::SlabsStale: a second update on the same gradient reads it from the buffer)
@@ -1782,6 +1880,8 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
 }
 
 int vv_step(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device) {
+  if (c && c->bank_count > 0)
+    return fail(VV_ERR_STATE, "vv_step: %d gradients are banked and this step's would not be among them (vv_forward_backward + vv_grads_bank + vv_apply_update, or vv_grads_bank_reset)", c->bank_count);
   int rc = vv_update_hint(c, cfg);                  // (nothing reads the gradient between the two halves of this call)
   if (rc) return rc;
   rc = vv_forward_backward(c, cfg, idx, idx_on_device);
@@ -2678,6 +2778,7 @@ int vv_comm_init(vv_ctx* c, int32_t world, int32_t rank, const char* id_path, in
 int vv_comm_overlap(vv_ctx* c, int on) {
   if (!c) return fail(VV_ERR_ARG, "vv_comm_overlap: ctx is NULL");
   if (on && c->clip >= 0.f) return fail(VV_ERR_STATE, "vv_comm_overlap: %s", kClipSchedule);
+  if (on && c->bank_count > 0) return fail(VV_ERR_STATE, "vv_comm_overlap: %s", kBankSchedule);
   if (on && c->comm_sharded && c->params_partial) { VV_ENTER(c); const int rcg = gather_params(c); if (rcg) return rcg; }   // (collective, as in vv_comm_schedule: leaving the sharded schedule)
   c->comm_overlap = on != 0;
   if (on) c->comm_sharded = false;
@@ -2688,6 +2789,7 @@ int vv_comm_schedule(vv_ctx* c, int schedule) {
   if (!c) return fail(VV_ERR_ARG, "vv_comm_schedule: ctx is NULL");
   if (schedule < 0 || schedule > 2) return fail(VV_ERR_ARG, "vv_comm_schedule: 0 sync, 1 overlap, 2 sharded");
   if (schedule != 0 && c->clip >= 0.f) return fail(VV_ERR_STATE, "vv_comm_schedule: %s", kClipSchedule);
+  if (schedule != 0 && c->bank_count > 0) return fail(VV_ERR_STATE, "vv_comm_schedule: %s", kBankSchedule);
   { const int rcg = upd_pending_guard(c, "vv_comm_schedule"); if (rcg) return rcg; }
   if (schedule != 2 && c->params_partial) { VV_ENTER(c); const int rcg = gather_params(c); if (rcg) return rcg; }     // (collective: the other schedules update the whole matrix)
   c->comm_overlap = schedule == 1;

@@ -1874,6 +1874,56 @@ __global__ __launch_bounds__(256) void k_grad_scale(ClipArgs a) {
 void launch_grad_sumsq(const ClipArgs& a, hipStream_t s) { VV_LAUNCH(k_grad_sumsq, dim3(CLIP_BLOCKS), dim3(256), 0, s, a); }
 void launch_grad_scale(const ClipArgs& a, hipStream_t s) { VV_LAUNCH(k_grad_scale, dim3(SGD_BLOCKS), dim3(256), 0, s, a); }
 
+// ------------------------------------------------------------------------------- gradient accumulation ----
+// BVLC Caffe's SolverParameter.iter_size (the reference tree has none): Solver::Step runs iter_size forward/backward passes whose layers
+// add into the parameter diffs, and SGDSolver::Normalize multiplies the sum by Dtype(1) / iter_size in front of the regulariser and the
+// rule.  k_grad_bank is the three element-wise passes of that over flat [dW | db] buffers (BankOp): Store dst = src, Add dst = dst + src
+// (one fp32 add), Scale dst = src * inv (one fp32 multiply; src == dst allowed).  A FIXED grid of BANK_BLOCKS x 256 threads; thread t owns
+// the 16-byte items t, t + grid, ... (non-temporal: each stream is read or written once per pass) and at most one of the scalar floats in
+// front of the first 16-byte boundary / behind the last whole item, split as clip_split does by dst's address.  The host gives src the
+// same offset from a boundary (the bank is placed that way); should the two ever differ -- a buffer bound in mid-cycle -- the launch
+// takes every element as a scalar.  Every element has one owner and there are no atomics: the result is bit-reproducible.
+// Thread 0 of the grid keeps the cycle's loss record (BankArgs::fold).
+template <BankOp OP> __device__ __forceinline__ float bank_op(float s, float d, float inv) {
+  if constexpr (OP == BankOp::Store) return s;
+  else if constexpr (OP == BankOp::Add) return d + s;
+  else return s * inv;
+}
+template <BankOp OP> __global__ __launch_bounds__(256) void k_grad_bank(BankArgs a) {
+  if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)BANK_BLOCKS * 256;
+  if (tid == 0 && a.fold == 1) {
+    AccumRec& r = *a.rec;
+    r.loss_sum = bank_op<OP>(a.loss2[0], r.loss_sum, 1.f); r.viol_sum = bank_op<OP>(a.loss2[1], r.viol_sum, 1.f);
+  }
+  if (tid == 0 && a.fold == 2) {
+    AccumRec& r = *a.rec;
+    r.last_mean_loss = r.loss_sum * a.inv; r.last_mean_viol = r.viol_sum * a.inv; r.last_count = a.m; r.updates += 1;
+  }
+  if ((((uintptr_t)a.src ^ (uintptr_t)a.dst) & 15) != 0) {          // no common 16-byte grid: scalars throughout
+    for (int64_t i = tid; i < a.n; i += nth) a.dst[i] = bank_op<OP>(a.src[i], OP == BankOp::Add ? a.dst[i] : 0.f, a.inv);
+    return;
+  }
+  const ClipSplit p = clip_split(a.dst, a.n);
+  for (int64_t i = tid; i < p.n4; i += nth) {
+    const int64_t o = p.head + i * 4;
+    const float4 s = nt_load4(a.src + o);
+    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (OP == BankOp::Add) d = nt_load4(a.dst + o);
+    nt_store4(a.dst + o, make_float4(bank_op<OP>(s.x, d.x, a.inv), bank_op<OP>(s.y, d.y, a.inv), bank_op<OP>(s.z, d.z, a.inv), bank_op<OP>(s.w, d.w, a.inv)));
+  }
+  if (tid < p.rest) {
+    const int64_t o = tid < p.head ? tid : p.tail0 + (tid - p.head);
+    a.dst[o] = bank_op<OP>(a.src[o], OP == BankOp::Add ? a.dst[o] : 0.f, a.inv);
+  }
+}
+void launch_grad_bank(BankOp op, const BankArgs& a, hipStream_t s) {
+  const dim3 grid(BANK_BLOCKS), block(256);
+  if (op == BankOp::Store) VV_LAUNCH(k_grad_bank<BankOp::Store>, grid, block, 0, s, a);
+  else if (op == BankOp::Add) VV_LAUNCH(k_grad_bank<BankOp::Add>, grid, block, 0, s, a);
+  else VV_LAUNCH(k_grad_bank<BankOp::Scale>, grid, block, 0, s, a);
+}
+
 __global__ void k_scale_update(Scales* sc, const float* wmax_blocks, int nblocks, int prec) { scale_update_body(sc, wmax_blocks, nblocks, prec); }
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s) {
   hipLaunchKernelGGL(k_scale_update, dim3(1), dim3(256), 0, s, sc, wmax_blocks, n_blocks, prec);

@@ -63,6 +63,14 @@ struct vv_ctx {
   float upd_clip = -1.f;                    // ... as it stood when vv_update_hint announced upd_cfg
   bool upd_announced = false;               // the last backward pass was announced by vv_update_hint and its vv_apply_update has not run yet
   vv::ClipRec* clip_rec = nullptr;          // device: the record, then CLIP_BLOCKS partial sums and the arrival counter (one allocation, made by vv_clip_gradients_set)
+  // vv_grads_bank (BVLC SolverParameter.iter_size): the bank, a second flat [dW | db] buffer.  ONE allocation made zero-filled by the first
+  // bank: the record, then D F + D floats and four of slack -- `bank` starts as many floats past a 16-byte boundary as the gradient buffer
+  // does (set by the first bank of every cycle), so that k_grad_bank finds one 16-byte grid in both.
+  vv::AccumRec* bank_rec = nullptr; float* bank = nullptr;
+  int bank_count = 0;                       // gradients in the bank (m); 0: vv_apply_update is what it always was
+  bool grad_banked = false;                 // the last backward pass's gradient has been banked, or the buffer holds an accumulated update's
+                                            // normalised sum in its place: not banked again (a backward pass clears it)
+  bool fb_hinted = false;                   // the last backward pass was announced by vv_update_hint: its gradient is not banked
   uint16_t* Wh = nullptr; vv::Scales* scales = nullptr; float* wmax_blocks = nullptr;
   int n_cu = 256;                           // compute units of the device
   bool scale_pending = false;               // k_sgd ran, its scale update has not (it rides in the next k_reduce)

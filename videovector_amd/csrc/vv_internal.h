@@ -461,6 +461,28 @@ struct ClipArgs {
   const uint32_t* skip_if = nullptr;  // as SgdArgs::skip_if: a failed exchange in front, the launch changes nothing
 };
 
+// Gradient accumulation (BVLC Caffe's SolverParameter.iter_size: Solver::Step's accumulating ForwardBackward passes and
+// SGDSolver::Normalize; vv_grads_bank): the cycle's loss and violation sums and what vv_accum_stats reports, kept by k_grad_bank's
+// first thread -- nothing synchronises per pass.
+struct AccumRec {
+  float loss_sum, viol_sum;           // of the gradients banked in this cycle, fp32, in banking order
+  float last_mean_loss, last_mean_viol; int32_t last_count; int32_t pad_;      // of the last completed accumulated update
+  int64_t updates;
+};
+constexpr int BANK_BLOCKS = 1024;     // k_grad_bank's fixed grid: 262 144 threads, one 16-byte item each per pass
+// dst[i] = src[i] (Store: the first bank of a cycle, and the bank into the gradient buffer in front of an exchange or of clipping),
+// dst[i] = dst[i] + src[i] (Add: every later bank), dst[i] = src[i] * inv (Scale: SGDSolver::Normalize, src == dst allowed)
+enum class BankOp : int { Store = 0, Add = 1, Scale = 2 };
+struct BankArgs {
+  const float* src; float* dst; int64_t n;
+  float inv = 1.f;                    // Scale: 1.0f / (float)m
+  // the loss: fold = 1 folds loss2 = {loss, violations} of the last forward pass into rec's sums (Store stores, Add adds); fold = 2 closes
+  // the cycle (means = sums * inv, last_count = m, updates += 1); 0: the record is not touched
+  int fold = 0; int32_t m = 0;
+  const float* loss2 = nullptr; AccumRec* rec = nullptr;
+  const uint32_t* skip_if = nullptr;  // as SgdArgs::skip_if: a failed exchange in front, the launch changes nothing
+};
+
 // Which kernels a context runs (vv_ctx::ko).  The launchers read the options of the context whose entry point is running on this
 // thread (g_ko, set by every ABI entry point next to hipSetDevice); nothing here is process-global, so two contexts of one process
 // do not inherit each other's choices.  Product options are set by vv_set_option (their environment variables are read ONCE per
@@ -535,6 +557,7 @@ void launch_reduce(const ReduceArgs& a, hipStream_t s);
 void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW = nullptr, float* vb = nullptr);
 void launch_grad_sumsq(const ClipArgs& a, hipStream_t s);            // -> ClipArgs::rec (no host synchronisation)
 void launch_grad_scale(const ClipArgs& a, hipStream_t s);            // g *= rec->scale where rec->clipped, else every workgroup returns at once
+void launch_grad_bank(BankOp op, const BankArgs& a, hipStream_t s);   // k_grad_bank: one owner per element, no atomics
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s);
 void launch_delay(int us, hipStream_t s);                             // test hook: occupies s for `us` microseconds       // flag <- seq (agent scope), behind everything queued on s
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s);

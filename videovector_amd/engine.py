@@ -59,6 +59,11 @@ class _ClipReport(C.Structure):
                 ("updates", C.c_int64), ("clipped_updates", C.c_int64)]
 
 
+class _AccumReport(C.Structure):
+    _fields_ = [("banked", C.c_int32), ("last_count", C.c_int32), ("last_mean_loss", C.c_float), ("last_mean_violations", C.c_float),
+                ("updates", C.c_int64)]
+
+
 class _ClassStats(C.Structure):
     _fields_ = [("mean_ap", C.c_float), ("hit_at_1", C.c_float), ("hit_at_5", C.c_float), ("n_scored", C.c_int32)]
 
@@ -144,6 +149,7 @@ def load_library():
         "vv_history2_set": [vp, vp, vp], "vv_history2_get": [vp, vp, vp],
         "vv_clip_gradients_set": [vp, f32], "vv_clip_gradients_get": [vp, C.POINTER(f32)],
         "vv_clip_stats": [vp, C.POINTER(_ClipReport)],
+        "vv_grads_bank": [vp], "vv_grads_bank_reset": [vp], "vv_accum_stats": [vp, C.POINTER(_AccumReport)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -478,6 +484,23 @@ class Engine:
         self._chk(self.L.vv_clip_stats(self.h, C.byref(r)))
         return {"norm": np.float32(r.norm), "scale": np.float32(r.scale), "clipped": int(r.clipped), "updates": int(r.updates),
                 "clipped_updates": int(r.clipped_updates)}
+
+    # ---- gradient accumulation (BVLC SolverParameter.iter_size; vv_grads_bank, vv_grads_bank_reset, vv_accum_stats)
+    def grads_bank(self):
+        """Add the last forward_backward's gradient (and its loss and violations) into the bank; the next apply_update consumes the bank:
+        the sum, clipped where clipping is active, times 1 / m, through the plain update."""
+        self._chk(self.L.vv_grads_bank(self.h))
+
+    def grads_bank_reset(self):
+        """Discard the banked gradients (BVLC Net::ClearParamDiffs)."""
+        self._chk(self.L.vv_grads_bank_reset(self.h))
+
+    def accum_stats(self):
+        """banked now; count / mean loss / mean violations of the last completed accumulated update (synchronises); their total."""
+        r = _AccumReport()
+        self._chk(self.L.vv_accum_stats(self.h, C.byref(r)))
+        return {"banked": int(r.banked), "last_count": int(r.last_count), "last_mean_loss": np.float32(r.last_mean_loss),
+                "last_mean_violations": np.float32(r.last_mean_violations), "updates": int(r.updates)}
 
     def _ext(self, cfg):
         """StepConfig's momentum2 / rms_decay / clip_gradients -> the context, in front of a call that takes cfg."""
