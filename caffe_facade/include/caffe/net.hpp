@@ -108,6 +108,10 @@ class Net {
   Dtype ForwardTest();
   vv_ctx* ctx_ = nullptr;            // train net: the process context; a TEST net owns a second one
   bool own_ctx_ = false;
+  // a TEST-phase net whose layers are the TRAIN graph (VIDEO_SAMPLED_SHOTS_DATA .. MAX_MARGIN_LOSS under include { phase: TEST }): the
+  // held-out branch.  Net::Forward runs the library's forward-only pass (vv_forward, dropout_ratio 0) on a context of its own
+  bool held_out_ = false;
+  Dtype ForwardHeldOut();
   void PushParamsToDevice();
   void PullParamsFromDevice();
   vector<shared_ptr<Layer<Dtype> > > layers_;

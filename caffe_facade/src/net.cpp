@@ -144,6 +144,26 @@ void Net<Dtype>::Init(const NetParameter& in_param) {
     }
   }
   if (sequential_) SetUpSequential(is_test);
+  // The held-out branch: the TRAIN graph under phase TEST, matched to the fused plan.  Net::Forward (net.hpp: ForwardPrefilled under
+  // Caffe::TEST, what Solver::Test calls test_iter times) is then the library's forward-only pass.  Like the retrieval TEST net it has
+  // its own data source, hence its own feature table and its own context: its batch shape is its own, and nothing of the training
+  // context is touched.  It gets its parameters through ShareTrainedLayersWith.  (Layer by layer such a net runs as it always did.)
+  {
+    const NetState st(param.get_msg("state"));     // (the phase FilterNet filtered by)
+    const int phase = st.has("phase") ? (int)st.get_int("phase") : (int)Caffe::phase();
+    held_out_ = !is_test && !sequential_ && phase == (int)Caffe::TEST;
+  }
+  if (held_out_) {
+    VV_CHECK(vv_create(Caffe::device(), getenv("VV_PREC") && !strcmp(getenv("VV_PREC"), "bf16") ? VV_PREC_BF16 : VV_PREC_F16, &ctx_));
+    own_ctx_ = true;
+    Caffe::register_ctx(ctx_);
+    static_cast<VideoSampledShotsDataLayer<Dtype>*>(layers_[plan_.data_layer].get())->dataset()->UploadTable(ctx_);
+    cfg_.dropout_ratio = 0.f;                       // (DropoutLayer::Forward under Caffe::TEST copies its input, dropout_layer.cpp:27-29)
+    PushParamsToDevice();
+    LOG(INFO) << "Held-out branch: Net::Forward runs the forward-only pass (no backward pass, no training state touched).";
+    LOG(INFO) << "Network initialization done.";
+    return;
+  }
   if (is_test) {
     // a TEST / extraction net has its own feature table, hence its own context on the same device
     VV_CHECK(vv_create(Caffe::device(), getenv("VV_PREC") && !strcmp(getenv("VV_PREC"), "bf16") ? VV_PREC_BF16 : VV_PREC_F16, &ctx_));
@@ -509,6 +529,7 @@ template <typename Dtype>
 Dtype Net<Dtype>::ForwardBackward(const vector<Blob<Dtype>*>&) {
   if (sequential_) return SequentialStep();
   if (plan_.test) return ForwardTest();
+  if (held_out_) return ForwardHeldOut();
   auto* data = static_cast<VideoSampledShotsDataLayer<Dtype>*>(layers_[plan_.data_layer].get());
   const double tp0 = g_hprof.on ? HostProf::now() : 0;
   data->NextBatch(&idx_, &last_src_, &label_);
@@ -537,6 +558,32 @@ Dtype Net<Dtype>::ForwardBackward(const vector<Blob<Dtype>*>&) {
   if (!plan_.violations_blob.empty()) blobs_[blob_names_index_[plan_.violations_blob]]->mutable_cpu_data()[0] = viol;
   last_loss_ = loss;
   return loss;
+}
+// Net::Forward of the held-out branch: one forward-only pass on the next batch of its own sampler.  The loss and train_violations tops
+// are the pass's fp32 values (vv_eval_report::last_*); Solver::Test averages them over test_iter passes.
+template <typename Dtype>
+Dtype Net<Dtype>::ForwardHeldOut() {
+  auto* data = static_cast<VideoSampledShotsDataLayer<Dtype>*>(layers_[plan_.data_layer].get());
+  data->NextBatch(&idx_, &last_src_, &label_);
+  cfg_.ctx_coeff = plan_.ctx_coeff.data();
+  cfg_.item_weight = nullptr;
+  if (plan_.weighted_loss) {
+    auto* ml = static_cast<MaxMarginLossLayer<Dtype>*>(layers_[plan_.loss_layer].get());
+    item_weight_.resize(plan_.B);
+    for (int i = 0; i < plan_.B; ++i) item_weight_[i] = ml->WeightOf((float)label_[i]);
+    cfg_.item_weight = item_weight_.data();
+  }
+  for (size_t i = 0; i < idx_.size(); ++i)
+    CHECK(idx_[i] == last_src_[i]) << "the held-out branch has no form of the same-video-negative quirk (max_same_video_negs > 0): "
+                                      "set max_same_video_negs: 0 in its data layer";
+  VV_CHECK(vv_forward(ctx_, &cfg_, idx_.data(), 0));
+  ++iter_;
+  vv_eval_report r;
+  VV_CHECK(vv_eval_stats(ctx_, &r));
+  if (has_blob(plan_.loss_blob)) blobs_[blob_names_index_[plan_.loss_blob]]->mutable_cpu_data()[0] = r.last_loss / (plan_.loss_weight ? plan_.loss_weight : 1.f);
+  if (!plan_.violations_blob.empty()) blobs_[blob_names_index_[plan_.violations_blob]]->mutable_cpu_data()[0] = r.last_violations;
+  last_loss_ = r.last_loss;
+  return r.last_loss;
 }
 template <typename Dtype>
 const vector<Blob<Dtype>*>& Net<Dtype>::Forward(const vector<Blob<Dtype>*>& bottom, Dtype* loss) {

@@ -54,7 +54,8 @@ int vv_synchronize(vv_ctx* ctx);
  * (InnerProductLayer::Forward, inner_product_layer.cu:12-27) runs once per distinct row and the gradient rows of
  * a row's instances are summed before the weight-gradient product (inner_product_layer.cu:36-42): the same
  * sums, reassociated.  Steps with dropout always take the dense path.  vv_dedup_stats reports the rows of
- * the last forward/backward pass and how many were distinct (rows == unique_rows on the dense path). */
+ * the last forward/backward pass and how many were distinct (rows == unique_rows on the dense path).  A forward-only pass (vv_forward)
+ * is a forward pass: until the next vv_forward_backward* vv_dedup_stats reports ITS batch. */
 int vv_set_dedup(vv_ctx* ctx, int on);
 /* Per-context execution switches by name; none of them changes a result beyond rounding, none is process-global (two contexts
  * of one process keep their own).  Each also has an environment variable that sets its INITIAL value when the context is
@@ -132,7 +133,9 @@ int vv_dedup_stats(vv_ctx* ctx, int64_t* rows, int64_t* unique_rows);
  * reports steer is bit-reproducible, and a host running ahead is never stalled).  flagged_steps / first_flagged_step (steps count from 0,
  * one per vv_forward_backward*) are therefore up to four steps behind, and under "h16_guard" 2 the four steps from the flagged one on have
  * still trained on f16 rows before the fallback holds: nothing is redone.  With f16 and with bf16 operands alike (the rows are f16 in both).
- * "h16_guard" 0, or a step on fp32 rows: both counts 0.  Library default 1; the Solver of the Caffe facade runs its engine with 2. */
+ * "h16_guard" 0, or a step on fp32 rows: both counts 0.  Library default 1; the Solver of the Caffe facade runs its engine with 2.
+ * A forward-only pass (vv_forward) counts nothing and is no step: after one, saturated / faint_rows and the flagged fields still describe
+ * the last TRAINING step; only rows_f16 (like "last_h16") describes the pass, until the next vv_forward_backward*. */
 typedef struct { int64_t saturated, faint_rows;     /* of the LAST completed step (synchronises, like vv_dedup_stats) */
                  int64_t flagged_steps;             /* steps with either count non-zero since vv_create, as read from the ring */
                  int64_t first_flagged_step;        /* its step number, -1: none */
@@ -335,6 +338,38 @@ int vv_update_hint(vv_ctx* ctx, const vv_step_cfg* cfg);
 /* Loss (already multiplied by loss_weight) and train_violations of the last forward; synchronises.
  * (the two tops of MAX_MARGIN_LOSS, max_margin_loss_layer.cpp:111-126.) */
 int vv_loss_get(vv_ctx* ctx, float* loss, float* violations);
+
+/* ---- the forward-only pass: Net::Forward / Net::ForwardPrefilled (include/caffe/net.hpp, src/caffe/net.cpp) under
+ * Caffe::set_phase(Caffe::TEST), one of the test_iter passes of Solver::Test (solver.cpp:251-317) over a net built like the TRAIN graph:
+ * gather -> fc7 -> ReLU (-> dropout) -> context mean -> L2 normalise -> scores -> max-margin loss and train_violations, and NO backward
+ * pass: the held-out loss with the current weights.  idx and idx_on_device as vv_forward_backward.
+ * Arithmetic: the training pass's own -- the same grouping, the same forward GEMM launch, the same score form, in forward-only
+ * instantiations of the score kernels -- so for equal weights, idx and cfg the loss and violations are bit for bit those of
+ * vv_forward_backward + vv_loss_get, in every score form, with "dedup" and "h16" on or off, with an explicit mask.  cfg->dropout_ratio is
+ * honoured as given (a TEST-phase caller passes 0); a counter-based mask reads the iteration counter and does not advance it.  The loss is
+ * divided by this batch's own B * Nn, as the training pass's is; cfg->global_count and the solver fields are checked and otherwise unused.
+ * Local to the rank: no collective.  Sets "last_score_form", "last_fwd_tile_rows", "last_h16" and vv_dedup_stats, as a forward pass does.
+ * Training state: the pass touches nothing a training step owns.  After fb(A); vv_forward(B); vv_apply_update the parameters, histories,
+ * the 16-bit copy, vv_loss_get, vv_grads_get and every later step are bit for bit those of fb(A); vv_apply_update: the gradient stays where
+ * it is (lazily reduced or not), the step's pending loss partials are not overwritten (the pass has partial buffers of its own; vv_loss_get
+ * keeps returning the TRAINING pass's loss), the gradient-scale and f16-row report rings, Adam's t, the clipping and accumulation records
+ * are not moved.  With an overlapped or sharded update in flight the pass first orders itself behind it.
+ * Afterwards vv_blobs_get returns ip2 and the two score blobs of THIS pass; its ip1_diff, and vv_dedup_groups_get, are VV_ERR_STATE until
+ * the next backward pass (after a training pass both are what they were).
+ * VV_ERR_STATE: between a vv_forward_backward* announced by vv_update_hint and its vv_apply_update; with a batch shape (B, C, Nn) other
+ * than the one the training step's buffers were sized for while that step's state is alive (the batch buffers are shared: evaluate with
+ * the training shape; before the first training pass, or after vv_params_set, any shape is taken).
+ * The result is read through the record below, not through vv_loss_get. */
+int vv_forward(vv_ctx* ctx, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device);
+/* Accumulation over passes (Solver::Test's test_score vector, solver.cpp:262-296, divided by test_iter at :304): a device record kept by
+ * one thread of the pass's loss reduction -- no host synchronisation per pass.  last_*: the fp32 values vv_loss_get would show for the
+ * last pass.  loss_sum / viol_sum: their sums in double, added in pass order (an fp32 value is exact in double); mean_* =
+ * (float)(sum / passes); terms: B * Nn per pass.  vv_eval_reset zeroes the record (queued behind the passes already issued);
+ * vv_params_set does not.  vv_eval_stats synchronises; before any pass it gives zeros. */
+typedef struct { int64_t passes; int64_t terms; double loss_sum, viol_sum; float last_loss, last_violations;
+                 float mean_loss, mean_violations; } vv_eval_report;
+int vv_eval_reset(vv_ctx* ctx);
+int vv_eval_stats(vv_ctx* ctx, vv_eval_report* out);
 
 /* ---- gradients.  The flat fp32 device buffer [dW (D*F) | db (D)] that a data-parallel host
  * all-reduces (RCCL) between vv_forward_backward and vv_apply_update; there is no counterpart in

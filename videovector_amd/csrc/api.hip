@@ -177,20 +177,24 @@ static int create_init(vv_ctx* c) {
   if (const char* v = lab_env("VV_TRACE_HOST")) c->trace_host_ms = atof(v);
   c->trace_waits = lab_env("VV_TRACE_WAITS") != nullptr;
   vv::g_ko = &c->ko;
-  HIPCHK(hipMalloc(&c->dd_info_all, vv_ctx::kDdSets * 4 * sizeof(int32_t)));
-  HIPCHK(hipMemset(c->dd_info_all, 0, vv_ctx::kDdSets * 4 * sizeof(int32_t)));
+  HIPCHK(hipMalloc(&c->dd_info_all, vv_ctx::kDdAll * 4 * sizeof(int32_t)));
+  HIPCHK(hipMemset(c->dd_info_all, 0, vv_ctx::kDdAll * 4 * sizeof(int32_t)));
   HIPCHK(hipStreamCreateWithFlags(&c->dd_stream, hipStreamNonBlocking));
   { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && ncu > 0) c->n_cu = ncu; }
-  for (int i = 0; i < vv_ctx::kDdSets; ++i) {
+  for (int i = 0; i < vv_ctx::kDdAll; ++i) {
     c->dd_set[i].info = c->dd_info_all + 4 * i;
     HIPCHK(hipEventCreateWithFlags(&c->dd_set[i].done, hipEventDisableTiming));
   }
   c->dd_info = c->dd_set[0].info;
   if (const char* v = lab_env("VV_DEDUP_ASYNC")) c->dd_async = atoi(v) != 0;
   if (const char* v = lab_env("VV_DEDUP_SPIN_US")) c->dd_spin_us = atof(v);
-  HIPCHK(hipHostMalloc((void**)&c->U_host, 2 * sizeof(int32_t), hipHostMallocMapped));   // {U, saturated f16 gradient sums}
-  c->U_host[0] = c->U_host[1] = 0;
+  HIPCHK(hipHostMalloc((void**)&c->U_host, 3 * sizeof(int32_t), hipHostMallocMapped));   // {U, saturated f16 gradient sums, U of the last forward-only pass}
+  c->U_host[0] = c->U_host[1] = c->U_host[2] = 0;
   HIPCHK(hipHostGetDevicePointer((void**)&c->U_host_dev, c->U_host, 0));
+  // the forward-only pass (vv_forward): its record and the event that marks the end of the pass that last read its grouping set
+  HIPCHK(hipMalloc((void**)&c->eval_rec, sizeof(EvalRec)));
+  HIPCHK(hipMemset(c->eval_rec, 0, sizeof(EvalRec)));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_eval, hipEventDisableTiming));
   HIPCHK(hipMalloc(&c->w_gate, (W_CHUNKS_MAX + 1) * W_GATE_STRIDE * sizeof(int32_t)));
   HIPCHK(hipMemset(c->w_gate, 0, (W_CHUNKS_MAX + 1) * W_GATE_STRIDE * sizeof(int32_t)));
   c->pub_count = c->w_gate + W_CHUNKS_MAX * W_GATE_STRIDE;      // the arrival counter of the publishing kernels: a line of its own
@@ -241,11 +245,13 @@ static void free_batch(vv_ctx* c) {
   dfree(c->coeff); dfree(c->slabs); dfree(c->item_w); c->item_w = nullptr;
   if (c->dd_stream) (void)hipStreamSynchronize(c->dd_stream);
   dfree(c->dd_agg); dfree(c->dd_pos); dfree(c->dYu);
-  for (int i = 0; i < vv_ctx::kDdSets; ++i) {
+  for (int i = 0; i < vv_ctx::kDdAll; ++i) {
     vv_ctx::DdSet& d = c->dd_set[i];
     dfree(d.rows); dfree(d.slot_of); dfree(d.uniq); dfree(d.map); dfree(d.ord); dfree(d.cnt); dfree(d.seg);
     d.rows = d.slot_of = d.uniq = d.map = d.ord = d.cnt = d.seg = nullptr; d.used_seq = 0;
   }
+  dfree(c->eval_loss_part); dfree(c->eval_viol_part); c->eval_loss_part = c->eval_viol_part = nullptr;
+  c->eval_set_used = false; c->last_fwd_only = false;
   c->dd_rows = nullptr;
   dfree(c->segV); dfree(c->seg_rec); dfree(c->seg_dbp); dfree(c->gg_slots); dfree(c->h16_cnt);
   c->segV = nullptr; c->seg_rec = nullptr; c->seg_dbp = nullptr; c->gg_slots = nullptr; c->gg_nslot = 0; c->h16_cnt = nullptr;
@@ -273,8 +279,14 @@ int vv_destroy(vv_ctx* c) {
   dfree(c->dd_key); dfree(c->dd_info_all); dfree(c->gg); dfree(c->gg_bound); dfree(c->w_gate);
   if (c->gate_err) (void)hipHostFree(c->gate_err);
   if (c->gmax_host) (void)hipHostFree(c->gmax_host);
-  for (int i = 0; i < vv_ctx::kDdSets; ++i) {
+  for (int i = 0; i < vv_ctx::kDdAll; ++i) {
     if (c->dd_set[i].done) (void)hipEventDestroy(c->dd_set[i].done);
+  }
+  dfree(c->eval_rec);
+  if (c->ev_eval) (void)hipEventDestroy(c->ev_eval);
+  for (int i = 0; i < vv_ctx::kEvalStage; ++i) {
+    if (c->eval_stage_host[i]) (void)hipHostFree(c->eval_stage_host[i]);
+    if (c->eval_stage_done[i]) (void)hipEventDestroy(c->eval_stage_done[i]);
   }
   if (c->dd_stream) (void)hipStreamDestroy(c->dd_stream);
   if (c->ev_chunk) (void)hipEventDestroy(c->ev_chunk);
@@ -394,7 +406,7 @@ int vv_set_dedup(vv_ctx* c, int on) {
 
 int vv_dedup_stats(vv_ctx* c, int64_t* rows, int64_t* unique_rows) {
   if (!c) return fail(VV_ERR_ARG, "vv_dedup_stats: ctx is NULL");
-  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_dedup_stats: no forward pass yet");
+  if (!grad_exists(c->grad) && !c->last_fwd_only) return fail(VV_ERR_STATE, "vv_dedup_stats: no forward pass yet");
   VV_ENTER(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   int32_t U = c->R;
@@ -406,7 +418,7 @@ int vv_dedup_stats(vv_ctx* c, int64_t* rows, int64_t* unique_rows) {
 
 int vv_h16_stats(vv_ctx* c, vv_h16_report* out) {
   if (!c || !out) return fail(VV_ERR_ARG, "vv_h16_stats: ctx / out is NULL");
-  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_h16_stats: no forward pass yet");
+  if (!grad_exists(c->grad) && !c->last_fwd_only) return fail(VV_ERR_STATE, "vv_h16_stats: no forward pass yet");
   VV_ENTER(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   out->saturated = out->faint_rows = 0;
@@ -878,7 +890,9 @@ static int ensure_batch(vv_ctx* c, int B, int C, int Nn) {
   c->dd_agg_stride = c->R / 1024 + 2;
   HIPCHK(hipMalloc(&c->dd_agg, (size_t)2 * c->dd_agg_stride * sizeof(unsigned long long)));
   HIPCHK(hipMemset(c->dd_agg, 0, (size_t)2 * c->dd_agg_stride * sizeof(unsigned long long)));
-  for (int i = 0; i < vv_ctx::kDdSets; ++i) {
+  HIPCHK(hipMalloc(&c->eval_loss_part, (size_t)B * 4));
+  HIPCHK(hipMalloc(&c->eval_viol_part, (size_t)B * 4));
+  for (int i = 0; i < vv_ctx::kDdAll; ++i) {
     vv_ctx::DdSet& d = c->dd_set[i];
     HIPCHK(hipMalloc(&d.rows, (size_t)c->Rp * 4));
     HIPCHK(hipMalloc(&d.slot_of, (size_t)c->Rp * 4));
@@ -899,7 +913,7 @@ static int ensure_batch(vv_ctx* c, int B, int C, int Nn) {
   c->gg_nslot = std::max(std::max(B, SEGB_BLOCKS), (c->Rp + 3) / 4);
   HIPCHK(hipMalloc(&c->gg_slots, (size_t)3 * 2 * c->gg_nslot * 4));
   HIPCHK(hipMemset(c->gg_slots, 0, (size_t)3 * 2 * c->gg_nslot * 4));
-  *c->U_host = 0;
+  c->U_host[0] = c->U_host[2] = 0;        // (the distinct-row hints of the old shape: the training batches' and the forward-only passes')
   return VV_OK;
 }
 
@@ -1102,7 +1116,10 @@ extern "C++" int vv_comm_join(vv_ctx* c) {
 
 // The grouping of one batch (k_dd_claim .. k_dd_segstart) into the next of the rotating output sets, on the grouping
 // stream; *set_out = the set.  The step that consumes the set binds it and orders its stream behind set.done (fb_impl).
-static int dd_issue(vv_ctx* c, const int32_t* didx, int idx_on_device, int64_t row_limit, int32_t seq, int* set_out) {
+// eval (vv_forward): the set that never rotates (vv_ctx::kDdEval).  Its last reader was the previous forward-only pass, on the step's
+// stream: the grouping stream waits for that pass's end event instead of a sequence stamp (a forward-only pass takes no sequence number),
+// and the distinct-row count goes to a host word of its own, so the hint the next TRAINING forward GEMM is sized by stays the training batches'.
+static int dd_issue(vv_ctx* c, const int32_t* didx, int idx_on_device, int64_t row_limit, int32_t seq, int* set_out, bool eval = false) {
   hipStream_t s = c->stream;
   const int D = c->D;
   {
@@ -1131,10 +1148,11 @@ static int dd_issue(vv_ctx* c, const int32_t* didx, int idx_on_device, int64_t r
       HIPCHK(hipMemsetAsync(c->dd_agg, 0, (size_t)2 * c->dd_agg_stride * sizeof(unsigned long long), ds));
       c->dd_epoch = 1;
     }
-    const int si = (int)(c->dd_step++ % vv_ctx::kDdSets);
+    const int si = eval ? vv_ctx::kDdEval : (int)(c->dd_step++ % vv_ctx::kDdSets);
     vv_ctx::DdSet& set = c->dd_set[si];
     *set_out = si;
-    if (c->dd_async && set.used_seq) {
+    if (eval && c->dd_async && c->eval_set_used) HIPCHK(hipStreamWaitEvent(ds, c->ev_eval, 0));
+    if (!eval && c->dd_async && set.used_seq) {
       // The set was last read by the step with sequence number used_seq.  The step's stream runs its kernels in order, so
       // once a kernel of ANY later step has stamped its number, every kernel of that step has finished.  The host waits
       // for that stamp (normally long there: it bounds how far the host runs ahead to kDdSets - 1 steps) -- an event
@@ -1159,14 +1177,14 @@ static int dd_issue(vv_ctx* c, const int32_t* didx, int idx_on_device, int64_t r
     }
     set.used_seq = seq;
     DedupArgs da;
-    da.idx = didx; da.rows = set.rows; da.u_host = c->U_host_dev; da.key = c->dd_key; da.agg = c->dd_agg; da.agg_stride = c->dd_agg_stride;
+    da.idx = didx; da.rows = set.rows; da.u_host = c->U_host_dev + (eval ? 2 : 0); da.key = c->dd_key; da.agg = c->dd_agg; da.agg_stride = c->dd_agg_stride;
     da.slot_of = set.slot_of; da.uniq_rows = set.uniq; da.map = set.map; da.ord = set.ord; da.cnt = set.cnt;
     da.seg_start = set.seg; da.pos = c->dd_pos; da.info = set.info; da.tickets = set.info + 2;
     {
       // placement of the grouping workgroups beside the forward GEMM (kernels_dedup.hip): only when that GEMM -- sized for
       // the previous step's distinct-row count, as launch_fwd_gemm will size it -- leaves at least 24 CUs idle
       const int lds_kb = c->dd_lds_kb;
-      const int hint = *(volatile int32_t*)c->U_host;
+      const int hint = *(volatile int32_t*)(c->U_host + (eval ? 2 : 0));
       const long tiles = fwd_gemm_plan(c->R, hint, D, nullptr);
       da.lds_bytes = lds_kb >= 0 ? lds_kb * 1024 : (c->dd_async && hint > 0 && tiles <= c->n_cu - 16 ? 36 * 1024 : 0);
     }
@@ -1364,6 +1382,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   }
   c->last_drop = (dd && drop_on) ? dsp : DropSpec();
   c->last_dedup = dd;
+  c->last_fwd_only = false;
   if (!dd) launch_map_rows(didx, c->rows, c->R, c->Rp, (int32_t)c->n_rows, (int32_t)row_limit, s);
   if (dd) {
     int si = 0;
@@ -1687,6 +1706,177 @@ int vv_forward_backward_q1(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx
   return fb_impl(c, cfg, c->stage_dev[sl], 2, c->n_rows + 1 + P, seq);
 }
 
+// ------------------------------------------------------------------------------- forward only --
+// A pinned, device-mapped staging buffer for a forward-only pass's host indices.  Two rotate, each with the event of the pass that last
+// read it: the host waits only when it is two evaluation passes ahead of the GPU.  (The training slots of stage_acquire are released by
+// the sequence stamps of training steps; a forward-only pass takes no sequence number.)
+static int eval_stage_acquire(vv_ctx* c, size_t bytes, int* slot) {
+  if (bytes != c->eval_stage_bytes) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->dd_stream) HIPCHK(hipStreamSynchronize(c->dd_stream));
+    for (int i = 0; i < vv_ctx::kEvalStage; ++i) {
+      if (c->eval_stage_host[i]) (void)hipHostFree(c->eval_stage_host[i]);
+      c->eval_stage_host[i] = c->eval_stage_dev[i] = nullptr; c->eval_stage_busy[i] = false;
+      HIPCHK(hipHostMalloc((void**)&c->eval_stage_host[i], bytes, hipHostMallocMapped));
+      HIPCHK(hipHostGetDevicePointer((void**)&c->eval_stage_dev[i], c->eval_stage_host[i], 0));
+      if (!c->eval_stage_done[i]) HIPCHK(hipEventCreateWithFlags(&c->eval_stage_done[i], hipEventDisableTiming));
+    }
+    c->eval_stage_bytes = bytes;
+  }
+  const int sl = c->eval_stage_next;
+  c->eval_stage_next = (sl + 1) % vv_ctx::kEvalStage;
+  if (c->eval_stage_busy[sl]) { HIPCHK(hipEventSynchronize(c->eval_stage_done[sl])); c->eval_stage_busy[sl] = false; }
+  *slot = sl;
+  return VV_OK;
+}
+
+// Net::Forward / Net::ForwardPrefilled under Caffe::set_phase(Caffe::TEST) (include/caffe/net.hpp, src/caffe/net.cpp), one of the test_iter
+// passes of Solver::Test (solver.cpp:251-317): the forward half of fb_impl -- the same grouping kernels, the same forward GEMM launch, the
+// same score form -- with the forward-only instantiations of the score kernels and a loss reduction of its own.  What a training step
+// owns is read, never written: the gradient's place (c->grad, the slabs, dbp, the gradient buffer, the bank), the step's pending loss and
+// violation partials, the sequence numbers with the two report rings behind them (gradient scale, f16 rows), c->sg, Adam's t, the
+// dropout counter c->iter, the clipping and accumulation records, the rotating grouping sets and their distinct-row hint.
+int vv_forward(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device) {
+  if (idx_on_device < 0 || idx_on_device > 2) return fail(VV_ERR_ARG, "vv_forward: idx_on_device must be 0, 1 or 2");
+  // (between a hinted vv_forward_backward* and its vv_apply_update the parameters are half-way: "another forward pass" is refused)
+  { const int rcg = upd_pending_guard(c, "vv_forward"); if (rcg) return rcg; }
+  if (c && c->upd_announced && grad_exists(c->grad))      // (... whether or not the announced update could ride in the weight-gradient GEMM: one rule for every shape)
+    return fail(VV_ERR_STATE, "vv_forward: the last backward pass was announced by vv_update_hint and its vv_apply_update has not run -- call vv_apply_update first");
+  int rc = check_cfg(c, cfg);
+  if (rc) return rc;
+  if (!idx) return fail(VV_ERR_ARG, "vv_forward: idx is NULL");
+  VV_ENTER(c);
+  const bool reshape = cfg->B != c->B || cfg->C != c->C || cfg->Nn != c->Nn || !c->H;
+  // the batch buffers are shared with the training step (ip2, the score blobs, the slabs): another shape would free a gradient that
+  // is still held and restart the gradient scale -- refused while a training pass's state is alive
+  if (reshape && grad_exists(c->grad))
+    return fail(VV_ERR_STATE, "vv_forward: a batch of %d x (%d + %d) while the training step's buffers hold %d x (%d + %d): the forward-only pass shares the "
+                              "step's batch buffers and leaves its state alone -- evaluate with the training shape", cfg->B, cfg->C, cfg->Nn, c->B, c->C, c->Nn);
+  // an overlapped or sharded update still in flight: this pass orders itself behind it, as every entry point that touches the parameters
+  // does (the next training forward GEMM then finds the update joined and runs ungated: the same values)
+  if ((rc = comm_join(c))) return rc;
+  if ((rc = ensure_batch(c, cfg->B, cfg->C, cfg->Nn))) return rc;
+  const int B = c->B, C = c->C, Nn = c->Nn, CN = C + Nn, D = c->D;
+  hipStream_t s = c->stream;
+
+  const int32_t* didx = idx;
+  int stage_slot = -1;
+  if (!idx_on_device) {
+    if ((rc = eval_stage_acquire(c, (size_t)c->R * 4, &stage_slot))) return rc;
+    int32_t* dst = c->eval_stage_host[stage_slot];
+    int bad = -1;
+    for (int i = 0; i < c->R; ++i) { const int32_t v = idx[i]; dst[i] = v; if (v < -1 || v >= c->n_rows) bad = i; }
+    if (bad >= 0) return fail(VV_ERR_ARG, "idx[%d] = %d out of range [-1, %lld)", bad, idx[bad], (long long)c->n_rows);
+    didx = c->eval_stage_dev[stage_slot];
+  }
+  // eltwise coefficients, item weights, an explicit mask: as fb_impl (the device copies are the step's own, read by kernels queued in front)
+  std::vector<float> coeff(C - 1);
+  for (int j = 0; j < C - 1; ++j) coeff[j] = cfg->ctx_coeff ? cfg->ctx_coeff[j] : 1.0f / (C - 1);
+  if (coeff != c->coeff_host) {
+    HIPCHK(hipMemcpyAsync(c->coeff, coeff.data(), coeff.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    c->coeff_host = coeff;
+  }
+  if (cfg->item_weight) {
+    for (int i = 0; i < B; ++i)
+      if (!(cfg->item_weight[i] >= 0.f)) return fail(VV_ERR_ARG, "item_weight[%d] = %g: All weights should be greater than 0 (max_margin_loss_layer.cpp:34)", i, (double)cfg->item_weight[i]);
+    HIPCHK(hipMemcpyAsync(c->item_w, cfg->item_weight, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  }
+  if (cfg->dropout_ratio > 0.f && cfg->dropout_mask) {
+    const size_t nb = (size_t)c->R * D;
+    if (nb > c->mask_bytes) { dfree(c->mask); c->mask = nullptr; HIPCHK(hipMalloc(&c->mask, nb)); c->mask_bytes = nb; }
+    HIPCHK(hipMemcpyAsync(c->mask, cfg->dropout_mask, nb, hipMemcpyHostToDevice, s));
+  }
+
+  // the execution the training pass would choose for this cfg (fb_impl): de-duplicated or dense, where dropout rides, f16 or fp32 rows
+  const bool drop_on = cfg->dropout_ratio > 0.f;
+  const bool drop_dd = drop_on && c->drop_dedup && c->seg_bwd && score_fwd_dropout_supported(c->drop_dedup, D, C, Nn);
+  const bool dd = c->dedup && (!drop_on || drop_dd) && !ablate_on();
+  DropSpec dsp;
+  if (drop_on) {
+    dsp.mode = cfg->dropout_mask ? 2 : 1;
+    dsp.thr = (uint32_t)(cfg->dropout_ratio * 65536.f + 0.5f);
+    dsp.s32 = (uint32_t)(mix64(cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter, 0x5eedull) >> 32);      // (the counter is read, not advanced)
+    dsp.scale = 1.f / (1.f - cfg->dropout_ratio);
+    dsp.mask = cfg->dropout_mask ? c->mask : nullptr;
+    dsp.B = B; dsp.CN = CN; dsp.D = D;
+  }
+  c->last_drop = (dd && drop_on) ? dsp : DropSpec();
+  c->last_dedup = dd;
+  c->last_fwd_only = true;
+  if (!dd) launch_map_rows(didx, c->rows, c->R, c->Rp, (int32_t)c->n_rows, (int32_t)c->n_rows, s);
+  if (dd) {
+    int si = 0;
+    if ((rc = dd_issue(c, didx, idx_on_device, c->n_rows, 0, &si, true))) return rc;
+    vv_ctx::DdSet& set = c->dd_set[si];
+    c->dd_rows = set.rows; c->dd_slot_of = set.slot_of; c->dd_uniq = set.uniq; c->dd_map = set.map; c->dd_ord = set.ord;
+    c->dd_cnt = set.cnt; c->dd_seg = set.seg; c->dd_info = set.info;
+    if (c->dd_async) HIPCHK(hipStreamWaitEvent(s, set.done, 0));
+  }
+
+  FwdArgs fa;
+  fa.table = c->table; fa.rows = dd ? c->dd_uniq : c->rows; fa.Wh = c->Wh; fa.bias = c->b; fa.scales = c->scales;
+  fa.H = c->H; fa.R = c->R; fa.D = D; fa.Fp = c->Fp; fa.relu = 1; fa.zero_row = (int32_t)c->n_rows;
+  fa.n_dev = dd ? c->dd_info : nullptr;
+  fa.R_hint = dd ? *(volatile int32_t*)(c->U_host + 2) : 0;
+  // (no sequence stamp: seq_host stays null -- the stamps release the TRAINING steps' staging slots and grouping sets)
+  const bool seg_path = dd && c->seg_bwd && (D == 512 || D == 1024);
+  const bool h16 = c->h16 && !c->h16_fallback && seg_path && !ablate_on();     // (the f16 rows' report ring is neither read nor fed: a pass counts nothing)
+  fa.h16 = h16 ? 1 : 0;
+  c->last_h16 = h16;
+  fa.drop_ratio = (dd && drop_on) ? 0.f : cfg->dropout_ratio;
+  fa.mask = (!(dd && drop_on) && cfg->dropout_ratio > 0.f && cfg->dropout_mask) ? c->mask : nullptr;
+  fa.drop_seed = cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter;
+  fa.B = B; fa.CN = CN;
+  PROFILED(c, "eval_fwd_gemm", launch_fwd_gemm(c->prec, fa, s));
+
+  const int64_t count = (int64_t)B * Nn;
+  const int64_t gcount = cfg->global_count > 0 ? cfg->global_count : count;
+  ScoreArgs sa;
+  sa.H = c->H; sa.dYh = nullptr; sa.dbp = nullptr; sa.loss_part = c->eval_loss_part; sa.viol_part = c->eval_viol_part;
+  sa.s_true = c->s_true; sa.s_bogus = c->s_bogus; sa.coeff = c->coeff;
+  sa.B = B; sa.C = C; sa.Nn = Nn; sa.D = D; sa.Dp = c->Dp;
+  sa.margin = cfg->margin; sa.norm = cfg->norm;
+  sa.grad_scale = cfg->loss_weight / (float)gcount;
+  sa.drop_scale = cfg->dropout_ratio > 0.f ? 1.f / (1.f - cfg->dropout_ratio) : 1.f;
+  sa.sg = 1.f;
+  sa.map = dd ? c->dd_map : nullptr; sa.seg_start = dd ? c->dd_seg : nullptr; sa.ord = dd ? c->dd_ord : nullptr;
+  sa.item_w = cfg->item_weight ? c->item_w : nullptr;
+  if (dd && drop_on) sa.drop = dsp;
+  sa.h16 = h16 ? 1 : 0;
+  sa.fwd_only = 1;
+  const bool seg = dd && c->seg_bwd && score_fwd_supported(sa);
+  if (seg != seg_path) return fail(VV_ERR_STATE, "internal error: the forward pass was planned for %s rows of ip2, the score kernels expect the other form", h16 ? "f16" : "fp32");
+  if (seg) PROFILED(c, "eval_score", launch_score_fwd(sa, s));
+  else PROFILED(c, "eval_score", launch_score_loss(c->prec, sa, s));
+  // the loss as the training path's loss workgroup folds it (ReduceArgs::loss_scale: this batch's own B Nn), and the record
+  PROFILED(c, "eval_loss", launch_eval_loss(c->eval_loss_part, c->eval_viol_part, B, cfg->loss_weight / (float)count, count, c->eval_rec, s));
+  HIPCHK(hipGetLastError());
+  if (dd && c->dd_async) { HIPCHK(hipEventRecord(c->ev_eval, s)); c->eval_set_used = true; }
+  if (stage_slot >= 0) { HIPCHK(hipEventRecord(c->eval_stage_done[stage_slot], s)); c->eval_stage_busy[stage_slot] = true; }
+  return VV_OK;
+}
+
+int vv_eval_reset(vv_ctx* c) {
+  if (!c) return fail(VV_ERR_ARG, "vv_eval_reset: ctx is NULL");
+  VV_ENTER(c);
+  HIPCHK(hipMemsetAsync(c->eval_rec, 0, sizeof(EvalRec), c->stream));      // (behind the passes already queued, in front of the next)
+  return VV_OK;
+}
+
+int vv_eval_stats(vv_ctx* c, vv_eval_report* out) {
+  if (!c || !out) return fail(VV_ERR_ARG, "vv_eval_stats: ctx / out is NULL");
+  VV_ENTER(c);
+  EvalRec r;
+  HIPCHK(hipMemcpyAsync(&r, c->eval_rec, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out->passes = r.passes; out->terms = r.terms; out->loss_sum = r.loss_sum; out->viol_sum = r.viol_sum;
+  out->last_loss = r.last_loss; out->last_violations = r.last_viol;
+  out->mean_loss = r.passes > 0 ? (float)(r.loss_sum / (double)r.passes) : 0.f;
+  out->mean_violations = r.passes > 0 ? (float)(r.viol_sum / (double)r.passes) : 0.f;
+  return VV_OK;
+}
+
 // The five forms of the update.  Each is handed the common SgdArgs (vv_apply_update's prologue), Adam's second history (vW / vb, or NULL)
 // and ends in finish_update.
 
@@ -1963,7 +2153,8 @@ int vv_grads_get(vv_ctx* c, float* dW, float* db) {
 
 int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_scores, float* ip1_diff) {
   if (!c) return fail(VV_ERR_ARG, "vv_blobs_get: ctx is NULL");
-  if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_blobs_get: no forward pass yet");
+  if (!grad_exists(c->grad) && !c->last_fwd_only) return fail(VV_ERR_STATE, "vv_blobs_get: no forward pass yet");
+  if (ip1_diff && c->last_fwd_only) return fail(VV_ERR_STATE, "vv_blobs_get: ip1_diff after vv_forward -- the forward-only pass computes no gradient (until the next backward pass)");
   VV_ENTER(c);
   { const int rcj = comm_join(c); if (rcj) return rcj; }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -2061,6 +2252,7 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
 int vv_dedup_groups_get(vv_ctx* c, int32_t* rows, int32_t* uniq_rows, int32_t* map, int32_t* ord, int32_t* cnt, int32_t* seg_start,
                         int32_t* pos, float* dyu, float* scale) {
   if (!c) return fail(VV_ERR_ARG, "vv_dedup_groups_get: ctx is NULL");
+  if (c->last_fwd_only) return fail(VV_ERR_STATE, "vv_dedup_groups_get: the last forward pass was vv_forward's -- its grouping belongs to no backward pass (until the next one)");
   if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_dedup_groups_get: no forward pass yet");
   if (!c->last_dedup) return fail(VV_ERR_STATE, "vv_dedup_groups_get: the last forward pass was dense (vv_set_dedup, dropout)");
   VV_ENTER(c);

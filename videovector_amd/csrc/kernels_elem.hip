@@ -114,7 +114,12 @@ __device__ __forceinline__ float block_sum_w(float v, float* red) {
 // NT threads per item: 256 (four waves) where a batch brings a thousand items; 1024 for wide rows in small batches (the reference's
 // shipped configuration: 128 items of 15 rows x 4096 columns -- with four waves per item half of the chip's SIMDs had no wave at all
 // and every row was one wave's serial chain of loads: 55 us for 47 MB)
-template <typename T, bool VEC, int NT = SL_THREADS>
+// FWD (ScoreArgs::fwd_only, vv_forward): the forward-only instantiation -- phases 1 to 3, then every workgroup leaves: scores, loss and violation
+// partials; nothing of the backward is computed or stored (dYh, dbp, the guard's slots).  The exit is a RUN-TIME test of a.fwd_only that only this
+// instantiation carries, not a truncated body: with phases 4 and 5 cut off at compile time the vectoriser formed phase 2's sums differently
+// (fma chains where the training kernel has packed multiplies and adds) and the target score moved by one ulp -- the pass must give the
+// training pass's bits.  FWD = false is the kernel as it always was, instruction for instruction.
+template <typename T, bool VEC, int NT = SL_THREADS, bool FWD = false>
 __global__ __launch_bounds__(NT) void k_score_loss(ScoreArgs a) {
   constexpr int NWV = NT / 64;
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -211,6 +216,7 @@ __global__ __launch_bounds__(NT) void k_score_loss(ScoreArgs a) {
     // are live: at the kernel's head it cost the RPW 7 form six registers and, at 133, an occupancy step)
     if (a.gate_host && b == 0) __hip_atomic_store(a.gate_host, a.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  if constexpr (FWD) { if (a.fwd_only) return; }      // the forward-only pass ends here (a run-time exit: see FWD above)
   __syncthreads();
   // per-row constants, once per row instead of once per (row, column group): g*sg = k1*Ah - k2*x, dAh += k3*x
   for (int qi = tid; qi < 1 + Nn; qi += NT) {
@@ -310,7 +316,8 @@ __device__ __forceinline__ void block_sum3_w(float& x, float& y, float& z, float
 // Eight waves with two rows each keep the register footprint small enough for every workgroup of a 1024-item batch to
 // be resident at once (the four-wave form held 13 row slots per wave: ~200 VGPRs, two rounds of workgroups, and the
 // block-wide sums of each phase were exposed latency).
-template <typename T, int NW, int RPW, int DV>
+// FWD: the forward-only instantiation, as k_score_loss's.
+template <typename T, int NW, int RPW, int DV, bool FWD = false>
 __global__ __launch_bounds__(64 * NW) void k_score_loss_reg(ScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int THREADS = 64 * NW;
@@ -425,6 +432,7 @@ __global__ __launch_bounds__(64 * NW) void k_score_loss_reg(ScoreArgs a) {
     // are live: at the kernel's head it cost the RPW 7 form six registers and, at 133, an occupancy step)
     if (a.gate_host && b == 0) __hip_atomic_store(a.gate_host, a.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  if constexpr (FWD) { if (a.fwd_only) return; }      // the forward-only pass ends here (a run-time exit: see FWD above)
   __syncthreads();
 
   // ---- phase 4: backward of this wave's rows from registers; one coalesced 512-B store per chunk.  Per row three
@@ -521,11 +529,21 @@ static bool launch_score_loss_reg(const ScoreArgs& a, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)k_score_loss_reg<T, 8, RPW, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     VV_LAUNCH((k_score_loss_reg<T, 8, RPW, 2>), dim3(a.B), dim3(512), lds, s, a);                         \
   } while (0)
+#define VV_SLRF(RPW)                                                                                      \
+  do {                                                                                                    \
+    (void)hipFuncSetAttribute((const void*)k_score_loss_reg<F16, 8, RPW, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    VV_LAUNCH((k_score_loss_reg<F16, 8, RPW, 2, true>), dim3(a.B), dim3(512), lds, s, a);                 \
+  } while (0)
+  if (rows > 56) return false;
+  if (a.fwd_only) {                               // (the forward-only pass rounds nothing to 16 bits: one operand type serves both)
+    if (rows <= 16) VV_SLRF(2); else if (rows <= 32) VV_SLRF(4); else VV_SLRF(7);
+    return true;
+  }
   if (rows <= 16) VV_SLR(2);
   else if (rows <= 32) VV_SLR(4);
-  else if (rows <= 56) VV_SLR(7);
-  else return false;
+  else VV_SLR(7);
 #undef VV_SLR
+#undef VV_SLRF
   return true;
 }
 
@@ -560,7 +578,9 @@ template <bool H16, int DV> __device__ __forceinline__ void h_row(const float* H
 // (Round 6, with f16 rows -- 86 VGPRs instead of 112-127 -- two more residencies were measured and not kept: capped at 80 VGPRs = three
 // workgroups per CU instead of two, 7 registers spilled: 22.9 -> 23.7 us; FOUR waves per item with 14 rows per wave, three or four 256-thread
 // workgroups per CU = all 1024 items resident at once: 23.0 -> 26.2-27.1 us.  tools/sessions/r06_log.md s5, s8.)
-template <int NW, int RPW, int DV, bool DROP = false, bool H16 = false>
+// FWD (ScoreArgs::fwd_only, vv_forward): the forward-only instantiation -- the same row loads, masks, sums and scores, ending behind the loss
+// and violation partials; neither the per-item vectors (V) nor the instances' records, positions or gradient bound are computed or stored.
+template <int NW, int RPW, int DV, bool DROP = false, bool H16 = false, bool FWD = false>
 __global__ __launch_bounds__(64 * NW) void k_score_fwd(ScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int THREADS = 64 * NW;
@@ -652,6 +672,7 @@ __global__ __launch_bounds__(64 * NW) void k_score_fwd(ScoreArgs a) {
   float cf[CXM];
 #pragma unroll
   for (int j = 0; j < CXM; ++j) cf[j] = j + 1 < C ? a.coeff[j] : 0.f;
+  if constexpr (!FWD)
   for (int ch = tid; ch < CN; ch += THREADS) {
     const int r = b * CN + ch;
     ooff[ch] = a.seg_start[a.map[r]] + a.ord[r];
@@ -675,7 +696,7 @@ __global__ __launch_bounds__(64 * NW) void k_score_fwd(ScoreArgs a) {
   for (int v = 0; v < CV; ++v) {
     const float ah = A[tid + v * THREADS] / nA;
     Ah[tid + v * THREADS] = ah;
-    Vb[tid + v * THREADS] = ah;
+    if constexpr (!FWD) Vb[tid + v * THREADS] = ah;
   }
   __syncthreads();
 
@@ -720,12 +741,12 @@ __global__ __launch_bounds__(64 * NW) void k_score_fwd(ScoreArgs a) {
     else { lsum += wb * fabsf(h); g = h > 0.f ? wb * a.grad_scale : 0.f; }
     vsum += d < 0.f ? 1.f : 0.f;
     gsum += g;
-    cq[ch] = g;
+    if constexpr (!FWD) cq[ch] = g;
     if (a.s_bogus) a.s_bogus[(int64_t)b * Nn + k] = sn;
   }
   block_sum3_w<NW>(lsum, vsum, gsum, red);
   if (tid == 0) {
-    cq[0] = -gsum;
+    if constexpr (!FWD) cq[0] = -gsum;
     a.loss_part[b] = lsum;
     a.viol_part[b] = vsum;
     if (a.s_true) a.s_true[b] = sp;
@@ -733,6 +754,7 @@ __global__ __launch_bounds__(64 * NW) void k_score_fwd(ScoreArgs a) {
     // are live: at the kernel's head it cost the RPW 7 form six registers and, at 133, an occupancy step)
     if (a.gate_host && b == 0) __hip_atomic_store(a.gate_host, a.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  if constexpr (FWD) return;                       // the forward-only pass ends here
   __syncthreads();
   SF_TS(3)
 
@@ -830,9 +852,11 @@ __global__ __launch_bounds__(64 * NW) void k_score_fwd(ScoreArgs a) {
 // applies its own mask and 1 / (1 - ratio) as its row arrives (context rows in the column-parallel mean, the target row of every wave, every
 // negative of the sweep); everything behind the masked rows is the kernel without DROP, and the records carry their one factor scale in
 // a.drop_scale as before.  A separate instantiation: without DROP nothing of it is compiled.
-template <int NW, int DV, bool H16 = false, bool V16 = false, bool DROP = false>
+// FWD: the forward-only instantiation, as k_score_fwd's -- the sweep keeps its loads, masks, reductions and sums, and stores scores and partials only.
+template <int NW, int DV, bool H16 = false, bool V16 = false, bool DROP = false, bool FWD = false>
 __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(ScoreArgs a) {
   static_assert(!DROP || !V16, "dropout steps run with v16 off");
+  static_assert(!FWD || !V16, "the forward-only pass stores no per-item vectors");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int THREADS = 64 * NW;
   constexpr int CV = 256 * DV / THREADS;
@@ -875,7 +899,7 @@ __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(Score
     const int d = tid + v * THREADS;
     const float ah = A[d] / nA;
     Ah[d] = ah;
-    if (V16) Vh[d] = (_Float16)ah; else Vb[d] = ah;
+    if constexpr (!FWD) { if (V16) Vh[d] = (_Float16)ah; else Vb[d] = ah; }
   }
   __syncthreads();
   float4 y[DV];
@@ -942,6 +966,9 @@ __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(Score
     else { lsum += wb * fabsf(h); g = h > 0.f ? wb * a.grad_scale : 0.f; }
     vsum += d < 0.f ? 1.f : 0.f;
     gsum += g;
+    if constexpr (FWD) {
+      if (lane == 0 && a.s_bogus) a.s_bogus[(int64_t)b * Nn + k] = sn;
+    } else {
     const float k3 = g * __builtin_amdgcn_rcpf(rs + eps);
     const float cd = g * __builtin_amdgcn_rcpf(sq * rs + eps) * a.drop_scale * a.sg;
     bnd = fmaxf(bnd, fabsf(cd * sq) + fabsf(cd * tq) * rs);          // |alpha| + |beta| |x|: GuardArgs::bound
@@ -953,6 +980,7 @@ __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(Score
 #pragma unroll
     for (int v = 0; v < DV; ++v) {
       pa[v].x += k3 * xc[v].x; pa[v].y += k3 * xc[v].y; pa[v].z += k3 * xc[v].z; pa[v].w += k3 * xc[v].w;
+    }
     }
     if (more) {
 #pragma unroll
@@ -972,6 +1000,7 @@ __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(Score
     if (a.s_true) a.s_true[b] = sp;
     if (a.gate_host && b == 0) __hip_atomic_store(a.gate_host, a.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  if constexpr (FWD) return;                        // the forward-only pass ends here
   // ---- the target row: coefficient -sum_k g_k (wave 0 adds it to its partial)
   if (wave == 0) {
     const float c = -gsum, rs = sqrtf(s0);
@@ -1084,7 +1113,19 @@ void launch_score_fwd(const ScoreArgs& a_in, hipStream_t s) {
       VV_LAUNCH((k_score_stream<8, DV, H16, false, true>), dim3(a.B), dim3(512), lds, s, a);               \
     } while (0)
     ko().last_score_form = a.D == 512 ? 2 : 3;
-    if (a.drop.mode) {                            // (fp32 vectors: dropout steps run with v16 off)
+    if (a.fwd_only) {                             // (no per-item vectors leave the kernel: v16 has nothing to choose)
+#define VV_SSF(DV, H16, DROP)                                                                              \
+    do {                                                                                                  \
+      (void)hipFuncSetAttribute((const void*)k_score_stream<8, DV, H16, false, DROP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      VV_LAUNCH((k_score_stream<8, DV, H16, false, DROP, true>), dim3(a.B), dim3(512), lds, s, a);         \
+    } while (0)
+#define VV_SSF2(DV) do { if (a.drop.mode) { if (a.h16) VV_SSF(DV, true, true); else VV_SSF(DV, false, true); } \
+                         else { if (a.h16) VV_SSF(DV, true, false); else VV_SSF(DV, false, false); } } while (0)
+      if (a.D == 512) VV_SSF2(2); else VV_SSF2(4);
+#undef VV_SSF2
+#undef VV_SSF
+    }
+    else if (a.drop.mode) {                       // (fp32 vectors: dropout steps run with v16 off)
       if (a.D == 512) { if (a.h16) VV_SSD(2, true); else VV_SSD(2, false); }
       else { if (a.h16) VV_SSD(4, true); else VV_SSD(4, false); }
     }
@@ -1110,11 +1151,28 @@ void launch_score_fwd(const ScoreArgs& a_in, hipStream_t s) {
     if (a.drop.mode) { if (a.h16) VV_SF1(RPW, true, true); else VV_SF1(RPW, true, false); }               \
     else { if (a.h16) VV_SF1(RPW, false, true); else VV_SF1(RPW, false, false); }                         \
   } while (0)
-  if (rows <= 16) VV_SF(2);
+#define VV_SFF1(RPW, DROP, H16)                                                                           \
+  do {                                                                                                    \
+    (void)hipFuncSetAttribute((const void*)k_score_fwd<8, RPW, 2, DROP, H16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    VV_LAUNCH((k_score_fwd<8, RPW, 2, DROP, H16, true>), dim3(a.B), dim3(512), lds, s, a);                 \
+  } while (0)
+#define VV_SFF(RPW)                                                                                       \
+  do {                                                                                                    \
+    if (a.drop.mode) { if (a.h16) VV_SFF1(RPW, true, true); else VV_SFF1(RPW, true, false); }             \
+    else { if (a.h16) VV_SFF1(RPW, false, true); else VV_SFF1(RPW, false, false); }                       \
+  } while (0)
+  if (a.fwd_only) {
+    // (no second-round prefetch: its LDS-DMA is never waited for, and this form ends a few instructions behind where it would be issued)
+    a.prefetch = 0;
+    if (rows <= 16) VV_SFF(2); else if (rows <= 32) VV_SFF(4); else VV_SFF(7);
+  }
+  else if (rows <= 16) VV_SF(2);
   else if (rows <= 32) VV_SF(4);
   else VV_SF(7);
 #undef VV_SF
 #undef VV_SF1
+#undef VV_SFF
+#undef VV_SFF1
 }
 
 // eight consecutive columns of a row of H (fp32: two 16-byte loads; f16, SegBwdArgs::h16: one)
@@ -1449,9 +1507,17 @@ void launch_score_loss(int prec, const ScoreArgs& a_in, hipStream_t s) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
     VV_LAUNCH((k_score_loss<T, V, NT>), grid, block, lds, s, a);                        \
   } while (0)
-  if (prec == 0) { if (wide) VV_SL(F16, true, 1024); else if (vec) VV_SL(F16, true, SL_THREADS); else VV_SL(F16, false, SL_THREADS); }
+#define VV_SLF(V, NT)                                                                            \
+  do {                                                                                           \
+    (void)hipFuncSetAttribute((const void*)k_score_loss<F16, V, NT, true>,                       \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
+    VV_LAUNCH((k_score_loss<F16, V, NT, true>), grid, block, lds, s, a);                \
+  } while (0)
+  if (a.fwd_only) { if (wide) VV_SLF(true, 1024); else if (vec) VV_SLF(true, SL_THREADS); else VV_SLF(false, SL_THREADS); }
+  else if (prec == 0) { if (wide) VV_SL(F16, true, 1024); else if (vec) VV_SL(F16, true, SL_THREADS); else VV_SL(F16, false, SL_THREADS); }
   else { if (wide) VV_SL(BF16, true, 1024); else if (vec) VV_SL(BF16, true, SL_THREADS); else VV_SL(BF16, false, SL_THREADS); }
 #undef VV_SL
+#undef VV_SLF
 }
 
 // loss = scale * sum(loss_part), violations = sum(viol_part); fixed-order (deterministic)
@@ -1466,6 +1532,26 @@ __global__ void k_final_loss(const float* lp, const float* vp, int B, float scal
 void launch_final_loss(const float* lp, const float* vp, int B, float scale, float* out2,
                        hipStream_t s) {
   hipLaunchKernelGGL(k_final_loss, dim3(1), dim3(256), 0, s, lp, vp, B, scale, out2);
+}
+
+// The forward-only pass's loss reduction (vv_forward): one workgroup, the fold of the training path's loss workgroup (reduce_loss below:
+// thread t adds partials t, t + 256, ... in order, then block_sum) -- the same bits from the same partials -- and the evaluation record:
+// thread 0 alone updates it, so the sums are added in pass order with no atomics and nothing synchronises per pass.
+__global__ __launch_bounds__(256) void k_eval_loss(const float* lp, const float* vp, int B, float scale, int64_t terms, EvalRec* rec) {
+  __shared__ float red[8];
+  float l = 0.f, v = 0.f;
+  for (int i = threadIdx.x; i < B; i += 256) { l += lp[i]; v += vp[i]; }
+  l = block_sum(l, red);
+  v = block_sum(v, red + 4);
+  if (threadIdx.x == 0) {
+    const float loss = l * scale;
+    rec->last_loss = loss; rec->last_viol = v;
+    rec->loss_sum += (double)loss; rec->viol_sum += (double)v;      // (an fp32 value is exact in double)
+    rec->passes += 1; rec->terms += terms;
+  }
+}
+void launch_eval_loss(const float* lp, const float* vp, int B, float scale, int64_t terms, EvalRec* rec, hipStream_t s) {
+  VV_LAUNCH(k_eval_loss, dim3(1), dim3(256), 0, s, lp, vp, B, scale, terms, rec);
 }
 
 // ------------------------------------------------------------------------------- reduce -------

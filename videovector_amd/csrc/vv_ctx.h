@@ -142,11 +142,14 @@ struct vv_ctx {
   // indices): four sets of their output arrays rotate (dd_* above point at the set of the step being issued), the forward
   // GEMM's sequence stamp says when the step that read a set is over, an event per set when its grouping is done.
   static constexpr int kDdSets = 4;
+  // ... and one more set that never rotates, for the forward-only pass (vv_forward): a training step's set -- which its pending reduction
+  // still names (ReduceArgs::gcnt) -- is never the one an evaluation pass regroups, however many passes run between two steps
+  static constexpr int kDdEval = kDdSets, kDdAll = kDdSets + 1;
   struct DdSet {
     int32_t *rows = nullptr, *slot_of = nullptr, *uniq = nullptr, *map = nullptr, *ord = nullptr, *cnt = nullptr, *seg = nullptr,
             *info = nullptr;
     hipEvent_t done = nullptr; int32_t used_seq = 0;      // sequence number of the step that last read the set
-  } dd_set[kDdSets];
+  } dd_set[kDdAll];
   int32_t* dd_info_all = nullptr;
   int32_t* dd_rows = nullptr;      // instance -> table row of the current set (k_dd_claim's output)
   hipStream_t dd_stream = nullptr;
@@ -160,6 +163,17 @@ struct vv_ctx {
   int32_t* stage_dev[kStage] = {};          // the device's alias of the same memory
   int32_t stage_seq[kStage] = {};           // sequence number of the step that last read the slot
   size_t stage_bytes = 0; int32_t stage_next = 0;
+  // The forward-only evaluation pass (vv_forward) owns: its loss / violation partials (per batch shape; the training step's are pending
+  // until its reduction runs), the record vv_eval_stats reads, the grouping set above with an event that says when the pass that read it
+  // is over, and two pinned index staging buffers of its own (the training slots are released by sequence stamps a pass does not take)
+  float *eval_loss_part = nullptr, *eval_viol_part = nullptr;
+  vv::EvalRec* eval_rec = nullptr;
+  bool last_fwd_only = false;               // the last forward pass was vv_forward's: the accessors of backward values refuse
+  hipEvent_t ev_eval = nullptr; bool eval_set_used = false;
+  static constexpr int kEvalStage = 2;
+  int32_t* eval_stage_host[kEvalStage] = {}; int32_t* eval_stage_dev[kEvalStage] = {};
+  hipEvent_t eval_stage_done[kEvalStage] = {}; bool eval_stage_busy[kEvalStage] = {};
+  size_t eval_stage_bytes = 0; int eval_stage_next = 0;
   int32_t* seq_host = nullptr;              // pinned + mapped, two words.  [0]: the forward GEMM stores the step's sequence
   int32_t* seq_host_dev = nullptr;          //   number here when it starts, i.e. "the kernels that read this step's index
                                             //   batch have finished"; [1]: the score kernel does when IT starts, i.e. "this

@@ -209,7 +209,10 @@ struct ScoreArgs {
   SegRec* rec = nullptr;             // [R]
   unsigned long long* bound_out = nullptr;   // GuardArgs::bound: (seq << 32) | bits of the largest per-instance element bound
   int32_t bound_seq = 0;
-  DropSpec drop;                     // de-duplicated execution with dropout (k_score_fwd): H holds the SHARED pre-dropout rows, every
+  int fwd_only = 0;                  // vv_forward: the launchers pick the forward-only instantiations (template parameter FWD) -- scores, loss and violation
+                                     // partials only; dYh / dbp / V / rec / bound_out / guard are not read.  (Sits in what was padding in front of
+                                     // `drop`: every other field, and the kernels' hidden arguments behind the struct, keep their offsets)
+  DropSpec drop;                    // de-duplicated execution with dropout (k_score_fwd): H holds the SHARED pre-dropout rows, every
                                      // instance applies its own mask as it reads its row
   int h16 = 0;                       // H holds f16 rows (FwdArgs::h16): launch_score_fwd's kernels only
   int v16 = 0;                       // V leaves as f16 (k_score_stream's V16 form; needs h16): SegBwdArgs::v16
@@ -217,6 +220,15 @@ struct ScoreArgs {
   int lab_hack = 0;                  // (lab builds, VV_LAB_SCORE_HACK: timing studies of k_score_fwd's row loads -- WRONG results) 1: rows 1 KiB apart (half the footprint, the same requests), 2: only the first half of every row is loaded (half the bytes and requests)
   uint32_t* lab_ts = nullptr;        // (lab builds, VV_LAB_SCORE_TS=1: 16 words per item -- shader-clock stamps of k_score_fwd's phases, 100 MHz
                                      //  real time of its start and end, the compute unit it ran on; the product never sets or reads it)
+};
+
+// The forward-only evaluation pass (vv_forward; Net::Forward under phase TEST called test_iter times by Solver::Test): what vv_eval_stats
+// reports, kept by k_eval_loss's first thread -- nothing synchronises per pass.  The sums are double: an fp32 value is exact in it, and
+// they are added in pass order.
+struct EvalRec {
+  int64_t passes, terms;              // passes since vv_eval_reset, and their loss terms (B Nn each)
+  double loss_sum, viol_sum;          // of last_loss / last_viol over those passes
+  float last_loss, last_viol;         // the fp32 values vv_loss_get would show for the last pass
 };
 
 // Row de-duplication of one batch (kernels_dedup.hip).  The sampler draws the negatives of every item
@@ -574,6 +586,8 @@ void launch_map_rows(const int32_t* idx, int32_t* rows, int R, int Rp, int32_t z
                      hipStream_t s);
 void launch_final_loss(const float* loss_part, const float* viol_part, int B, float scale,
                        float* out2, hipStream_t s);
+// vv_forward's loss reduction: the fold of k_reduce's loss workgroup (same order, same bits) into rec->last_*, and the record's sums
+void launch_eval_loss(const float* loss_part, const float* viol_part, int B, float scale, int64_t terms, EvalRec* rec, hipStream_t s);
 void launch_dyh_to_float(int prec, const uint16_t* dYh, int R, int D, int Dp, float inv_sg,
                          float* out, hipStream_t s);
 void launch_row_normalize(float* x, int n, int D, hipStream_t s);

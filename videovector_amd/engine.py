@@ -64,6 +64,25 @@ class _AccumReport(C.Structure):
                 ("updates", C.c_int64)]
 
 
+class _EvalReport(C.Structure):
+    _fields_ = [("passes", C.c_int64), ("terms", C.c_int64), ("loss_sum", C.c_double), ("viol_sum", C.c_double),
+                ("last_loss", C.c_float), ("last_violations", C.c_float), ("mean_loss", C.c_float), ("mean_violations", C.c_float)]
+
+
+class EvalStats:
+    """vv_eval_report: the forward-only passes since eval_reset().  last_* / mean_* are np.float32, the sums Python floats (double)."""
+    __slots__ = ("passes", "terms", "loss_sum", "viol_sum", "last_loss", "last_violations", "mean_loss", "mean_violations")
+
+    def __init__(self, r):
+        self.passes, self.terms = int(r.passes), int(r.terms)
+        self.loss_sum, self.viol_sum = float(r.loss_sum), float(r.viol_sum)
+        self.last_loss, self.last_violations = np.float32(r.last_loss), np.float32(r.last_violations)
+        self.mean_loss, self.mean_violations = np.float32(r.mean_loss), np.float32(r.mean_violations)
+
+    def __repr__(self):
+        return "EvalStats(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
 class _ClassStats(C.Structure):
     _fields_ = [("mean_ap", C.c_float), ("hit_at_1", C.c_float), ("hit_at_5", C.c_float), ("n_scored", C.c_int32)]
 
@@ -150,6 +169,7 @@ def load_library():
         "vv_clip_gradients_set": [vp, f32], "vv_clip_gradients_get": [vp, C.POINTER(f32)],
         "vv_clip_stats": [vp, C.POINTER(_ClipReport)],
         "vv_grads_bank": [vp], "vv_grads_bank_reset": [vp], "vv_accum_stats": [vp, C.POINTER(_AccumReport)],
+        "vv_forward": [vp, vp, vp, C.c_int], "vv_eval_reset": [vp], "vv_eval_stats": [vp, C.POINTER(_EvalReport)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -527,6 +547,29 @@ class Engine:
             idx = np.ascontiguousarray(idx, dtype=np.int32)
             assert idx.shape == (cfg.c.B, cfg.c.C + cfg.c.Nn)
             self._chk(self.L.vv_forward_backward(self.h, C.byref(cfg.c), _ptr(idx), 0))
+
+    # ---- the forward-only pass (Net::Forward under phase TEST; vv_forward, vv_eval_reset, vv_eval_stats)
+    def forward(self, cfg, idx, on_device=0):
+        """Held-out loss and violations with the current weights, no backward pass: nothing a training step owns is touched.
+        idx: host array [B][C+Nn] (on_device=0), or a device pointer (1: produced on the context's stream, 2: complete already).
+        The result accumulates in the record eval_stats() reads; loss() keeps returning the last TRAINING pass's values."""
+        self._ext(cfg)
+        if on_device:
+            self._chk(self.L.vv_forward(self.h, C.byref(cfg.c), C.c_void_p(int(idx)), int(on_device)))
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            assert idx.shape == (cfg.c.B, cfg.c.C + cfg.c.Nn)
+            self._chk(self.L.vv_forward(self.h, C.byref(cfg.c), _ptr(idx), 0))
+
+    def eval_reset(self):
+        """Zero the evaluation record (queued behind the passes already issued)."""
+        self._chk(self.L.vv_eval_reset(self.h))
+
+    def eval_stats(self):
+        """An EvalStats of the passes since eval_reset(): counts, double sums, the last pass's fp32 values, the means (synchronises)."""
+        r = _EvalReport()
+        self._chk(self.L.vv_eval_stats(self.h, C.byref(r)))
+        return EvalStats(r)
 
     def forward_backward_q1(self, cfg, idx, last_src):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

@@ -29,12 +29,19 @@ def train_net(source, B, C, Nn, D, *, max_buffer=5000, swap=50, max_same=0, drop
               norm="L2", name="videovec_train", w_std=0.001, test_source=None, test_batch=673, test_frames=4,
               id_to_class_file=None, id_to_weight_file=None, use_direct_weight=False, ip_regularization=0.0,
               context_type="WINDOW", rand_skip=0, negative_dataset=None, output_shot_distance=False,
-              max_shot_distance=None):
-    """test_source: also emit the TEST branch of the shipped file (window data -> average_for_test ->
+              max_shot_distance=None, held_out_source=None, held_out_batch=None):
+    """held_out_source: also emit the HELD-OUT branch -- a second VIDEO_SAMPLED_SHOTS_DATA layer on that source under
+    include { phase: TEST } (batch_size held_out_batch, default B; max_same_video_negs 0), and every TRAIN-phase layer behind it gains
+    include { phase: TEST } beside its include { phase: TRAIN } (include rules are alternatives): the TEST-phase net is the TRAIN graph
+    on held-out videos, which the facade runs as the forward-only pass (Solver::Test then prints its mean loss and train_violations;
+    `test_compute_loss: true` in the solver adds `Test loss:`).  Not together with test_source (one TEST-phase graph per file).
+    test_source: also emit the TEST branch of the shipped file (window data -> average_for_test ->
     [shared fc7 / fc7_relu] -> test_norm -> retrieval_stats).
     id_to_weight_file / use_direct_weight: the weighted loss -- the data layer's video ids, replicated to (B, Nn)
     by a SUM layer, become MAX_MARGIN_LOSS's third bottom (max_margin_loss_layer.cpp:18-37, 82-97)."""
     weighted = bool(id_to_weight_file) or use_direct_weight
+    if held_out_source and test_source:
+        raise ValueError("held_out_source and test_source both ask for the file's TEST-phase graph: give one")
     L = []
     a = L.append
     a('name: "%s"' % name)
@@ -50,6 +57,15 @@ def train_net(source, B, C, Nn, D, *, max_buffer=5000, swap=50, max_same=0, drop
                                           ('    negative_dataset: "%s"\n' % negative_dataset if negative_dataset else '') +
                                           ('    output_shot_distance: true\n' if output_shot_distance else '') +
                                           ('    max_shot_distance: %g\n' % max_shot_distance if max_shot_distance is not None else '')))
+    n_data = len(L)
+    if held_out_source:
+        a('layers {\n  name: "held_out_shot_windows"\n  type: VIDEO_SAMPLED_SHOTS_DATA\n  top: "data"\n' +
+          ('  top: "train_video_ids"\n' if weighted else '') +
+          '  video_sampled_shots_data_param {\n    source: "%s"\n    backend: LMDB\n    batch_size: %d\n'
+          '    num_negative_samples: %d\n    max_buffer_size: %d\n    negative_swap_percentage: %d\n'
+          '    max_same_video_negs: 0\n    context_type: %s\n    context_size: %d\n  }\n'
+          '  include: { phase: TEST }\n}' % (held_out_source, held_out_batch or B, Nn, max_buffer, swap, context_type, C))
+        n_data = len(L)
     if context_type == "PAIRWISE":
         C = 2                    # video_sampled_shots_data_layer.cpp:200-201
     datums = ["target_datum"] + ["context_datum_%d" % j for j in range(1, C)] + \
@@ -113,6 +129,9 @@ def train_net(source, B, C, Nn, D, *, max_buffer=5000, swap=50, max_same=0, drop
       % ('  bottom: "term_video_ids"\n' if weighted else '', norm, margin,
          '    id_to_weight_file: "%s"\n' % id_to_weight_file if id_to_weight_file else '',
          '    use_direct_weight: true\n' if use_direct_weight else ''))
+    if held_out_source:       # every layer behind the two data layers runs in both phases
+        for i in range(n_data, len(L)):
+            L[i] = L[i].replace("  include: { phase: TRAIN }\n", "  include: { phase: TRAIN }\n  include: { phase: TEST }\n")
     if test_source:
         a('layers {\n  name: "test_norm"\n  type: NORMALIZATION\n  bottom: "ip2"\n  top: "ip2_norm"\n'
           '  include: { phase: TEST }\n}')
@@ -141,7 +160,7 @@ def extraction_net(source, batch, D, *, normalize=False, w_std=0.001):
 def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_policy="inv", gamma=0.001,
            power=0.75, stepsize=0, display=10, max_iter=100, snapshot=0, snapshot_prefix="videovec",
            random_seed=-1, snapshot_after_train=True, test_iter=0, test_interval=0, solver_type=None, delta=None,
-           snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None):
+           snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None, test_compute_loss=False):
     """Same fields as projects/videovec_embedding/mednet_embedding_train_solver.prototxt (+ solver_type / delta, and BVLC Caffe's
     rms_decay / momentum2 for RMSPROP / ADAM, clip_gradients and iter_size, written only when given)."""
     s = ['net: "%s"' % net_path, "base_lr: %g" % base_lr, "momentum: %g" % momentum,
@@ -150,6 +169,8 @@ def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_pol
          "snapshot: %d" % snapshot, 'snapshot_prefix: "%s"' % snapshot_prefix, "solver_mode: GPU"]
     if test_iter:
         s += ["test_iter: %d" % test_iter, "test_interval: %d" % test_interval]
+    if test_compute_loss:
+        s.append("test_compute_loss: true")
     if stepsize:
         s.append("stepsize: %d" % stepsize)
     if random_seed >= 0:
