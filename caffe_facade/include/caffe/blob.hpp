@@ -22,6 +22,9 @@ class SyncedMemory {            // syncedmem.hpp:40-68
   void* mutable_gpu_data();
   SyncedHead head() const { return head_; }
   size_t size() const { return size_; }
+  // Blob::asum_data / asum_diff (blob.cpp:138-165) where the head is on the device: the statistics of the first n floats by vv_op_asum,
+  // nothing is downloaded.  false: the head is on the host (or there is no context) and nothing was computed.
+  bool device_asum(int64_t n, vv_abs_stat* out);
  private:
   void to_cpu();
   void to_gpu();

@@ -130,6 +130,14 @@ class Net {
   vector<float> params_lr_, params_weight_decay_;
   bool params_stale_ = false;        // device copy is newer than the host blobs
   bool debug_info_ = false;
+  // debug_info (net.cpp:580-636).  The layer-by-layer executor prints every layer's lines as the reference does; the fc layer's parameter
+  // lines -- its diffs and the master parameters live in the context -- and everything the fused plan prints come from
+  // vv_debug_stats_queue, around vv_debug_mark_update and the update, with one vv_debug_stats_get per display iteration (Update).
+  void ForwardDebugInfo(int layer_id);
+  void BackwardDebugInfo(int layer_id);
+  void UpdateDebugInfo(const vv_abs_stat* st);     // the fc layer's two [Update] lines
+  void FusedDebugInfo(const vv_abs_stat* st);      // the fused plan's [Forward] / [Backward] lines
+  int TopLayerOf(const string& blob_name) const;   // the layer that has the blob as a top (-1: none)
   FusedPlan plan_;
   struct BlobSym { int kind = 0, a = 0, reps = 1; };
   vector<BlobSym> blob_sym_;     // what every named blob of the TRAIN graph is in terms of the fused plan (blob_by_name)

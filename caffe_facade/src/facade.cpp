@@ -142,6 +142,11 @@ const void* SyncedMemory::cpu_data() { to_cpu(); return host_.data(); }
 void* SyncedMemory::mutable_cpu_data() { to_cpu(); head_ = HEAD_AT_CPU; return host_.data(); }
 const void* SyncedMemory::gpu_data() { to_gpu(); return dev_; }
 void* SyncedMemory::mutable_gpu_data() { to_gpu(); head_ = HEAD_AT_GPU; return dev_; }
+bool SyncedMemory::device_asum(int64_t n, vv_abs_stat* out) {
+  if (!dev_ || (head_ != HEAD_AT_GPU && head_ != SYNCED) || n < 1 || !Caffe::has_ctx()) return false;
+  VV_CHECK(vv_op_asum(ctx(), (const float*)dev_, n, out));
+  return true;
+}
 
 // ------------------------------------------------------------------------------- Blob ----------
 template <typename Dtype>
@@ -160,10 +165,20 @@ void Blob<Dtype>::Update() {
   Dtype* d = mutable_cpu_data(); const Dtype* g = cpu_diff();
   for (int i = 0; i < count_; ++i) d[i] -= g[i];
 }
+// blob.cpp:138-165 (caffe_gpu_asum where the head is on the device): there the sum is the library's, over the finite elements in double
+// (vv_op_asum), and only the record comes back; a head on the host is summed here as before
 template <typename Dtype>
-Dtype Blob<Dtype>::asum_data() const { Dtype s = 0; for (int i = 0; i < count_; ++i) s += std::fabs(cpu_data()[i]); return s; }
+Dtype Blob<Dtype>::asum_data() const {
+  vv_abs_stat st;
+  if (sizeof(Dtype) == sizeof(float) && data_ && data_->device_asum(count_, &st)) return (Dtype)st.asum;
+  Dtype s = 0; for (int i = 0; i < count_; ++i) s += std::fabs(cpu_data()[i]); return s;
+}
 template <typename Dtype>
-Dtype Blob<Dtype>::asum_diff() const { Dtype s = 0; for (int i = 0; i < count_; ++i) s += std::fabs(cpu_diff()[i]); return s; }
+Dtype Blob<Dtype>::asum_diff() const {
+  vv_abs_stat st;
+  if (sizeof(Dtype) == sizeof(float) && diff_ && diff_->device_asum(count_, &st)) return (Dtype)st.asum;
+  Dtype s = 0; for (int i = 0; i < count_; ++i) s += std::fabs(cpu_diff()[i]); return s;
+}
 template <typename Dtype>
 void Blob<Dtype>::CopyFrom(const Blob<Dtype>& source, bool copy_diff, bool reshape) {
   if (num_ != source.num() || channels_ != source.channels() || height_ != source.height() || width_ != source.width()) {

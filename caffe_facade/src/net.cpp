@@ -424,6 +424,7 @@ Dtype Net<Dtype>::ForwardFromTo(int start, int end) {
     const Dtype l = layers_[li]->Forward(bottom_vecs_[li], &top_vecs_[li]);
     loss += l;
     if (debug_info_) LOG(INFO) << "    [Forward] Layer " << layer_names_[li] << ", loss " << l;
+    if (debug_info_) ForwardDebugInfo(li);                                                // net.cpp:511
   }
   return loss;
 }
@@ -443,6 +444,7 @@ void Net<Dtype>::BackwardFromTo(int start, int end) {
     }
     layers_[li]->set_accumulate_bottom(acc);
     layers_[li]->Backward(top_vecs_[li], bottom_need_backward_[li], &bottom_vecs_[li]);
+    if (debug_info_) BackwardDebugInfo(li);                                               // net.cpp:575
   }
 }
 
@@ -546,6 +548,11 @@ Dtype Net<Dtype>::ForwardBackward(const vector<Blob<Dtype>*>&) {
   for (size_t i = 0; i < idx_.size() && !q1; ++i) q1 = idx_[i] != last_src_[i];
   if (q1) VV_CHECK(vv_forward_backward_q1(ctx_, &cfg_, idx_.data(), last_src_.data()));
   else VV_CHECK(vv_forward_backward(ctx_, &cfg_, idx_.data(), 0));
+  if (debug_info_) {                   // this pass's scores and gradient (with iter_size > 1 the last micro-batch's stand); printed by Update
+    uint32_t mask = 1u << VV_STAT_TARGET_SCORE | 1u << VV_STAT_NEGATIVE_SCORES;
+    for (int k = 0; k < 2; ++k) if (cfg_.lr_mult[k] != 0.f) mask |= 1u << (VV_STAT_DW + k);
+    VV_CHECK(vv_debug_stats_queue(ctx_, mask));
+  }
   ++iter_;
   const double tp2 = g_hprof.on ? HostProf::now() : 0;
   if (g_hprof.on) { g_hprof.t_batch += tp1 - tp0; g_hprof.t_fb += tp2 - tp1; ++g_hprof.n; }
@@ -743,10 +750,102 @@ void Net<Dtype>::HintUpdate() {
   if (sequential_ || plan_.test || debug_info_ || !ctx_) return;
   VV_CHECK(vv_update_hint(ctx_, &cfg_));
 }
+// ---- debug_info (net.cpp:580-636): the mean absolute value of blobs, asum / count
+namespace {
+inline float MeanAbs(const vv_abs_stat& s) { return s.count ? (float)(s.asum / (double)s.count) : 0.f; }
+}
+template <typename Dtype>
+void Net<Dtype>::ForwardDebugInfo(int li) {                    // net.cpp:580-590
+  for (size_t t = 0; t < top_vecs_[li].size(); ++t) {
+    const Blob<Dtype>& blob = *top_vecs_[li][t];
+    const Dtype v = blob.asum_data() / blob.count();
+    LOG(INFO) << "    [Forward] Layer " << layer_names_[li] << ", top blob " << blob_names_[top_id_vecs_[li][t]] << " data: " << v;
+  }
+}
+template <typename Dtype>
+void Net<Dtype>::BackwardDebugInfo(int li) {                   // net.cpp:592-613
+  for (size_t b = 0; b < bottom_vecs_[li].size(); ++b) {
+    if (!bottom_need_backward_[li][b]) continue;
+    const Blob<Dtype>& blob = *bottom_vecs_[li][b];
+    const Dtype v = blob.asum_diff() / blob.count();
+    LOG(INFO) << "    [Backward] Layer " << layer_names_[li] << ", bottom blob " << blob_names_[bottom_id_vecs_[li][b]] << " diff: " << v;
+  }
+  if (li == plan_.ip_layer) {
+    // the fc layer's diffs are the context's gradient buffer (vv_op_inner_product_bwd); param_propagate_down = a non-zero blobs_lr (net.cpp:113-118)
+    uint32_t mask = 0;
+    for (int k = 0; k < 2; ++k) if (cfg_.lr_mult[k] != 0.f) mask |= 1u << (VV_STAT_DW + k);
+    if (!mask) return;
+    vv_abs_stat st[VV_STAT_N];
+    VV_CHECK(vv_debug_stats_queue(ctx_, mask));
+    VV_CHECK(vv_debug_stats_get(ctx_, st));
+    for (int k = 0; k < 2; ++k)
+      if (mask >> (VV_STAT_DW + k) & 1u)
+        LOG(INFO) << "    [Backward] Layer " << layer_names_[li] << ", param blob " << k << " diff: " << MeanAbs(st[VV_STAT_DW + k]);
+    return;
+  }
+  for (size_t k = 0; k < layers_[li]->blobs().size(); ++k) {
+    if (!layers_[li]->param_propagate_down((int)k)) continue;
+    const Blob<Dtype>& blob = *layers_[li]->blobs()[k];
+    const Dtype v = blob.asum_diff() / blob.count();
+    LOG(INFO) << "    [Backward] Layer " << layer_names_[li] << ", param blob " << k << " diff: " << v;
+  }
+}
+template <typename Dtype>
+int Net<Dtype>::TopLayerOf(const string& blob_name) const {
+  const auto it = blob_names_index_.find(blob_name);
+  if (it == blob_names_index_.end()) return -1;
+  for (size_t li = 0; li < layers_.size(); ++li)
+    for (int id : top_id_vecs_[li]) if (id == it->second) return (int)li;
+  return -1;
+}
+// The fused plan holds no per-layer blobs: it prints the lines of what it holds -- the two score blobs, the loss layer's tops (kept
+// current on a display iteration), the fc layer's parameter diffs -- in layer order.  VV_FACADE_SEQUENTIAL=1 gives every layer's lines.
+template <typename Dtype>
+void Net<Dtype>::FusedDebugInfo(const vv_abs_stat* st) {
+  struct Line { int layer; string blob; float v; };
+  vector<Line> fwd;
+  auto add = [&](const string& blob, float v) { const int li = TopLayerOf(blob); if (li >= 0) fwd.push_back(Line{li, blob, v}); };
+  add(plan_.target_score_blob, MeanAbs(st[VV_STAT_TARGET_SCORE]));
+  add(plan_.negative_scores_blob, MeanAbs(st[VV_STAT_NEGATIVE_SCORES]));
+  for (const string& name : {plan_.loss_blob, plan_.violations_blob})
+    if (has_blob(name)) add(name, (float)std::fabs(blobs_[blob_names_index_[name]]->cpu_data()[0]));
+  std::stable_sort(fwd.begin(), fwd.end(), [](const Line& a, const Line& b) { return a.layer < b.layer; });
+  for (const Line& l : fwd) LOG(INFO) << "    [Forward] Layer " << layer_names_[l.layer] << ", top blob " << l.blob << " data: " << l.v;
+  for (int k = 0; k < 2; ++k)
+    if (cfg_.lr_mult[k] != 0.f)
+      LOG(INFO) << "    [Backward] Layer " << layer_names_[plan_.ip_layer] << ", param blob " << k << " diff: " << MeanAbs(st[VV_STAT_DW + k]);
+}
+// net.cpp:615-636 for the fc layer's two blobs (nothing is shared: param_owner < 0; the display name is the parameter's index in the
+// net, net.cpp:433-438).  data: the parameter in front of the update; diff: what the update subtracted (vv_debug_mark_update).
+template <typename Dtype>
+void Net<Dtype>::UpdateDebugInfo(const vv_abs_stat* st) {
+  int p0 = 0;
+  for (int li = 0; li < plan_.ip_layer; ++li) p0 += (int)layers_[li]->blobs().size();
+  for (int k = 0; k < 2; ++k)
+    LOG(INFO) << "    [Update] Layer " << layer_names_[plan_.ip_layer] << ", param " << p0 + k << " data: " << MeanAbs(st[VV_STAT_W + k])
+              << "; diff: " << MeanAbs(st[VV_STAT_UPD_W + k]);
+}
 template <typename Dtype>
 void Net<Dtype>::Update() {
+  if (!debug_info_) {
+    VV_CHECK(vv_apply_update(ctx_, &cfg_));
+    params_stale_ = true;
+    return;
+  }
+  const uint32_t data_mask = 1u << VV_STAT_W | 1u << VV_STAT_B, upd_mask = 1u << VV_STAT_UPD_W | 1u << VV_STAT_UPD_B;
+  VV_CHECK(vv_debug_stats_queue(ctx_, data_mask));             // the parameters before they change, as net.cpp:616-626 reads them
+  VV_CHECK(vv_debug_mark_update(ctx_));
   VV_CHECK(vv_apply_update(ctx_, &cfg_));
   params_stale_ = true;
+  VV_CHECK(vv_debug_stats_queue(ctx_, upd_mask));
+  vv_abs_stat st[VV_STAT_N];
+  VV_CHECK(vv_debug_stats_get(ctx_, st));                      // the one synchronisation of a display iteration's lines
+  if (!sequential_) FusedDebugInfo(st);
+  UpdateDebugInfo(st);
+  static const char* const kNames[VV_STAT_N] = {"W", "b", "history W", "history b", "dW", "db", "target_score", "negative_scores", "update W", "update b"};
+  std::ostringstream bad;
+  for (int e = 0; e < VV_STAT_N; ++e) if (st[e].nonfinite) bad << (bad.tellp() > 0 ? ", " : "") << kNames[e] << " " << (long long)st[e].nonfinite;
+  if (bad.tellp() > 0) LOG(INFO) << "    [Debug] non-finite: " << bad.str();
 }
 
 template <typename Dtype>

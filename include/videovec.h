@@ -245,6 +245,60 @@ typedef struct { int32_t banked;                    /* gradients in the bank now
                  int64_t updates; } vv_accum_report;    /* accumulated updates since vv_create */
 int vv_accum_stats(vv_ctx* ctx, vv_accum_report* out);
 
+/* ---- magnitude statistics: the reference's SolverParameter.debug_info (caffe.proto field 23).  Net::ForwardDebugInfo, BackwardDebugInfo
+ * and UpdateDebugInfo (net.cpp:580-636) print asum / count -- the mean absolute value -- of top blobs, bottom and parameter diffs and
+ * parameters; Blob::asum_data / asum_diff (blob.cpp:138-165) are one caffe_gpu_asum each.  Here one kernel (k_abs_stats) measures up to
+ * eight device buffers per launch on the step's stream and leaves one record per buffer; nothing is downloaded but the records.
+ *   asum       the sum of |x| over the FINITE elements, accumulated in double in a fixed order (no atomics: the same buffer gives the
+ *              same bits on every run)
+ *   amax       the largest finite |x|
+ *   nonfinite  the number of NaN and +-Inf elements; they count neither in asum nor in amax (the reference's asum would be NaN or Inf)
+ *   count      the number of elements
+ * The reference's printed value is (float)(asum / count). */
+typedef struct { double asum; float amax; int32_t reserved_; int64_t count, nonfinite; } vv_abs_stat;
+/* Blob::asum_data / asum_diff (blob.cpp:138-165; the lines of net.cpp:580-636 are built on them) without the download: the statistics of
+ * n fp32 elements of DEVICE memory of this context (vv_dev_alloc), read as they are on the context's stream.  Synchronises.  n >= 1,
+ * else VV_ERR_ARG. */
+int vv_op_asum(vv_ctx* ctx, const float* x_dev, int64_t n, vv_abs_stat* out);
+/* The tensors of the fused training step that vv_debug_stats_queue can measure. */
+enum { VV_STAT_W, VV_STAT_B,                              /* the fp32 master parameters (net.cpp:616-626, "[Update] ... data") */
+       VV_STAT_HIST_W, VV_STAT_HIST_B,                    /* the solver's (first) history */
+       VV_STAT_DW, VV_STAT_DB,                            /* the gradient (net.cpp:604-612, "[Backward] ... param blob k diff") */
+       VV_STAT_TARGET_SCORE, VV_STAT_NEGATIVE_SCORES,     /* the two score blobs (net.cpp:580-590, "[Forward] ... top blob B data") */
+       VV_STAT_UPD_W, VV_STAT_UPD_B,                      /* what the last update subtracted (net.cpp:616-626, "[Update] ... diff") */
+       VV_STAT_N };
+/* vv_debug_stats_queue (Net::ForwardDebugInfo / BackwardDebugInfo / UpdateDebugInfo, net.cpp:580-636; Blob::asum_*, blob.cpp:138-165):
+ * queues one k_abs_stats launch (two where mask names more than eight entries) on the step's stream for the entries named by mask
+ * (bit VV_STAT_x), as they are at that point of the stream.  No host synchronisation; the record block is allocated by the first call
+ * that measures and never on the step path afterwards.  The kernel only reads what it measures: with nothing queued a training step is
+ * in every respect what it was, and parameters, histories, the 16-bit copy, loss and gradients of a run that queues statistics are bit
+ * for bit those of one that does not.
+ *   DW / DB     bring the gradient into the flat buffer as a reader of the gradient would (the lazy reduction of vv_grads_get): the values
+ *               vv_grads_get would return at that moment -- after a clipping or accumulated update, the clipped / normalised buffer
+ *   scores      the two score buffers of the last forward pass (vv_forward_backward* or vv_forward).  target_score is held once per item
+ *               (count = B; the blob repeats each value num_negative_samples times, which changes neither the mean nor the maximum),
+ *               negative_scores has B x Nn values
+ *   UPD_W / _B  see vv_debug_mark_update
+ * mask == 0 or a bit from VV_STAT_N on: VV_ERR_ARG.  VV_ERR_STATE: gradient entries before any backward pass; gradient entries for a step
+ * announced by vv_update_hint (vv_step), between its backward pass and its update and after it -- that gradient is not kept; gradient entries
+ * while the buffer is laid out for the overlapped or sharded schedule; parameter, history and UPD entries between a hinted backward pass
+ * and its vv_apply_update (the parameters are half-way); score entries before any forward pass; UPD_* without a preceding
+ * vv_debug_mark_update; W / history / UPD entries while the sharded schedule (2) is selected (the master copy is complete on its owner only). */
+int vv_debug_stats_queue(vv_ctx* ctx, uint32_t mask);
+/* Of the debug lines (net.cpp:580-636, over Blob::asum_*, blob.cpp:138-165) the "[Update] ... diff" one (Net::UpdateDebugInfo,
+ * net.cpp:616-626, over Blob::asum_diff, blob.cpp:152-165) reads the diff blob,
+ * which the solver has overwritten with the value Net::Update subtracts.  The update kernels here keep no such buffer, so the library
+ * measures the subtraction itself: vv_debug_mark_update copies W and b into a shadow buffer, device to device on the step's stream (the
+ * shadow is allocated by the first call and never on the step path afterwards); VV_STAT_UPD_W / VV_STAT_UPD_B, queued after the
+ * following vv_apply_update, are the statistics of shadow - current, elementwise in fp32 -- one definition for all five solver rules.
+ * It differs from the reference's update value by the rounding of ONE fp32 subtraction per element: the reference measures u where
+ * W_new = fl(W - u), this measures fl(W - W_new).  A mark stays valid until vv_params_set.  VV_ERR_STATE: no parameters; between a hinted
+ * backward pass and its vv_apply_update; while the sharded schedule (2) is selected. */
+int vv_debug_mark_update(vv_ctx* ctx);
+/* What the lines of net.cpp:580-636 print (over blob.cpp:138-165): the record of every entry as its LAST queued launch left it.
+ * Synchronises the step's stream.  Entries never queued read all-zero. */
+int vv_debug_stats_get(vv_ctx* ctx, vv_abs_stat out[VV_STAT_N]);
+
 /* ---- one training iteration */
 typedef struct {
   /* shapes: VideoSampledShotsDataParameter batch_size / context_size / num_negative_samples

@@ -274,7 +274,7 @@ int vv_destroy(vv_ctx* c) {
   vv_ops_release(c);
   free_batch(c);
   dfree(c->table); dfree(c->patch_desc); dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh);
-  dfree(c->clip_rec); dfree(c->bank_rec);
+  dfree(c->clip_rec); dfree(c->bank_rec); dfree(c->stat_rec); dfree(c->upd_shadow);
   dfree(c->scales); dfree(c->wmax_blocks); dfree(c->grads_own); dfree(c->mask); dfree(c->loss2);
   dfree(c->dd_key); dfree(c->dd_info_all); dfree(c->gg); dfree(c->gg_bound); dfree(c->w_gate);
   if (c->gate_err) (void)hipHostFree(c->gate_err);
@@ -571,6 +571,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   if (D != c->D) {
     dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh); dfree(c->grads_own);
     dfree(c->bank_rec); c->bank_rec = nullptr; c->bank = nullptr;      // (the bank has the gradient buffer's size: the next vv_grads_bank allocates it anew)
+    dfree(c->upd_shadow); c->upd_shadow = nullptr;                     // (... and so has vv_debug_mark_update's shadow)
     c->W = c->b = c->hW = c->hb = c->hW2 = c->hb2 = nullptr; c->Wh = nullptr; c->grads = c->grads_own = nullptr;
     c->D = D; c->Dp = (int)round_up(D, D_ALIGN);
 #ifdef VV_LAB
@@ -609,6 +610,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   if (c->hW2) { HIPCHK(hipMemset(c->hW2, 0, nW * 4)); HIPCHK(hipMemset(c->hb2, 0, D * 4)); }
   c->adam_t = 0; c->hist2_partial = false;
   c->bank_count = 0; c->grad_banked = false; c->fb_hinted = false;      // banked gradients belonged to the old parameters (vv_grads_bank_reset)
+  c->upd_marked = false;                     // (vv_debug_mark_update's shadow too)
   // scale for the half copy from max|W|, then convert (a scale update still pending from an earlier SGD step is void)
   c->scale_pending = false;
   // (a gradient nobody asked for goes with the parameters it belonged to, when the call has succeeded: grad_discard below)
@@ -2244,6 +2246,120 @@ int vv_blobs_get(vv_ctx* c, float* ip2, float* target_score, float* negative_sco
     HIPCHK(hipMemcpy(tmp.data(), d, n * 4, hipMemcpyDeviceToHost));
     reorder(tmp, ip1_diff);
   }
+  return VV_OK;
+}
+
+// ---- magnitude statistics (the reference's debug_info: Net::ForwardDebugInfo / BackwardDebugInfo / UpdateDebugInfo, net.cpp:580-636,
+// over Blob::asum_data / asum_diff, blob.cpp:138-165)
+static_assert(sizeof(vv_abs_stat) == sizeof(AbsRec) && offsetof(vv_abs_stat, amax) == offsetof(AbsRec, amax) &&
+              offsetof(vv_abs_stat, count) == offsetof(AbsRec, count) && offsetof(vv_abs_stat, nonfinite) == offsetof(AbsRec, nonfinite),
+              "k_abs_stats writes the ABI's records");
+static constexpr int kStatRecs = VV_STAT_N + 1;              // the named entries, then vv_op_asum's own
+static constexpr size_t kStatParts = (size_t)STAT_SEGS * STAT_BLOCKS;
+// the record block: here on the first call that measures, never on the step path afterwards
+static int stats_ensure(vv_ctx* c) {
+  if (c->stat_rec) return VV_OK;
+  const size_t bytes = kStatRecs * sizeof(AbsRec) + kStatParts * (sizeof(double) + sizeof(unsigned long long) + sizeof(float)) + 16;
+  HIPCHK(hipMalloc((void**)&c->stat_rec, bytes));
+  HIPCHK(hipMemset(c->stat_rec, 0, bytes));
+  HIPCHK(hipDeviceSynchronize());            // (the fill is complete before a kernel of any stream reads it)
+  return VV_OK;
+}
+static AbsStatsArgs stats_args(vv_ctx* c) {
+  AbsStatsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rec = c->stat_rec;
+  a.part_sum = (double*)(c->stat_rec + kStatRecs);
+  a.part_nf = (unsigned long long*)(a.part_sum + kStatParts);
+  a.part_max = (float*)(a.part_nf + kStatParts);
+  a.arrived = (uint32_t*)(a.part_max + kStatParts);
+  return a;
+}
+int vv_op_asum(vv_ctx* c, const float* x_dev, int64_t n, vv_abs_stat* out) {
+  if (!c || !x_dev || !out) return fail(VV_ERR_ARG, "vv_op_asum: NULL argument");
+  if (n < 1) return fail(VV_ERR_ARG, "vv_op_asum: n = %lld (at least one element)", (long long)n);
+  VV_ENTER(c);
+  int rc = stats_ensure(c);
+  if (rc) return rc;
+  AbsStatsArgs a = stats_args(c);
+  a.seg[0] = {x_dev, nullptr, n, STAT_F32, VV_STAT_N};
+  a.nseg = 1;
+  PROFILED(c, "abs_stats", launch_abs_stats(a, c->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, c->stat_rec + VV_STAT_N, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return VV_OK;
+}
+static inline size_t shadow_b_off(const vv_ctx* c) { return round_up((size_t)c->D * c->F, (size_t)4); }      // b's copy: on a 16-byte boundary, as b itself
+static const char* const kStatSharded = "the sharded schedule (2) is selected -- the fp32 master copy and the history are complete on their owner only (vv_comm_schedule(0))";
+int vv_debug_mark_update(vv_ctx* c) {
+  if (!c) return fail(VV_ERR_ARG, "vv_debug_mark_update: ctx is NULL");
+  if (!c->W) return fail(VV_ERR_STATE, "vv_debug_mark_update: no parameters");
+  if (c->comm_sharded) return fail(VV_ERR_STATE, "vv_debug_mark_update: %s", kStatSharded);
+  int rc = upd_pending_guard(c, "vv_debug_mark_update");       // (a hinted step's parameters are half-way until its vv_apply_update)
+  if (rc) return rc;
+  VV_ENTER(c);
+  if ((rc = comm_join(c))) return rc;
+  if (!c->upd_shadow) {                      // the one allocation: here, never on the step path afterwards
+    HIPCHK(hipMalloc((void**)&c->upd_shadow, (shadow_b_off(c) + c->D) * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  HIPCHK(hipMemcpyAsync(c->upd_shadow, c->W, (size_t)c->D * c->F * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->upd_shadow + shadow_b_off(c), c->b, (size_t)c->D * 4, hipMemcpyDeviceToDevice, c->stream));
+  c->upd_marked = true;
+  return VV_OK;
+}
+int vv_debug_stats_queue(vv_ctx* c, uint32_t mask) {
+  if (!c) return fail(VV_ERR_ARG, "vv_debug_stats_queue: ctx is NULL");
+  if (mask == 0 || mask >= (1u << VV_STAT_N)) return fail(VV_ERR_ARG, "vv_debug_stats_queue: mask 0x%x names no entry, or one past VV_STAT_N", mask);
+  auto has = [&](int e) { return (mask >> e & 1u) != 0; };
+  const bool want_grad = has(VV_STAT_DW) || has(VV_STAT_DB), want_score = has(VV_STAT_TARGET_SCORE) || has(VV_STAT_NEGATIVE_SCORES);
+  const bool want_upd = has(VV_STAT_UPD_W) || has(VV_STAT_UPD_B);
+  const bool want_master = has(VV_STAT_W) || has(VV_STAT_HIST_W) || has(VV_STAT_HIST_B) || want_upd;
+  const bool want_param = want_master || has(VV_STAT_B);
+  if ((want_param || want_grad) && !c->W) return fail(VV_ERR_STATE, "vv_debug_stats_queue: no parameters");
+  int rc;
+  if (want_master && c->comm_sharded) return fail(VV_ERR_STATE, "vv_debug_stats_queue: W / history entries while %s", kStatSharded);
+  if (want_param && (rc = upd_pending_guard(c, "vv_debug_stats_queue"))) return rc;
+  if (want_upd && !c->upd_marked) return fail(VV_ERR_STATE, "vv_debug_stats_queue: UPD_W / UPD_B without a vv_debug_mark_update in front of the update");
+  if (want_score && !grad_exists(c->grad) && !c->last_fwd_only) return fail(VV_ERR_STATE, "vv_debug_stats_queue: score entries before any forward pass");
+  if (want_grad) {
+    if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_debug_stats_queue: gradient entries before any backward pass");
+    if (c->fb_hinted || c->grad.at == GradAt::SlabsWUpdated || c->grad.at == GradAt::Lost)
+      return fail(VV_ERR_STATE, "vv_debug_stats_queue: gradient entries of a step announced by vv_update_hint: its gradient is not kept (run the step without the hint to measure it)");
+    if (c->grad.at == GradAt::Buffer && c->grad.buf.layout != GradLayout::Flat)
+      return fail(VV_ERR_STATE, "vv_debug_stats_queue: this step's gradient was laid out chunk- or shard-major for the overlapped / sharded schedule (vv_comm_schedule(0))");
+  }
+  VV_ENTER(c);
+  if ((rc = comm_join(c))) return rc;
+  if ((rc = stats_ensure(c))) return rc;
+  if (want_grad && (rc = reduce_now(c))) return rc;            // the gradient into the flat buffer, as any reader brings it (vv_grads_get)
+  const int64_t nW = (int64_t)c->D * c->F, D = c->D, B = c->B;
+  const float* const sh = c->upd_shadow;
+  const AbsSeg all[VV_STAT_N] = {
+    {c->W, nullptr, nW, STAT_F32, VV_STAT_W}, {c->b, nullptr, D, STAT_F32, VV_STAT_B},
+    {c->hW, nullptr, nW, STAT_F32, VV_STAT_HIST_W}, {c->hb, nullptr, D, STAT_F32, VV_STAT_HIST_B},
+    {c->grads, nullptr, nW, STAT_F32, VV_STAT_DW}, {c->grads ? c->grads + nW : nullptr, nullptr, D, STAT_F32, VV_STAT_DB},
+    {c->s_true, nullptr, B, STAT_F32, VV_STAT_TARGET_SCORE}, {c->s_bogus, nullptr, B * c->Nn, STAT_F32, VV_STAT_NEGATIVE_SCORES},
+    {sh, c->W, nW, STAT_F32, VV_STAT_UPD_W}, {sh ? sh + shadow_b_off(c) : nullptr, c->b, D, STAT_F32, VV_STAT_UPD_B}};
+  AbsStatsArgs a = stats_args(c);
+  for (int e = 0; e < VV_STAT_N; ++e) {
+    if (!has(e)) continue;
+    if (!all[e].p || all[e].n < 1) return fail(VV_ERR_STATE, "vv_debug_stats_queue: entry %d has no buffer yet", e);
+    a.seg[a.nseg++] = all[e];
+    if (a.nseg == STAT_SEGS) { PROFILED(c, "abs_stats", launch_abs_stats(a, c->stream)); a.nseg = 0; }      // (more than STAT_SEGS entries: a second launch behind the first)
+  }
+  if (a.nseg) PROFILED(c, "abs_stats", launch_abs_stats(a, c->stream));
+  HIPCHK(hipGetLastError());
+  return VV_OK;
+}
+int vv_debug_stats_get(vv_ctx* c, vv_abs_stat* out) {
+  if (!c || !out) return fail(VV_ERR_ARG, "vv_debug_stats_get: ctx / out is NULL");
+  memset(out, 0, VV_STAT_N * sizeof(*out));
+  if (!c->stat_rec) return VV_OK;              // nothing was ever queued
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out, c->stat_rec, VV_STAT_N * sizeof(*out), hipMemcpyDeviceToHost));
   return VV_OK;
 }
 

@@ -2010,6 +2010,103 @@ void launch_grad_bank(BankOp op, const BankArgs& a, hipStream_t s) {
   else VV_LAUNCH(k_grad_bank<BankOp::Scale>, grid, block, 0, s, a);
 }
 
+// ------------------------------------------------------------------------------- magnitude statistics ----
+// The reference's debug_info (Net::ForwardDebugInfo / BackwardDebugInfo / UpdateDebugInfo, net.cpp:580-636) prints asum / count of blobs;
+// Blob::asum_data / asum_diff (blob.cpp:138-165) are caffe_gpu_asum calls.  k_abs_stats is k_grad_sumsq's reduction over |x| instead of
+// x^2, for up to STAT_SEGS buffers in one launch: a FIXED grid of STAT_BLOCKS x 256 threads walks the buffers one after the other; in each,
+// thread t takes the 16-byte items t, t + grid, ... in that order into four double sums (element j of an item into sum j & 3), folds
+// them as (x + y) + (z + w) and adds its scalar element (the elements in front of the first 16-byte boundary and behind the last whole
+// item, split as clip_split does: thread j of the grid takes the j-th); the wave folds by halves, the workgroup adds its four waves in
+// order, and the workgroup that arrives last adds the STAT_BLOCKS partials of every buffer in index order.  No atomics on the sums: the
+// same buffers give the same bits on every run.  A NaN or +-Inf element counts in `nonfinite` and in nothing else.  The kernel reads the
+// buffers it measures and writes its own partials, arrival counter and records, nothing else.
+struct AbsAcc { double s; float mx; unsigned long long nf; };
+__device__ __forceinline__ void abs_add(double& s, float& mx, unsigned long long& nf, float v) {
+  const float a = fabsf(v);
+  if (a <= 3.402823466e38f) { s += (double)a; mx = fmaxf(mx, a); }      // (false for NaN and Inf)
+  else ++nf;
+}
+// EB: bytes per element (4: fp32, optionally minus a second fp32 buffer; 2: f16 / bf16)
+template <typename T16> __device__ __forceinline__ AbsAcc abs_segment(const AbsSeg& g, int64_t tid, int64_t nth) {
+  constexpr bool F32 = std::is_same<T16, float>::value;
+  constexpr int EB = F32 ? 4 : 2, PER = 16 / EB;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  AbsAcc r; r.mx = 0.f; r.nf = 0;
+  const char* p = (const char*)g.p;
+  const float* q = F32 ? (const float*)g.q : nullptr;
+  auto elem = [&](int64_t i) -> float {
+    if constexpr (F32) { const float v = ((const float*)p)[i]; return q ? v - q[i] : v; }
+    else return T16::to_float(((const uint16_t*)p)[i]);
+  };
+  if (q && (((uintptr_t)p ^ (uintptr_t)q) & 15) != 0) {         // no common 16-byte grid: scalars throughout
+    for (int64_t i = tid; i < g.n; i += nth) abs_add(s[0], r.mx, r.nf, elem(i));
+    r.s = s[0];
+    return r;
+  }
+  const int64_t head = std::min<int64_t>(g.n, (int64_t)(((16 - ((uintptr_t)p & 15)) & 15) / EB));
+  const int64_t nv = (g.n - head) / PER, tail0 = head + nv * PER, rest = head + (g.n - tail0);      // rest: at most 2 (PER - 1) scalars
+  for (int64_t i = tid; i < nv; i += nth) {
+    const int64_t o = head + i * PER;
+    if constexpr (F32) {
+      float4 v = *(const float4*)(p + o * 4);
+      if (q) { const float4 w = *(const float4*)(q + o); v.x -= w.x; v.y -= w.y; v.z -= w.z; v.w -= w.w; }
+      abs_add(s[0], r.mx, r.nf, v.x); abs_add(s[1], r.mx, r.nf, v.y); abs_add(s[2], r.mx, r.nf, v.z); abs_add(s[3], r.mx, r.nf, v.w);
+    } else {
+      const uint4 v = *(const uint4*)(p + o * 2);
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) abs_add(s[j & 3], r.mx, r.nf, T16::to_float((uint16_t)(w[j >> 1] >> ((j & 1) * 16))));
+    }
+  }
+  r.s = (s[0] + s[1]) + (s[2] + s[3]);
+  if (tid < rest) abs_add(r.s, r.mx, r.nf, elem(tid < head ? tid : tail0 + (tid - head)));
+  return r;
+}
+__global__ __launch_bounds__(256) void k_abs_stats(AbsStatsArgs a) {
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)STAT_BLOCKS * 256;
+  __shared__ double ws[STAT_SEGS][4];
+  __shared__ float wm[STAT_SEGS][4];
+  __shared__ unsigned long long wn[STAT_SEGS][4];
+  __shared__ int last;
+  for (int k = 0; k < a.nseg; ++k) {
+    const AbsSeg& g = a.seg[k];
+    AbsAcc r = g.type == STAT_F32 ? abs_segment<float>(g, tid, nth) : g.type == STAT_F16 ? abs_segment<F16>(g, tid, nth) : abs_segment<BF16>(g, tid, nth);
+    for (int o = 32; o > 0; o >>= 1) {
+      r.s += __shfl_down(r.s, o, 64);
+      r.mx = fmaxf(r.mx, __shfl_down(r.mx, o, 64));
+      r.nf += __shfl_down(r.nf, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { ws[k][threadIdx.x >> 6] = r.s; wm[k][threadIdx.x >> 6] = r.mx; wn[k][threadIdx.x >> 6] = r.nf; }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < a.nseg; ++k) {
+      const int o = k * STAT_BLOCKS + blockIdx.x;
+      __hip_atomic_store(a.part_sum + o, ((ws[k][0] + ws[k][1]) + ws[k][2]) + ws[k][3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(a.part_max + o, fmaxf(fmaxf(wm[k][0], wm[k][1]), fmaxf(wm[k][2], wm[k][3])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(a.part_nf + o, wn[k][0] + wn[k][1] + wn[k][2] + wn[k][3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // (release: the partials are visible at agent scope before the count; acquire: the last arrival sees every other workgroup's)
+    last = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)STAT_BLOCKS - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  if ((int)threadIdx.x < a.nseg) {             // one thread per buffer, the partials in index order
+    const int k = threadIdx.x;
+    double sum = 0.0; float mx = 0.f; unsigned long long nf = 0;
+#pragma unroll 8
+    for (int i = 0; i < STAT_BLOCKS; ++i) {
+      sum += __hip_atomic_load(a.part_sum + k * STAT_BLOCKS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      mx = fmaxf(mx, __hip_atomic_load(a.part_max + k * STAT_BLOCKS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      nf += __hip_atomic_load(a.part_nf + k * STAT_BLOCKS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    AbsRec& r = a.rec[a.seg[k].slot];
+    r.asum = sum; r.amax = mx; r.reserved_ = 0; r.count = a.seg[k].n; r.nonfinite = (int64_t)nf;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the next launch
+}
+void launch_abs_stats(const AbsStatsArgs& a, hipStream_t s) { VV_LAUNCH(k_abs_stats, dim3(STAT_BLOCKS), dim3(256), 0, s, a); }
+
 __global__ void k_scale_update(Scales* sc, const float* wmax_blocks, int nblocks, int prec) { scale_update_body(sc, wmax_blocks, nblocks, prec); }
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s) {
   hipLaunchKernelGGL(k_scale_update, dim3(1), dim3(256), 0, s, sc, wmax_blocks, n_blocks, prec);

@@ -71,6 +71,12 @@ struct vv_ctx {
   bool grad_banked = false;                 // the last backward pass's gradient has been banked, or the buffer holds an accumulated update's
                                             // normalised sum in its place: not banked again (a backward pass clears it)
   bool fb_hinted = false;                   // the last backward pass was announced by vv_update_hint: its gradient is not banked
+  // vv_op_asum / vv_debug_stats_queue (the reference's debug_info, net.cpp:580-636).  stat_rec: ONE allocation made zero-filled by the first
+  // call that measures, never on the step path afterwards -- VV_STAT_N records and vv_op_asum's own, then k_abs_stats' partials and its
+  // arrival counter.  upd_shadow: vv_debug_mark_update's copy of W, then (on the next 16-byte boundary) of b, allocated by the first mark.
+  vv::AbsRec* stat_rec = nullptr;
+  float* upd_shadow = nullptr;
+  bool upd_marked = false;                  // the shadow holds the parameters of a vv_debug_mark_update (vv_params_set clears it)
   uint16_t* Wh = nullptr; vv::Scales* scales = nullptr; float* wmax_blocks = nullptr;
   int n_cu = 256;                           // compute units of the device
   bool scale_pending = false;               // k_sgd ran, its scale update has not (it rides in the next k_reduce)

@@ -495,6 +495,23 @@ struct BankArgs {
   const uint32_t* skip_if = nullptr;  // as SgdArgs::skip_if: a failed exchange in front, the launch changes nothing
 };
 
+// Magnitude statistics (the reference's debug_info: Net::ForwardDebugInfo / BackwardDebugInfo / UpdateDebugInfo, net.cpp:580-636, over
+// Blob::asum_data / asum_diff, blob.cpp:138-165; vv_op_asum, vv_debug_stats_queue): k_abs_stats measures up to STAT_SEGS buffers in one
+// launch and leaves one record per buffer -- the layout of include/videovec.h's vv_abs_stat.  asum: the sum of |x| over the FINITE
+// elements in double, in a fixed order; amax: the largest finite |x|; nonfinite: NaN and +-Inf elements, which count in neither.
+struct AbsRec { double asum; float amax; int32_t reserved_; int64_t count, nonfinite; };
+constexpr int STAT_BLOCKS = 256;      // k_abs_stats' fixed grid = the per-workgroup partials its last stage folds in index order
+constexpr int STAT_SEGS = 8;          // buffers per launch
+enum : int { STAT_F32 = 0, STAT_F16 = 1, STAT_BF16 = 2 };
+// One buffer: n elements of `type` at p.  q (fp32 only): a second buffer of the same length -- the element is p[i] - q[i], one fp32 subtract.
+struct AbsSeg { const void* p; const void* q; int64_t n; int type; int slot; };      // slot: the record it fills
+struct AbsStatsArgs {
+  AbsSeg seg[STAT_SEGS]; int nseg;
+  AbsRec* rec;                        // the records (indexed by AbsSeg::slot)
+  double* part_sum; float* part_max; unsigned long long* part_nf;      // [STAT_SEGS][STAT_BLOCKS] each: the workgroups' partials
+  uint32_t* arrived;                  // arrival counter of the workgroups (0 between launches)
+};
+
 // Which kernels a context runs (vv_ctx::ko).  The launchers read the options of the context whose entry point is running on this
 // thread (g_ko, set by every ABI entry point next to hipSetDevice); nothing here is process-global, so two contexts of one process
 // do not inherit each other's choices.  Product options are set by vv_set_option (their environment variables are read ONCE per
@@ -570,6 +587,7 @@ void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW = nullptr, 
 void launch_grad_sumsq(const ClipArgs& a, hipStream_t s);            // -> ClipArgs::rec (no host synchronisation)
 void launch_grad_scale(const ClipArgs& a, hipStream_t s);            // g *= rec->scale where rec->clipped, else every workgroup returns at once
 void launch_grad_bank(BankOp op, const BankArgs& a, hipStream_t s);   // k_grad_bank: one owner per element, no atomics
+void launch_abs_stats(const AbsStatsArgs& a, hipStream_t s);          // k_abs_stats: reads its buffers, writes its partials and records only
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s);
 void launch_delay(int us, hipStream_t s);                             // test hook: occupies s for `us` microseconds       // flag <- seq (agent scope), behind everything queued on s
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s);

@@ -59,6 +59,14 @@ class _ClipReport(C.Structure):
                 ("updates", C.c_int64), ("clipped_updates", C.c_int64)]
 
 
+class _AbsStat(C.Structure):
+    _fields_ = [("asum", C.c_double), ("amax", C.c_float), ("reserved_", C.c_int32), ("count", C.c_int64), ("nonfinite", C.c_int64)]
+
+
+# include/videovec.h's VV_STAT_* in order: name -> bit of vv_debug_stats_queue's mask, index of vv_debug_stats_get's record
+STAT_NAMES = ("W", "B", "HIST_W", "HIST_B", "DW", "DB", "TARGET_SCORE", "NEGATIVE_SCORES", "UPD_W", "UPD_B")
+
+
 class _AccumReport(C.Structure):
     _fields_ = [("banked", C.c_int32), ("last_count", C.c_int32), ("last_mean_loss", C.c_float), ("last_mean_violations", C.c_float),
                 ("updates", C.c_int64)]
@@ -170,6 +178,8 @@ def load_library():
         "vv_clip_stats": [vp, C.POINTER(_ClipReport)],
         "vv_grads_bank": [vp], "vv_grads_bank_reset": [vp], "vv_accum_stats": [vp, C.POINTER(_AccumReport)],
         "vv_forward": [vp, vp, vp, C.c_int], "vv_eval_reset": [vp], "vv_eval_stats": [vp, C.POINTER(_EvalReport)],
+        "vv_op_asum": [vp, vp, i64, C.POINTER(_AbsStat)],
+        "vv_debug_stats_queue": [vp, C.c_uint32], "vv_debug_mark_update": [vp], "vv_debug_stats_get": [vp, C.POINTER(_AbsStat)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -521,6 +531,39 @@ class Engine:
         self._chk(self.L.vv_accum_stats(self.h, C.byref(r)))
         return {"banked": int(r.banked), "last_count": int(r.last_count), "last_mean_loss": np.float32(r.last_mean_loss),
                 "last_mean_violations": np.float32(r.last_mean_violations), "updates": int(r.updates)}
+
+    # ---- magnitude statistics (the reference's debug_info, net.cpp:580-636; vv_op_asum, vv_debug_stats_*, vv_debug_mark_update)
+    @staticmethod
+    def _abs_stat(r):
+        return (float(r.asum), np.float32(r.amax), int(r.count), int(r.nonfinite))
+
+    def op_asum(self, buf, n=None, offset=0):
+        """(asum, amax, count, nonfinite) of n fp32 elements of a DevBuf (or a device pointer), `offset` floats into it; synchronises."""
+        ptr = buf.ptr.value if isinstance(buf, DevBuf) else int(buf.value if isinstance(buf, C.c_void_p) else buf)
+        if n is None:
+            n = int(np.prod(buf.shape)) - offset
+        r = _AbsStat()
+        self._chk(self.L.vv_op_asum(self.h, C.c_void_p(ptr + 4 * int(offset)), int(n), C.byref(r)))
+        return self._abs_stat(r)
+
+    def debug_stats_queue(self, names):
+        """Queue one measurement of the named tensors (STAT_NAMES; a single name or an iterable) as they are at this point of the stream."""
+        mask = 0
+        for name in ([names] if isinstance(names, str) else names):
+            if name not in STAT_NAMES:
+                raise VVError("debug_stats_queue: unknown entry %r (one of %s)" % (name, ", ".join(STAT_NAMES)))
+            mask |= 1 << STAT_NAMES.index(name)
+        self._chk(self.L.vv_debug_stats_queue(self.h, mask))
+
+    def debug_mark_update(self):
+        """Copy W and b into the shadow buffer: UPD_W / UPD_B queued after the next apply_update measure what it subtracted."""
+        self._chk(self.L.vv_debug_mark_update(self.h))
+
+    def debug_stats(self):
+        """name -> (asum, amax, count, nonfinite) of every entry as its last queued measurement left it (synchronises); never queued: zeros."""
+        arr = (_AbsStat * len(STAT_NAMES))()
+        self._chk(self.L.vv_debug_stats_get(self.h, arr))
+        return {name: self._abs_stat(arr[i]) for i, name in enumerate(STAT_NAMES)}
 
     def _ext(self, cfg):
         """StepConfig's momentum2 / rms_decay / clip_gradients -> the context, in front of a call that takes cfg."""

@@ -160,7 +160,7 @@ def extraction_net(source, batch, D, *, normalize=False, w_std=0.001):
 def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_policy="inv", gamma=0.001,
            power=0.75, stepsize=0, display=10, max_iter=100, snapshot=0, snapshot_prefix="videovec",
            random_seed=-1, snapshot_after_train=True, test_iter=0, test_interval=0, solver_type=None, delta=None,
-           snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None, test_compute_loss=False):
+           snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None, test_compute_loss=False, debug_info=False):
     """Same fields as projects/videovec_embedding/mednet_embedding_train_solver.prototxt (+ solver_type / delta, and BVLC Caffe's
     rms_decay / momentum2 for RMSPROP / ADAM, clip_gradients and iter_size, written only when given)."""
     s = ['net: "%s"' % net_path, "base_lr: %g" % base_lr, "momentum: %g" % momentum,
@@ -191,4 +191,6 @@ def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_pol
         s.append("iter_size: %d" % iter_size)
     if snapshot_diff:
         s.append("snapshot_diff: true")
+    if debug_info:
+        s.append("debug_info: true")
     return "\n".join(s) + "\n"
