@@ -47,6 +47,12 @@ class Net {
   void CopyTrainedLayersFrom(const NetParameter& param);        // net.cpp:691-764
   void CopyTrainedLayersFrom(const string trained_filename);
   void ToProto(NetParameter* param, bool write_diff = false);   // net.cpp:773-801
+  // The moving average of the trained parameters (SolverParameter.ema_decay; vv_ema_*; this project's own), in the fc layer's place:
+  // ToProto with the average as that layer's blobs (same layer and blob names: usable wherever a caffemodel is), the average taken from
+  // such a model (a resumed run), and a TEST net given the train net's average instead of its weights
+  void ToProtoAveraged(NetParameter* param);
+  void CopyAveragedLayersFrom(const NetParameter& param);
+  void ShareAveragedLayersWith(Net* other);
 
   inline const string& name() const { return name_; }
   inline const vector<string>& layer_names() const { return layer_names_; }

@@ -51,6 +51,7 @@ class Solver {
   int iter_;
   float clip_gradients_ = -1.f;        // SolverParameter.clip_gradients (BVLC; < 0: off), handed to the engine by Init
   int iter_size_ = 1;                  // SolverParameter.iter_size (BVLC): forward/backward passes banked per update (Step)
+  float ema_decay_ = -1.f;             // SolverParameter.ema_decay (this project's own; < 0: off), handed to the engine by Init
   bool h16_warned_ = false;           // the one warning line of the f16 rows' fallback has been written (Step)
   shared_ptr<Net<Dtype> > net_;
   vector<shared_ptr<Net<Dtype> > > test_nets_;

@@ -1015,6 +1015,41 @@ void Net<Dtype>::ToProto(NetParameter* param, bool write_diff) {
   }
 }
 
+// ---- the moving average of the parameters (vv_ema_*) in the fc layer's place
+template <typename Dtype>
+void Net<Dtype>::ToProtoAveraged(NetParameter* param) {
+  PullParamsFromDevice();
+  Layer<Dtype>* ip = layers_[plan_.ip_layer].get();
+  Blob<Dtype> W, b;                                  // the trained values, put back below
+  W.CopyFrom(*ip->blobs()[0], false, true); b.CopyFrom(*ip->blobs()[1], false, true);
+  VV_CHECK(vv_ema_get(ctx_, ip->blobs()[0]->mutable_cpu_data(), ip->blobs()[1]->mutable_cpu_data()));
+  ToProto(param, false);
+  ip->blobs()[0]->CopyFrom(W); ip->blobs()[1]->CopyFrom(b);
+}
+template <typename Dtype>
+void Net<Dtype>::CopyAveragedLayersFrom(const NetParameter& param) {
+  const string& fc = layer_names_[plan_.ip_layer];
+  for (int i = 0; i < param.size("layers"); ++i) {
+    const LayerParameter& src = param.get_msg("layers", i);
+    if (src.get_str("name") != fc) continue;
+    CHECK_EQ(src.size("blobs"), 2) << "Incompatible number of blobs for layer " << fc;
+    Blob<Dtype> W, b;
+    W.FromProto(src.get_msg("blobs", 0)); b.FromProto(src.get_msg("blobs", 1));
+    CHECK_EQ(W.count(), plan_.D * plan_.F); CHECK_EQ(b.count(), plan_.D);
+    VV_CHECK(vv_ema_put(ctx_, W.cpu_data(), b.cpu_data()));
+    return;
+  }
+  LOG(FATAL) << "the averaged model holds no layer " << fc;
+}
+template <typename Dtype>
+void Net<Dtype>::ShareAveragedLayersWith(Net* other) {
+  CHECK_EQ(plan_.D, other->plan_.D); CHECK_EQ(plan_.F, other->plan_.F);
+  Layer<Dtype>* dst = layers_[plan_.ip_layer].get();
+  CHECK(layer_names_[plan_.ip_layer] == other->layer_names_[other->plan_.ip_layer]) << "layers are shared by name (net.cpp:641-648)";
+  VV_CHECK(vv_ema_get(other->ctx_, dst->blobs()[0]->mutable_cpu_data(), dst->blobs()[1]->mutable_cpu_data()));
+  PushParamsToDevice();
+}
+
 template class Net<float>;
 
 }  // namespace caffe

@@ -105,7 +105,10 @@ static const std::vector<MsgDef>& Msgs() {
         OPTD(135, "clip_gradients", T_FLOAT, "-1"),
         // BVLC Caffe's SolverParameter.iter_size is field 36, which the fork gave to snapshot_vis_dir: here it is 136, by the same rule
         // (Solver::Init holds it to CHECK_GE(iter_size, 1))
-        OPTD(136, "iter_size", T_INT32, "1")}},
+        OPTD(136, "iter_size", T_INT32, "1"),
+        // This project's own (neither the fork nor BVLC Caffe has them; 137 and 138 continue 135 / 136 and are free in both): the decay of the
+        // moving average of the parameters (vv_ema_set; < 0: off) and whether Solver::Test evaluates on it
+        OPTD(137, "ema_decay", T_FLOAT, "-1"), OPTD(138, "test_with_ema", T_BOOL, "false")}},
       {"SolverState",                                                               // :176-180
        {OPT(1, "iter", T_INT32), OPT(2, "learned_net", T_STRING), RMSG(3, "history", "BlobProto")}},
       {"LayerParameter",                                                            // :215-389

@@ -130,6 +130,20 @@ void Solver<Dtype>::Init(const SolverParameter& param) {
     }
     LOG(INFO) << "iter_size: " << iter_size_ << " -- " << iter_size_ << " forward/backward passes are banked per update; iterations, the learning-rate policy and snapshots count updates";
   }
+  // ema_decay (this project's own; vv_ema_set): the moving average of the parameters, kept on the device behind every update.  Every rank
+  // averages the whole, identical matrix: a data-parallel job with the average runs the sync exchange schedule
+  ema_decay_ = (float)param_.get_num("ema_decay");
+  CHECK(ema_decay_ < 1.f) << "ema_decay must be negative (off) or in [0, 1)";
+  if (ema_decay_ >= 0) {
+    CHECK(!net_->sequential()) << "ema_decay: " << ema_decay_ << " needs the fused training step (this net runs layer by layer)";
+    if (Caffe::world() > 1) {
+      VV_CHECK(vv_comm_schedule(Caffe::ctx(), 0));
+      LOG(INFO) << "ema_decay: " << ema_decay_ << " -- the gradient exchange runs on the sync schedule (every rank averages the whole parameter matrix)";
+    }
+    VV_CHECK(vv_ema_set(Caffe::ctx(), ema_decay_));
+    LOG(INFO) << "ema_decay: " << ema_decay_ << " -- a moving average of the parameters is kept behind every update and written beside every snapshot (.ema.caffemodel)";
+  }
+  if (param_.get_bool("test_with_ema")) CHECK(ema_decay_ >= 0) << "test_with_ema needs ema_decay";
   LOG(INFO) << "Solver scaffolding done.";
 }
 
@@ -272,7 +286,12 @@ void Solver<Dtype>::Test(const int test_net_id) {
   LOG(INFO) << "Iteration " << iter_ << ", Testing net (#" << test_net_id << ")";
   Caffe::set_phase(Caffe::TEST);
   Net<Dtype>& net = *test_nets_[test_net_id];
-  net.ShareTrainedLayersWith(net_.get());
+  if (param_.get_bool("test_with_ema")) {           // the test net's own context is given the average in the weights' place
+    LOG(INFO) << "    Testing on the moving average of the parameters (ema_decay " << ema_decay_ << ")";
+    net.ShareAveragedLayersWith(net_.get());
+  } else {
+    net.ShareTrainedLayersWith(net_.get());
+  }
   const int passes = (int)param_.get_int("test_iter", test_net_id);
   const bool want_loss = param_.get_bool("test_compute_loss");
   vector<Dtype> mean;
@@ -313,6 +332,13 @@ void Solver<Dtype>::Snapshot() {
   state.set_str("learned_net", model_file);
   LOG(INFO) << "Snapshotting solver state to " << state_file;
   pl::WriteProtoToBinaryFile(state, state_file);
+  if (ema_decay_ >= 0) {                            // the average, under the same layer and blob names (the solverstate does not name it)
+    const string ema_file = stem + ".ema.caffemodel";
+    NetParameter averaged("NetParameter");
+    net_->ToProtoAveraged(&averaged);
+    LOG(INFO) << "Snapshotting the moving average to " << ema_file;
+    pl::WriteProtoToBinaryFile(averaged, ema_file);
+  }
 }
 
 // Solver::Restore (solver.cpp:418-429)
@@ -327,6 +353,24 @@ void Solver<Dtype>::Restore(const char* state_file) {
   }
   iter_ = (int)state.get_int("iter");
   RestoreSolverState(state);
+  if (ema_decay_ >= 0) {                            // (behind the history: every vv_params_set starts the average from the weights)
+    string ema_file;
+    if (state.has("learned_net")) {
+      const string model = state.get_str("learned_net"), ext = ".caffemodel";
+      if (model.size() > ext.size() && model.compare(model.size() - ext.size(), ext.size(), ext) == 0)
+        ema_file = model.substr(0, model.size() - ext.size()) + ".ema.caffemodel";
+    }
+    FILE* f = ema_file.empty() ? nullptr : fopen(ema_file.c_str(), "rb");
+    if (f) {
+      fclose(f);
+      NetParameter averaged("NetParameter");
+      pl::ReadProtoFromBinaryFileOrDie(ema_file, &averaged);
+      net_->CopyAveragedLayersFrom(averaged);
+      LOG(INFO) << "Restoring the moving average from " << ema_file;
+    } else {
+      LOG(INFO) << "No averaged model beside the restored weights" << (ema_file.empty() ? string() : " (" + ema_file + ")") << ": the moving average starts from the restored weights";
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------- SGD -----------

@@ -299,6 +299,41 @@ int vv_debug_mark_update(vv_ctx* ctx);
  * Synchronises the step's stream.  Entries never queued read all-zero. */
 int vv_debug_stats_get(vv_ctx* ctx, vv_abs_stat out[VV_STAT_N]);
 
+/* ---- an exponential moving average of the parameters, for evaluation (Polyak averaging).  Neither the reference tree nor BVLC Caffe has
+ * a counterpart: the semantics are this project's own.  decay < 0 (the default, -1) turns it off and every call is what it was;
+ * 0 <= decay < 1 turns it on; NaN or decay >= 1 is VV_ERR_ARG.  Sticky on the context until set again.  The activation makes the one
+ * allocation -- eW [D][F] and eb [D] in fp32, with room for their 16-bit copy -- and starts the average from the current W and b with a
+ * device copy; nothing is allocated on the step path afterwards.  vv_params_set while active starts it again from the new values; another
+ * decay while active keeps the average; turning it off releases it.
+ * While active, every completed vv_apply_update (an accumulated one and the finishing call of a step announced by vv_update_hint too: once
+ * per update) is followed by ONE launch of k_ema on the step's stream, behind the update:
+ *     e' = decay * e + om * w        om = 1.0f - decay, formed once on the host in fp32
+ * for every element of W and of b -- two fp32 products and one fp32 sum, each rounded as written (no contraction into an fma).  No host
+ * synchronisation, no atomics.  The update kernels are not touched: k_ema reads W and b after them, and parameters, histories, the 16-bit
+ * copy, loss and gradients of a run with the average are bit for bit those of a run without it.
+ * vv_ema_get: the average as host fp32 (either pointer may be NULL); synchronises.  VV_ERR_STATE while the average is off.
+ * vv_ema_use(1): from here on the forward-only readers -- vv_forward, vv_embed, vv_embed_mean, vv_gallery_from_table -- read the averaged
+ * parameters: their 16-bit copy and its scale are produced on demand on the context's stream, exactly as vv_params_set would produce them
+ * for these fp32 values (max |e| -> the power-of-two scale -> round to nearest even), and are cached until the next k_ema.  So their
+ * results are bit for bit those of a second context given vv_params_set(vv_ema_get()).  While in use every call that trains or replaces
+ * the parameters is VV_ERR_STATE: vv_forward_backward*, vv_step, vv_apply_update, vv_params_set (and vv_ema_set(< 0)).  VV_ERR_STATE for
+ * vv_ema_use(1) while the average is off, or between a backward pass announced by vv_update_hint and its vv_apply_update.
+ * vv_ema_use(0) restores the training view; it moves nothing a training step owns (the guarantee vv_forward states), so the next
+ * training step is bit for bit that of an undisturbed run.  The per-layer operators (vv_op_*) always read the training parameters.
+ * Data parallel: on the sync schedule only -- every rank averages identical parameters.  VV_ERR_STATE: vv_ema_set(>= 0) while schedule 1
+ * or 2 is selected, and vv_comm_schedule(1 or 2) / vv_comm_overlap(1) while the average is active. */
+int vv_ema_set(vv_ctx* ctx, float decay);
+int vv_ema_get_decay(vv_ctx* ctx, float* decay);
+int vv_ema_get(vv_ctx* ctx, float* W, float* b);
+/* The inverse of vv_ema_get, for a run that resumes: replaces the average by host fp32 values (either pointer may be NULL: that part
+ * stays); synchronises.  VV_ERR_STATE while the average is off. */
+int vv_ema_put(vv_ctx* ctx, const float* W, const float* b);
+int vv_ema_use(vv_ctx* ctx, int on);
+typedef struct { int64_t updates;                  /* k_ema launches since the activation (0 while off) */
+                 float decay;                      /* as vv_ema_get_decay */
+                 int32_t in_use; } vv_ema_report;  /* 1: vv_ema_use(1) is in effect */
+int vv_ema_stats(vv_ctx* ctx, vv_ema_report* out);
+
 /* ---- one training iteration */
 typedef struct {
   /* shapes: VideoSampledShotsDataParameter batch_size / context_size / num_negative_samples

@@ -33,6 +33,9 @@ using namespace vv;
 
 static inline int upd_pending_guard(vv_ctx* c, const char* who) { return vv_upd_pending_guard(c, who); }      // (vv_update_hint, below)
 static int ensure_history2(vv_ctx* c);                         // (the second history of a two-history solver, below)
+static int ema_init(vv_ctx* c);                                // (the moving average of the parameters, below)
+static void ema_release(vv_ctx* c);
+static const char* const kEmaInUse = "the averaged parameters are in use (vv_ema_use(1)): this call trains or replaces the parameters -- vv_ema_use(0) first";
 thread_local char vv_g_err[512] = "";
 int vv_fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -274,7 +277,7 @@ int vv_destroy(vv_ctx* c) {
   vv_ops_release(c);
   free_batch(c);
   dfree(c->table); dfree(c->patch_desc); dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh);
-  dfree(c->clip_rec); dfree(c->bank_rec); dfree(c->stat_rec); dfree(c->upd_shadow);
+  dfree(c->clip_rec); dfree(c->bank_rec); dfree(c->stat_rec); dfree(c->upd_shadow); dfree(c->eW);
   dfree(c->scales); dfree(c->wmax_blocks); dfree(c->grads_own); dfree(c->mask); dfree(c->loss2);
   dfree(c->dd_key); dfree(c->dd_info_all); dfree(c->gg); dfree(c->gg_bound); dfree(c->w_gate);
   if (c->gate_err) (void)hipHostFree(c->gate_err);
@@ -473,6 +476,7 @@ static int table_alloc(vv_ctx* c, int64_t n_rows, int F) {
 
 static int set_sx(vv_ctx* c, float sx) {
   c->sx = sx;
+  c->ema_packed = false;                     // (the average's 16-bit view carries the table's scale too)
   HIPCHK(hipMemcpyAsync(&c->scales->sx, &c->sx, sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return VV_OK;
@@ -562,6 +566,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
                   const float* hb) {
   if (!c || !W || D <= 0) return fail(VV_ERR_ARG, "vv_params_set: bad argument");
   if (!c->table) return fail(VV_ERR_STATE, "vv_params_set: set the feature table first (defines F)");
+  if (c->ema_in_use) return fail(VV_ERR_STATE, "vv_params_set: %s", kEmaInUse);
   VV_ENTER(c);
   { const int rcj = comm_join(c); if (rcj) return rcj; }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -572,6 +577,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
     dfree(c->W); dfree(c->b); dfree(c->hW); dfree(c->hb); dfree(c->hW2); dfree(c->hb2); dfree(c->Wh); dfree(c->grads_own);
     dfree(c->bank_rec); c->bank_rec = nullptr; c->bank = nullptr;      // (the bank has the gradient buffer's size: the next vv_grads_bank allocates it anew)
     dfree(c->upd_shadow); c->upd_shadow = nullptr;                     // (... and so has vv_debug_mark_update's shadow)
+    ema_release(c);                                                    // (... and the moving average: allocated anew below while it is active)
     c->W = c->b = c->hW = c->hb = c->hW2 = c->hb2 = nullptr; c->Wh = nullptr; c->grads = c->grads_own = nullptr;
     c->D = D; c->Dp = (int)round_up(D, D_ALIGN);
 #ifdef VV_LAB
@@ -626,6 +632,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   launch_absmax(c->W, (int64_t)nW, &c->scales->wmax_bits, c->stream);
   c->wmax_seed_live = true;
   HIPCHK(hipGetLastError());
+  if (c->ema_decay >= 0.f) { const int rce = ema_init(c); if (rce) return rce; }      // the average starts again from the new values
   HIPCHK(hipStreamSynchronize(c->stream));
   grad_discard(c->grad);
   return VV_OK;
@@ -768,6 +775,117 @@ static ClipArgs clip_args(vv_ctx* c) {
   a.rec = c->clip_rec; a.part = (double*)(c->clip_rec + 1); a.arrived = (uint32_t*)(a.part + CLIP_BLOCKS);
   a.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
   return a;
+}
+
+// ---- the exponential moving average of the parameters (this project's own: neither the reference tree nor BVLC Caffe keeps one)
+static const char* const kEmaSchedule = "the moving average runs on the sync exchange schedule only (every rank averages the whole, identical parameter "
+                                        "matrix behind its update): vv_ema_set(< 0) or vv_comm_schedule(0)";
+static void ema_release(vv_ctx* c) {
+  dfree(c->eW);
+  c->eW = c->eb = nullptr; c->escales = nullptr; c->eWh = nullptr; c->ema_packed = false;
+}
+// the one allocation (per D) and the start of the average: a device copy of W and b as they stand behind everything queued
+static int ema_init(vv_ctx* c) {
+  static_assert(sizeof(Scales) == 16, "the average's 16-bit copy starts on a 16-byte boundary behind its Scales block");
+  const size_t nW = (size_t)c->D * c->F, off_b = (size_t)round_up((int64_t)nW, 4), off_s = off_b + (size_t)round_up(c->D, 4);
+  if (!c->eW) {
+    const size_t bytes = off_s * 4 + sizeof(Scales) + (size_t)c->Dp * c->Fp * 2;
+    HIPCHK(hipMalloc((void**)&c->eW, bytes));
+    HIPCHK(hipMemset(c->eW, 0, bytes));          // (the padding of the 16-bit copy reads zero, as Wh's)
+    HIPCHK(hipDeviceSynchronize());              // (the fill is complete before a kernel of any stream reads it)
+    c->eb = c->eW + off_b; c->escales = (Scales*)(c->eW + off_s); c->eWh = (uint16_t*)(c->escales + 1);
+  }
+  HIPCHK(hipMemcpyAsync(c->eW, c->W, nW * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->eb, c->b, (size_t)c->D * 4, hipMemcpyDeviceToDevice, c->stream));
+  c->ema_packed = false;
+  return VV_OK;
+}
+int vv_ema_set(vv_ctx* c, float decay) {
+  if (!c) return fail(VV_ERR_ARG, "vv_ema_set: ctx is NULL");
+  if (!(decay == decay) || decay >= 1.f) return fail(VV_ERR_ARG, "vv_ema_set: decay must be < 0 (off) or in [0, 1)");
+  if (decay < 0.f) {
+    if (c->ema_in_use) return fail(VV_ERR_STATE, "vv_ema_set: the averaged parameters are in use (vv_ema_use(0) first)");
+    if (c->eW) { VV_ENTER(c); HIPCHK(hipStreamSynchronize(c->stream)); ema_release(c); }      // (a k_ema still queued writes it)
+    c->ema_decay = -1.f;
+    return VV_OK;
+  }
+  if (c->comm_overlap || c->comm_sharded) return fail(VV_ERR_STATE, "vv_ema_set: %s", kEmaSchedule);
+  if (c->ema_decay < 0.f) {                    // activation: the average starts from the parameters as they stand
+    if (!c->W) return fail(VV_ERR_STATE, "vv_ema_set: no parameters (vv_params_set first: the average starts from them)");
+    { const int rcg = upd_pending_guard(c, "vv_ema_set"); if (rcg) return rcg; }      // (a hinted step half-way: new matrix, old bias)
+    VV_ENTER(c);
+    int rc = comm_join(c);                     // (an overlapped update of an earlier schedule may still be writing W)
+    if (rc) return rc;
+    if (c->params_partial && (rc = gather_params(c))) return rc;
+    if ((rc = ema_init(c))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->ema_updates = 0;
+  }
+  c->ema_decay = decay;                        // (another decay while active: the average is kept)
+  return VV_OK;
+}
+int vv_ema_get_decay(vv_ctx* c, float* decay) {
+  if (!c || !decay) return fail(VV_ERR_ARG, "vv_ema_get_decay: NULL argument");
+  *decay = c->ema_decay;
+  return VV_OK;
+}
+int vv_ema_get(vv_ctx* c, float* W, float* b) {
+  if (!c) return fail(VV_ERR_ARG, "vv_ema_get: ctx is NULL");
+  if (c->ema_decay < 0.f) return fail(VV_ERR_STATE, "vv_ema_get: the moving average is off (vv_ema_set)");
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (W) HIPCHK(hipMemcpy(W, c->eW, (size_t)c->D * c->F * 4, hipMemcpyDeviceToHost));
+  if (b) HIPCHK(hipMemcpy(b, c->eb, (size_t)c->D * 4, hipMemcpyDeviceToHost));
+  return VV_OK;
+}
+int vv_ema_put(vv_ctx* c, const float* W, const float* b) {
+  if (!c) return fail(VV_ERR_ARG, "vv_ema_put: ctx is NULL");
+  if (c->ema_decay < 0.f) return fail(VV_ERR_STATE, "vv_ema_put: the moving average is off (vv_ema_set)");
+  VV_ENTER(c);
+  HIPCHK(hipStreamSynchronize(c->stream));     // (a k_ema still queued reads and writes it)
+  if (W) HIPCHK(hipMemcpy(c->eW, W, (size_t)c->D * c->F * 4, hipMemcpyHostToDevice));
+  if (b) HIPCHK(hipMemcpy(c->eb, b, (size_t)c->D * 4, hipMemcpyHostToDevice));
+  c->ema_packed = false;
+  return VV_OK;
+}
+// The 16-bit copy of the average and its scale, as vv_params_set makes W's: max |e| -> the power-of-two scale -> round to nearest even.
+// Cached until the next k_ema (or re-initialisation, or another table scale).
+static int ema_pack(vv_ctx* c) {
+  if (c->ema_packed) return VV_OK;
+  hipStream_t s = c->stream;
+  HIPCHK(hipMemcpyAsync(&c->escales->sx, &c->scales->sx, sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemsetAsync(&c->escales->wmax_bits, 0, sizeof(unsigned), s));
+  launch_absmax(c->eW, (int64_t)c->D * c->F, &c->escales->wmax_bits, s);
+  launch_scale_update(c->prec, c->escales, nullptr, 0, s);
+  PROFILED(c, "ema_pack", launch_w_convert(c->prec, c->eW, c->eWh, c->D, c->F, c->Dp, c->Fp, c->escales, s));
+  HIPCHK(hipGetLastError());
+  c->ema_packed = true;
+  return VV_OK;
+}
+int vv_ema_use(vv_ctx* c, int on) {
+  if (!c) return fail(VV_ERR_ARG, "vv_ema_use: ctx is NULL");
+  if (!on) { c->ema_in_use = false; return VV_OK; }      // the training view again: nothing a step owns was moved
+  if (c->ema_decay < 0.f) return fail(VV_ERR_STATE, "vv_ema_use: the moving average is off (vv_ema_set)");
+  { const int rcg = upd_pending_guard(c, "vv_ema_use"); if (rcg) return rcg; }
+  if (c->upd_announced && grad_exists(c->grad))
+    return fail(VV_ERR_STATE, "vv_ema_use: the last backward pass was announced by vv_update_hint and its vv_apply_update has not run -- call vv_apply_update first");
+  c->upd_hint = false;                         // (a hint not yet consumed announced a step that cannot come now)
+  c->ema_in_use = true;
+  return VV_OK;
+}
+int vv_ema_stats(vv_ctx* c, vv_ema_report* out) {
+  if (!c || !out) return fail(VV_ERR_ARG, "vv_ema_stats: ctx / out is NULL");
+  out->updates = c->ema_decay >= 0.f ? c->ema_updates : 0; out->decay = c->ema_decay; out->in_use = c->ema_in_use ? 1 : 0;
+  return VV_OK;
+}
+// What the forward-only readers (vv_forward, vv_embed, vv_embed_mean, vv_gallery_from_table) read: the training parameters' 16-bit copy,
+// bias and scales, or under vv_ema_use(1) the average's (packed on demand, on the context's stream)
+struct ParamView { const uint16_t* Wh; const float* b; const Scales* scales; };
+static int param_view(vv_ctx* c, ParamView* v) {
+  if (!c->ema_in_use) { v->Wh = c->Wh; v->b = c->b; v->scales = c->scales; return VV_OK; }
+  const int rc = ema_pack(c);
+  v->Wh = c->eWh; v->b = c->eb; v->scales = c->escales;
+  return rc;
 }
 
 // ---- gradient accumulation (BVLC Caffe's SolverParameter.iter_size: Solver::Step and SGDSolver::Normalize; the reference tree has none)
@@ -1029,6 +1147,15 @@ static int finish_update(vv_ctx* c, int n_slots) {
   if (c->adam_pending) { c->adam_t++; c->adam_pending = false; }      // the Adam update is queued: its t is taken
   c->upd_announced = false;
   HIPCHK(hipGetLastError());
+  if (c->ema_decay >= 0.f) {                   // the moving average, once per completed update: k_ema behind it on the step's stream, reading the new W and b
+    EmaArgs e;
+    e.W = c->W; e.b = c->b; e.eW = c->eW; e.eb = c->eb; e.nW = (int64_t)c->D * c->F; e.nb = c->D;
+    e.decay = c->ema_decay; e.om = 1.0f - c->ema_decay;
+    e.skip_if = c->comm ? vv::comm_fail_flag(c->comm) : nullptr;
+    PROFILED(c, "ema", launch_ema(e, c->F % 4 == 0, c->stream));
+    HIPCHK(hipGetLastError());
+    c->ema_updates++; c->ema_packed = false;
+  }
   c->iter++;
   c->prof_calls++;
   return VV_OK;
@@ -1320,6 +1447,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   { const int rcg = upd_pending_guard(c, "vv_forward_backward"); if (rcg) return rcg; }
   const bool upd_hint = c && c->upd_hint;       // (consumed by this call whatever path it takes)
   if (c) c->upd_hint = false;
+  if (c && c->ema_in_use) return fail(VV_ERR_STATE, "vv_forward_backward: %s", kEmaInUse);
   int rc = check_cfg(c, cfg);
   if (rc) return rc;
   if (!idx) return fail(VV_ERR_ARG, "vv_forward_backward: idx is NULL");
@@ -1631,6 +1759,7 @@ int vv_forward_backward_ring(vv_ctx* c, const vv_step_cfg* cfg, vv_batch_ring* r
   HintScope hint_scope(c);
   int rc = check_cfg(c, cfg);
   if (rc) return rc;
+  if (c->ema_in_use) return fail(VV_ERR_STATE, "vv_forward_backward_ring: %s", kEmaInUse);      // (before a batch is taken from the ring)
   if (!ring) return fail(VV_ERR_ARG, "vv_forward_backward_ring: ring is NULL");
   int32_t rb = 0, rcn = 0;
   if (vv_batch_ring_info(ring, &rb, &rcn, nullptr, nullptr)) return fail(VV_ERR_ARG, "vv_forward_backward_ring: bad ring");
@@ -1679,6 +1808,7 @@ int vv_forward_backward_q1(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx
   HintScope hint_scope(c);
   int rc = check_cfg(c, cfg);
   if (rc) return rc;
+  if (c->ema_in_use) return fail(VV_ERR_STATE, "vv_forward_backward_q1: %s", kEmaInUse);
   if (!idx || !last_src) return fail(VV_ERR_ARG, "vv_forward_backward_q1: NULL index array");
   VV_ENTER(c);
   const int64_t R = (int64_t)cfg->B * (cfg->C + cfg->Nn);
@@ -1816,8 +1946,10 @@ int vv_forward(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on
     if (c->dd_async) HIPCHK(hipStreamWaitEvent(s, set.done, 0));
   }
 
+  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
+  if ((rc = param_view(c, &pv))) return rc;
   FwdArgs fa;
-  fa.table = c->table; fa.rows = dd ? c->dd_uniq : c->rows; fa.Wh = c->Wh; fa.bias = c->b; fa.scales = c->scales;
+  fa.table = c->table; fa.rows = dd ? c->dd_uniq : c->rows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
   fa.H = c->H; fa.R = c->R; fa.D = D; fa.Fp = c->Fp; fa.relu = 1; fa.zero_row = (int32_t)c->n_rows;
   fa.n_dev = dd ? c->dd_info : nullptr;
   fa.R_hint = dd ? *(volatile int32_t*)(c->U_host + 2) : 0;
@@ -2009,6 +2141,7 @@ static int update_plain(vv_ctx* c, const SgdArgs& a, float* vW, float* vb) {
 int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   int rc = check_cfg(c, cfg);
   if (rc) return rc;
+  if (c->ema_in_use) return fail(VV_ERR_STATE, "vv_apply_update: %s", kEmaInUse);
   if (!grad_exists(c->grad)) return fail(VV_ERR_STATE, "vv_apply_update: no gradients (call vv_forward_backward)");
   if ((rc = upd_pending_guard(c, "vv_apply_update"))) return rc;     // (GradAt::Lost: a second update on a gradient that was never stored)
   // Banked gradients (vv_grads_bank, m >= 1): the update consumes the bank -- BVLC SGDSolver::ApplyUpdate on the accumulated diffs
@@ -2031,6 +2164,7 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
   if (c->upd_announced && c->clip != c->upd_clip)
     return fail(VV_ERR_ARG, "vv_apply_update: the solver parameters differ from those announced by vv_update_hint (vv_clip_gradients_set's threshold)");
   if (clip_on && (overlapped || sharded)) return fail(VV_ERR_STATE, "vv_apply_update: this step's gradient was laid out for another schedule -- %s", kClipSchedule);
+  if (c->ema_decay >= 0.f && (overlapped || sharded)) return fail(VV_ERR_STATE, "vv_apply_update: this step's gradient was laid out for another schedule -- %s", kEmaSchedule);
   const bool on_comm_stream = overlapped || (sharded && !c->comm_inline);
   if ((c->upd_sync == UpdSync::InFlight || (c->upd_sync == UpdSync::Gated && !on_comm_stream)) && (rc = comm_join(c))) return rc;
   // A sharded update left the other ranks' rows of the fp32 master W and of the history stale here; an update of the WHOLE matrix needs
@@ -2072,6 +2206,7 @@ int vv_apply_update(vv_ctx* c, const vv_step_cfg* cfg) {
 }
 
 int vv_step(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device) {
+  if (c && c->ema_in_use) return fail(VV_ERR_STATE, "vv_step: %s", kEmaInUse);
   if (c && c->bank_count > 0)
     return fail(VV_ERR_STATE, "vv_step: %d gradients are banked and this step's would not be among them (vv_forward_backward + vv_grads_bank + vv_apply_update, or vv_grads_bank_reset)", c->bank_count);
   int rc = vv_update_hint(c, cfg);                  // (nothing reads the gradient between the two halves of this call)
@@ -2428,8 +2563,10 @@ static int embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, in
   DevTmp<int32_t> drows;
   HIPCHK(drows.alloc((size_t)Rp));
   HIPCHK(hipMemcpyAsync(drows, h.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
+  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
+  { const int rcv = param_view(c, &pv); if (rcv) return rcv; }
   FwdArgs fa;
-  fa.table = c->table; fa.rows = drows; fa.Wh = c->Wh; fa.bias = c->b; fa.scales = c->scales;
+  fa.table = c->table; fa.rows = drows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
   fa.H = dout; fa.R = (int)n; fa.D = D; fa.Fp = c->Fp; fa.relu = relu ? 1 : 0; fa.zero_row = (int32_t)c->n_rows;
   fa.drop_ratio = 0.f; fa.mask = nullptr; fa.drop_seed = 0; fa.B = 1; fa.CN = 1;
   launch_fwd_gemm(c->prec, fa, c->stream);
@@ -2458,8 +2595,10 @@ static int embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, in
   HIPCHK(hipMemcpyAsync(drows, h.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dcoeff, hc.data(), (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
   launch_mean_rows(c->prec, c->table, drows_in, n, k, dcoeff, c->n_rows + 1, c->Fp, c->stream);
+  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
+  { const int rcv = param_view(c, &pv); if (rcv) return rcv; }
   FwdArgs fa;
-  fa.table = c->table; fa.rows = drows; fa.Wh = c->Wh; fa.bias = c->b; fa.scales = c->scales;
+  fa.table = c->table; fa.rows = drows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
   fa.H = dout; fa.R = (int)n; fa.D = D; fa.Fp = c->Fp; fa.relu = relu ? 1 : 0; fa.zero_row = (int32_t)c->n_rows;
   fa.drop_ratio = 0.f; fa.mask = nullptr; fa.drop_seed = 0; fa.B = 1; fa.CN = 1;
   launch_fwd_gemm(c->prec, fa, c->stream);
@@ -3087,6 +3226,7 @@ int vv_comm_overlap(vv_ctx* c, int on) {
   if (!c) return fail(VV_ERR_ARG, "vv_comm_overlap: ctx is NULL");
   if (on && c->clip >= 0.f) return fail(VV_ERR_STATE, "vv_comm_overlap: %s", kClipSchedule);
   if (on && c->bank_count > 0) return fail(VV_ERR_STATE, "vv_comm_overlap: %s", kBankSchedule);
+  if (on && c->ema_decay >= 0.f) return fail(VV_ERR_STATE, "vv_comm_overlap: %s", kEmaSchedule);
   if (on && c->comm_sharded && c->params_partial) { VV_ENTER(c); const int rcg = gather_params(c); if (rcg) return rcg; }   // (collective, as in vv_comm_schedule: leaving the sharded schedule)
   c->comm_overlap = on != 0;
   if (on) c->comm_sharded = false;
@@ -3098,6 +3238,7 @@ int vv_comm_schedule(vv_ctx* c, int schedule) {
   if (schedule < 0 || schedule > 2) return fail(VV_ERR_ARG, "vv_comm_schedule: 0 sync, 1 overlap, 2 sharded");
   if (schedule != 0 && c->clip >= 0.f) return fail(VV_ERR_STATE, "vv_comm_schedule: %s", kClipSchedule);
   if (schedule != 0 && c->bank_count > 0) return fail(VV_ERR_STATE, "vv_comm_schedule: %s", kBankSchedule);
+  if (schedule != 0 && c->ema_decay >= 0.f) return fail(VV_ERR_STATE, "vv_comm_schedule: %s", kEmaSchedule);
   { const int rcg = upd_pending_guard(c, "vv_comm_schedule"); if (rcg) return rcg; }
   if (schedule != 2 && c->params_partial) { VV_ENTER(c); const int rcg = gather_params(c); if (rcg) return rcg; }     // (collective: the other schedules update the whole matrix)
   c->comm_overlap = schedule == 1;

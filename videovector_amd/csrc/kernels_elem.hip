@@ -2010,6 +2010,44 @@ void launch_grad_bank(BankOp op, const BankArgs& a, hipStream_t s) {
   else VV_LAUNCH(k_grad_bank<BankOp::Scale>, grid, block, 0, s, a);
 }
 
+// ------------------------------------------------------------------------------- moving average of the parameters ----
+// vv_ema_set (this project's own; neither the reference tree nor BVLC Caffe keeps one): e = decay * e + om * w behind every update.
+// k_ema streams the matrix and then the bias in k_grad_bank's shape: a FIXED grid of EMA_BLOCKS x 256 threads; VEC -- thread t owns the
+// 16-byte items t, t + grid, ... of each stream (non-temporal: 4 bytes read of W, 4 read and 4 written of e per element, none of it read
+// again before the next update) and the bias's D % 4 last floats go one to a thread; scalar (F % 4 != 0) -- one float per thread and
+// pass.  One owner per element, no atomics.  The two products and the sum are separate fp32 operations (contraction is off in
+// ema_rule), so the result is the numpy-float32 restatement's bit for bit.
+__device__ __forceinline__ float ema_rule(float e, float w, float decay, float om) {
+#pragma clang fp contract(off)
+  const float p = decay * e;
+  const float q = om * w;
+  return p + q;
+}
+template <bool VEC> __device__ __forceinline__ void ema_stream(const float* w, float* e, int64_t n, float decay, float om, int64_t tid, int64_t nth) {
+  if constexpr (VEC) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = tid; i < n4; i += nth) {
+      const float4 x = nt_load4(w + i * 4), y = nt_load4(e + i * 4);
+      nt_store4(e + i * 4, make_float4(ema_rule(y.x, x.x, decay, om), ema_rule(y.y, x.y, decay, om), ema_rule(y.z, x.z, decay, om), ema_rule(y.w, x.w, decay, om)));
+    }
+    const int64_t o = n4 * 4 + tid;             // the floats behind the last whole item: at most three
+    if (o < n) e[o] = ema_rule(e[o], w[o], decay, om);
+  } else {
+    for (int64_t i = tid; i < n; i += nth) e[i] = ema_rule(e[i], w[i], decay, om);
+  }
+}
+template <bool VEC> __global__ __launch_bounds__(256) void k_ema(EmaArgs a) {
+  if (a.skip_if && __hip_atomic_load(a.skip_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)EMA_BLOCKS * 256;
+  ema_stream<VEC>(a.W, a.eW, a.nW, a.decay, a.om, tid, nth);
+  ema_stream<VEC>(a.b, a.eb, (int64_t)a.nb, a.decay, a.om, tid, nth);
+}
+void launch_ema(const EmaArgs& a, bool vec, hipStream_t s) {
+  const dim3 grid(EMA_BLOCKS), block(256);
+  if (vec) VV_LAUNCH(k_ema<true>, grid, block, 0, s, a);
+  else VV_LAUNCH(k_ema<false>, grid, block, 0, s, a);
+}
+
 // ------------------------------------------------------------------------------- magnitude statistics ----
 // The reference's debug_info (Net::ForwardDebugInfo / BackwardDebugInfo / UpdateDebugInfo, net.cpp:580-636) prints asum / count of blobs;
 // Blob::asum_data / asum_diff (blob.cpp:138-165) are caffe_gpu_asum calls.  k_abs_stats is k_grad_sumsq's reduction over |x| instead of

@@ -77,6 +77,14 @@ struct vv_ctx {
   vv::AbsRec* stat_rec = nullptr;
   float* upd_shadow = nullptr;
   bool upd_marked = false;                  // the shadow holds the parameters of a vv_debug_mark_update (vv_params_set clears it)
+  // vv_ema_set (the exponential moving average of the parameters; this project's own): < 0 off; sticky.  ONE allocation made by the
+  // activation (and again by a vv_params_set of another D), never on the step path: eW [D][F], eb [D] on the next 16-byte boundary, the
+  // average's own Scales block, its 16-bit copy eWh [Dp][Fp].  While active every finish_update queues k_ema behind the update.
+  float ema_decay = -1.f;
+  float *eW = nullptr, *eb = nullptr; vv::Scales* escales = nullptr; uint16_t* eWh = nullptr;
+  bool ema_packed = false;                  // eWh / escales are those of the average as it stands (k_ema and a re-initialisation clear it)
+  bool ema_in_use = false;                  // vv_ema_use(1): the forward-only readers take eWh / eb / escales; everything that trains refuses
+  int64_t ema_updates = 0;                  // k_ema launches since the activation
   uint16_t* Wh = nullptr; vv::Scales* scales = nullptr; float* wmax_blocks = nullptr;
   int n_cu = 256;                           // compute units of the device
   bool scale_pending = false;               // k_sgd ran, its scale update has not (it rides in the next k_reduce)

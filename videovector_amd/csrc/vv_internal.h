@@ -495,6 +495,19 @@ struct BankArgs {
   const uint32_t* skip_if = nullptr;  // as SgdArgs::skip_if: a failed exchange in front, the launch changes nothing
 };
 
+// The exponential moving average of the parameters (vv_ema_set; this project's own: neither the reference tree nor BVLC Caffe has
+// one).  k_ema: e[i] = decay * e[i] + om * w[i] over two streams, the matrix (nW = D F elements) and the bias (nb = D) -- two fp32
+// products and one fp32 sum per element, each rounded as written (no contraction).  om = 1.0f - decay, formed by the host.  All four
+// bases are on 16-byte boundaries (allocation starts; eb sits behind eW on the next one).
+constexpr int EMA_BLOCKS = 1024;      // k_ema's fixed grid: 262 144 threads, one 16-byte item (vec) or one element each per pass
+struct EmaArgs {
+  const float* W; const float* b;     // the fp32 master parameters, read after the update in front
+  float* eW; float* eb;               // the average
+  int64_t nW; int32_t nb;
+  float decay, om;
+  const uint32_t* skip_if = nullptr;  // as SgdArgs::skip_if: a failed exchange in front, the launch changes nothing
+};
+
 // Magnitude statistics (the reference's debug_info: Net::ForwardDebugInfo / BackwardDebugInfo / UpdateDebugInfo, net.cpp:580-636, over
 // Blob::asum_data / asum_diff, blob.cpp:138-165; vv_op_asum, vv_debug_stats_queue): k_abs_stats measures up to STAT_SEGS buffers in one
 // launch and leaves one record per buffer -- the layout of include/videovec.h's vv_abs_stat.  asum: the sum of |x| over the FINITE
@@ -588,6 +601,7 @@ void launch_grad_sumsq(const ClipArgs& a, hipStream_t s);            // -> ClipA
 void launch_grad_scale(const ClipArgs& a, hipStream_t s);            // g *= rec->scale where rec->clipped, else every workgroup returns at once
 void launch_grad_bank(BankOp op, const BankArgs& a, hipStream_t s);   // k_grad_bank: one owner per element, no atomics
 void launch_abs_stats(const AbsStatsArgs& a, hipStream_t s);          // k_abs_stats: reads its buffers, writes its partials and records only
+void launch_ema(const EmaArgs& a, bool vec, hipStream_t s);           // k_ema: vec -- 16-byte items (nW % 4 == 0), else one element per thread and pass
 void launch_publish(int32_t* flag, int32_t seq, hipStream_t s);
 void launch_delay(int us, hipStream_t s);                             // test hook: occupies s for `us` microseconds       // flag <- seq (agent scope), behind everything queued on s
 void launch_scale_update(int prec, Scales* sc, const float* wmax_blocks, int n_blocks, hipStream_t s);

@@ -3,6 +3,7 @@
 Mirrors the reference's solver-side view of the path (Solver::Solve loop body, solver.cpp:194-220):
 `forward_backward()` == Net::ForwardBackward, `apply_update()` == ComputeUpdateValue + Net::Update.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -57,6 +58,10 @@ class _H16Report(C.Structure):
 class _ClipReport(C.Structure):
     _fields_ = [("norm", C.c_float), ("scale", C.c_float), ("clipped", C.c_int32), ("reserved_", C.c_int32),
                 ("updates", C.c_int64), ("clipped_updates", C.c_int64)]
+
+
+class _EmaReport(C.Structure):
+    _fields_ = [("updates", C.c_int64), ("decay", C.c_float), ("in_use", C.c_int32)]
 
 
 class _AbsStat(C.Structure):
@@ -180,6 +185,8 @@ def load_library():
         "vv_forward": [vp, vp, vp, C.c_int], "vv_eval_reset": [vp], "vv_eval_stats": [vp, C.POINTER(_EvalReport)],
         "vv_op_asum": [vp, vp, i64, C.POINTER(_AbsStat)],
         "vv_debug_stats_queue": [vp, C.c_uint32], "vv_debug_mark_update": [vp], "vv_debug_stats_get": [vp, C.POINTER(_AbsStat)],
+        "vv_ema_set": [vp, f32], "vv_ema_get_decay": [vp, C.POINTER(f32)], "vv_ema_get": [vp, vp, vp], "vv_ema_put": [vp, vp, vp], "vv_ema_use": [vp, C.c_int],
+        "vv_ema_stats": [vp, C.POINTER(_EmaReport)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -564,6 +571,42 @@ class Engine:
         arr = (_AbsStat * len(STAT_NAMES))()
         self._chk(self.L.vv_debug_stats_get(self.h, arr))
         return {name: self._abs_stat(arr[i]) for i, name in enumerate(STAT_NAMES)}
+
+    # ---- the exponential moving average of the parameters (vv_ema_*; this project's own)
+    def ema_set(self, decay):
+        """decay < 0 turns the average off, 0 <= decay < 1 turns it on (started from the current W and b) or, while on, changes the decay."""
+        self._chk(self.L.vv_ema_set(self.h, float(decay)))
+
+    def ema_get(self):
+        """(eW [D][F], eb [D]): the average as host fp32 (synchronises)."""
+        W = np.empty((self.D, self.F), np.float32); b = np.empty(self.D, np.float32)
+        self._chk(self.L.vv_ema_get(self.h, _ptr(W), _ptr(b)))
+        return W, b
+
+    def ema_put(self, W=None, b=None):
+        """Replace the average by host values (a resumed run); None leaves that part."""
+        cv = lambda a, shape: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+        W, b = cv(W, (self.D, self.F)), cv(b, (self.D,))
+        self._chk(self.L.vv_ema_put(self.h, _ptr(W), _ptr(b)))
+
+    def ema_use(self, on=True):
+        """While on, forward / embed / embed_mean / gallery_from_table read the averaged parameters and everything that trains refuses."""
+        self._chk(self.L.vv_ema_use(self.h, int(bool(on))))
+
+    def ema_stats(self):
+        """updates (k_ema launches since the activation), decay, in_use."""
+        r = _EmaReport()
+        self._chk(self.L.vv_ema_stats(self.h, C.byref(r)))
+        return {"updates": int(r.updates), "decay": np.float32(r.decay), "in_use": bool(r.in_use)}
+
+    @contextlib.contextmanager
+    def ema(self):
+        """with eng.ema(): ... -- ema_use(True) around the block, the training view again behind it."""
+        self.ema_use(True)
+        try:
+            yield self
+        finally:
+            self.ema_use(False)
 
     def _ext(self, cfg):
         """StepConfig's momentum2 / rms_decay / clip_gradients -> the context, in front of a call that takes cfg."""

@@ -160,9 +160,10 @@ def extraction_net(source, batch, D, *, normalize=False, w_std=0.001):
 def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_policy="inv", gamma=0.001,
            power=0.75, stepsize=0, display=10, max_iter=100, snapshot=0, snapshot_prefix="videovec",
            random_seed=-1, snapshot_after_train=True, test_iter=0, test_interval=0, solver_type=None, delta=None,
-           snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None, test_compute_loss=False, debug_info=False):
+           snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None, test_compute_loss=False, debug_info=False,
+           ema_decay=None, test_with_ema=None):
     """Same fields as projects/videovec_embedding/mednet_embedding_train_solver.prototxt (+ solver_type / delta, and BVLC Caffe's
-    rms_decay / momentum2 for RMSPROP / ADAM, clip_gradients and iter_size, written only when given)."""
+    rms_decay / momentum2 for RMSPROP / ADAM, clip_gradients and iter_size, and this project's ema_decay / test_with_ema, written only when given)."""
     s = ['net: "%s"' % net_path, "base_lr: %g" % base_lr, "momentum: %g" % momentum,
          "weight_decay: %g" % weight_decay, 'lr_policy: "%s"' % lr_policy, "gamma: %g" % gamma,
          "power: %g" % power, "display: %d" % display, "max_iter: %d" % max_iter,
@@ -193,4 +194,8 @@ def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_pol
         s.append("snapshot_diff: true")
     if debug_info:
         s.append("debug_info: true")
+    if ema_decay is not None:
+        s.append("ema_decay: %r" % float(ema_decay))
+    if test_with_ema is not None:
+        s.append("test_with_ema: %s" % ("true" if test_with_ema else "false"))
     return "\n".join(s) + "\n"
