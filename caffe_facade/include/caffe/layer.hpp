@@ -144,8 +144,15 @@ class VideoSampledShotsDataLayer : public Layer<Dtype> {
   int num_negative_samples() const { return num_negative_samples_; }
   int feature_size() const { return feature_size_; }
   const shared_ptr<VideoDataset>& dataset() const { return dataset_; }
+  // SolverParameter.snapshot_data_state (vv_sampler_state_*, include/videovec.h): the sampler's state after the last batch this layer
+  // delivered, and its way back into a layer that has delivered none yet (a fresh sampler takes the state, then the prefetch threads
+  // start again).  One process only: with a ring shared by the ranks no consumer position exists.
+  string SamplerState();
+  void RestoreSamplerState(const string& blob);
  private:
   shared_ptr<VideoDataset> dataset_;
+  vv_sampler_param sp_;                    // what the sampler was created with (RestoreSamplerState creates it anew)
+  void CreateSampler();
   // prefetch: the sampler's background threads keep kPrefetchDepth index batches ahead of the solver
   // (BasePrefetchingDataLayer, base_data_layer.cpp:52-95; InternalThread, internal_thread.cpp:14-37)
   static constexpr int kPrefetchDepth = 128;   // covers the stretches in which the sampler falls behind the GPU step

@@ -42,6 +42,10 @@ class Solver {
 
   void Snapshot();                                           // solver.cpp:320-341
   void Restore(const char* solverstate);                     // solver.cpp:418-429
+  // SolverParameter.snapshot_data_state: <prefix>_iter_<N>.datastate -- the samplers' and the step's carried state, so that a restored
+  // run continues the SAME run (the reference's snapshot, solver.cpp:320-341, 578-596, leaves the data layer out)
+  void SnapshotDataState(const string& file);
+  void RestoreDataState(const string& file);
   void TestAll();
   void Step(bool display);                                   // one iteration of Solve's loop body (solver.cpp:194-220)
   void ReportOutputs(const Net<Dtype>& net, const char* prefix, bool with_iter, const vector<Dtype>& values);

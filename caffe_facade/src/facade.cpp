@@ -496,6 +496,38 @@ void VideoSampledShotsDataLayer<Dtype>::CreatePrefetchThread() {
 }
 template <typename Dtype>
 void VideoSampledShotsDataLayer<Dtype>::JoinPrefetchThread() {}
+template <typename Dtype>
+void VideoSampledShotsDataLayer<Dtype>::CreateSampler() {
+  const int rc = vv_sampler_create_neg(&sp_, (int)dataset_->video_id.size(), dataset_->video_id.data(), dataset_->n_shots.data(),
+                                       dataset_->row_base.data(), dataset_->shot_ids.data(), (int)dataset_->neg_video_id.size(),
+                                       dataset_->neg_video_id.data(), dataset_->neg_n_shots.data(), dataset_->neg_row_base.data(),
+                                       dataset_->neg_shot_ids.data(), &sampler_);
+  CHECK_EQ(rc, 0) << "Could not add requested number of negatives";                     // …:344
+}
+// The reference's snapshot holds nothing of this layer (solver.cpp:320-341, 578-596), so its restored run reads the run's first batches
+// again (…data_layer.cpp:768-909 carries the cursor, the negative buffer and rand() from batch to batch).  With
+// SolverParameter.snapshot_data_state the solver asks for the state here and hands it back to the layer of the restored run.
+template <typename Dtype>
+string VideoSampledShotsDataLayer<Dtype>::SamplerState() {
+  CHECK(Caffe::world() == 1 && sampler_) << "snapshot_data_state: one process only (the ranks of a data-parallel job share or split the stream)";
+  int64_t n = 0, w = 0;
+  CHECK_EQ(vv_sampler_state_size(sampler_, &n), 0) << vv_sampler_state_error();
+  string blob((size_t)n, '\0');
+  CHECK_EQ(vv_sampler_state_get(sampler_, &blob[0], n, &w), 0) << vv_sampler_state_error();
+  CHECK_EQ(w, n);
+  return blob;
+}
+template <typename Dtype>
+void VideoSampledShotsDataLayer<Dtype>::RestoreSamplerState(const string& blob) {
+  CHECK(Caffe::world() == 1 && sampler_) << "snapshot_data_state: one process only";
+  // the running sampler is ahead of a consumer that has taken nothing: a fresh one takes the state, then its pipeline starts
+  vv_sampler_destroy(sampler_);
+  sampler_ = nullptr; ring_ = nullptr; prefetching_ = false;
+  CreateSampler();
+  if (vv_sampler_state_put(sampler_, blob.data(), (int64_t)blob.size()) != 0)
+    LOG(FATAL) << "data state of layer " << this->layer_param_.get_str("name") << " does not fit this net: " << vv_sampler_state_error();
+  CreatePrefetchThread();
+}
 
 template <typename Dtype>
 void VideoSampledShotsDataLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>&, vector<Blob<Dtype>*>* top) {
@@ -557,13 +589,8 @@ void VideoSampledShotsDataLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>&, 
       LOG(INFO) << "Data-parallel rank " << Caffe::rank() << ": one logical sampler of the global batch on rank 0";
     }
   }
-  if (Caffe::rank() == 0 || per_rank_) {
-    const int rc = vv_sampler_create_neg(&sp, (int)dataset_->video_id.size(), dataset_->video_id.data(), dataset_->n_shots.data(),
-                                         dataset_->row_base.data(), dataset_->shot_ids.data(), (int)dataset_->neg_video_id.size(),
-                                         dataset_->neg_video_id.data(), dataset_->neg_n_shots.data(), dataset_->neg_row_base.data(),
-                                         dataset_->neg_shot_ids.data(), &sampler_);
-    CHECK_EQ(rc, 0) << "Could not add requested number of negatives";                     // …:344
-  }
+  sp_ = sp;
+  if (Caffe::rank() == 0 || per_rank_) CreateSampler();
   (*top)[0]->Reshape(batch_size_, context_size_ + num_negative_samples_, feature_size_, 1);  // …:214-218
   LOG(INFO) << "output data size: " << (*top)[0]->num() << "," << (*top)[0]->channels() << "," << (*top)[0]->height()
             << "," << (*top)[0]->width();

@@ -108,7 +108,8 @@ static const std::vector<MsgDef>& Msgs() {
         OPTD(136, "iter_size", T_INT32, "1"),
         // This project's own (neither the fork nor BVLC Caffe has them; 137 and 138 continue 135 / 136 and are free in both): the decay of the
         // moving average of the parameters (vv_ema_set; < 0: off) and whether Solver::Test evaluates on it
-        OPTD(137, "ema_decay", T_FLOAT, "-1"), OPTD(138, "test_with_ema", T_BOOL, "false")}},
+        OPTD(137, "ema_decay", T_FLOAT, "-1"), OPTD(138, "test_with_ema", T_BOOL, "false"),
+        OPTD(139, "snapshot_data_state", T_BOOL, "false")}},
       {"SolverState",                                                               // :176-180
        {OPT(1, "iter", T_INT32), OPT(2, "learned_net", T_STRING), RMSG(3, "history", "BlobProto")}},
       {"LayerParameter",                                                            // :215-389

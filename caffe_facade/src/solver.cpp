@@ -313,6 +313,86 @@ void Solver<Dtype>::Test(const int test_net_id) {
   Caffe::set_phase(Caffe::TRAIN);
 }
 
+// ---- SolverParameter.snapshot_data_state (field 139, default false): <prefix>_iter_<N>.datastate beside the solverstate.
+// The reference's snapshot (solver.cpp:320-341, 578-596) carries the iteration, the weights and the history; what the RUN carries from one
+// iteration to the next -- the data layer's stream (…data_layer.cpp:768-909) and the step's own hidden state -- is left out, so its
+// restored run is another run.  The file holds, in this order: the sampler state of the training net's VIDEO_SAMPLED_SHOTS_DATA layer,
+// one per such layer of every TEST net (the held-out branches: their "Test loss" lines continue too), and the training context's run state
+// (vv_run_state_*).  The retrieval TEST net's VIDEO_SHOT_WINDOW_TEST_DATA layer restarts with every run, as it always did.
+namespace {
+const char kDataStateMagic[8] = {'V', 'V', 'D', 'A', 'T', 'S', 'T', '1'};
+template <typename Dtype>
+void DataLayersOf(const shared_ptr<Net<Dtype> >& net, int net_id, vector<std::pair<string, VideoSampledShotsDataLayer<Dtype>*> >* out) {
+  for (size_t i = 0; i < net->layers().size(); ++i)
+    if (VideoSampledShotsDataLayer<Dtype>* d = dynamic_cast<VideoSampledShotsDataLayer<Dtype>*>(net->layers()[i].get()))
+      out->push_back(std::make_pair((net_id < 0 ? string("train/") : "test" + std::to_string(net_id) + "/") + net->layer_names()[i], d));
+}
+void PutBlob(FILE* f, const string& s) { const uint64_t n = s.size(); fwrite(&n, 8, 1, f); if (n) fwrite(s.data(), 1, n, f); }
+bool GetBlob(FILE* f, string* s) {
+  uint64_t n = 0;
+  if (fread(&n, 8, 1, f) != 1 || n > ((uint64_t)1 << 34)) return false;
+  s->resize((size_t)n);
+  return n == 0 || fread(&(*s)[0], 1, (size_t)n, f) == n;
+}
+string DataStateFileOf(const string& model_or_state_file, const string& ext) {
+  if (model_or_state_file.size() > ext.size() && model_or_state_file.compare(model_or_state_file.size() - ext.size(), ext.size(), ext) == 0)
+    return model_or_state_file.substr(0, model_or_state_file.size() - ext.size()) + ".datastate";
+  return string();
+}
+}  // namespace
+
+template <typename Dtype>
+void Solver<Dtype>::SnapshotDataState(const string& file) {
+  CHECK_EQ(Caffe::world(), 1) << "snapshot_data_state: one process only";
+  vector<std::pair<string, VideoSampledShotsDataLayer<Dtype>*> > layers;
+  DataLayersOf(net_, -1, &layers);
+  for (size_t t = 0; t < test_nets_.size(); ++t) DataLayersOf(test_nets_[t], (int)t, &layers);
+  int64_t n = 0, w = 0;
+  VV_CHECK(vv_run_state_size(Caffe::ctx(), &n));
+  string run((size_t)n, '\0');
+  VV_CHECK(vv_run_state_get(Caffe::ctx(), &run[0], n, &w));
+  FILE* f = fopen(file.c_str(), "wb");
+  CHECK(f) << "cannot write " << file;
+  fwrite(kDataStateMagic, 1, 8, f);
+  const uint32_t count = (uint32_t)layers.size();
+  fwrite(&count, 4, 1, f);
+  for (size_t i = 0; i < layers.size(); ++i) { PutBlob(f, layers[i].first); PutBlob(f, layers[i].second->SamplerState()); }
+  PutBlob(f, run);
+  CHECK_EQ(fclose(f), 0) << "cannot write " << file;
+  LOG(INFO) << "Snapshotting data state to " << file << " (" << count << " sampler" << (count == 1 ? "" : "s") << ", the step's carried state)";
+}
+
+template <typename Dtype>
+void Solver<Dtype>::RestoreDataState(const string& file) {
+  FILE* f = file.empty() ? nullptr : fopen(file.c_str(), "rb");
+  if (!f) {
+    LOG(INFO) << "No data state beside the restored solver state" << (file.empty() ? string() : " (" + file + ")") << ": the data layers start over, this run sees the first batches again";
+    return;
+  }
+  vector<std::pair<string, VideoSampledShotsDataLayer<Dtype>*> > layers;
+  DataLayersOf(net_, -1, &layers);
+  for (size_t t = 0; t < test_nets_.size(); ++t) DataLayersOf(test_nets_[t], (int)t, &layers);
+  char magic[8]; uint32_t count = 0;
+  CHECK(fread(magic, 1, 8, f) == 8 && !memcmp(magic, kDataStateMagic, 8) && fread(&count, 4, 1, f) == 1) << file << " is not a data state file";
+  if (count != layers.size())
+    LOG(FATAL) << "data state " << file << " does not fit this solver: it holds " << count << " samplers, the nets have " << layers.size() << " VIDEO_SAMPLED_SHOTS_DATA layers";
+  vector<string> blobs(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    string name;
+    CHECK(GetBlob(f, &name) && GetBlob(f, &blobs[i])) << file << " is truncated";
+    if (name != layers[i].first) LOG(FATAL) << "data state " << file << " does not fit this solver: its sampler " << i << " belongs to layer " << name << ", here that is " << layers[i].first;
+  }
+  string run;
+  CHECK(GetBlob(f, &run)) << file << " is truncated";
+  fclose(f);
+  // the order of include/videovec.h: parameters, histories and the update count are in place (Restore) -- then the run state, which
+  // vv_params_set would reset in part; the samplers are independent of it
+  if (vv_run_state_put(Caffe::ctx(), run.data(), (int64_t)run.size()) != 0)
+    LOG(FATAL) << "data state " << file << " does not fit this solver: " << vv_last_error();
+  for (uint32_t i = 0; i < count; ++i) layers[i].second->RestoreSamplerState(blobs[i]);
+  LOG(INFO) << "Restoring data state from " << file << ": " << count << " sampler" << (count == 1 ? "" : "s") << " and the step's carried state continue where the snapshot left them";
+}
+
 // Solver::Snapshot (solver.cpp:320-341): <prefix>_iter_<N>.caffemodel + .solverstate naming the model file.
 template <typename Dtype>
 void Solver<Dtype>::Snapshot() {
@@ -339,6 +419,7 @@ void Solver<Dtype>::Snapshot() {
     LOG(INFO) << "Snapshotting the moving average to " << ema_file;
     pl::WriteProtoToBinaryFile(averaged, ema_file);
   }
+  if (param_.get_bool("snapshot_data_state")) SnapshotDataState(stem + ".datastate");
 }
 
 // Solver::Restore (solver.cpp:418-429)
@@ -371,6 +452,8 @@ void Solver<Dtype>::Restore(const char* state_file) {
       LOG(INFO) << "No averaged model beside the restored weights" << (ema_file.empty() ? string() : " (" + ema_file + ")") << ": the moving average starts from the restored weights";
     }
   }
+  // last: everything above goes through vv_params_set, which resets part of the run state
+  if (param_.get_bool("snapshot_data_state")) RestoreDataState(DataStateFileOf(state_file, ".solverstate"));
 }
 
 // ------------------------------------------------------------------------------- SGD -----------

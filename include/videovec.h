@@ -184,6 +184,27 @@ int vv_solver_iter_get(vv_ctx* ctx, int64_t* count);
 int vv_history2_set(vv_ctx* ctx, const float* vW, const float* vb);
 int vv_history2_get(vv_ctx* ctx, float* vW, float* vb);
 
+/* ---- the step's carried state, for a run that resumes bit for bit.  The reference's SGDSolver::SnapshotSolverState / RestoreSolverState
+ * (src/caffe/solver.cpp:578-596, with Solver::Snapshot, :320-341) carry the iteration and the history; its step carries nothing else
+ * from one iteration to the next.  This one does (a counter-based dropout mask, 16-bit operands with lagging power-of-two scales, report
+ * rings read at a fixed lag), and these calls carry it: an opaque, versioned blob of what a training step reads that earlier steps left
+ * and that vv_params_get, vv_history2_get, vv_solver_iter_get and vv_ema_get do not return --
+ *   the dropout counter; the steps' sequence number; the W -> 16-bit scales (Scales: they follow max |W| one update late, where
+ *   vv_params_set computes them from the values it is given), the per-block maxima the next scale update folds, and the 16-bit copy of W
+ *   rounded at those scales; the gradient scale's adjustment and the report ring it is steered by; the f16 rows' guard (which reports are
+ *   due, the fallback); the gradient guard's device record; the distinct-row hints that size the next forward GEMM's tiles.
+ * Not carried: statistics counted since vv_create that no step reads (vv_clip_stats, vv_accum_stats, vv_eval_stats, vv_ema_stats's count).
+ * Order on the resuming side: vv_params_set, vv_history2_set, vv_solver_iter_set (vv_ema_set / vv_ema_put), THEN vv_run_state_put --
+ * vv_params_set resets part of this state.  Options (vv_set_option) and the table are the caller's to set up as they were.
+ * vv_run_state_get synchronises.  Both return VV_ERR_STATE without parameters; while a backward pass's gradient waits for its
+ * vv_apply_update (get), or any gradient is held (put: the context comes fresh from vv_params_set); while a step announced by
+ * vv_update_hint is under way; while gradients are banked; while the overlapped or sharded schedule is selected or an update of theirs is
+ * in flight; while the average is in use (vv_ema_use(1)).  vv_run_state_put: a blob of another version, D, F or operand type, a truncated
+ * or over-long one: VV_ERR_ARG, nothing past `bytes` is read and the context is untouched. */
+int vv_run_state_size(vv_ctx* ctx, int64_t* bytes);
+int vv_run_state_get(vv_ctx* ctx, void* buf, int64_t cap, int64_t* written);
+int vv_run_state_put(vv_ctx* ctx, const void* buf, int64_t bytes);
+
 /* ---- gradient clipping by the global L2 norm: BVLC Caffe's SolverParameter.clip_gradients and SGDSolver::ClipGradients (sgd_solver.cpp);
  * the reference tree has no such function, so the semantics are BVLC's.  clip < 0 (the default, -1) disables it and a step is in every
  * respect what it was; clip >= 0 makes it active; NaN is VV_ERR_ARG.  Sticky on the context until set again.  In an active
@@ -761,7 +782,9 @@ int vv_sampler_prefetch_stop(vv_sampler* s);
  * 7 = the 512-bit forms of the walk and the slot draw are in use (0/1: the host has AVX-512 F/BW/DQ/VL/VBMI2 and
  * VV_SAMPLER_AVX512 is not 0; same indices either way), 8 = ticks the walk stage waited for the stream-generating
  * thread (four-thread pipeline), 9 = cores held for the stage threads (4: one each, claimed against other samplers
- * of the host through /dev/shm/vv_sampler_cpu_<n> locks; 0: the threads share the caller's group of CPUs).  -1 = unknown. */
+ * of the host through /dev/shm/vv_sampler_cpu_<n> locks; 0: the threads share the caller's group of CPUs), 10 = whole batches the
+ * running pipeline has produced, 11 = batches its consumers have all taken (10 minus 11 = how far the pipeline is ahead; both -1
+ * without a pipeline).  -1 = unknown. */
 int64_t vv_sampler_stat(vv_sampler* s, int32_t which);
 
 /* A reader's view of a sampler's batch ring.  vv_sampler_ring: the producer process's own handle (owned by the
@@ -776,6 +799,31 @@ int vv_batch_ring_info(vv_batch_ring* r, int32_t* batch_size, int32_t* slots_per
 int vv_batch_ring_next(vv_batch_ring* r, int32_t consumer, int32_t item_begin, int32_t item_count, int32_t* idx,
                        int32_t* label, double timeout_s);
 int vv_batch_ring_detach(vv_batch_ring* r);
+
+/* ---- the sampler's state, for a run that resumes bit for bit.  The reference's snapshot (Solver::Snapshot / SGDSolver::SnapshotSolverState,
+ * src/caffe/solver.cpp:320-341, 578-596) saves the iteration, the learned net and the history and NOTHING of the data layer: neither the DB
+ * cursor, nor the negative buffer, nor the rand() state that its batch loop (video_sampled_shots_data_layer.cpp:768-909) carries from one
+ * batch to the next, so a restored reference run reads the run's first batches again.  These three calls carry that state.
+ * The state meant is that of the reference's ONE sequential stream after the last batch DELIVERED to the consumer -- returned by
+ * vv_sampler_next, or taken from the ring by its single consumer -- not after the last batch the prefetch pipeline has produced:
+ *   the libc stream (its 31 state words, oldest first: the order is the position), the DB cursor and the negative dataset's own, the
+ *   negative buffer (rows, keys; the membership set or bitmap is rebuilt from them), the persistent slot permutation (buffer_ids_), and on
+ *   the general path the persistent slot contents that quirk Q1's last_src depends on.
+ * The blob is opaque: a magic, a version, a fingerprint (every field of vv_sampler_param, the number of videos, the shot counts, the
+ * negative dataset's shape; bytes [24, 112)) and the state.  Its size depends on the fingerprint alone (vv_sampler_state_size).
+ * vv_sampler_state_get: never changes a batch delivered later, with the pipeline running or not; two calls with no batch delivered in
+ *   between return identical bytes.  With the pipeline running nothing is stopped or rewound: a private serial sampler is replayed, in the
+ *   calling thread, over the batches delivered since vv_sampler_prefetch_start or the previous call (the cost falls here, not on a batch).
+ *   Call it from the consumer's thread, or while the consumer is quiet.  cap < the state's size: VV_ERR_ARG.  VV_ERR_STATE where no single
+ *   consumer position exists: a ring with more than one consumer, VV_SAMPLER_MODE=node in the environment, after vv_sampler_prefetch_stop
+ *   (it drops batches the pipeline has produced).
+ * vv_sampler_state_put: only on a sampler that has neither delivered a batch nor started its pipeline, else VV_ERR_STATE.  A blob of
+ *   another fingerprint, a truncated, over-long or damaged one: VV_ERR_ARG; nothing past `bytes` is read and the sampler is untouched.
+ * vv_sampler_state_error: this thread's last message of these calls (which fingerprint field differs, and how). */
+int vv_sampler_state_size(vv_sampler* s, int64_t* bytes);
+int vv_sampler_state_get(vv_sampler* s, void* buf, int64_t cap, int64_t* written);
+int vv_sampler_state_put(vv_sampler* s, const void* buf, int64_t bytes);
+const char* vv_sampler_state_error(void);
 /* BasePrefetchingDataLayer::Forward_gpu (src/caffe/layers/base_data_layer.cu:7-21: join the prefetch thread, copy the
  * batch to the device) + Net::ForwardBackward: take this consumer's next batch out of the ring -- items
  * [item_begin, item_begin + cfg->B) of it -- send the indices to the device through a pinned staging buffer with an

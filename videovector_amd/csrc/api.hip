@@ -266,6 +266,7 @@ static void free_batch(vv_ctx* c) {
   c->loss_part = c->viol_part = c->s_true = c->s_bogus = c->coeff = nullptr; c->slabs = nullptr;
   c->slab_bytes = 0; c->B = c->C = c->Nn = c->R = c->Rp = 0; c->coeff_host.clear();
   grad_discard(c->grad);                      // (a reduction that was still due named the buffers just freed: red_args)
+  c->grad_unapplied = false;
 }
 
 int vv_destroy(vv_ctx* c) {
@@ -635,6 +636,7 @@ int vv_params_set(vv_ctx* c, int32_t D, const float* W, const float* b, const fl
   if (c->ema_decay >= 0.f) { const int rce = ema_init(c); if (rce) return rce; }      // the average starts again from the new values
   HIPCHK(hipStreamSynchronize(c->stream));
   grad_discard(c->grad);
+  c->grad_unapplied = false;
   return VV_OK;
 }
 
@@ -701,6 +703,129 @@ int vv_solver_iter_get(vv_ctx* c, int64_t* t) {
   *t = c->adam_t;
   return VV_OK;
 }
+// ---- the step's carried state (vv_run_state_*): what a training step reads that earlier steps left and no other getter returns.
+// DESIGN.md, "Resume bit for bit", lists every member with the line that reads it.
+extern "C++" int ensure_batch(vv_ctx* c, int B, int C, int Nn);
+namespace {
+constexpr uint64_t kRunMagic = 0x3154534e55525656ull;        // "VVRUNST1"
+constexpr uint32_t kRunVersion = 1;
+struct RunHdr {
+  uint64_t magic; uint32_t version, hdr_bytes;
+  int64_t total_bytes;
+  int32_t D, F, Dp, Fp, prec, pad0_;
+  int32_t B, C, Nn, pad2_;                                   // the batch shape the per-shape members below belong to (0: no step yet)
+  uint64_t iter;                                             // the dropout counter (the counter mask's argument)
+  int32_t step_seq, gg_seq0, sg_adj, h16_arm_seq;            // the steps' sequence numbers; the gradient scale's steering
+  float sg; int32_t h16_fallback;
+  int64_t gg_repeats, h16_flagged_steps, h16_first_flagged, h16_flag_step, h16_flag_sat, h16_flag_faint;
+  int32_t h16_counted[GMAX_ENTRIES];                         // which report entries the f16 rows' guard still has to read
+  int32_t u_hint[3], wmax_cur;                               // the distinct-row hints; the per-block maxima buffer the last update wrote
+  int32_t wmax_n, scale_pending, wmax_seed_live, pad1_;
+  Scales scales;                                             // device: sw_cur / sw_next lag max |W| by one update
+  GradGuard gg;                                              // device
+  unsigned long long gmax[GMAX_ENTRIES * GMAX_ENTRY_WORDS];  // the report ring both guards read at a fixed lag
+};
+static_assert(sizeof(RunHdr) % 8 == 0, "RunHdr");
+int64_t run_state_bytes(const vv_ctx* c) { return (int64_t)sizeof(RunHdr) + (int64_t)2 * WMAX_SLOTS * 4 + (int64_t)c->Dp * c->Fp * 2; }
+// where neither call has a defined answer
+int run_state_guard(vv_ctx* c, const char* who, bool put) {
+  if (!c->W) return fail(VV_ERR_STATE, "%s: no parameters", who);
+  if (put ? grad_exists(c->grad) : c->grad_unapplied)
+    return fail(VV_ERR_STATE, put ? "%s: a gradient is held: the state goes into a context fresh from vv_params_set" : "%s: a gradient is held that no update has consumed: the state would miss it (vv_apply_update first)", who);
+  if (c->upd_hint || c->upd_announced) return fail(VV_ERR_STATE, "%s: a step announced by vv_update_hint is under way", who);
+  if (c->bank_count > 0) return fail(VV_ERR_STATE, "%s: %d gradients are banked (vv_apply_update or vv_grads_bank_reset first)", who, c->bank_count);
+  if (c->comm_overlap || c->comm_sharded || c->upd_sync != UpdSync::Joined || c->params_partial)
+    return fail(VV_ERR_STATE, "%s: the overlapped / sharded schedule keeps an update in flight between steps (vv_comm_schedule(0) first)", who);
+  if (c->ema_in_use) return fail(VV_ERR_STATE, "%s: %s", who, kEmaInUse);
+  return VV_OK;
+}
+}  // namespace
+
+int vv_run_state_size(vv_ctx* c, int64_t* bytes) {
+  if (!c || !bytes) return fail(VV_ERR_ARG, "vv_run_state_size: NULL argument");
+  if (!c->W) return fail(VV_ERR_STATE, "vv_run_state_size: no parameters (the size depends on D and F)");
+  *bytes = run_state_bytes(c);
+  return VV_OK;
+}
+
+int vv_run_state_get(vv_ctx* c, void* buf, int64_t cap, int64_t* written) {
+  if (!c || !buf) return fail(VV_ERR_ARG, "vv_run_state_get: NULL argument");
+  if (written) *written = 0;
+  { const int rcg = run_state_guard(c, "vv_run_state_get", false); if (rcg) return rcg; }
+  const int64_t need = run_state_bytes(c);
+  if (cap < need) return fail(VV_ERR_ARG, "vv_run_state_get: %lld bytes of room, the state has %lld", (long long)cap, (long long)need);
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->dd_stream) HIPCHK(hipStreamSynchronize(c->dd_stream));
+  RunHdr h; memset(&h, 0, sizeof(h));
+  h.magic = kRunMagic; h.version = kRunVersion; h.hdr_bytes = (uint32_t)sizeof(RunHdr); h.total_bytes = need;
+  h.D = c->D; h.F = c->F; h.Dp = c->Dp; h.Fp = c->Fp; h.prec = c->prec;
+  h.B = c->B; h.C = c->C; h.Nn = c->Nn;
+  h.iter = c->iter;
+  h.step_seq = c->step_seq; h.gg_seq0 = c->gg_seq0; h.sg_adj = c->sg_adj; h.h16_arm_seq = c->h16_arm_seq;
+  h.sg = c->sg; h.h16_fallback = c->h16_fallback ? 1 : 0;
+  h.gg_repeats = c->gg_repeats; h.h16_flagged_steps = c->h16_flagged_steps; h.h16_first_flagged = c->h16_first_flagged;
+  h.h16_flag_step = c->h16_flag_step; h.h16_flag_sat = c->h16_flag_sat; h.h16_flag_faint = c->h16_flag_faint;
+  memcpy(h.h16_counted, c->h16_counted, sizeof(h.h16_counted));
+  for (int i = 0; i < 3; ++i) h.u_hint[i] = *(volatile int32_t*)(c->U_host + i);
+  h.wmax_cur = c->wmax_cur; h.wmax_n = c->wmax_n; h.scale_pending = c->scale_pending ? 1 : 0; h.wmax_seed_live = c->wmax_seed_live ? 1 : 0;
+  HIPCHK(hipMemcpy(&h.scales, c->scales, sizeof(Scales), hipMemcpyDeviceToHost));
+  if (c->gg) HIPCHK(hipMemcpy(&h.gg, c->gg, sizeof(GradGuard), hipMemcpyDeviceToHost));
+  for (int i = 0; i < GMAX_ENTRIES * GMAX_ENTRY_WORDS; ++i) h.gmax[i] = __atomic_load_n(c->gmax_host + i, __ATOMIC_ACQUIRE);
+  unsigned char* q = (unsigned char*)buf;
+  memcpy(q, &h, sizeof(h)); q += sizeof(h);
+  HIPCHK(hipMemcpy(q, c->wmax_blocks, (size_t)2 * WMAX_SLOTS * 4, hipMemcpyDeviceToHost)); q += (size_t)2 * WMAX_SLOTS * 4;
+  HIPCHK(hipMemcpy(q, c->Wh, (size_t)c->Dp * c->Fp * 2, hipMemcpyDeviceToHost));
+  if (written) *written = need;
+  return VV_OK;
+}
+
+int vv_run_state_put(vv_ctx* c, const void* buf, int64_t bytes) {
+  if (!c || !buf) return fail(VV_ERR_ARG, "vv_run_state_put: NULL argument");
+  { const int rcg = run_state_guard(c, "vv_run_state_put", true); if (rcg) return rcg; }
+  if (bytes < (int64_t)sizeof(RunHdr)) return fail(VV_ERR_ARG, "vv_run_state_put: %lld bytes hold no header", (long long)bytes);
+  RunHdr h; memcpy(&h, buf, sizeof(h));
+  if (h.magic != kRunMagic) return fail(VV_ERR_ARG, "vv_run_state_put: not a run state (magic)");
+  if (h.version != kRunVersion || h.hdr_bytes != sizeof(RunHdr)) return fail(VV_ERR_ARG, "vv_run_state_put: state version %u, this library reads %u", h.version, kRunVersion);
+  if (h.D != c->D || h.F != c->F) return fail(VV_ERR_ARG, "vv_run_state_put: the state was taken at D = %d, F = %d, this context has D = %d, F = %d", h.D, h.F, c->D, c->F);
+  if (h.prec != c->prec) return fail(VV_ERR_ARG, "vv_run_state_put: the state was taken with operand type %d, this context has %d", h.prec, c->prec);
+  if (h.Dp != c->Dp || h.Fp != c->Fp || h.total_bytes != run_state_bytes(c) || bytes != h.total_bytes)
+    return fail(VV_ERR_ARG, "vv_run_state_put: %lld bytes given, the state of this context has %lld (truncated or over-long)", (long long)bytes, (long long)run_state_bytes(c));
+  if (h.wmax_cur < 0 || h.wmax_cur > 1 || h.wmax_n < 0 || h.wmax_n > WMAX_SLOTS) return fail(VV_ERR_ARG, "vv_run_state_put: damaged state (per-block maxima)");
+  if (h.B < 0 || h.C < 0 || h.Nn < 0 || (h.B > 0 && h.C < 2)) return fail(VV_ERR_ARG, "vv_run_state_put: damaged state (batch shape)");
+  VV_ENTER(c);
+  { const int rcj = comm_join(c); if (rcj) return rcj; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->dd_stream) HIPCHK(hipStreamSynchronize(c->dd_stream));
+  // The gradient scale's steering and the distinct-row hints belong to a batch shape: sizing the batch buffers starts them afresh
+  // (free_batch, ensure_batch).  So the buffers are sized for the state's shape FIRST -- the resumed run's first step then finds them
+  // as the interrupted run's next step would have -- and the state is written over the fresh start.
+  if (h.B > 0) { const int rcb = ensure_batch(c, h.B, h.C, h.Nn); if (rcb) return rcb; }
+  c->iter = h.iter;
+  c->step_seq = h.step_seq; c->gg_seq0 = h.gg_seq0; c->sg_adj = h.sg_adj; c->h16_arm_seq = h.h16_arm_seq;
+  c->sg = h.sg; c->h16_fallback = h.h16_fallback != 0;
+  c->gg_repeats = h.gg_repeats; c->h16_flagged_steps = h.h16_flagged_steps; c->h16_first_flagged = h.h16_first_flagged;
+  c->h16_flag_step = h.h16_flag_step; c->h16_flag_sat = h.h16_flag_sat; c->h16_flag_faint = h.h16_flag_faint;
+  memcpy(c->h16_counted, h.h16_counted, sizeof(h.h16_counted));
+  for (int i = 0; i < 3; ++i) c->U_host[i] = h.u_hint[i];
+  c->wmax_cur = h.wmax_cur; c->wmax_n = h.wmax_n; c->scale_pending = h.scale_pending != 0; c->wmax_seed_live = h.wmax_seed_live != 0;
+  // every earlier step is over: both stamps stand at the last sequence number, as they would behind a synchronised run
+  c->seq_host[0] = c->seq_host[1] = h.step_seq;
+  for (int i = 0; i < vv_ctx::kDdAll; ++i) c->dd_set[i].used_seq = 0;
+  for (int i = 0; i < vv_ctx::kStage; ++i) c->stage_seq[i] = h.step_seq;
+  h.scales.sx = c->sx;                                       // (the table is this context's own)
+  HIPCHK(hipMemcpy(c->scales, &h.scales, sizeof(Scales), hipMemcpyHostToDevice));
+  if (c->gg) HIPCHK(hipMemcpy(c->gg, &h.gg, sizeof(GradGuard), hipMemcpyHostToDevice));
+  for (int i = 0; i < GMAX_ENTRIES * GMAX_ENTRY_WORDS; ++i) __atomic_store_n(c->gmax_host + i, h.gmax[i], __ATOMIC_RELEASE);
+  const unsigned char* q = (const unsigned char*)buf + sizeof(RunHdr);
+  HIPCHK(hipMemcpy(c->wmax_blocks, q, (size_t)2 * WMAX_SLOTS * 4, hipMemcpyHostToDevice)); q += (size_t)2 * WMAX_SLOTS * 4;
+  HIPCHK(hipMemcpy(c->Wh, q, (size_t)c->Dp * c->Fp * 2, hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());
+  c->ema_packed = false;
+  return VV_OK;
+}
+
 int vv_history2_set(vv_ctx* c, const float* vW, const float* vb) {
   if (!c) return fail(VV_ERR_ARG, "vv_history2_set: ctx is NULL");
   { const int rcg = upd_pending_guard(c, "vv_history2_set"); if (rcg) return rcg; }
@@ -973,7 +1098,7 @@ static int bank_to_buffer(vv_ctx* c, bool clip_on) {
 }
 
 // ------------------------------------------------------------------------------- step ---------
-static int ensure_batch(vv_ctx* c, int B, int C, int Nn) {
+extern "C++" int ensure_batch(vv_ctx* c, int B, int C, int Nn) {
   if (B == c->B && C == c->C && Nn == c->Nn && c->H) return VV_OK;
   HIPCHK(hipStreamSynchronize(c->stream));
   free_batch(c);
@@ -1146,6 +1271,7 @@ static int finish_update(vv_ctx* c, int n_slots) {
   c->scale_pending = true;
   if (c->adam_pending) { c->adam_t++; c->adam_pending = false; }      // the Adam update is queued: its t is taken
   c->upd_announced = false;
+  c->grad_unapplied = false;
   HIPCHK(hipGetLastError());
   if (c->ema_decay >= 0.f) {                   // the moving average, once per completed update: k_ema behind it on the step's stream, reading the new W and b
     EmaArgs e;
@@ -1393,6 +1519,7 @@ static int wgrad_to_destination(vv_ctx* c, WgradArgs& wa, ReduceArgs& ra, bool u
   // Gradient clipping announced with the hint: the update needs the whole gradient's norm first -- the hint changes nothing either.)
   c->upd_announced = upd_hint;
   c->fb_hinted = upd_hint; c->grad_banked = false;       // (vv_grads_bank: a new gradient, bankable once unless it was announced)
+  c->grad_unapplied = true;
   const bool fuse_w = upd_hint && c->wgrad_update && lazy && c->S == 1 && wgrad_can_fuse_update() && !c->fuse_keep_grads &&
                       (c->Dp / BM) * (c->Fp / BN) <= WMAX_SLOTS && c->upd_cfg.solver_type != VV_SOLVER_ADAM && !(c->upd_clip >= 0.f);
   if (fuse_w) {

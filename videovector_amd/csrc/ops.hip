@@ -429,6 +429,7 @@ int vv_op_inner_product_bwd(vv_ctx* c, const float* dY, int64_t R, float ip_regu
   vv::grad_to_buffer(c->grad, vv::GradLayout::Flat, !c->comm, false);
   c->upd_announced = false;            // (this gradient is the operator's: no vv_update_hint announced its update)
   c->fb_hinted = false; c->grad_banked = false;     // ... and vv_grads_bank may take it, once
+  c->grad_unapplied = true;
   return VV_OK;
 }
 

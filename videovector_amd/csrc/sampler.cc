@@ -25,6 +25,7 @@
 #include <atomic>
 #include <cerrno>
 #include <chrono>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -191,6 +192,18 @@ class LibcRand {
     for (int b = 0; b < 2; ++b) { blk_[b].clear(); blk_[b].shrink_to_fit(); blkf_[b].clear(); blkf_[b].shrink_to_fit(); blkp_[b].clear(); blkp_[b].shrink_to_fit(); }
   }
   uint64_t wait_ticks() const { return wait_ticks_; }         // time-stamp-counter ticks the consumer waited for the helper's next block
+  // ---- the stream's state (vv_sampler_state_*): the 31 words in front of the next unconsumed value, oldest first -- glibc's state array
+  // read from its front pointer on.  The order IS the position: no separate front / rear pointer is kept in this linear form.
+  static constexpr int kStateWords = 31;
+  void get_history(uint32_t* w) const { memcpy(w, base_ + pos_ - kStateWords, kStateWords * sizeof(uint32_t)); }
+  void set_history(const uint32_t* w) {        // (single-buffer mode only: the caller holds no helper thread)
+    uint32_t* h = h_.data();
+    for (int i = 0; i < kStateWords; ++i) h[kHist - kStateWords + i] = w[i];
+    for (int i = kHist - kStateWords - 1; i >= 0; --i) h[i] = h[i + 31] - h[i + 28];
+    generate(h + kHist, aux_ ? hf_.data() + kHist : nullptr, aux_ ? hp_.data() + kHist : nullptr, 0);
+    base_ = h + kHist; pos_ = 0; avail_ = n_;
+    if (aux_) { basef_ = hf_.data() + kHist; basep_ = hp_.data() + kHist; }
+  }
   void pin_helper_like_caller(const cpu_set_t* set) { helper_set_ = set ? *set : cpu_set_t(); helper_pin_ = set != nullptr; }
 
  private:
@@ -595,6 +608,18 @@ struct vv_sampler {
   void run_walk();
   void run_negs(bool also_frames);
   void run_frames();
+
+  // ---- state for a bit-exact resume (vv_sampler_state_*).  The logical state is the one sequential stream's after the last batch
+  // DELIVERED to the consumer.  Without a ring this object is at that position.  With the pipeline running its chains are ahead of the
+  // consumer at three different positions, so the position is kept apart: the blob of the state at vv_sampler_prefetch_start (base_blob),
+  // and from the first vv_sampler_state_get on a private serial sampler (shadow) that is replayed up to the ring's released count.
+  int rng_block = 0;                          // LibcRand::init's block size (the shadow's stream is set up the same way)
+  int32_t neg_cursor = 0;                     // the negative dataset's own cursor after the fill (:253-286; not moved afterwards)
+  int32_t neg_videos = 0; int64_t neg_total_shots = 0;
+  bool started = false;                       // vv_sampler_next or vv_sampler_prefetch_start has run: vv_sampler_state_put is over
+  bool ring_stopped = false;                  // vv_sampler_prefetch_stop dropped produced batches: no consumer position any more
+  std::vector<unsigned char> base_blob;
+  vv_sampler* shadow = nullptr; int64_t shadow_at = 0;     // ring batches delivered at the shadow's (or base_blob's) position
 };
 
 // ---- the three chains of one item -----------------------------------------------------------------------------
@@ -1230,6 +1255,154 @@ int vv_sampler::sample_batch(int32_t* idx, int32_t* last_src, int32_t* label) {
   return VV_OK;
 }
 
+// ---- the sampler's state as a blob (vv_sampler_state_*) -----------------------------------------------------------
+// What the reference's snapshot leaves out (solver.cpp:320-341, 578-596 save the iteration, the learned net and the history; nothing of
+// the data layer) and what its batch loop carries from one batch to the next (video_sampled_shots_data_layer.cpp:768-909): the libc
+// stream, the DB cursor (and the negative dataset's own), the negative buffer with its key set, the persistent slot permutation
+// (buffer_ids_) and, on the general path, the slot contents quirk Q1's last_src depends on.
+// Layout (host byte order): StateHdr, then buf_key uint64 [mb] (only when membership is a key set: with the row bitmap the rows ARE the
+// keys), buf_row int32 [mb], buffer_ids int32 [mb], slots {row, last} int32 [n_slots][2].  The size follows from the fingerprint alone.
+namespace {
+constexpr uint64_t kStateMagic = 0x3154535053565656ull;      // "VVVSPST1"
+constexpr uint32_t kStateVersion = 1;
+struct StateHdr {
+  uint64_t magic; uint32_t version, hdr_bytes;
+  int64_t total_bytes;
+  // the fingerprint, bytes [24, 112): a blob goes back only into a sampler built from the same parameters over the same records
+  vv_sampler_param p;
+  int32_t n_videos, neg_videos;
+  int64_t total_shots, neg_total_shots;
+  uint64_t shots_hash;                        // FNV-1a over the records' shot counts
+  int32_t dense_keys, n_slots;
+  // the state
+  int32_t cursor, neg_cursor;
+  uint32_t rng[LibcRand::kStateWords]; uint32_t pad_;
+};
+static_assert(sizeof(StateHdr) == 248, "StateHdr has no implicit padding");
+thread_local char g_state_err[256] = "";
+int state_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int state_fail(int code, const char* fmt, ...) {
+  va_list ap; va_start(ap, fmt); vsnprintf(g_state_err, sizeof(g_state_err), fmt, ap); va_end(ap);
+  return code;
+}
+
+void state_fingerprint(const vv_sampler* s, StateHdr* h) {
+  memset(h, 0, sizeof(*h));
+  h->magic = kStateMagic; h->version = kStateVersion; h->hdr_bytes = (uint32_t)sizeof(StateHdr);
+  h->p = s->p;
+  h->n_videos = (int32_t)s->video_id.size(); h->neg_videos = s->neg_videos; h->neg_total_shots = s->neg_total_shots;
+  uint64_t hash = 0xcbf29ce484222325ull; int64_t total = 0;
+  for (const int32_t n : s->n_shots) {
+    total += n;
+    for (int k = 0; k < 4; ++k) { hash ^= (uint64_t)(((uint32_t)n >> (8 * k)) & 0xff); hash *= 0x100000001b3ull; }
+  }
+  h->total_shots = total; h->shots_hash = hash;
+  h->dense_keys = s->dense_keys ? 1 : 0; h->n_slots = (int32_t)s->slots.size();
+  const int64_t mb = (int64_t)s->buffer_ids.size();
+  h->total_bytes = (int64_t)sizeof(StateHdr) + (s->dense_keys ? 0 : mb * 8) + mb * 4 + mb * 4 + (int64_t)s->slots.size() * 8;
+}
+int64_t state_bytes(const vv_sampler* s) { StateHdr h; state_fingerprint(s, &h); return h.total_bytes; }
+
+// the state of s as it stands: s is quiet (no pipeline touches it)
+void sampler_serialize(const vv_sampler* s, std::vector<unsigned char>* out) {
+  StateHdr h; state_fingerprint(s, &h);
+  h.cursor = s->cursor; h.neg_cursor = s->neg_cursor;
+  s->rng.get_history(h.rng);
+  out->assign((size_t)h.total_bytes, 0);
+  unsigned char* q = out->data();
+  memcpy(q, &h, sizeof(h)); q += sizeof(h);
+  const size_t mb = s->buffer_ids.size();
+  if (!s->dense_keys && mb) { memcpy(q, s->buf_key.data(), mb * 8); q += mb * 8; }
+  if (mb) { memcpy(q, s->buf_row.data(), mb * 4); q += mb * 4; memcpy(q, s->buffer_ids.data(), mb * 4); q += mb * 4; }
+  if (!s->slots.empty()) memcpy(q, s->slots.data(), s->slots.size() * 8);
+}
+
+// Checks the whole blob against s, then -- and only then -- writes it into s.  Reads nothing past `bytes`.
+int sampler_apply(vv_sampler* s, const unsigned char* buf, int64_t bytes) {
+  StateHdr want; state_fingerprint(s, &want);
+  if (!buf || bytes < (int64_t)sizeof(StateHdr)) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: %lld bytes hold no header", (long long)bytes);
+  StateHdr h; memcpy(&h, buf, sizeof(h));
+  if (h.magic != kStateMagic) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: not a sampler state (magic)");
+  if (h.version != kStateVersion || h.hdr_bytes != sizeof(StateHdr)) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: state version %u, this library reads %u", h.version, kStateVersion);
+#define VV_FP_FIELD(f, name) if (h.f != want.f) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: %s differs: the state was taken with %lld, this sampler has %lld", name, (long long)h.f, (long long)want.f)
+  VV_FP_FIELD(p.batch_size, "batch_size"); VV_FP_FIELD(p.context_size, "context_size"); VV_FP_FIELD(p.num_negative_samples, "num_negative_samples");
+  VV_FP_FIELD(p.max_buffer_size, "max_buffer_size"); VV_FP_FIELD(p.negative_swap_percentage, "negative_swap_percentage");
+  VV_FP_FIELD(p.max_same_video_negs, "max_same_video_negs"); VV_FP_FIELD(p.max_tries_for_negs, "max_tries_for_negs");
+  VV_FP_FIELD(p.context_type, "context_type"); VV_FP_FIELD(p.initial_cursor, "initial_cursor (rand_skip)");
+  VV_FP_FIELD(p.output_shot_distance, "output_shot_distance"); VV_FP_FIELD(p.rand_seed, "rand_seed");
+  if (memcmp(&h.p.max_shot_distance, &want.p.max_shot_distance, sizeof(float)))
+    return state_fail(VV_ERR_ARG, "vv_sampler_state_put: max_shot_distance differs: the state was taken with %g, this sampler has %g", (double)h.p.max_shot_distance, (double)want.p.max_shot_distance);
+  VV_FP_FIELD(n_videos, "the number of videos"); VV_FP_FIELD(total_shots, "the number of shots");
+  if (h.shots_hash != want.shots_hash) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: the videos' shot counts differ (same total, another distribution)");
+  VV_FP_FIELD(neg_videos, "the negative dataset's number of videos"); VV_FP_FIELD(neg_total_shots, "the negative dataset's number of shots");
+  VV_FP_FIELD(dense_keys, "the key layout (row bitmap / key set)"); VV_FP_FIELD(n_slots, "the number of persistent slots");
+#undef VV_FP_FIELD
+  if (h.total_bytes != want.total_bytes || bytes != want.total_bytes)
+    return state_fail(VV_ERR_ARG, "vv_sampler_state_put: %lld bytes given, the state of this sampler has %lld (truncated or over-long)", (long long)bytes, (long long)want.total_bytes);
+  const int32_t V = (int32_t)s->video_id.size();
+  if (h.cursor < 0 || h.cursor >= V) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: cursor %d outside the %d records", h.cursor, V);
+  const size_t mb = s->buffer_ids.size();
+  const unsigned char* q = buf + sizeof(StateHdr);
+  const unsigned char* q_key = q; if (!s->dense_keys) q += mb * 8;
+  const unsigned char* q_row = q; q += mb * 4;
+  const unsigned char* q_ids = q; q += mb * 4;
+  const unsigned char* q_slots = q;
+  {
+    std::vector<uint8_t> seen(mb, 0);          // buffer_ids index the buffer: it must be a permutation of its slots
+    for (size_t i = 0; i < mb; ++i) {
+      int32_t id; memcpy(&id, q_ids + 4 * i, 4);
+      if (id < 0 || (size_t)id >= mb || seen[(size_t)id]) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: the slot permutation is damaged at %zu", i);
+      seen[(size_t)id] = 1;
+    }
+    if (s->dense_keys) {                       // the rows index the membership bitmap
+      const int64_t span = (int64_t)s->row_in_buf.size() - 64;
+      std::vector<uint8_t> in((size_t)span, 0);
+      for (size_t i = 0; i < mb; ++i) {
+        int32_t r; memcpy(&r, q_row + 4 * i, 4);
+        const int64_t o = (int64_t)r - s->row_min;
+        if (o < 0 || o >= span || in[(size_t)o]) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: buffer slot %zu holds row %d: not a row of this dataset, or held twice", i, r);
+        in[(size_t)o] = 1;
+      }
+    }
+  }
+  // ---- valid: write it
+  s->cursor = h.cursor; s->neg_cursor = h.neg_cursor;
+  s->rng.set_history(h.rng);
+  if (mb) { memcpy(s->buf_row.data(), q_row, mb * 4); memcpy(s->buffer_ids.data(), q_ids, mb * 4); }
+  if (s->dense_keys) {
+    std::fill(s->row_in_buf.begin(), s->row_in_buf.end(), (uint8_t)0);
+    for (size_t i = 0; i < mb; ++i) s->row_in_buf[(size_t)(s->buf_row[i] - s->row_min)] = 1;
+  } else {
+    if (mb) memcpy(s->buf_key.data(), q_key, mb * 8);
+    s->keys.clear();
+    for (size_t i = 0; i < mb; ++i) s->keys.insert(s->buf_key[i]);
+  }
+  if (!s->slots.empty()) memcpy(s->slots.data(), q_slots, s->slots.size() * 8);
+  return VV_OK;
+}
+
+// a serial sampler over the same records, its state still to be written by sampler_apply
+vv_sampler* sampler_clone_static(const vv_sampler* s) {
+  vv_sampler* c = new (std::nothrow) vv_sampler();
+  if (!c) return nullptr;
+  c->p = s->p;
+  c->video_id = s->video_id; c->n_shots = s->n_shots; c->shot_ids = s->shot_ids; c->row_base = s->row_base; c->shot_off = s->shot_off;
+  c->has_ids = s->has_ids; c->max_n = s->max_n; c->fm = s->fm;
+  c->dense_keys = s->dense_keys; c->row_min = s->row_min; c->row_in_buf.assign(s->row_in_buf.size(), 0);
+  c->fast = s->fast; c->CA = s->CA; c->rec_words = s->rec_words; c->wide = s->wide; c->inv_mb = s->inv_mb;
+  c->rec1.assign((size_t)s->rec_words, 0u);
+  c->perm.reserve((size_t)s->max_n);
+  c->rng_block = s->rng_block;
+  const int Nn = s->p.num_negative_samples;
+  c->rng.init(s->rng_block, Nn > 0 ? s->p.negative_swap_percentage : 0, (uint32_t)s->p.rand_seed, s->wide, Nn > 0 ? s->p.max_buffer_size : 0);
+  const size_t mb = s->buffer_ids.size();
+  c->buffer_ids.assign(mb, 0); c->buf_row.assign(mb, 0); c->buf_key.assign(mb, 0);
+  c->slots.assign(s->slots.size(), Slot());
+  c->neg_videos = s->neg_videos; c->neg_total_shots = s->neg_total_shots;
+  return c;
+}
+}  // namespace
+
 extern "C" {
 
 void vv_sampler_param_default(vv_sampler_param* p) {
@@ -1328,8 +1501,11 @@ int vv_sampler_create_neg(const vv_sampler_param* p_in, int32_t n_videos, const 
     if (const char* e = getenv("VV_SAMPLER_BLOCK")) want = std::max<int64_t>(1024, atoll(e));      // (tuning: words per generated block)
     const int64_t block = (std::max<int64_t>(want, 4 * per_item) + 15) / 16 * 16;
     if (block > (1ll << 28)) { delete s; return VV_ERR_ARG; }
+    s->rng_block = (int)block;
     s->rng.init((int)block, Nn > 0 ? p->negative_swap_percentage : 0, (uint32_t)p->rand_seed, s->wide, Nn > 0 ? p->max_buffer_size : 0);
   }
+  s->neg_videos = neg_videos;
+  for (int v = 0; v < neg_videos; ++v) s->neg_total_shots += neg_n_shots[v];
   if (!s->fast) s->slots.assign((size_t)p->batch_size * CN, Slot());
   const int mb = Nn > 0 ? p->max_buffer_size : 0;
   s->buffer_ids.resize(mb);
@@ -1357,6 +1533,7 @@ int vv_sampler_create_neg(const vv_sampler_param* p_in, int32_t n_videos, const 
       }
     }
     if ((int)s->buf_row.size() != mb) { delete s; return VV_ERR_ARG; }
+    s->neg_cursor = cur;
   } else if (mb > 0) {
     const int64_t tries = (int64_t)p->max_tries_for_negs * mb;
     for (int64_t t = 0; t < tries && (int)s->buf_row.size() < mb; ++t) {
@@ -1400,6 +1577,7 @@ static int pop_batch(vv_batch_ring* r, int consumer, int32_t item_begin, int32_t
 
 int vv_sampler_next(vv_sampler* s, int32_t* idx, int32_t* last_src, int32_t* label) {
   if (!s) return VV_ERR_ARG;
+  s->started = true;
   if (s->ring) return pop_batch(s->ring, 0, 0, s->p.batch_size, idx, last_src, label, 0.0);
   return s->sample_batch(idx, last_src, label);
 }
@@ -1409,6 +1587,10 @@ int vv_sampler_prefetch_start(vv_sampler* s, int32_t depth, int32_t threads, con
   const int B = s->p.batch_size, CN = s->p.context_size + s->p.num_negative_samples;
   s->ring = ring_create(shm_name, depth, B, CN, consumers, !s->fast);
   if (!s->ring) return VV_ERR_STATE;
+  // the consumer's position from here on: this state + the batches the ring's consumer releases (vv_sampler_state_get).  A restarted
+  // pipeline continues behind batches that vv_sampler_prefetch_stop dropped: no position a consumer ever saw
+  s->started = true;
+  if (!s->ring_stopped && consumers == 1) { sampler_serialize(s, &s->base_blob); s->shadow_at = 0; }
   s->stop.store(0);
 #ifdef VV_SAMPLER_LAB
   g_plab = getenv("VV_SAMPLER_LAB") ? atoi(getenv("VV_SAMPLER_LAB")) : 0;
@@ -1475,6 +1657,9 @@ int vv_sampler_prefetch_stop(vv_sampler* s) {
   ring_free(s->ring);
   s->ring = nullptr;
   s->n_stage_threads = 0;
+  s->ring_stopped = true;               // (the stages stop at different items and produced batches are dropped)
+  s->base_blob.clear(); s->base_blob.shrink_to_fit();
+  delete s->shadow; s->shadow = nullptr;
   return VV_OK;
 }
 
@@ -1496,6 +1681,8 @@ int64_t vv_sampler_stat(vv_sampler* s, int32_t which) {
     case 6: return (int64_t)s->wait_frames.load(std::memory_order_relaxed);   // ... the frame stage
     case 7: return s->wide ? 1 : 0;              // 512-bit forms in use
     case 9: return s->n_core_fds;                // cores claimed for the stage threads (4 = one each; 0 = the common set)
+    case 10: return s->ring ? std::min(s->ring->hdr->done_negs.load(std::memory_order_acquire), s->ring->hdr->done_frames.load(std::memory_order_acquire)) / s->p.batch_size : -1;   // whole batches the running pipeline has produced
+    case 11: return s->ring ? s->ring->min_released() : -1;     // ... and batches every consumer has taken
     case 8: return (int64_t)s->rng.wait_ticks(); // ticks the walk stage waited for the stream-generating thread's next block (read when the pipeline is quiet or approximately)
     default: return -1;
   }
@@ -1505,6 +1692,52 @@ int vv_sampler_destroy(vv_sampler* s) {
   if (s) vv_sampler_prefetch_stop(s);
   delete s;
   return VV_OK;
+}
+
+const char* vv_sampler_state_error(void) { return g_state_err; }
+
+int vv_sampler_state_size(vv_sampler* s, int64_t* bytes) {
+  if (!s || !bytes) return state_fail(VV_ERR_ARG, "vv_sampler_state_size: NULL argument");
+  *bytes = state_bytes(s);
+  return VV_OK;
+}
+
+int vv_sampler_state_get(vv_sampler* s, void* buf, int64_t cap, int64_t* written) {
+  if (!s || !buf) return state_fail(VV_ERR_ARG, "vv_sampler_state_get: NULL argument");
+  const int64_t need = state_bytes(s);
+  if (written) *written = 0;
+  if (cap < need) return state_fail(VV_ERR_ARG, "vv_sampler_state_get: %lld bytes of room, the state has %lld", (long long)cap, (long long)need);
+  { const char* sm = getenv("VV_SAMPLER_MODE");
+    if (sm && !strcmp(sm, "node")) return state_fail(VV_ERR_STATE, "vv_sampler_state_get: VV_SAMPLER_MODE=node serves every rank from one ring: no single consumer position"); }
+  if (s->ring_stopped) return state_fail(VV_ERR_STATE, "vv_sampler_state_get: vv_sampler_prefetch_stop dropped batches the pipeline had produced: the stream has no consumer position any more");
+  std::vector<unsigned char> blob;
+  if (!s->ring) {
+    sampler_serialize(s, &blob);              // no pipeline: this object is at the consumer's position
+  } else {
+    if (s->ring->hdr->consumers != 1) return state_fail(VV_ERR_STATE, "vv_sampler_state_get: the ring has %d consumers: no single consumer position", s->ring->hdr->consumers);
+    // The pipeline's chains are ahead of the consumer, at three different stream positions; it is neither stopped nor rewound.  A private
+    // serial sampler is replayed from the last known position to the batches the consumer has released since (the serial path and the
+    // pipeline produce the same indices), in this thread, and stays at that position for the next call.
+    if (!s->shadow) {
+      s->shadow = sampler_clone_static(s);
+      if (!s->shadow) return state_fail(VV_ERR_STATE, "vv_sampler_state_get: out of memory");
+      if (sampler_apply(s->shadow, s->base_blob.data(), (int64_t)s->base_blob.size())) { delete s->shadow; s->shadow = nullptr; return VV_ERR_STATE; }
+      s->base_blob.clear(); s->base_blob.shrink_to_fit();
+    }
+    const int64_t delivered = s->ring->hdr->released[0].v.load(std::memory_order_acquire);
+    std::vector<int32_t> scratch(s->fast ? (size_t)s->p.batch_size * (s->p.context_size + s->p.num_negative_samples) : 0);
+    for (; s->shadow_at < delivered; ++s->shadow_at) s->shadow->sample_batch(s->fast ? scratch.data() : nullptr, nullptr, nullptr);
+    sampler_serialize(s->shadow, &blob);
+  }
+  memcpy(buf, blob.data(), blob.size());
+  if (written) *written = (int64_t)blob.size();
+  return VV_OK;
+}
+
+int vv_sampler_state_put(vv_sampler* s, const void* buf, int64_t bytes) {
+  if (!s || !buf) return state_fail(VV_ERR_ARG, "vv_sampler_state_put: NULL argument");
+  if (s->started) return state_fail(VV_ERR_STATE, "vv_sampler_state_put: only before vv_sampler_prefetch_start and the first vv_sampler_next");
+  return sampler_apply(s, (const unsigned char*)buf, bytes);
 }
 
 int vv_batch_ring_attach(const char* shm_name, double timeout_s, vv_batch_ring** out) {

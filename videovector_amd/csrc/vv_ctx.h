@@ -71,6 +71,8 @@ struct vv_ctx {
   bool grad_banked = false;                 // the last backward pass's gradient has been banked, or the buffer holds an accumulated update's
                                             // normalised sum in its place: not banked again (a backward pass clears it)
   bool fb_hinted = false;                   // the last backward pass was announced by vv_update_hint: its gradient is not banked
+  bool grad_unapplied = false;              // a backward pass has left a gradient that no completed vv_apply_update has consumed yet (vv_run_state_get
+                                            // refuses: the blob would miss it); cleared by finish_update and wherever the gradient is discarded
   // vv_op_asum / vv_debug_stats_queue (the reference's debug_info, net.cpp:580-636).  stat_rec: ONE allocation made zero-filled by the first
   // call that measures, never on the step path afterwards -- VV_STAT_N records and vv_op_asum's own, then k_abs_stats' partials and its
   // arrival counter.  upd_shadow: vv_debug_mark_update's copy of W, then (on the next 16-byte boundary) of b, allocated by the first mark.

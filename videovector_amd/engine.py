@@ -14,7 +14,11 @@ PREC = {"f16": 0, "bf16": 1}
 
 
 class VVError(RuntimeError):
-    pass
+    """code: the VV_ERR_* value of the call that failed, where one call did (None otherwise)."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def lib_path():
@@ -187,11 +191,16 @@ def load_library():
         "vv_debug_stats_queue": [vp, C.c_uint32], "vv_debug_mark_update": [vp], "vv_debug_stats_get": [vp, C.POINTER(_AbsStat)],
         "vv_ema_set": [vp, f32], "vv_ema_get_decay": [vp, C.POINTER(f32)], "vv_ema_get": [vp, vp, vp], "vv_ema_put": [vp, vp, vp], "vv_ema_use": [vp, C.c_int],
         "vv_ema_stats": [vp, C.POINTER(_EmaReport)],
+        "vv_run_state_size": [vp, C.POINTER(i64)], "vv_run_state_get": [vp, vp, i64, C.POINTER(i64)], "vv_run_state_put": [vp, vp, i64],
+        "vv_sampler_state_size": [vp, C.POINTER(i64)], "vv_sampler_state_get": [vp, vp, i64, C.POINTER(i64)],
+        "vv_sampler_state_put": [vp, vp, i64],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = None if name == "vv_step_cfg_default" else C.c_int
+    L.vv_sampler_state_error.argtypes = []
+    L.vv_sampler_state_error.restype = C.c_char_p
     _lib = L
     return L
 
@@ -389,7 +398,23 @@ class Engine:
 
     def _chk(self, rc):
         if rc != 0:
-            raise VVError("videovec error %d: %s" % (rc, self.L.vv_last_error().decode()))
+            raise VVError("videovec error %d: %s" % (rc, self.L.vv_last_error().decode()), rc)
+
+    # ---- the step's carried state (vv_run_state_*): a run that resumes bit for bit
+    def run_state(self):
+        """What a training step reads that earlier steps left and no other getter returns (the dropout counter, the lagging 16-bit
+        scales and the copy of W rounded at them, the report rings ...), as opaque bytes.  Synchronises."""
+        n = C.c_int64()
+        self._chk(self.L.vv_run_state_size(self.h, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        w = C.c_int64()
+        self._chk(self.L.vv_run_state_get(self.h, buf, n.value, C.byref(w)))
+        return buf.raw[:w.value]
+
+    def set_run_state(self, blob):
+        """After params_set, history2_set and solver_iter (params_set resets part of this state)."""
+        blob = bytes(blob)
+        self._chk(self.L.vv_run_state_put(self.h, C.create_string_buffer(blob, len(blob)) if blob else None, len(blob)))
 
     def close(self):
         if getattr(self, "h", None) and self.h:
@@ -942,6 +967,25 @@ class Sampler:
         if want_last or want_label:
             return idx, last, label
         return idx
+
+    def state(self):
+        """The state of the reference's one sequential stream after the last batch DELIVERED (by next(), or taken from the ring by its
+        single consumer), as opaque bytes; with the pipeline running a private serial sampler is replayed to that position."""
+        n = C.c_int64()
+        rc = self.L.vv_sampler_state_size(self.h, C.byref(n))
+        buf = C.create_string_buffer(max(n.value, 1))
+        w = C.c_int64()
+        rc = rc or self.L.vv_sampler_state_get(self.h, buf, n.value, C.byref(w))
+        if rc != 0:
+            raise VVError("vv_sampler_state_get failed (%d): %s" % (rc, self.L.vv_sampler_state_error().decode()), rc)
+        return buf.raw[:w.value]
+
+    def set_state(self, blob):
+        """Only before prefetch_start() and the first next(); a blob of other parameters or another dataset is refused."""
+        blob = bytes(blob)
+        rc = self.L.vv_sampler_state_put(self.h, C.create_string_buffer(blob, max(len(blob), 1)), len(blob))
+        if rc != 0:
+            raise VVError("vv_sampler_state_put failed (%d): %s" % (rc, self.L.vv_sampler_state_error().decode()), rc)
 
     def prefetch_start(self, depth=4, threads=4, shm_name=None, consumers=1):
         """Background threads keep `depth` batches ahead (BasePrefetchingDataLayer, base_data_layer.cpp:52-95); next()

@@ -161,7 +161,7 @@ def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_pol
            power=0.75, stepsize=0, display=10, max_iter=100, snapshot=0, snapshot_prefix="videovec",
            random_seed=-1, snapshot_after_train=True, test_iter=0, test_interval=0, solver_type=None, delta=None,
            snapshot_diff=False, rms_decay=None, momentum2=None, clip_gradients=None, iter_size=None, test_compute_loss=False, debug_info=False,
-           ema_decay=None, test_with_ema=None):
+           ema_decay=None, test_with_ema=None, snapshot_data_state=None):
     """Same fields as projects/videovec_embedding/mednet_embedding_train_solver.prototxt (+ solver_type / delta, and BVLC Caffe's
     rms_decay / momentum2 for RMSPROP / ADAM, clip_gradients and iter_size, and this project's ema_decay / test_with_ema, written only when given)."""
     s = ['net: "%s"' % net_path, "base_lr: %g" % base_lr, "momentum: %g" % momentum,
@@ -198,4 +198,6 @@ def solver(net_path, *, base_lr=0.001, momentum=0.9, weight_decay=0.0005, lr_pol
         s.append("ema_decay: %r" % float(ema_decay))
     if test_with_ema is not None:
         s.append("test_with_ema: %s" % ("true" if test_with_ema else "false"))
+    if snapshot_data_state is not None:       # this project's own (field 139): the samplers' and the step's carried state beside every snapshot
+        s.append("snapshot_data_state: %s" % ("true" if snapshot_data_state else "false"))
     return "\n".join(s) + "\n"
