@@ -685,7 +685,9 @@ int vv_gallery_class_stats(vv_ctx* ctx, vv_gallery* gallery, const int32_t* map_
  *   vv_op_gather_rows the data layer's batch copy (base_data_layer.cu:7-21): table rows idx (host int32 [n], -1 = zeros) as fp32
  *   vv_op_inner_product(_bwd)  INNER_PRODUCT with the context's parameters (inner_product_layer.cu:12-59): Y = X W^T + b;
  *                     backward writes dW (scaled by 1 + regularization / 2 when > 0) and db into the flat gradient buffer,
- *                     from which vv_apply_update updates.  No gradient w.r.t. X (the layer sits on the data layer). */
+ *                     from which vv_apply_update updates.  No gradient w.r.t. X (the layer sits on the data layer).
+ *   vv_op_gram        out [n][n] = alpha x x^T for x [n][dim]: the distance matrix of RETRIEVAL_STATS (retrieval_stats_layer.cpp:208-209,
+ *                     alpha = -2), the launch vv_retrieval_stats makes; n < 1 or dim < 1: VV_ERR_ARG */
 int vv_dev_alloc(vv_ctx* ctx, size_t bytes, void** out);     /* zero-filled */
 int vv_dev_free(vv_ctx* ctx, void* p);
 int vv_dev_upload(vv_ctx* ctx, void* dst_dev, const void* src_host, size_t bytes);
@@ -709,6 +711,7 @@ int vv_op_max_margin_bwd(vv_ctx* ctx, int32_t count, const float* s_true, const 
 int vv_op_gather_rows(vv_ctx* ctx, const int32_t* idx, int64_t n, float* out);
 int vv_op_inner_product(vv_ctx* ctx, const float* X, int64_t R, float* Y);
 int vv_op_inner_product_bwd(vv_ctx* ctx, const float* dY, int64_t R, float ip_regularization);
+int vv_op_gram(vv_ctx* ctx, const float* x_dev, int32_t n, int32_t dim, float alpha, float* out_dev);
 
 /* ---- triplet sampler (host side, integer only).  Replaces VideoSampledShotsDataLayer's
  * DataLayerSetUp / AddSamplesToTop / InternalThreadEntry / AddToBuffer / RandomShuffleTopids

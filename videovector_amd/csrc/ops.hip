@@ -12,6 +12,7 @@
 //   MAX_MARGIN_LOSS          max_margin_loss_layer.cpp:53-214 (CPU only in the reference)          -> vv_op_max_margin, _bwd
 //   INNER_PRODUCT            inner_product_layer.cu:12-59                                         -> vv_op_inner_product, _bwd
 //   VIDEO_SAMPLED_SHOTS_DATA base_data_layer.cu:7-21 (the batch copy)                             -> vv_op_gather_rows
+//   RETRIEVAL_STATS          retrieval_stats_layer.cpp:208-209 (the distance matrix, cblas there)  -> vv_op_gram
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -342,6 +343,16 @@ int vv_op_gather_rows(vv_ctx* c, const int32_t* idx, int64_t n, float* out) {
   HIPCHK(hipMemcpyAsync(d, h.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   launch_table_read(c->prec, c->table, d, n, c->F, c->Fp, 1.f / c->sx, out, c->stream);
   HIPCHK(hipStreamSynchronize(c->stream));
+  return VV_OK;
+}
+
+// out = alpha X X^T: the distance matrix of RetrievalStatsLayer (retrieval_stats_layer.cpp:208-209, alpha = -2) as an operator --
+// the launch vv_retrieval_stats makes, on the caller's device buffers
+int vv_op_gram(vv_ctx* c, const float* x_dev, int32_t n, int32_t dim, float alpha, float* out_dev) {
+  NEED(c);
+  if (!x_dev || !out_dev || n < 1 || dim < 1) return vv_fail(VV_ERR_ARG, "vv_op_gram: bad argument");
+  launch_gram(x_dev, n, dim, alpha, out_dev, c->stream);
+  HIPCHK(hipGetLastError());
   return VV_OK;
 }
 
