@@ -349,6 +349,23 @@ class RetrievalRankStatsFixedRefLayer : public Layer<Dtype> {
   int batch_size_ = 0, feature_dimension_ = 0, num_reference_points_ = 0;
 };
 
+// CLASSIFICATION_STATS (classification_stats_layer.cpp:13-95): bottoms = scores (n, C, 1, 1) and labels (n, 1, 1, 1); tops =
+// per-class accuracy (1, C, 1, 1), per-class average precision (1, C, 1, 1), total accuracy (1, 1, 1, 1).  Forward reads the
+// scores where they are, on the device (vv_classification_stats with scores_on_device = 1): nothing is sorted.
+template <typename Dtype>
+class ClassificationStatsLayer : public Layer<Dtype> {
+  VV_LAYER_BOILER(ClassificationStatsLayer, "CLASSIFICATION_STATS")
+  virtual int ExactNumBottomBlobs() const { return 2; }
+  virtual int ExactNumTopBlobs() const { return 3; }
+  virtual void LayerSetUp(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top);
+  virtual void Reshape(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top);
+  // of the last Forward: the mean of the per-class average precisions over the classes present (this project's own figure)
+  float mean_ap() const { return mean_ap_; }
+ private:
+  int num_classes_ = 0;
+  float mean_ap_ = 0.f;
+};
+
 // layer_factory.cpp:177-309: the 13 hot-path types (+SPLIT); LOG(FATAL) on anything else
 template <typename Dtype>
 Layer<Dtype>* GetLayer(const LayerParameter& param);

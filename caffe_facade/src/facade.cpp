@@ -684,6 +684,22 @@ void RetrievalStatsLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>& bottom, vec
 template class RetrievalStatsLayer<float>;
 
 template <typename Dtype>
+void ClassificationStatsLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>&, vector<Blob<Dtype>*>*) {
+  num_classes_ = (int)this->layer_param_.get_msg("classification_stats_param").get_int("num_classes");   // classification_stats_layer.cpp:16
+}
+template <typename Dtype>
+void ClassificationStatsLayer<Dtype>::Reshape(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top) {
+  CHECK_EQ(bottom[0]->num(), bottom[1]->num()) << "The data and label should have the same number.";            // :22-23
+  CHECK_EQ(num_classes_, bottom[0]->count() / bottom[0]->num())
+      << "The input score count should be equal to number of classes.";                                          // :24-25
+  CHECK_EQ(bottom[1]->channels(), 1); CHECK_EQ(bottom[1]->height(), 1); CHECK_EQ(bottom[1]->width(), 1);          // :26-28
+  (*top)[0]->Reshape(1, num_classes_, 1, 1);      // accuracy per class (:30)
+  (*top)[1]->Reshape(1, num_classes_, 1, 1);      // average precision per class (:31)
+  (*top)[2]->Reshape(1, 1, 1, 1);                 // total accuracy (:32)
+}
+template class ClassificationStatsLayer<float>;
+
+template <typename Dtype>
 void RetrievalRankStatsFixedRefLayer<Dtype>::LayerSetUp(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>*) {
   // retrieval_rank_stats_fixed_ref_layer.cpp:21-27.  num_reference_points and source are declared by the parameter message
   // (caffe.proto:950-954) and read by nothing in the reference layer; they are parsed and ignored here too.
@@ -830,6 +846,7 @@ Layer<Dtype>* GetLayer(const LayerParameter& param) {
   if (type == "MAX_MARGIN_LOSS") return new MaxMarginLossLayer<Dtype>(param);
   if (type == "VIDEO_SHOT_WINDOW_TEST_DATA") return new VideoShotWindowTestDataLayer<Dtype>(param);
   if (type == "RETRIEVAL_STATS") return new RetrievalStatsLayer<Dtype>(param);
+  if (type == "CLASSIFICATION_STATS") return new ClassificationStatsLayer<Dtype>(param);
   if (type == "RETRIEVAL_RANK_STATS_FIXED_REF") return new RetrievalRankStatsFixedRefLayer<Dtype>(param);
   if (type == "NONE") LOG(FATAL) << "Layer " << name << " has unspecified type.";            // layer_factory.cpp:303
   LOG(FATAL) << "Layer " << name << " has type " << type << ", which is outside the videovec training path built here.";

@@ -451,7 +451,25 @@ void RetrievalRankStatsFixedRefLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype
 template <typename Dtype>
 void RetrievalRankStatsFixedRefLayer<Dtype>::Backward_gpu(const vector<Blob<Dtype>*>&, const vector<bool>&, vector<Blob<Dtype>*>*) {}
 
+// ---------------------------------------------------------------------------------------------- CLASSIFICATION_STATS
+// classification_stats_layer.cpp:36-95 (Forward_cpu in the reference): the scores are read on the device, the argmax, the counts
+// behind every average-precision term and their sums run there (vv_classification_stats); the host casts the labels (:52).
+template <typename Dtype>
+void ClassificationStatsLayer<Dtype>::Forward_gpu(const vector<Blob<Dtype>*>& bottom, vector<Blob<Dtype>*>* top) {
+  const int n = bottom[0]->num();
+  vector<int32_t> labels((size_t)n);
+  for (int i = 0; i < n; ++i) labels[i] = static_cast<int>(bottom[1]->cpu_data()[i]);                             // :52
+  vv_classification_report rep;
+  VV_CHECK(vv_classification_stats(X(), bottom[0]->gpu_data(), n, num_classes_, labels.data(), 1, (*top)[0]->mutable_cpu_data(),
+                                   (*top)[1]->mutable_cpu_data(), nullptr, &rep));
+  (*top)[2]->mutable_cpu_data()[0] = rep.total_accuracy;                                                          // :93
+  mean_ap_ = rep.mean_ap;
+}
+template <typename Dtype>
+void ClassificationStatsLayer<Dtype>::Backward_gpu(const vector<Blob<Dtype>*>&, const vector<bool>&, vector<Blob<Dtype>*>*) {}
+
 template class Layer<float>;
+template class ClassificationStatsLayer<float>;
 template class RetrievalRankStatsFixedRefLayer<float>;
 template class VideoSampledShotsDataLayer<float>;
 template class VideoShotWindowTestDataLayer<float>;

@@ -119,7 +119,7 @@ static const std::vector<MsgDef>& Msgs() {
         {1002, "blob_share_mode", T_ENUM, true, false, "DimCheckMode", ""},
         REP(7, "blobs_lr", T_FLOAT), REP(8, "weight_decay", T_FLOAT), REP(35, "loss_weight", T_FLOAT),
         OMSG(27, "accuracy_param", "Opaque"), OMSG(23, "argmax_param", "Opaque"),
-        OMSG(42, "classification_stats_param", "Opaque"), OMSG(9, "concat_param", "ConcatParameter"),
+        OMSG(42, "classification_stats_param", "ClassificationStatsParameter"), OMSG(9, "concat_param", "ConcatParameter"),
         OMSG(40, "contrastive_loss_param", "Opaque"), OMSG(10, "convolution_param", "Opaque"),
         OMSG(11, "data_param", "Opaque"), OMSG(12, "dropout_param", "DropoutParameter"),
         OMSG(26, "dummy_data_param", "Opaque"), OMSG(24, "eltwise_param", "EltwiseParameter"),
@@ -158,6 +158,7 @@ static const std::vector<MsgDef>& Msgs() {
       {"RetrievalRankStatsFixedRefParameter",                                       // :950-954
        {OPTD(1, "stats_output_file", T_STRING, ""), OPTD(2, "num_reference_points", T_INT32, "0"),
         OPTD(3, "source", T_STRING, "")}},
+      {"ClassificationStatsParameter", {OPT(1, "num_classes", T_UINT32)}},          // required uint32 num_classes = 1
       {"RetrievalStatsParameter",                                                   // :955-966
        {OPT(1, "id_to_class_file", T_STRING), OPTD(2, "stats_output_file", T_STRING, ""),
         OPTD(3, "exclude_same_video_shots", T_BOOL, "true"), OPTD(4, "video_level_retrieval", T_BOOL, "false"),

@@ -1,0 +1,110 @@
+// classification_stats -- per-class accuracy and average precision of a score file without Python: builds one
+// CLASSIFICATION_STATS layer directly (as class_stats builds its RETRIEVAL_STATS layer), feeds it a score file in the
+// text_output.txt format extract_features writes (one row per item, one column per class) plus one integer label per line,
+// runs SetUp / Forward and prints `accuracy_c<k> = `, `ap_c<k> = ` for every class, then `total_accuracy = ` and `mean_ap = `.
+//   classification_stats scores.txt labels.txt [--prototxt net.prototxt] [--num_classes K] [--label_channels K]
+//   classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt
+// --prototypes: features.txt holds embeddings, not scores.  The training items become a device gallery whose ids are their
+//   classes, vv_gallery_pool_by_id turns it into one mean per class (ascending class), vv_gallery_scores writes the dot products of
+//   every test embedding with every class mean into device memory, and the layer reads them there: a nearest-class-mean
+//   classifier whose scores never visit the host.  Column k is the k-th class present in train_labels.txt; they must be 0 .. C-1.
+// --prototxt: the layer's parameter is the first CLASSIFICATION_STATS layer of that net file (its num_classes included) instead of
+//   one made here with num_classes = the number of columns.
+// --num_classes / --label_channels: override num_classes / give the label blob K channels -- the layer's shape CHECKs then fire.
+#include <cstring>
+#include <set>
+
+#include "feature_files.hpp"
+
+using namespace caffe;
+
+static int CountRows(const char* path) {
+  std::ifstream f(path);
+  CHECK(f.good()) << "Failed to open " << path;
+  string line;
+  int n = 0;
+  while (std::getline(f, line))
+    if (!line.empty() && line[0] != '#') ++n;
+  return n;
+}
+
+int main(int argc, char** argv) {
+  vector<const char*> pos;
+  const char *proto = nullptr, *train_feat = nullptr, *train_lab = nullptr;
+  int num_classes = -1, label_channels = 1;
+  for (int i = 1; i < argc; ++i) {
+    if (!strcmp(argv[i], "--prototypes") && i + 2 < argc) { train_feat = argv[i + 1]; train_lab = argv[i + 2]; i += 2; }
+    else if (!strcmp(argv[i], "--prototxt") && i + 1 < argc) proto = argv[++i];
+    else if (!strcmp(argv[i], "--num_classes") && i + 1 < argc) num_classes = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--label_channels") && i + 1 < argc) label_channels = atoi(argv[++i]);
+    else pos.push_back(argv[i]);
+  }
+  if (pos.size() != 2 || label_channels < 1) {
+    fprintf(stderr, "usage: classification_stats scores.txt labels.txt [--prototxt net.prototxt] [--num_classes K] [--label_channels K]\n"
+                    "       classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt\n");
+    return 2;
+  }
+  Caffe::SetDevice(0);
+  Caffe::set_mode(Caffe::GPU);
+  Caffe::set_phase(Caffe::TEST);
+  vector<float> fv;
+  int n = 0, dim = 0;
+  ReadFeatures(pos[0], &fv, &n, &dim);
+  Blob<float> x, labels, t0, t1, t2;
+  int C = dim;
+  if (train_feat) {
+    vector<float> tv;
+    int tn = 0, tdim = 0;
+    ReadFeatures(train_feat, &tv, &tn, &tdim);
+    CHECK_EQ(tdim, dim) << "training and test embeddings differ in dimension";
+    Blob<float> tl;
+    ReadIds(train_lab, tn, &tl);
+    vector<int32_t> cls((size_t)tn);
+    for (int i = 0; i < tn; ++i) cls[i] = static_cast<int>(tl.cpu_data()[i]);
+    std::set<int32_t> distinct(cls.begin(), cls.end());
+    C = (int)distinct.size();
+    CHECK(*distinct.begin() == 0 && *distinct.rbegin() == C - 1) << "the training labels must cover the classes 0 .. " << C - 1;
+    vv_gallery *items = nullptr, *means = nullptr;
+    VV_CHECK(vv_gallery_create(Caffe::ctx(), tv.data(), tn, dim, cls.data(), &items));
+    VV_CHECK(vv_gallery_pool_by_id(Caffe::ctx(), items, &means));
+    x.Reshape(n, C, 1, 1);
+    VV_CHECK(vv_gallery_scores(Caffe::ctx(), means, fv.data(), n, x.mutable_gpu_data()));
+    VV_CHECK(vv_gallery_destroy(Caffe::ctx(), means));
+    VV_CHECK(vv_gallery_destroy(Caffe::ctx(), items));
+  } else {
+    Fill(fv, n, dim, &x);
+  }
+  const int nl = CountRows(pos[1]);                 // (its own count: a label file of another length is the layer's CHECK to make)
+  ReadIds(pos[1], nl, &labels);
+  if (label_channels > 1) {
+    vector<float> keep(labels.cpu_data(), labels.cpu_data() + nl);
+    labels.Reshape(nl, label_channels, 1, 1);
+    for (int i = 0; i < nl * label_channels; ++i) labels.mutable_cpu_data()[i] = keep[i / label_channels];
+  }
+
+  LayerParameter param("LayerParameter");
+  if (proto) {
+    pl::Message net("NetParameter");
+    pl::ReadProtoFromTextFileOrDie(proto, &net);
+    int found = -1;
+    for (int i = 0; i < net.size("layers") && found < 0; ++i)
+      if (net.get_msg("layers", i).get_enum("type") == "CLASSIFICATION_STATS") found = i;
+    CHECK_GE(found, 0) << proto << " has no CLASSIFICATION_STATS layer";
+    param = net.get_msg("layers", found);
+  } else {
+    param.set_str("name", "classification_stats");
+    param.set_enum("type", "CLASSIFICATION_STATS");
+    param.mutable_msg("classification_stats_param")->set_int("num_classes", C);
+  }
+  if (num_classes >= 0) param.mutable_msg("classification_stats_param")->set_int("num_classes", num_classes);
+  shared_ptr<Layer<float> > layer(GetLayer<float>(param));
+  vector<Blob<float>*> bottom{&x, &labels}, top{&t0, &t1, &t2};
+  layer->SetUp(bottom, &top);
+  layer->Forward(bottom, &top);
+  const int K = t0.count();
+  for (int k = 0; k < K; ++k) printf("accuracy_c%d = %.9g\n", k, (double)t0.cpu_data()[k]);
+  for (int k = 0; k < K; ++k) printf("ap_c%d = %.9g\n", k, (double)t1.cpu_data()[k]);
+  printf("total_accuracy = %.9g\n", (double)t2.cpu_data()[0]);
+  printf("mean_ap = %.9g\n", (double)static_cast<ClassificationStatsLayer<float>*>(layer.get())->mean_ap());
+  return 0;
+}

@@ -665,6 +665,49 @@ int vv_gallery_pool_by_id(vv_ctx* ctx, vv_gallery* gallery, vv_gallery** out);
 int vv_gallery_class_stats(vv_ctx* ctx, vv_gallery* gallery, const int32_t* map_ids, const int32_t* map_cls, int32_t n_map,
                            int exclude_same_id, vv_class_stats* out, float* ap, float* acc1, float* acc5, int32_t* top5_idx);
 
+/* ---- event classification: ClassificationStatsLayer (src/caffe/layers/classification_stats_layer.cpp:13-95).
+ * vv_gallery_scores: out_dev [n_q][n_ref], DEVICE fp32 of this context owned by the caller (vv_dev_alloc), = the fp32 dot products
+ * dot(q_i, r_g) of which vv_gallery_topk's distance is the -2 multiple: the float the similarity kernel stored, times -0.5f (both
+ * factors powers of two: exact; nothing is evaluated a second way).  q: host fp32 [n_q][dim], processed in query blocks as the
+ * other gallery calls do; synchronises.  HAS NO REFERENCE COUNTERPART.  With a gallery of class prototypes (vv_gallery_create with
+ * ref_ids = the class of each item, then vv_gallery_pool_by_id: one prototype per class, ascending class) this is a
+ * nearest-class-mean classifier's score matrix, ready for vv_classification_stats(scores_on_device = 1) without a host round trip.
+ *
+ * vv_classification_stats: Forward_cpu (:36-95).  scores: fp32 [n][num_classes] row-major (bottom[0], :38); labels: host int32 [n],
+ * the true class of each row (bottom[1], :39, :52).
+ *   predicted class of a row: the LOWEST column attaining the row's maximum (the walk starts at column 0 and replaces on strict >,
+ *     :50-61; -0.0f and 0.0f compare equal)
+ *   count[c]: rows of label c (:53); accuracy[c] = (float)correct_c / (float)count_c, correct_c the rows of label c predicted c
+ *     (:63-66, :71), 0 where count[c] == 0 (:88); out->total_accuracy = (float)(sum of correct_c) / (float)n (:93).  The reference
+ *     counts in floats; every count here is an integer below 2^24, so these outputs are exact and fully determined
+ *   ap[c] (:72-85), the reference's quirk included: it sorts n dummy entries (0, false) together with the n real (score, label == c)
+ *     pairs by std::greater<pair> and walks only the first n.  So a row whose score in column c is below 0 never contributes (at
+ *     least n dummies precede it) but still counts in the divisor count[c]; among equal scores positives precede the others and the
+ *     dummies; a positive with score exactly 0 or -0 is visited.  For a visited positive p with score s:
+ *       G = rows (any label) with score > s,  P = positives of c with score > s,  E = positives of c with score == s and index < p
+ *       (item order breaks ties among interchangeable entries),  term(p) = (P + E + 1) / (G + E + 1)
+ *     ap[c] = (float)(sum of term(p) / count[c]), terms and sum in double, positives in a fixed order of ascending item index
+ *     through a fixed reduction tree, no floating-point atomics: two calls give identical bits.  (The reference sums the same terms
+ *     as a serial fp32 chain.)  0 where count[c] == 0 (:89).  G, P and E are COUNTED on the device; nothing of size n x n, or sorted,
+ *     ever exists
+ *   out->mean_ap: the mean of the double quotients over the classes with count > 0, rounded once (THIS PROJECT'S OWN: the layer
+ *     has no such top); classes_present: their number; n: the rows
+ * scores_on_device = 0: host scores, uploaded in column blocks so that the call's device scratch stays within the gallery path's
+ * 1 GiB ("scratch_limit_bytes") for any n x num_classes; 1: device memory of this context (vv_dev_alloc), read on the context's
+ * stream.  accuracy / ap / count: host [num_classes], each may be NULL.  The call synchronises.
+ * VV_ERR_ARG: n < 1, num_classes < 1, n > 2^24 (above it the reference's float counters stop counting: 2^24 + 1 is not a float);
+ * a label outside [0, num_classes) (an out-of-bounds index in the reference); any NaN score (the reference's sort is undefined on
+ * them; the device counts them and vv_last_error gives the count).  +-Inf are ordinary values.
+ * vv_set_option "cls_pass_tiles" (16384; 1 .. 65535): 256-positive tiles of one counting launch; "cls_block_cols" (0 = as many as
+ * the scratch limit admits): columns of one block at most -- small values are how the tests reach several launches and blocks at
+ * small shapes; results do not depend on either.  Read-only "last_cls_passes" (counting launches of the largest block),
+ * "last_cls_segments" (workgroups along a column), "last_cls_blocks", "last_cls_row_ms" / "last_cls_count_ms" (device time of the
+ * row pass + column pack / of the counting and final passes) describe the last call. */
+typedef struct { float total_accuracy, mean_ap; int32_t classes_present, reserved_; int64_t n; } vv_classification_report;
+int vv_classification_stats(vv_ctx* ctx, const float* scores, int64_t n, int32_t num_classes, const int32_t* labels,
+                            int scores_on_device, float* accuracy, float* ap, int32_t* count, vv_classification_report* out);
+int vv_gallery_scores(vv_ctx* ctx, vv_gallery* gallery, const float* q, int32_t n_q, float* out_dev);
+
 /* ---- per-layer operators.  The reference's operator interface is Layer<Dtype>::{Forward_gpu, Backward_gpu}
  * (include/caffe/layer.hpp:308-337); its sequential executor (Net::ForwardFromTo / BackwardFromTo, net.cpp:501-578) calls
  * them layer by layer.  Training here runs the fused plan above; these entry points are what the C++ facade's layer classes

@@ -320,7 +320,8 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     return fail(VV_ERR_ARG, "vv_set_option: option '%s' is retired; only its fixed value 0 is accepted", name);
   }
   if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form" || n == "last_score_form" || n == "last_h16" ||
-      n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows")
+      n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows" ||
+      n == "last_cls_passes" || n == "last_cls_segments" || n == "last_cls_blocks" || n == "last_cls_row_ms" || n == "last_cls_count_ms")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
@@ -355,6 +356,16 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
   if (n == "nearest_select_min_k") {
     if (iv < 1 || iv > RT_MAX_K + 1) return fail(VV_ERR_ARG, "vv_set_option: nearest_select_min_k = %d is outside 1 .. %d", iv, RT_MAX_K + 1);
     c->nearest_select_min_k = iv;
+    return VV_OK;
+  }
+  if (n == "cls_pass_tiles") {
+    if (iv < 1 || iv > 65535) return fail(VV_ERR_ARG, "vv_set_option: cls_pass_tiles = %d is outside 1 .. 65535", iv);
+    c->cls_pass_tiles = iv;
+    return VV_OK;
+  }
+  if (n == "cls_block_cols") {
+    if (iv < 0) return fail(VV_ERR_ARG, "vv_set_option: cls_block_cols = %d is negative", iv);
+    c->cls_block_cols = iv;
     return VV_OK;
   }
 #ifdef VV_LAB
@@ -393,6 +404,13 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "comm_chunks") *value = c->n_chunks;
   else if (n == "comm_test_delay_us") *value = c->comm_test_delay_us;
   else if (n == "nearest_select_min_k") *value = c->nearest_select_min_k;
+  else if (n == "cls_pass_tiles") *value = c->cls_pass_tiles;
+  else if (n == "cls_block_cols") *value = c->cls_block_cols;
+  else if (n == "last_cls_passes") *value = c->last_cls_passes;
+  else if (n == "last_cls_segments") *value = c->last_cls_segments;
+  else if (n == "last_cls_blocks") *value = c->last_cls_blocks;
+  else if (n == "last_cls_row_ms") *value = c->last_cls_row_ms;
+  else if (n == "last_cls_count_ms") *value = c->last_cls_count_ms;
   else if (n == "last_fwd_tile_rows") *value = c->ko.last_fwd_tile_rows;
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
   else if (n == "last_update_form") *value = c->ko.last_update_form;
@@ -3330,6 +3348,136 @@ int vv_gallery_class_stats(vv_ctx* c, vv_gallery* g, const int32_t* map_ids, con
   out->mean_ap = (float)(s_ap / n_scored); out->hit_at_1 = (float)(s_1 / n_scored); out->hit_at_5 = (float)(s_5 / n_scored);   // :351-353
   out->n_scored = n_scored;
   return gallery_call_end(c, g);
+}
+
+// The fp32 dot products of a query block, as the other gallery calls see them: the float k_sim_f32 stored, times -0.5f.
+int vv_gallery_scores(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, float* out_dev) {
+  if (!c || !g || !q || !out_dev) return fail(VV_ERR_ARG, "vv_gallery_scores: NULL argument");
+  if (g->ctx != c) return fail(VV_ERR_ARG, "vv_gallery_scores: the gallery belongs to another context");
+  if (n_q < 1) return fail(VV_ERR_ARG, "vv_gallery_scores: n_q = %d", n_q);
+  VV_ENTER(c);
+  int rc = gallery_call_begin(c, g, n_q);
+  if (rc) return rc;
+  for (int q0 = 0; q0 < n_q; q0 += g->qb_cap) {
+    const int rows = std::min(g->qb_cap, n_q - q0);
+    if ((rc = gallery_block_sim(c, g, q, q0, rows))) return rc;
+    launch_scores_out(g->dist, g->pitch, rows, (int)g->n_ref, out_dev + (size_t)q0 * g->n_ref, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));                   // (the next block's upload reuses qdev)
+    if ((rc = gallery_block_done(c, g))) return rc;
+  }
+  return gallery_call_end(c, g);
+}
+
+// ------------------------------------------------------------------------------- classification statistics ------
+// ClassificationStatsLayer::Forward_cpu (classification_stats_layer.cpp:36-95).  The host validates the labels and builds the
+// per-class lists of positives in ascending item index (as gallery_init builds its id lists); everything that touches a score
+// runs in kernels_classify.hip, one column block at a time; the host divides the integer counts (:71, :93).
+namespace {
+struct EvTmp {                                            // events that live for one API call
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  ~EvTmp() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+}  // namespace
+
+int vv_classification_stats(vv_ctx* c, const float* scores, int64_t n, int32_t num_classes, const int32_t* labels,
+                            int scores_on_device, float* accuracy, float* ap, int32_t* count, vv_classification_report* out) {
+  if (!c || !scores || !labels || !out) return fail(VV_ERR_ARG, "vv_classification_stats: NULL argument");
+  if (n < 1 || n > (1ll << 24) || num_classes < 1)
+    return fail(VV_ERR_ARG, "vv_classification_stats: %lld rows of %d classes (1 <= n <= 2^24, num_classes >= 1)", (long long)n, num_classes);
+  const int C = num_classes, N = (int)n;
+  std::vector<int32_t> hcount((size_t)C, 0), hstart((size_t)C + 1, 0);
+  for (int i = 0; i < N; ++i) {
+    if (labels[i] < 0 || labels[i] >= C)
+      return fail(VV_ERR_ARG, "vv_classification_stats: label %d of row %d is outside 0 .. %d", labels[i], i, C - 1);
+    ++hcount[labels[i]];                                                                   // :53
+  }
+  VV_ENTER(c);
+  c->last_cls_passes = c->last_cls_segments = c->last_cls_blocks = 0; c->last_cls_row_ms = c->last_cls_count_ms = 0;
+  const int64_t np = round_up(n, 64);
+  for (int k = 0; k < C; ++k) hstart[k + 1] = hstart[k] + hcount[k];
+  std::vector<int32_t> hpos((size_t)N), fill(hstart.begin(), hstart.end() - 1), hlab((size_t)np, -1);
+  for (int i = 0; i < N; ++i) { hpos[fill[labels[i]]++] = i; hlab[i] = labels[i]; }
+  // the counting pass's tiles, class by class: {first position in hpos, positives, class, 0}; tbegin[k]: the first tile of class k
+  std::vector<int4> htiles; std::vector<int32_t> tbegin((size_t)C + 1, 0);
+  for (int k = 0; k < C; ++k) {
+    tbegin[k] = (int32_t)htiles.size();
+    for (int o = 0; o < hcount[k]; o += CLS_TILE) htiles.push_back(make_int4(hstart[k] + o, std::min(CLS_TILE, hcount[k] - o), k, 0));
+  }
+  tbegin[C] = (int32_t)htiles.size();
+  // device buffers of the call, all of them within the gallery path's scratch limit
+  const bool host = !scores_on_device;
+  const size_t fixed = (size_t)np * 4 + (size_t)N * (4 + 12 + 4 + 4) + ((size_t)C + 1) * 4 + (size_t)C * (4 + 8 + 4) + 8 + htiles.size() * 16 + 4096;
+  const size_t per_col = (size_t)np * 4 + (host ? (size_t)N * 4 : 0);
+  if (fixed + per_col > GALLERY_SCRATCH_MAX)
+    return fail(VV_ERR_ARG, "vv_classification_stats: %lld rows of %d classes do not fit one column into the scratch limit", (long long)n, C);
+  int cb_max = (int)std::min<size_t>((size_t)C, (GALLERY_SCRATCH_MAX - fixed) / per_col);
+  if (c->cls_block_cols > 0) cb_max = std::min(cb_max, c->cls_block_cols);
+  DevTmp<int32_t> dlab, dpos, dstart, rarg; DevTmp<uint32_t> cnt, correct; DevTmp<float> rmax, col, upl, dap; DevTmp<double> dapd;
+  DevTmp<unsigned long long> dnan; DevTmp<int4> dtiles;
+  HIPCHK(dlab.alloc((size_t)np)); HIPCHK(dpos.alloc((size_t)N)); HIPCHK(dstart.alloc((size_t)C + 1)); HIPCHK(rarg.alloc((size_t)N));
+  HIPCHK(cnt.alloc((size_t)N * 3)); HIPCHK(correct.alloc((size_t)C)); HIPCHK(rmax.alloc((size_t)N));
+  HIPCHK(col.alloc((size_t)cb_max * np)); HIPCHK(dap.alloc((size_t)C)); HIPCHK(dapd.alloc((size_t)C)); HIPCHK(dnan.alloc(1));
+  HIPCHK(dtiles.alloc(htiles.size() + 1));
+  if (host) HIPCHK(upl.alloc((size_t)cb_max * N));
+  EvTmp ev;
+  for (int i = 0; i < 3; ++i) HIPCHK(hipEventCreate(&ev.e[i]));
+  hipStream_t s = c->stream;
+  HIPCHK(hipMemcpyAsync(dlab, hlab.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dpos, hpos.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dstart, hstart.data(), ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
+  if (!htiles.empty()) HIPCHK(hipMemcpyAsync(dtiles, htiles.data(), htiles.size() * 16, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)N * 12, s));
+  HIPCHK(hipMemsetAsync(correct, 0, (size_t)C * 4, s));
+  HIPCHK(hipMemsetAsync(dnan, 0, 8, s));
+  // counting segments: as the gallery's row kernels, at most GALLERY_SEG_MAX per column
+  const int seg = std::max(4 * CLS_STAGE, (int)round_up((n + GALLERY_SEG_MAX - 1) / GALLERY_SEG_MAX, CLS_STAGE));
+  const int S = (int)((n + seg - 1) / seg);
+  c->last_cls_segments = S;
+  for (int c0 = 0; c0 < C; c0 += cb_max) {
+    const int cb = std::min(cb_max, C - c0);
+    const float* src = scores + c0; int64_t pitch = C;
+    if (host) {                                                  // the block's columns, uploaded as a [n][cb] matrix
+      if (cb == C) HIPCHK(hipMemcpyAsync(upl, scores, (size_t)N * C * 4, hipMemcpyHostToDevice, s));
+      else HIPCHK(hipMemcpy2DAsync(upl, (size_t)cb * 4, scores + c0, (size_t)C * 4, (size_t)cb * 4, (size_t)N, hipMemcpyHostToDevice, s));
+      src = upl; pitch = cb;
+    }
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    launch_cls_rows(src, pitch, N, c0, cb, c0 + cb == C ? 1 : 0, dlab, rmax, rarg, correct, dnan, s);       // :49-67
+    launch_cls_pack(src, pitch, N, cb, col, np, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    int passes = 0;
+    for (int t0 = tbegin[c0]; t0 < tbegin[c0 + cb]; t0 += c->cls_pass_tiles, ++passes)
+      launch_cls_count(col, np, N, seg, S, c0, dlab, dpos, dtiles, t0, std::min(c->cls_pass_tiles, tbegin[c0 + cb] - t0), cnt, s);
+    launch_cls_final(col, np, c0, cb, dpos, dstart, cnt, dapd, dap, s);                                     // :76-85
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e[2], s));
+    HIPCHK(hipEventSynchronize(ev.e[2]));                        // (the next block's upload reuses upl)
+    float ms_rows = 0, ms_count = 0;
+    HIPCHK(hipEventElapsedTime(&ms_rows, ev.e[0], ev.e[1])); HIPCHK(hipEventElapsedTime(&ms_count, ev.e[1], ev.e[2]));
+    c->last_cls_row_ms += ms_rows; c->last_cls_count_ms += ms_count;
+    c->last_cls_passes = std::max(c->last_cls_passes, passes); c->last_cls_blocks += 1;
+  }
+  std::vector<uint32_t> hcorrect((size_t)C); std::vector<float> hap((size_t)C); std::vector<double> hapd((size_t)C);
+  unsigned long long nans = 0;
+  HIPCHK(hipMemcpyAsync(hcorrect.data(), correct, (size_t)C * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(hap.data(), dap, (size_t)C * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(hapd.data(), dapd, (size_t)C * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&nans, dnan, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (nans) return fail(VV_ERR_ARG, "vv_classification_stats: %llu NaN scores (the reference's sort is undefined on them)", nans);
+  int64_t total = 0; int present = 0; double sum_ap = 0;
+  for (int k = 0; k < C; ++k) {
+    total += hcorrect[k];
+    if (hcount[k] > 0) { present += 1; sum_ap += hapd[k]; }
+    if (accuracy) accuracy[k] = hcount[k] > 0 ? (float)hcorrect[k] / (float)hcount[k] : 0.f;              // :71, :88
+    if (ap) ap[k] = hap[k];                                                                              // :85, :89
+    if (count) count[k] = hcount[k];
+  }
+  out->total_accuracy = (float)total / (float)n;                                                        // :93
+  out->mean_ap = (float)(sum_ap / present);
+  out->classes_present = present; out->reserved_ = 0; out->n = n;
+  return VV_OK;
 }
 
 // ------------------------------------------------------------------------------- data parallel -

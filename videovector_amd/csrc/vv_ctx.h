@@ -214,6 +214,12 @@ struct vv_ctx {
   uint32_t* lab_score_ts = nullptr;         // (lab builds) device buffer of k_score_fwd's phase stamps, api.hip
   bool comm_inline = true;                  // option "comm_inline" (VV_COMM_INLINE): the sharded update queued on the compute stream itself (no second stream, no gate)
   int nearest_select_min_k = 33;    // "nearest_select_min_k" / VV_NEAREST_SELECT_MIN_K: vv_gallery_nearest* use the selection form from this k on (1 .. 33)
+  // vv_classification_stats: "cls_pass_tiles" (positive tiles of one counting launch, 1 .. 65535) and "cls_block_cols" (columns of one
+  // block at most; 0: as many as the scratch limit admits) -- both exist so that the tests reach several passes / blocks at small shapes;
+  // then what the last call ran (read-only "last_cls_*")
+  int cls_pass_tiles = 16384, cls_block_cols = 0;
+  int last_cls_passes = 0, last_cls_segments = 0, last_cls_blocks = 0;
+  double last_cls_row_ms = 0, last_cls_count_ms = 0;
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

@@ -671,6 +671,26 @@ void launch_pool_by_id(const float* feat, int Dp, const int32_t* pos_idx, const 
                        hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Classification statistics (kernels_classify.hip): ClassificationStatsLayer, one column block of the score matrix at a time.
+// ---------------------------------------------------------------------------------------------
+constexpr int CLS_TILE = 256;                         // positives of one class per counting workgroup, one per thread
+constexpr int CLS_STAGE = 1024;                       // keys of the class's column staged in LDS at a time (4 per thread)
+// src: the block's first column of row 0, pitch floats between rows; columns c0 .. c0 + cb - 1; last: the matrix's last block
+void launch_cls_rows(const float* src, int64_t pitch, int n, int c0, int cb, int last, const int32_t* labels, float* rmax,
+                     int32_t* rarg, uint32_t* correct, unsigned long long* nan_count, hipStream_t s);
+// col: [cb][npitch], npitch a multiple of 64
+void launch_cls_pack(const float* src, int64_t pitch, int n, int cb, float* col, int64_t npitch, hipStream_t s);
+// seg: items per workgroup (a multiple of CLS_STAGE), S = ceil(n / seg); labels: [npitch]; tiles[t] = {first position in pos_idx,
+// positives (<= CLS_TILE), class, 0}, the class's keys in column class - c0 of col; cnt: uint32 [n][3] by position in pos_idx, zero on entry
+void launch_cls_count(const float* col, int64_t npitch, int n, int seg, int S, int c0, const int32_t* labels, const int32_t* pos_idx,
+                      const int4* tiles, int tile0, int ntiles, uint32_t* cnt, hipStream_t s);
+// cstart: int32 [C + 1], the groups of pos_idx by class; apd / ap: [C]
+void launch_cls_final(const float* col, int64_t npitch, int c0, int cb, const int32_t* pos_idx, const int32_t* cstart,
+                      const uint32_t* cnt, double* apd, float* ap, hipStream_t s);
+// out [rows][ng] = -0.5f * dist [rows][pitch]
+void launch_scores_out(const float* dist, int64_t pitch, int rows, int ng, float* out, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // 16-bit operand types
 // ---------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));

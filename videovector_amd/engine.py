@@ -104,6 +104,11 @@ class _ClassStats(C.Structure):
     _fields_ = [("mean_ap", C.c_float), ("hit_at_1", C.c_float), ("hit_at_5", C.c_float), ("n_scored", C.c_int32)]
 
 
+class _ClassificationReport(C.Structure):
+    _fields_ = [("total_accuracy", C.c_float), ("mean_ap", C.c_float), ("classes_present", C.c_int32), ("reserved_", C.c_int32),
+                ("n", C.c_int64)]
+
+
 def load_library():
     """Load libvideovec.so; raises (never falls back) when the HIP library is not built."""
     global _lib
@@ -177,6 +182,8 @@ def load_library():
         "vv_gallery_class_stats": [vp, vp, vp, vp, i32, C.c_int, C.POINTER(_ClassStats), vp, vp, vp, vp],
         "vv_gallery_nearest": [vp, vp, vp, i32, vp, i32, vp, vp],
         "vv_gallery_nearest_self": [vp, vp, i32, C.c_int, vp, vp],
+        "vv_gallery_scores": [vp, vp, vp, i32, vp],
+        "vv_classification_stats": [vp, vp, i64, i32, vp, C.c_int, vp, vp, vp, C.POINTER(_ClassificationReport)],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
@@ -288,6 +295,17 @@ class Gallery:
         if per_query:
             out.update(best_rank=br, ap=ap, top5_idx=t5i, top5_dist=t5d)
         return out
+
+    def scores(self, q, out_dev=None):
+        """The fp32 dot products of q [n_q][dim] with every reference item into DEVICE memory (vv_gallery_scores): out_dev is a
+        DevBuf (or a device pointer) of [n_q][n_ref] floats; None allocates one.  Returns it -- get() downloads, and it feeds
+        Engine.classification_stats without a host round trip."""
+        q = self._queries(q)
+        if out_dev is None:
+            out_dev = DevBuf(self.eng, (q.shape[0], self.n_ref))
+        ptr = out_dev.ptr if isinstance(out_dev, DevBuf) else C.c_void_p(int(out_dev.value if isinstance(out_dev, C.c_void_p) else out_dev))
+        self.eng._chk(self.eng.L.vv_gallery_scores(self.eng.h, self.h, _ptr(q), q.shape[0], ptr))
+        return out_dev
 
     def rows(self):
         """The gallery's fp32 rows [n_ref][dim], downloaded from the device."""
@@ -812,6 +830,28 @@ class Engine:
         self._chk(self.L.vv_retrieval_stats(self.h, _ptr(feat), feat.shape[0], feat.shape[1], _ptr(vid), _ptr(mi),
                                             _ptr(mc), len(mi), int(exclude_same_video), *[C.byref(x) for x in o]))
         return tuple(x.value for x in o)
+
+    def classification_stats(self, scores, labels, num_classes, n=None):
+        """ClassificationStatsLayer on the device (vv_classification_stats): (accuracy fp32 [C], ap fp32 [C], count int32 [C], report)
+        with report a dict(total_accuracy, mean_ap, classes_present, n).  scores: a numpy array [n][C] (host scores), or a DevBuf /
+        device pointer of n x C floats (then n = len(labels) unless given); labels: [n] integers in 0 .. C - 1."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        Cn = int(num_classes)
+        if isinstance(scores, np.ndarray):
+            sc = np.ascontiguousarray(scores, dtype=np.float32)
+            if sc.ndim != 2 or sc.shape[1] != Cn or sc.shape[0] != lab.shape[0]:
+                raise VVError("classification_stats: scores must be [len(labels)][num_classes]")
+            ptr, on_dev, rows = _ptr(sc), 0, sc.shape[0]
+        else:
+            ptr = scores.ptr if isinstance(scores, DevBuf) else C.c_void_p(int(scores.value if isinstance(scores, C.c_void_p) else scores))
+            on_dev, rows = 1, lab.shape[0] if n is None else int(n)
+            if rows != lab.shape[0]:
+                raise VVError("classification_stats: labels must be [n]")
+        acc, ap, cnt = np.zeros(max(Cn, 0), np.float32), np.zeros(max(Cn, 0), np.float32), np.zeros(max(Cn, 0), np.int32)
+        rep = _ClassificationReport()
+        self._chk(self.L.vv_classification_stats(self.h, ptr, rows, Cn, _ptr(lab), on_dev, _ptr(acc), _ptr(ap), _ptr(cnt), C.byref(rep)))
+        return acc, ap, cnt, dict(total_accuracy=np.float32(rep.total_accuracy), mean_ap=np.float32(rep.mean_ap),
+                                  classes_present=int(rep.classes_present), n=int(rep.n))
 
     def gallery(self, feat, ids=None):
         """A fixed reference set on the device (vv_gallery_create): feat fp32 [n_ref][dim], ids [n_ref] or None (top-k only)."""
