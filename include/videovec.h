@@ -113,6 +113,10 @@ int vv_set_dedup(vv_ctx* ctx, int on);
  *   "last_score_form"                what the last forward pass launched for scores and loss: 1 k_score_fwd (register-resident), 2 k_score_stream at
  *                                    D = 512, 3 k_score_stream at D = 1024, 4 the per-instance kernels (dense or row-writing execution); 0 before the first step
  *   "last_h16"                       1: the last forward pass stored ip2 as f16 rows, 0: fp32 rows (or no step yet)
+ *   "last_grad_shift", "last_grad_shift_round1", "last_grad_repeat"   the f16 gradient-scale guard after the last vv_forward_backward: the powers
+ *                                    of two the device took off the host's scale in the end (signed: the segment-wise backward shifts both ways)
+ *                                    and in the first guard round (meaningful where the step had two; 0 behind the segment-wise backward), and 1 if a conditional repeat really ran
+ *                                    in that step.  0 for bf16 and before any step.  Reading them synchronises the stream (48 bytes are copied)
  *   "h16_fallback"                   1: "h16_guard" 2 has switched this context to fp32 rows (vv_h16_report::fallback, without synchronising);
  *   "h16_flagged_step", "h16_flagged_saturated", "h16_flagged_faint_rows"   the step whose report started that fallback -- with none, the first
  *                                    flagged step -- and its two counts (-1, 0, 0: none flagged so far)

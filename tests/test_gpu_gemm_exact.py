@@ -115,7 +115,7 @@ def fwd_tile(eng):
 
 def test_launch_records_are_read_only(vv):  # noqa: F811
     eng = vv.Engine(0, "f16")
-    for name in ("last_fwd_tile_rows", "last_wgrad_splits", "last_update_form"):
+    for name in ("last_fwd_tile_rows", "last_wgrad_splits", "last_update_form", "last_grad_shift", "last_grad_shift_round1", "last_grad_repeat"):
         assert eng.get_option(name) == 0
         with pytest.raises(vv.VVError, match="videovec error 1: .*read-only"):          # VV_ERR_ARG
             eng.set_option(name, 128)

@@ -320,6 +320,7 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     return fail(VV_ERR_ARG, "vv_set_option: option '%s' is retired; only its fixed value 0 is accepted", name);
   }
   if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form" || n == "last_score_form" || n == "last_h16" ||
+      n == "last_grad_shift" || n == "last_grad_shift_round1" || n == "last_grad_repeat" ||
       n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows" ||
       n == "last_cls_passes" || n == "last_cls_segments" || n == "last_cls_blocks" || n == "last_cls_row_ms" || n == "last_cls_count_ms")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
@@ -415,6 +416,19 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
   else if (n == "last_update_form") *value = c->ko.last_update_form;
   else if (n == "last_score_form") *value = c->ko.last_score_form;
+  else if (n == "last_grad_shift" || n == "last_grad_shift_round1" || n == "last_grad_repeat") {
+    // the guard's state as the last vv_forward_backward's kernels left it (GradGuard: on the device); bf16 / no step yet: 0
+    *value = 0;
+    if (!c->gg_last_seq || !c->gg) return VV_OK;
+    VV_ENTER(c);
+    { const int rcj = comm_join(c); if (rcj) return rcj; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    GradGuard gh;
+    HIPCHK(hipMemcpy(&gh, c->gg, sizeof(gh), hipMemcpyDeviceToHost));
+    if (n == "last_grad_shift") *value = gh.shift[3];
+    else if (n == "last_grad_shift_round1") *value = c->gg_last_rounds > 0 ? gh.shift[1] : 0;      // (the proactive form has no round 1)
+    else *value = gh.repeat_seq == c->gg_last_seq ? 1 : 0;
+  }
   else return fail(VV_ERR_ARG, "vv_get_option: unknown option '%s'", name);
   return VV_OK;
 }
@@ -835,6 +849,7 @@ int vv_run_state_put(vv_ctx* c, const void* buf, int64_t bytes) {
   h.scales.sx = c->sx;                                       // (the table is this context's own)
   HIPCHK(hipMemcpy(c->scales, &h.scales, sizeof(Scales), hipMemcpyHostToDevice));
   if (c->gg) HIPCHK(hipMemcpy(c->gg, &h.gg, sizeof(GradGuard), hipMemcpyHostToDevice));
+  c->gg_last_seq = 0;                                        // (the launch records speak of steps of this context: none since the state was set)
   for (int i = 0; i < GMAX_ENTRIES * GMAX_ENTRY_WORDS; ++i) __atomic_store_n(c->gmax_host + i, h.gmax[i], __ATOMIC_RELEASE);
   const unsigned char* q = (const unsigned char*)buf + sizeof(RunHdr);
   HIPCHK(hipMemcpy(c->wmax_blocks, q, (size_t)2 * WMAX_SLOTS * 4, hipMemcpyHostToDevice)); q += (size_t)2 * WMAX_SLOTS * 4;
@@ -1747,7 +1762,7 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // The segment-wise backward then settles the scale on the device, from a bound on the step's own gradients, before it
   // rounds anything (GuardArgs::proactive).  On the other paths the host's scale follows the data: every step reports its
   // largest |dY| (k_reduce, a host-visible ring); when the max of step seq - 4 -- a FIXED lag, so that the scale sequence
-  // does not depend on host timing and runs stay bit-reproducible -- lies outside [2^5, 2^13) in the current scaled units,
+  // does not depend on host timing and runs stay bit-reproducible -- lies outside [2^4, 2^13) in the current scaled units,
   // the scale moves so that it lies in [2^9, 2^10).  That only keeps the guard's repeats rare: a value past f16's range never
   // reaches the weight-gradient GEMM either way (GradGuard).
   if (c->prec == VV_PREC_F16) {
@@ -1811,11 +1826,13 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // rows + their sums (k_segsum): sums of clipped rows say nothing about the true sums, which the second round sees.
   GuardArgs gd;
   if (c->prec == VV_PREC_F16) { gd.gg = c->gg; gd.slots = c->gg_slots; gd.nslot = c->gg_nslot; gd.seq = seq; }
+  c->gg_last_seq = gd.gg ? seq : 0;
   // (the segment-wise backward needs no repeat at all: its score kernel bounds every instance's gradient and k_seg_bwd
   // settles the scale before it rounds anything -- GuardArgs::proactive)
   const bool proactive_on = c->guard_proactive;   // (lab) false: the repeat form on this path too (A/B)
   const bool proactive = seg && proactive_on;
   const int n_rounds = c->prec != VV_PREC_F16 ? 0 : (proactive ? 0 : (dd && !seg ? 2 : 1));
+  c->gg_last_rounds = n_rounds;
   gd.n_of[0] = seg ? 0 : B;
   gd.n_of[1] = seg ? SEGB_BLOCKS : (dd ? (c->Rp + 3) / 4 : 0);
   SegBwdArgs ba;

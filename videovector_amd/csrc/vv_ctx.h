@@ -126,6 +126,8 @@ struct vv_ctx {
   int sg_adj = 0;                   // powers of two on top of the count-based default scale (follows the reported maxima)
   int32_t gg_seq0 = 0;              // first step since the guard's state was reset (no reports older than that)
   int64_t gg_repeats = 0;           // steps whose gradients had to be produced again at a smaller scale
+  int32_t gg_last_seq = 0;          // the last vv_forward_backward that ran with the guard (f16); 0: none ("last_grad_shift", ...)
+  int gg_last_rounds = 0;           // ... and its guard rounds (0: the proactive form, which writes no shift[1])
   float gg_last_mul = 1.f;          // (debug accessors) final scale multiplier of the last step, read back on demand
   unsigned long long* dd_key = nullptr; int64_t dd_key_cap = 0;
   unsigned long long* dd_agg = nullptr; int dd_agg_stride = 0;
