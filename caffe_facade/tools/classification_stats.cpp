@@ -8,6 +8,12 @@
 //   classes, vv_gallery_pool_by_id turns it into one mean per class (ascending class), vv_gallery_scores writes the dot products of
 //   every test embedding with every class mean into device memory, and the layer reads them there: a nearest-class-mean
 //   classifier whose scores never visit the host.  Column k is the k-th class present in train_labels.txt; they must be 0 .. C-1.
+//   classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x]
+//                        [--momentum m] [--weight_decay w]
+// --linear: as --prototypes, but the classifier is a softmax linear layer trained on the training items (the reference's
+//   INNER_PRODUCT under SOFTMAX_LOSS): they become a device gallery, vv_linear_fit runs N steps of SGD with momentum on it
+//   (vv_linear_cfg_default's values unless given), vv_linear_scores writes the test items' logits into device memory and the
+//   layer reads them there.  Prints `Linear fit: steps = N loss = first -> last` in front of the statistics.
 // --prototxt: the layer's parameter is the first CLASSIFICATION_STATS layer of that net file (its num_classes included) instead of
 //   one made here with num_classes = the number of columns.
 // --num_classes / --label_channels: override num_classes / give the label blob K channels -- the layer's shape CHECKs then fire.
@@ -32,8 +38,17 @@ int main(int argc, char** argv) {
   vector<const char*> pos;
   const char *proto = nullptr, *train_feat = nullptr, *train_lab = nullptr;
   int num_classes = -1, label_channels = 1;
+  bool linear = false;
+  vv_linear_cfg lcfg;
+  vv_linear_cfg_default(&lcfg);
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--prototypes") && i + 2 < argc) { train_feat = argv[i + 1]; train_lab = argv[i + 2]; i += 2; }
+    else if (!strcmp(argv[i], "--linear") && i + 2 < argc) { train_feat = argv[i + 1]; train_lab = argv[i + 2]; linear = true; i += 2; }
+    else if (!strcmp(argv[i], "--iters") && i + 1 < argc) lcfg.iters = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--batch") && i + 1 < argc) lcfg.batch = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--lr") && i + 1 < argc) lcfg.lr = (float)atof(argv[++i]);
+    else if (!strcmp(argv[i], "--momentum") && i + 1 < argc) lcfg.momentum = (float)atof(argv[++i]);
+    else if (!strcmp(argv[i], "--weight_decay") && i + 1 < argc) lcfg.weight_decay = (float)atof(argv[++i]);
     else if (!strcmp(argv[i], "--prototxt") && i + 1 < argc) proto = argv[++i];
     else if (!strcmp(argv[i], "--num_classes") && i + 1 < argc) num_classes = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--label_channels") && i + 1 < argc) label_channels = atoi(argv[++i]);
@@ -41,7 +56,8 @@ int main(int argc, char** argv) {
   }
   if (pos.size() != 2 || label_channels < 1) {
     fprintf(stderr, "usage: classification_stats scores.txt labels.txt [--prototxt net.prototxt] [--num_classes K] [--label_channels K]\n"
-                    "       classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt\n");
+                    "       classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt\n"
+                    "       classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x] [--momentum m] [--weight_decay w]\n");
     return 2;
   }
   Caffe::SetDevice(0);
@@ -66,10 +82,20 @@ int main(int argc, char** argv) {
     CHECK(*distinct.begin() == 0 && *distinct.rbegin() == C - 1) << "the training labels must cover the classes 0 .. " << C - 1;
     vv_gallery *items = nullptr, *means = nullptr;
     VV_CHECK(vv_gallery_create(Caffe::ctx(), tv.data(), tn, dim, cls.data(), &items));
-    VV_CHECK(vv_gallery_pool_by_id(Caffe::ctx(), items, &means));
     x.Reshape(n, C, 1, 1);
-    VV_CHECK(vv_gallery_scores(Caffe::ctx(), means, fv.data(), n, x.mutable_gpu_data()));
-    VV_CHECK(vv_gallery_destroy(Caffe::ctx(), means));
+    if (linear) {
+      vv_linear* lin = nullptr;
+      vv_linear_report rep;
+      VV_CHECK(vv_linear_create(Caffe::ctx(), dim, C, 1, &lin));
+      VV_CHECK(vv_linear_fit(Caffe::ctx(), lin, items, cls.data(), &lcfg, nullptr, nullptr, &rep));
+      printf("Linear fit: steps = %lld loss = %.9g -> %.9g\n", (long long)rep.steps, (double)rep.loss_first, (double)rep.loss_last);
+      VV_CHECK(vv_linear_scores(Caffe::ctx(), lin, nullptr, fv.data(), n, x.mutable_gpu_data()));
+      VV_CHECK(vv_linear_destroy(Caffe::ctx(), lin));
+    } else {
+      VV_CHECK(vv_gallery_pool_by_id(Caffe::ctx(), items, &means));
+      VV_CHECK(vv_gallery_scores(Caffe::ctx(), means, fv.data(), n, x.mutable_gpu_data()));
+      VV_CHECK(vv_gallery_destroy(Caffe::ctx(), means));
+    }
     VV_CHECK(vv_gallery_destroy(Caffe::ctx(), items));
   } else {
     Fill(fv, n, dim, &x);

@@ -712,6 +712,60 @@ int vv_classification_stats(vv_ctx* ctx, const float* scores, int64_t n, int32_t
                             int scores_on_device, float* accuracy, float* ap, int32_t* count, vv_classification_report* out);
 int vv_gallery_scores(vv_ctx* ctx, vv_gallery* gallery, const float* q, int32_t n_q, float* out_dev);
 
+/* ---- a softmax linear classifier trained on gallery embeddings: the reference's INNER_PRODUCT layer under SOFTMAX_LOSS
+ * (src/caffe/layers/softmax_layer.cpp:25-59, softmax_loss_layer.cpp:34-83, inner_product_layer.cu:12-59) with SGDSolver's
+ * momentum rule and L2 decay (src/caffe/solver.cpp:485-531).  Its logits are the score matrix vv_classification_stats reads.
+ * vv_linear: W fp32 [num_classes][dim], b [num_classes] (bias != 0), their momentum histories, a step counter and the batch cursor,
+ * all on the device; created all zero.  vv_linear_get / vv_linear_put: host copies, each pointer may be NULL (put: left as it is);
+ * put sets the step counter and returns the cursor to 0.  With bias == 0, b / hb read as zeros and are ignored by put.
+ * One step over `count` rows x_i of the training gallery with labels y_i (host int32 [n_ref], each in [0, num_classes)):
+ *   z = X W^T + b (inner_product_layer.cu:12-27); the row maximum is the FIRST maximum (softmax_layer.cpp:38-44)
+ *   p = exp(z - max) / sum exp(z - max)  (:46-57)
+ *   loss = loss_weight (1 / count) sum_i -log(max(p_i[y_i], FLT_MIN))  (softmax_loss_layer.cpp:44-51), summed in double in a fixed order
+ *   dz = (p - onehot) (loss_weight / count)  (:68-81; the quotient is formed once, in fp32);  dW = dz^T X, db = sum_i dz_i
+ *     (inner_product_layer.cu:33-49)
+ *   h = lr (g + weight_decay W) + momentum h;  W = W - h  (solver.cpp:497-523); no decay on b (the shipped nets' decay_mult 0)
+ * vv_linear_fit: cfg->iters steps.  batch == 0: every step takes the whole gallery; else count = min(batch, n_ref - cursor) consecutive
+ * items from the cursor (a database read in order; a batch never wraps), the cursor returns to 0 behind the last batch of an epoch and
+ * is carried across calls.  lr_schedule[t] (host [iters]) replaces cfg->lr for step t when given.  All steps are queued on the context's
+ * stream with no host synchronisation in between; the call synchronises once at its end and fills loss_trace (host [iters], may be
+ * NULL) and *out: loss_first / loss_last, accuracy_last (the share of the last batch's rows whose first-maximum column is the label),
+ * steps (the object's counter), nonfinite_rows (rows of any step with a logit that is not finite).
+ * vv_linear_grad: the gradient of the batch [first, first + count) at the current W, b: dW host [num_classes][dim], db [num_classes], *loss
+ * (each may be NULL); nothing is updated, the cursor does not move.
+ * vv_linear_scores: out_dev [n_q][num_classes] fp32 DEVICE memory of the caller (vv_dev_alloc) = z, bias included, for the rows of host
+ * q [n_q][dim] (src NULL), or for the device rows of gallery src (q NULL; n_q must be its item count).  Exactly one of the two.
+ * vv_op_softmax_loss: the softmax kernel on the caller's logits z_dev [rows][pitch] (pitch >= cols floats between rows; labels host
+ * [rows]): prob_dev / dz_dev [rows][pitch] device or NULL (dz's columns cols .. pitch - 1 are written zero), *loss and *correct (rows whose
+ * first maximum is the label) may be NULL.  Synchronises.
+ * vv_op_gemm_tn: out_dev [m][n] = A^T B for A_dev [k][m] (lda floats between rows) and B_dev [k][n] (ldb): the weight-gradient launch and
+ * its slab reduction, exact fp32 (an ordered fmaf chain per split, the splits added in order).  Synchronises.
+ * Every sum has a fixed order and no floating-point atomic exists: the same inputs give the same bits on every call.
+ * VV_ERR_ARG: num_classes outside 1 .. 4096; dim < 1 or different from the gallery's; a label outside [0, num_classes); iters < 1;
+ * batch < 0; first / count outside the gallery; rows, cols, k, m or n below 1 (cols above 4096, pitch < cols, lda < m, ldb < n).
+ * None of these calls touches the training step's state: they may be made between vv_forward_backward* and vv_apply_update.
+ * vv_set_option "lin_split_rows" (0 = the library's plan): rows of one split of the weight-gradient product; a row block of a batch holds
+ * at most 128 splits, so small values are how the tests reach several splits and row blocks at small shapes.  Read-only
+ * "last_lin_splits" (splits of the largest row block), "last_lin_blocks" (row blocks of one batch), "last_lin_fwd_ms" /
+ * "last_lin_softmax_ms" / "last_lin_wgrad_ms" / "last_lin_update_ms" (device time of the four legs in the last step of the last fit). */
+typedef struct vv_linear vv_linear;
+int vv_linear_create(vv_ctx* ctx, int32_t dim, int32_t num_classes, int bias, vv_linear** out);
+int vv_linear_destroy(vv_ctx* ctx, vv_linear* lin);
+int vv_linear_get(vv_ctx* ctx, vv_linear* lin, float* W, float* b, float* hW, float* hb, int64_t* steps);
+int vv_linear_put(vv_ctx* ctx, vv_linear* lin, const float* W, const float* b, const float* hW, const float* hb, int64_t steps);
+typedef struct { int32_t iters, batch; float lr, momentum, weight_decay, loss_weight; } vv_linear_cfg;
+typedef struct { float loss_first, loss_last, accuracy_last; int32_t reserved_; int64_t steps, nonfinite_rows; } vv_linear_report;
+void vv_linear_cfg_default(vv_linear_cfg* cfg);     /* iters 100, batch 0, lr 0.1, momentum 0.9, weight_decay 0, loss_weight 1 */
+int vv_linear_fit(vv_ctx* ctx, vv_linear* lin, vv_gallery* train, const int32_t* labels, const vv_linear_cfg* cfg,
+                  const float* lr_schedule, float* loss_trace, vv_linear_report* out);
+int vv_linear_grad(vv_ctx* ctx, vv_linear* lin, vv_gallery* train, const int32_t* labels, int64_t first, int64_t count,
+                   float loss_weight, float* dW, float* db, float* loss);
+int vv_linear_scores(vv_ctx* ctx, vv_linear* lin, vv_gallery* src_or_null, const float* q, int64_t n_q, float* out_dev);
+int vv_op_softmax_loss(vv_ctx* ctx, const float* z_dev, int64_t rows, int32_t cols, int64_t pitch, const int32_t* labels,
+                       float loss_weight, float* prob_dev, float* dz_dev, float* loss, int64_t* correct);
+int vv_op_gemm_tn(vv_ctx* ctx, const float* A_dev, int64_t lda, const float* B_dev, int64_t ldb, int64_t k, int32_t m, int32_t n,
+                  float* out_dev);
+
 /* ---- per-layer operators.  The reference's operator interface is Layer<Dtype>::{Forward_gpu, Backward_gpu}
  * (include/caffe/layer.hpp:308-337); its sequential executor (Net::ForwardFromTo / BackwardFromTo, net.cpp:501-578) calls
  * them layer by layer.  Training here runs the fused plan above; these entry points are what the C++ facade's layer classes

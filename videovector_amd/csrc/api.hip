@@ -322,7 +322,8 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
   if (n == "last_fwd_tile_rows" || n == "last_wgrad_splits" || n == "last_update_form" || n == "last_score_form" || n == "last_h16" ||
       n == "last_grad_shift" || n == "last_grad_shift_round1" || n == "last_grad_repeat" ||
       n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows" ||
-      n == "last_cls_passes" || n == "last_cls_segments" || n == "last_cls_blocks" || n == "last_cls_row_ms" || n == "last_cls_count_ms")
+      n == "last_cls_passes" || n == "last_cls_segments" || n == "last_cls_blocks" || n == "last_cls_row_ms" || n == "last_cls_count_ms" ||
+      n == "last_lin_splits" || n == "last_lin_blocks" || n == "last_lin_fwd_ms" || n == "last_lin_softmax_ms" || n == "last_lin_wgrad_ms" || n == "last_lin_update_ms")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
@@ -369,6 +370,11 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
     c->cls_block_cols = iv;
     return VV_OK;
   }
+  if (n == "lin_split_rows") {
+    if (iv < 0) return fail(VV_ERR_ARG, "vv_set_option: lin_split_rows = %d is negative", iv);
+    c->lin_split_rows = iv;
+    return VV_OK;
+  }
 #ifdef VV_LAB
   if (n == "ablate") { c->ko.ablate = iv; return VV_OK; }
   if (n == "lab_fwd_abl") { c->ko.lab_fwd_abl = iv; return VV_OK; }
@@ -412,6 +418,13 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "last_cls_blocks") *value = c->last_cls_blocks;
   else if (n == "last_cls_row_ms") *value = c->last_cls_row_ms;
   else if (n == "last_cls_count_ms") *value = c->last_cls_count_ms;
+  else if (n == "lin_split_rows") *value = c->lin_split_rows;
+  else if (n == "last_lin_splits") *value = c->last_lin_splits;
+  else if (n == "last_lin_blocks") *value = c->last_lin_blocks;
+  else if (n == "last_lin_fwd_ms") *value = c->last_lin_ms[0];
+  else if (n == "last_lin_softmax_ms") *value = c->last_lin_ms[1];
+  else if (n == "last_lin_wgrad_ms") *value = c->last_lin_ms[2];
+  else if (n == "last_lin_update_ms") *value = c->last_lin_ms[3];
   else if (n == "last_fwd_tile_rows") *value = c->ko.last_fwd_tile_rows;
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
   else if (n == "last_update_form") *value = c->ko.last_update_form;
@@ -2882,6 +2895,8 @@ struct vv_gallery {
   double last_sim_ms = 0, last_device_ms = 0; int last_passes = 0;
   int last_nearest_form = 0;             // vv_gallery_nearest*: 1 streaming, 2 selection; 0 before the first call
 };
+
+extern "C++" vv::GalleryRows vv::gallery_rows(const vv_gallery* g) { return {g->feat, g->n_ref, g->dim, g->Dp, g->ctx}; }      // (linear.hip)
 
 static void gallery_free_scratch(vv_gallery* g) {
   dfree(g->dist); dfree(g->qdev); dfree(g->out_dist); dfree(g->part); dfree(g->bins); dfree(g->out_idx);

@@ -222,6 +222,12 @@ struct vv_ctx {
   int cls_pass_tiles = 16384, cls_block_cols = 0;
   int last_cls_passes = 0, last_cls_segments = 0, last_cls_blocks = 0;
   double last_cls_row_ms = 0, last_cls_count_ms = 0;
+  // the linear classifier (linear.hip): "lin_split_rows" (rows of one split of the weight-gradient product; 0: the library's plan) -- it
+  // exists so that the tests reach several splits and row blocks at small shapes; then what the last call ran (read-only "last_lin_*":
+  // the splits of the largest row block, the row blocks of one batch, the four legs' device time in the last step of the last fit)
+  int lin_split_rows = 0;
+  int last_lin_splits = 0, last_lin_blocks = 0;
+  double last_lin_ms[4] = {0, 0, 0, 0};
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

@@ -5,6 +5,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+struct vv_gallery;
+
 namespace vv {
 
 // Floats between two split-K slabs of the weight gradient.  Exactly D_p x F_p (8 MiB at 512 x 4096) puts the eight streams that k_reduce /
@@ -689,6 +691,52 @@ void launch_cls_final(const float* col, int64_t npitch, int c0, int cb, const in
                       const uint32_t* cnt, double* apd, float* ap, hipStream_t s);
 // out [rows][ng] = -0.5f * dist [rows][pitch]
 void launch_scores_out(const float* dist, int64_t pitch, int rows, int ng, float* out, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Softmax linear classifier on gallery embeddings (kernels_linear.hip, linear.hip)
+// ---------------------------------------------------------------------------------------------
+constexpr int LIN_BM = 128, LIN_BN = 128, LIN_BK = 32;   // the weight-gradient product's output tile and K step
+constexpr int LIN_TARGET_BLOCKS = 512;                  // workgroups the split plan aims at (a constant, not the device's CU count)
+constexpr int LIN_MIN_SPLIT_ROWS = 128;                 // rows of one split at least, in the library's plan (four K steps)
+constexpr int LIN_MAX_SPLITS = 128;                     // slabs at most; a batch of more rows than 128 splits runs in row blocks
+constexpr int LIN_SM_BLOCKS = 512;                      // k_softmax_xent's fixed grid = the partials its last stage adds in index order
+constexpr int LIN_UPD_BLOCKS = 1024;                    // k_lin_update's fixed grid
+struct LinRec { double loss_sum; int64_t correct, nonfinite; };   // one batch: sum of the rows' loss terms, rows won by the label, rows with a non-finite logit
+struct LinSoftmaxArgs {
+  const float* sim; int64_t pitch; int64_t rows; int cols;        // z = mul sim + bias: mul -0.5f on what k_sim_f32 stored, 1 on logits
+  float mul;
+  const float* bias;                                              // [cols] or NULL
+  const int32_t* labels;                                          // device [rows]
+  float scale;                                                    // loss_weight / (float)count of the whole batch
+  float* dz; float* prob;                                         // [rows][pitch] each, either may be NULL
+  float* row_loss; int32_t* row_flags;                            // [rows] (both or neither): the row's term; bit 0 correct, bit 1 non-finite
+  int wd;                                                         // lanes per row: 32 (cols <= 32) or 64
+  LinRec* rec; int first_block;                                   // first_block: rec is stored, else added to
+  double* part_loss; uint32_t* part_cnt; uint32_t* arrived;       // [LIN_SM_BLOCKS], [LIN_SM_BLOCKS][2], the arrival counter (0 between launches)
+};
+struct LinWgradArgs {
+  const float* A; int64_t lda; const float* B; int64_t ldb;       // A [k][m], B [k][n]
+  int64_t k; int m, n;
+  int64_t split_rows; int S;                                      // split s: rows [s split_rows, (s + 1) split_rows) of k
+  float* slabs; int64_t slab_stride;                              // [S][m][n], slab_stride floats apart
+  float* dbs;                                                     // [S][m] column sums of A, or NULL
+  int accumulate; int vec_a, vec_b;                               // vec_*: base and leading dimension on 16 bytes
+};
+struct LinPlan { int64_t split_rows = 0, block_rows = 0; int S = 0, blocks = 0; };    // S: splits of the first (largest) row block
+LinPlan lin_plan(int64_t k, int m, int n, int64_t forced_split_rows);
+struct LinUpdArgs {
+  const float* slabs; int64_t slab_stride; int S; int64_t nW;     // nW = m n elements
+  const float* dbs; int64_t db_stride; int nb;                    // nb: bias elements (0: none)
+  float *W, *hW, *b, *hb;                                         // rule == 0: W / b are the outputs, hW / hb unused
+  float lr, momentum, wd; int rule; int vec;
+};
+void launch_softmax_xent(const LinSoftmaxArgs& a, hipStream_t s);
+void launch_lin_scores_out(const float* sim, int64_t pitch, int64_t rows, int cols, const float* bias, float* out, hipStream_t s);
+void launch_lin_wgrad(const LinWgradArgs& a, hipStream_t s);
+void launch_lin_update(const LinUpdArgs& a, hipStream_t s);
+// api.hip: a gallery's device rows ([n_ref][Dp] fp32, columns dim .. Dp - 1 zero) and the context it belongs to
+struct GalleryRows { const float* feat; int64_t n_ref; int dim, Dp; const void* ctx; };
+GalleryRows gallery_rows(const ::vv_gallery* g);
 
 // ---------------------------------------------------------------------------------------------
 // 16-bit operand types

@@ -109,6 +109,16 @@ class _ClassificationReport(C.Structure):
                 ("n", C.c_int64)]
 
 
+class _LinearCfg(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("batch", C.c_int32), ("lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float),
+                ("loss_weight", C.c_float)]
+
+
+class _LinearReport(C.Structure):
+    _fields_ = [("loss_first", C.c_float), ("loss_last", C.c_float), ("accuracy_last", C.c_float), ("reserved_", C.c_int32),
+                ("steps", C.c_int64), ("nonfinite_rows", C.c_int64)]
+
+
 def load_library():
     """Load libvideovec.so; raises (never falls back) when the HIP library is not built."""
     global _lib
@@ -184,6 +194,14 @@ def load_library():
         "vv_gallery_nearest_self": [vp, vp, i32, C.c_int, vp, vp],
         "vv_gallery_scores": [vp, vp, vp, i32, vp],
         "vv_classification_stats": [vp, vp, i64, i32, vp, C.c_int, vp, vp, vp, C.POINTER(_ClassificationReport)],
+        "vv_linear_create": [vp, i32, i32, C.c_int, C.POINTER(vp)], "vv_linear_destroy": [vp, vp],
+        "vv_linear_get": [vp, vp, vp, vp, vp, vp, C.POINTER(i64)], "vv_linear_put": [vp, vp, vp, vp, vp, vp, i64],
+        "vv_linear_cfg_default": [C.POINTER(_LinearCfg)],
+        "vv_linear_fit": [vp, vp, vp, vp, C.POINTER(_LinearCfg), vp, vp, C.POINTER(_LinearReport)],
+        "vv_linear_grad": [vp, vp, vp, vp, i64, i64, f32, vp, vp, C.POINTER(f32)],
+        "vv_linear_scores": [vp, vp, vp, vp, i64, vp],
+        "vv_op_softmax_loss": [vp, vp, i64, i32, i64, vp, f32, vp, vp, C.POINTER(f32), C.POINTER(i64)],
+        "vv_op_gemm_tn": [vp, vp, i64, vp, i64, i64, i32, i32, vp],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
@@ -206,7 +224,7 @@ def load_library():
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
-        fn.restype = None if name == "vv_step_cfg_default" else C.c_int
+        fn.restype = None if name in ("vv_step_cfg_default", "vv_linear_cfg_default") else C.c_int
     L.vv_sampler_state_error.argtypes = []
     L.vv_sampler_state_error.restype = C.c_char_p
     _lib = L
@@ -355,6 +373,99 @@ class Gallery:
 
 
 SOLVER_TYPES = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADAM": 5}     # (4, BVLC's ADADELTA: not implemented)
+
+
+def _dev_ptr(x):
+    """A DevBuf, a ctypes pointer or an integer device address as a c_void_p (None stays None)."""
+    if x is None:
+        return None
+    if isinstance(x, DevBuf):
+        return x.ptr
+    return C.c_void_p(int(x.value if isinstance(x, C.c_void_p) else x))
+
+
+class Linear:
+    """A softmax linear classifier held on the device by an Engine (vv_linear_*): the reference's INNER_PRODUCT layer under
+    SOFTMAX_LOSS, trained by SGD with momentum on a Gallery's embeddings."""
+
+    def __init__(self, eng, handle, dim, num_classes, bias):
+        self.eng, self.h, self.dim, self.num_classes, self.bias = eng, handle, int(dim), int(num_classes), bool(bias)
+
+    def _labels(self, gallery, labels):
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if lab.shape[0] != gallery.n_ref:
+            raise VVError("labels must be [n_ref]")
+        return lab
+
+    def fit(self, gallery, labels, iters=100, batch=0, lr=0.1, momentum=0.9, weight_decay=0.0, loss_weight=1.0, lr_schedule=None):
+        """vv_linear_fit: `iters` steps on the gallery's items; returns (loss_trace fp32 [iters], report dict).  lr_schedule: [iters]
+        learning rates that replace lr step by step."""
+        lab = self._labels(gallery, labels)
+        cfg = _LinearCfg(int(iters), int(batch), lr, momentum, weight_decay, loss_weight)
+        sched = None if lr_schedule is None else np.ascontiguousarray(lr_schedule, dtype=np.float32)
+        if sched is not None and sched.shape != (int(iters),):
+            raise VVError("lr_schedule must be [iters]")
+        trace = np.zeros(max(int(iters), 0), np.float32)
+        rep = _LinearReport()
+        self.eng._chk(self.eng.L.vv_linear_fit(self.eng.h, self.h, gallery.h, _ptr(lab), C.byref(cfg), _ptr(sched), _ptr(trace), C.byref(rep)))
+        return trace, dict(loss_first=np.float32(rep.loss_first), loss_last=np.float32(rep.loss_last),
+                           accuracy_last=np.float32(rep.accuracy_last), steps=int(rep.steps), nonfinite_rows=int(rep.nonfinite_rows))
+
+    def grad(self, gallery, labels, first=0, count=None, loss_weight=1.0):
+        """vv_linear_grad: (dW [C][dim], db [C], loss) of the batch [first, first + count) at the current parameters; nothing moves."""
+        lab = self._labels(gallery, labels)
+        count = gallery.n_ref - int(first) if count is None else int(count)
+        dW, db = np.zeros((self.num_classes, self.dim), np.float32), np.zeros(self.num_classes, np.float32)
+        loss = C.c_float()
+        self.eng._chk(self.eng.L.vv_linear_grad(self.eng.h, self.h, gallery.h, _ptr(lab), int(first), count, loss_weight, _ptr(dW), _ptr(db),
+                                                C.byref(loss)))
+        return dW, db, np.float32(loss.value)
+
+    def scores(self, src, out=None):
+        """vv_linear_scores: the logits [n][C] of a Gallery's device rows or of a host array [n][dim], as a DevBuf (`out`, or a new one):
+        what Engine.classification_stats reads on the device."""
+        if isinstance(src, Gallery):
+            n, gh, q = src.n_ref, src.h, None
+        else:
+            q = np.ascontiguousarray(src, dtype=np.float32)
+            if q.ndim != 2 or q.shape[1] != self.dim:
+                raise VVError("scores: the rows must be [n][%d]" % self.dim)
+            n, gh = q.shape[0], None
+        out = DevBuf(self.eng, (n, self.num_classes)) if out is None else out
+        self.eng._chk(self.eng.L.vv_linear_scores(self.eng.h, self.h, gh, _ptr(q), n, _dev_ptr(out)))
+        return out
+
+    def get(self):
+        """(W [C][dim], b [C], hW, hb, steps)"""
+        W, hW = (np.zeros((self.num_classes, self.dim), np.float32) for _ in range(2))
+        b, hb = (np.zeros(self.num_classes, np.float32) for _ in range(2))
+        steps = C.c_int64()
+        self.eng._chk(self.eng.L.vv_linear_get(self.eng.h, self.h, _ptr(W), _ptr(b), _ptr(hW), _ptr(hb), C.byref(steps)))
+        return W, b, hW, hb, steps.value
+
+    def put(self, W=None, b=None, hW=None, hb=None, steps=0):
+        """vv_linear_put: None leaves that array as it is; the batch cursor returns to 0."""
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise VVError("put: an array of shape %r is expected" % (shape,))
+            return a
+        ws, bs = (self.num_classes, self.dim), (self.num_classes,)
+        W, hW, b, hb = arr(W, ws), arr(hW, ws), arr(b, bs), arr(hb, bs)
+        self.eng._chk(self.eng.L.vv_linear_put(self.eng.h, self.h, _ptr(W), _ptr(b), _ptr(hW), _ptr(hb), int(steps)))
+
+    def close(self):
+        if self.h is not None and getattr(self.eng, "h", None):
+            self.eng.L.vv_linear_destroy(self.eng.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class StepConfig:
@@ -852,6 +963,27 @@ class Engine:
         self._chk(self.L.vv_classification_stats(self.h, ptr, rows, Cn, _ptr(lab), on_dev, _ptr(acc), _ptr(ap), _ptr(cnt), C.byref(rep)))
         return acc, ap, cnt, dict(total_accuracy=np.float32(rep.total_accuracy), mean_ap=np.float32(rep.mean_ap),
                                   classes_present=int(rep.classes_present), n=int(rep.n))
+
+    def linear(self, dim, num_classes, bias=True):
+        """A softmax linear classifier on the device, all zero (vv_linear_create)."""
+        h = C.c_void_p()
+        self._chk(self.L.vv_linear_create(self.h, int(dim), int(num_classes), int(bool(bias)), C.byref(h)))
+        return Linear(self, h, dim, num_classes, bias)
+
+    def op_softmax_loss(self, z, rows, cols, pitch, labels, loss_weight=1.0, prob=None, dz=None):
+        """vv_op_softmax_loss on device logits z [rows][pitch] (DevBuf or device pointer); prob / dz: DevBufs [rows][pitch] or None.
+        Returns (loss, correct)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if lab.shape[0] != int(rows):
+            raise VVError("op_softmax_loss: labels must be [rows]")
+        loss, correct = C.c_float(), C.c_int64()
+        self._chk(self.L.vv_op_softmax_loss(self.h, _dev_ptr(z), int(rows), int(cols), int(pitch), _ptr(lab), loss_weight, _dev_ptr(prob),
+                                            _dev_ptr(dz), C.byref(loss), C.byref(correct)))
+        return np.float32(loss.value), int(correct.value)
+
+    def op_gemm_tn(self, A, lda, B, ldb, k, m, n, out):
+        """vv_op_gemm_tn: out [m][n] = A^T B for device A [k][lda >= m], B [k][ldb >= n] (DevBufs or device pointers)."""
+        self._chk(self.L.vv_op_gemm_tn(self.h, _dev_ptr(A), int(lda), _dev_ptr(B), int(ldb), int(k), int(m), int(n), _dev_ptr(out)))
 
     def gallery(self, feat, ids=None):
         """A fixed reference set on the device (vv_gallery_create): feat fp32 [n_ref][dim], ids [n_ref] or None (top-k only)."""
