@@ -1616,37 +1616,23 @@ static int wgrad_to_destination(vv_ctx* c, WgradArgs& wa, ReduceArgs& ra, bool u
   return VV_OK;
 }
 
-static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device, int64_t row_limit, int32_t seq = 0) {
-  { const int rcg = upd_pending_guard(c, "vv_forward_backward"); if (rcg) return rcg; }
-  const bool upd_hint = c && c->upd_hint;       // (consumed by this call whatever path it takes)
-  if (c) c->upd_hint = false;
-  if (c && c->ema_in_use) return fail(VV_ERR_STATE, "vv_forward_backward: %s", kEmaInUse);
-  int rc = check_cfg(c, cfg);
-  if (rc) return rc;
-  if (!idx) return fail(VV_ERR_ARG, "vv_forward_backward: idx is NULL");
-  VV_ENTER(c);
-  // (an overlapped update of the previous step may still be arriving: see the forward GEMM below)
-  if (c->upd_sync == UpdSync::InFlight && (cfg->B != c->B || cfg->C != c->C || cfg->Nn != c->Nn || !c->H) && (rc = comm_join(c))) return rc;
-  if ((rc = ensure_batch(c, cfg->B, cfg->C, cfg->Nn))) return rc;
-  const int B = c->B, C = c->C, Nn = c->Nn, CN = C + Nn, D = c->D;
+// ---- the stages of a pass over one batch.  The training pass (fb_impl) and the forward-only pass (vv_forward) are sequences of these; what
+// differs between the two stands at the two call sites.
+
+// Host indices: checked while they are copied into a pinned staging slot that the first kernel reads in place.  The slot is the caller's
+// (training slots are released by sequence stamps, evaluation slots by events).
+static int stage_indices(vv_ctx* c, const int32_t* idx, int64_t row_limit, int32_t* dst) {
+  int bad = -1;
+  for (int i = 0; i < c->R; ++i) { const int32_t v = idx[i]; dst[i] = v; if (v < -1 || v >= row_limit) bad = i; }
+  if (bad >= 0) return fail(VV_ERR_ARG, "idx[%d] = %d out of range [-1, %lld)", bad, idx[bad], (long long)c->n_rows);
+  return VV_OK;
+}
+
+// The cfg's host inputs, onto the device on the context's stream: the eltwise coefficients (cached on the device until they change -- the one
+// synchronise), the item weights, an explicit dropout mask.  The device copies are the step's own, read by kernels queued in front.
+static int stage_cfg_inputs(vv_ctx* c, const vv_step_cfg* cfg) {
+  const int B = c->B, C = c->C;
   hipStream_t s = c->stream;
-
-  const int32_t* didx = idx;
-  if (!idx_on_device) {
-    // host indices: checked while they are copied into a pinned staging slot that the first kernel reads in place
-    int sl = 0;
-    if ((rc = stage_acquire(c, (size_t)c->R * 4, &sl))) return rc;
-    int32_t* dst = c->stage_host[sl];
-    int bad = -1;
-    for (int i = 0; i < c->R; ++i) { const int32_t v = idx[i]; dst[i] = v; if (v < -1 || v >= row_limit) bad = i; }
-    if (bad >= 0) return fail(VV_ERR_ARG, "idx[%d] = %d out of range [-1, %lld)", bad, idx[bad], (long long)c->n_rows);
-    if (!seq) seq = ++c->step_seq;
-    c->stage_seq[sl] = seq;
-    didx = c->stage_dev[sl];
-  }
-  if (!seq) seq = ++c->step_seq;          // every step has a sequence number; its forward GEMM stamps it into host-visible memory
-
-  // eltwise coefficients (cached on the device until they change)
   std::vector<float> coeff(C - 1);
   for (int j = 0; j < C - 1; ++j) coeff[j] = cfg->ctx_coeff ? cfg->ctx_coeff[j] : 1.0f / (C - 1);
   if (coeff != c->coeff_host) {
@@ -1660,71 +1646,102 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     HIPCHK(hipMemcpyAsync(c->item_w, cfg->item_weight, (size_t)B * 4, hipMemcpyHostToDevice, s));
   }
   if (cfg->dropout_ratio > 0.f && cfg->dropout_mask) {
-    const size_t nb = (size_t)c->R * D;
+    const size_t nb = (size_t)c->R * c->D;
     if (nb > c->mask_bytes) { dfree(c->mask); c->mask = nullptr; HIPCHK(hipMalloc(&c->mask, nb)); c->mask_bytes = nb; }
     HIPCHK(hipMemcpyAsync(c->mask, cfg->dropout_mask, nb, hipMemcpyHostToDevice, s));
   }
+  return VV_OK;
+}
 
-  // De-duplicate the batch rows.  Dropout sits BEHIND the projection (fc7 -> ReLU -> drop2, mednet_embedding_train.prototxt:190-230): the
-  // projection of equal rows is equal, only the mask differs per instance.  The segment-wise pair carries the masks (k_score_fwd /
-  // k_score_stream + k_seg_bwd at D = 512 and 1024: every instance masks its row as it reads it, the backward sums m_i-weighted terms per
-  // distinct row), and option "drop_dedup" says on which of its shapes dropout rides the de-duplicated path: 1, the default, the shapes of
-  // the register-resident k_score_fwd; 2 every shape of the pair; 0 none.  Elsewhere it stays dense (the mask in the forward GEMM's
-  // epilogue).  The two executions evaluate the same mask function (vv_internal.h: DropSpec).
-  const bool drop_on = cfg->dropout_ratio > 0.f;
-  const bool drop_dd = drop_on && c->drop_dedup && c->seg_bwd && score_fwd_dropout_supported(c->drop_dedup, D, C, Nn);
-  const bool dd = c->dedup && (!drop_on || drop_dd) && !ablate_on();
+// The execution of this pass (vv_pass_plan.h), from the context's options and the cfg
+static PassPlan plan_pass(const vv_ctx* c, const vv_step_cfg* cfg, bool fwd_only) {
+  PassPlanIn in;
+  in.dedup = c->dedup; in.seg_bwd = c->seg_bwd; in.drop_dedup = c->drop_dedup; in.h16 = c->h16; in.h16_fallback = c->h16_fallback; in.v16 = c->v16;
+  in.ablate = ablate_on(); in.D = c->D; in.C = c->C; in.Nn = c->Nn; in.dropout = cfg->dropout_ratio > 0.f; in.fwd_only = fwd_only;
+  return pass_plan(in);
+}
+
+// The dropout mask of this pass as a function (vv_internal.h: DropSpec; mode 0 without dropout).  The counter c->iter is read, not advanced:
+// vv_apply_update advances it, so a forward-only pass draws the mask the next training step will draw and leaves it to that step.
+static DropSpec make_drop_spec(const vv_ctx* c, const vv_step_cfg* cfg) {
   DropSpec dsp;
-  if (drop_on) {
-    dsp.mode = cfg->dropout_mask ? 2 : 1;
-    dsp.thr = (uint32_t)(cfg->dropout_ratio * 65536.f + 0.5f);
+  if (cfg->dropout_ratio > 0.f) {
+    dsp.mode = cfg->dropout_mask ? 2 : 1; dsp.thr = (uint32_t)(cfg->dropout_ratio * 65536.f + 0.5f);
     dsp.s32 = (uint32_t)(mix64(cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter, 0x5eedull) >> 32);
     dsp.scale = 1.f / (1.f - cfg->dropout_ratio);
     dsp.mask = cfg->dropout_mask ? c->mask : nullptr;
-    dsp.B = B; dsp.CN = CN; dsp.D = D;
+    dsp.B = c->B; dsp.CN = c->C + c->Nn; dsp.D = c->D;
   }
-  c->last_drop = (dd && drop_on) ? dsp : DropSpec();
-  c->last_dedup = dd;
-  c->last_fwd_only = false;
-  if (!dd) launch_map_rows(didx, c->rows, c->R, c->Rp, (int32_t)c->n_rows, (int32_t)row_limit, s);
-  if (dd) {
-    int si = 0;
-    if ((rc = dd_issue(c, didx, idx_on_device, row_limit, seq, &si))) return rc;
-    vv_ctx::DdSet& set = c->dd_set[si];
-    set.used_seq = seq;
-    c->dd_rows = set.rows; c->dd_slot_of = set.slot_of; c->dd_uniq = set.uniq; c->dd_map = set.map; c->dd_ord = set.ord;
-    c->dd_cnt = set.cnt; c->dd_seg = set.seg; c->dd_info = set.info;
-    if (c->dd_async) {
-      // The grouping takes ~30 us on an idle second stream and the host is normally several steps ahead of the GPU: it
-      // can afford to watch the event for a moment.  Once the event has fired nothing needs to be put into the step's
-      // stream at all (a wait packet in front of the forward GEMM costs ~6 us of stream time even when already satisfied);
-      // otherwise the stream waits as usual.
-      bool fired = hipEventQuery(set.done) == hipSuccess;
-      // (an idle step stream -- the first step after a synchronisation -- means a grouping just queued cannot have run yet:
-      // watching it would hold the host for its whole 40 us while the GPU then waits for the step's launches; queue the wait)
-      if (!fired && c->dd_spin_us > 0 && hipStreamQuery(s) != hipSuccess) {
-        const double t0 = host_now_ms();
-        do { fired = hipEventQuery(set.done) == hipSuccess; } while (!fired && (host_now_ms() - t0) * 1e3 < c->dd_spin_us);
-        c->wait_ms[2] += host_now_ms() - t0;
-      }
-      if (!fired) HIPCHK(hipStreamWaitEvent(s, set.done, 0));
-    }
-  }
+  return dsp;
+}
 
+// what the accessors of the last forward pass's values read (vv_blobs_get, vv_dedup_stats, vv_h16_stats, option "last_h16")
+static void record_plan(vv_ctx* c, const PassPlan& p, const DropSpec& dsp) {
+  c->last_drop = p.drop_rides_dd ? dsp : DropSpec(); c->last_dedup = p.dd; c->last_h16 = p.h16;
+}
+
+// the grouping set this pass reads (dd_issue)
+static void bind_dd_set(vv_ctx* c, const vv_ctx::DdSet& set) {
+  c->dd_rows = set.rows; c->dd_slot_of = set.slot_of; c->dd_uniq = set.uniq; c->dd_map = set.map; c->dd_ord = set.ord;
+  c->dd_cnt = set.cnt; c->dd_seg = set.seg; c->dd_info = set.info;
+}
+
+// The forward GEMM of a pass: the batch's rows (distinct rows when de-duplicated, R_hint of them expected) through pv's parameters into ip2.
+// A training step adds its sequence stamp and, under an overlapped update, the gate.
+static FwdArgs fwd_args(const vv_ctx* c, const vv_step_cfg* cfg, const PassPlan& p, const ParamView& pv, int R_hint) {
   FwdArgs fa;
-  fa.table = c->table; fa.rows = dd ? c->dd_uniq : c->rows; fa.Wh = c->Wh; fa.bias = c->b; fa.scales = c->scales;
-  fa.H = c->H; fa.R = c->R; fa.D = D; fa.Fp = c->Fp; fa.relu = 1; fa.zero_row = (int32_t)c->n_rows;
-  fa.n_dev = dd ? c->dd_info : nullptr;
-  fa.R_hint = dd ? *(volatile int32_t*)c->U_host : 0;
-  fa.seq_host = c->seq_host_dev; fa.seq = seq;
+  fa.table = c->table; fa.rows = p.dd ? c->dd_uniq : c->rows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
+  fa.H = c->H; fa.R = c->R; fa.D = c->D; fa.Fp = c->Fp; fa.relu = 1; fa.zero_row = (int32_t)c->n_rows;
+  fa.n_dev = p.dd ? c->dd_info : nullptr; fa.R_hint = p.dd ? R_hint : 0; fa.h16 = p.h16 ? 1 : 0;
+  fa.drop_ratio = p.drop_rides_dd ? 0.f : cfg->dropout_ratio;      // (de-duplicated: H holds the shared pre-dropout rows, the instances mask them)
+  fa.mask = (!p.drop_rides_dd && cfg->dropout_ratio > 0.f && cfg->dropout_mask) ? c->mask : nullptr;
+  fa.drop_seed = cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter;
+  fa.B = c->B; fa.CN = c->C + c->Nn;
+  return fa;
+}
 
-  // ip2 as f16 (option "h16"): only where the segment-wise pair reads it -- de-duplicated batches of D = 512 / 1024 (k_score_fwd / k_score_stream /
-  // k_seg_bwd carry the f16 row loads; the dense and the generic kernels keep fp32 rows), D % 8 == 0, the phase-staggered forward kernel
-  const bool seg_path = dd && c->seg_bwd && (D == 512 || D == 1024);
-  // ... and their range loss (option "h16_guard"): a step that stored f16 rows had them counted (k_seg_bwd_cnt), its counts ride in its report
-  // entry, and the entry of step seq - kLag is read HERE, at a fixed lag like the gradient scale's, so that whatever it steers -- value 2: this
-  // and every later step store fp32 rows, exactly the execution of h16 = 0, until the caller sets h16 again -- does not depend on host timing.
-  // Up to kLag steps have trained on the flagged rows by then: the price of never stalling a host that runs ahead; it is reported.
+// the loss terms the gradient is normalised by: the caller's count over all ranks, or this batch's own B Nn
+static inline int64_t global_count(const vv_ctx* c, const vv_step_cfg* cfg) { return cfg->global_count > 0 ? cfg->global_count : (int64_t)c->B * c->Nn; }
+
+// The score kernels' arguments that every pass fills alike.  The caller adds where the gradient and the loss partials go (dYh, dbp, loss_part,
+// viol_part), the gradient scale sg, and what only one of the passes has: the stamp and v16 (training), fwd_only.
+static ScoreArgs score_args(const vv_ctx* c, const vv_step_cfg* cfg, const PassPlan& p, const DropSpec& dsp) {
+  ScoreArgs sa{};
+  sa.H = c->H; sa.s_true = c->s_true; sa.s_bogus = c->s_bogus; sa.coeff = c->coeff;
+  sa.B = c->B; sa.C = c->C; sa.Nn = c->Nn; sa.D = c->D; sa.Dp = c->Dp;
+  sa.margin = cfg->margin; sa.norm = cfg->norm; sa.grad_scale = cfg->loss_weight / (float)global_count(c, cfg);
+  sa.drop_scale = cfg->dropout_ratio > 0.f ? 1.f / (1.f - cfg->dropout_ratio) : 1.f;
+  sa.map = p.dd ? c->dd_map : nullptr; sa.seg_start = p.dd ? c->dd_seg : nullptr; sa.ord = p.dd ? c->dd_ord : nullptr;
+  sa.item_w = cfg->item_weight ? c->item_w : nullptr;
+  if (p.drop_rides_dd) sa.drop = dsp;
+  sa.h16 = p.h16 ? 1 : 0;
+  return sa;
+}
+
+// ---- what only a training step does: its stream behind its grouping (DdSet::done).
+// The grouping takes ~30 us on an idle second stream and the host is normally several steps ahead of the GPU: it
+// can afford to watch the event for a moment.  Once the event has fired nothing needs to be put into the step's
+// stream at all (a wait packet in front of the forward GEMM costs ~6 us of stream time even when already satisfied);
+// otherwise the stream waits as usual.
+static int dd_wait(vv_ctx* c, vv_ctx::DdSet& set, hipStream_t s) {
+  bool fired = hipEventQuery(set.done) == hipSuccess;
+  // (an idle step stream -- the first step after a synchronisation -- means a grouping just queued cannot have run yet:
+  // watching it would hold the host for its whole 40 us while the GPU then waits for the step's launches; queue the wait)
+  if (!fired && c->dd_spin_us > 0 && hipStreamQuery(s) != hipSuccess) {
+    const double t0 = host_now_ms();
+    do { fired = hipEventQuery(set.done) == hipSuccess; } while (!fired && (host_now_ms() - t0) * 1e3 < c->dd_spin_us);
+    c->wait_ms[2] += host_now_ms() - t0;
+  }
+  if (!fired) HIPCHK(hipStreamWaitEvent(s, set.done, 0));
+  return VV_OK;
+}
+
+// The f16 rows' range loss (option "h16_guard"): a step that stored f16 rows had them counted (k_seg_bwd_cnt), its counts ride in its report
+// entry, and the entry of step seq - kLag is read HERE, at a fixed lag like the gradient scale's, so that whatever it steers -- value 2: this
+// and every later step store fp32 rows, exactly the execution of h16 = 0, until the caller sets h16 again -- does not depend on host timing.
+// Up to kLag steps have trained on the flagged rows by then: the price of never stalling a host that runs ahead; it is reported.
+// Runs before the step is planned: the plan reads the fallback this may switch.
+static void h16_guard_read(vv_ctx* c, int32_t seq, hipStream_t s) {
   if (c->h16_guard >= 1 && c->h16_counted[(seq - kLag) & (GMAX_ENTRIES - 1)] == seq - kLag) {
     const int32_t want = seq - kLag;
     if (report_wait(c, want, s)) {
@@ -1740,44 +1757,34 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     }
     c->h16_counted[(seq - kLag) & (GMAX_ENTRIES - 1)] = INT32_MIN;
   }
-  const bool h16 = c->h16 && !c->h16_fallback && seg_path && !ablate_on();
-  const bool h16_count = h16 && c->h16_guard >= 1;
-  fa.h16 = h16 ? 1 : 0;
-  c->last_h16 = h16;
-  c->last_h16_counted = h16_count;
-  if (h16_count) c->h16_counted[seq & (GMAX_ENTRIES - 1)] = seq;
-  fa.drop_ratio = (dd && drop_on) ? 0.f : cfg->dropout_ratio;      // (de-duplicated: H holds the shared pre-dropout rows, the instances mask them)
-  fa.mask = (!(dd && drop_on) && cfg->dropout_ratio > 0.f && cfg->dropout_mask) ? c->mask : nullptr;
-  fa.drop_seed = cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter;
-  fa.B = B; fa.CN = CN;
-  if (c->upd_sync == UpdSync::InFlight) {
-    // Data-parallel overlap: the previous step's update is still arriving on the communication stream, F-chunk by
-    // F-chunk.  The forward GEMM starts anyway and waits per chunk inside the kernel -- provided its persistent
-    // workgroups leave compute units free for the update's own kernels (all-reduce, SGD: they must be able to run
-    // BESIDE the waiting GEMM, or nothing would ever release it); otherwise the stream joins here, as without overlap.
-    const long tiles = fwd_gemm_plan(c->R, dd ? fa.R_hint : 0, D, nullptr);
-    const bool no_gate = !c->comm_gate;
-    if (!no_gate && !ablate_on() && fwd_gemm_can_gate(fa) && (!dd || fa.R_hint > 0) && tiles <= c->n_cu - 16) {
-      fa.gate = c->w_gate; fa.gate_seq = c->upd_seq; fa.gate_err = c->gate_err_dev;
-      if (c->grad.buf.layout == GradLayout::Sharded) { fa.gate_n = 1; fa.gate_kt[0] = 0; fa.gate_kt[1] = c->Fp / BK; }        // the sharded update publishes once
-      else { fa.gate_n = chunk_plan(c); for (int i = 0; i <= fa.gate_n; ++i) fa.gate_kt[i] = c->chunk_kt[i]; }
-      // whatever follows the forward GEMM on this stream follows every PUBLISHED store of the update; its plain stores (W, the history) only
-      // behind the event: vv_comm_join for whoever reads those
-      upd_gated(c->upd_sync);
-    } else if ((rc = comm_join(c))) return rc;
-  }
-  PROFILED(c, "fwd_gemm", launch_fwd_gemm(c->prec, fa, s));
+}
 
-  const int64_t count = (int64_t)B * Nn;
-  const int64_t gcount = cfg->global_count > 0 ? cfg->global_count : count;
-  // half-precision gradient scale: a power of two near the loss count keeps dY*sg around 1
-  int e; frexpf((float)gcount, &e);
-  // The segment-wise backward then settles the scale on the device, from a bound on the step's own gradients, before it
-  // rounds anything (GuardArgs::proactive).  On the other paths the host's scale follows the data: every step reports its
-  // largest |dY| (k_reduce, a host-visible ring); when the max of step seq - 4 -- a FIXED lag, so that the scale sequence
-  // does not depend on host timing and runs stay bit-reproducible -- lies outside [2^4, 2^13) in the current scaled units,
-  // the scale moves so that it lies in [2^9, 2^10).  That only keeps the guard's repeats rare: a value past f16's range never
-  // reaches the weight-gradient GEMM either way (GradGuard).
+// Data-parallel overlap: the previous step's update is still arriving on the communication stream, F-chunk by
+// F-chunk.  The forward GEMM starts anyway and waits per chunk inside the kernel -- provided its persistent
+// workgroups leave compute units free for the update's own kernels (all-reduce, SGD: they must be able to run
+// BESIDE the waiting GEMM, or nothing would ever release it); otherwise the stream joins here, as without overlap.
+static int fwd_gate_or_join(vv_ctx* c, FwdArgs& fa, bool dd) {
+  const long tiles = fwd_gemm_plan(c->R, dd ? fa.R_hint : 0, c->D, nullptr);
+  const bool no_gate = !c->comm_gate;
+  if (!no_gate && !ablate_on() && fwd_gemm_can_gate(fa) && (!dd || fa.R_hint > 0) && tiles <= c->n_cu - 16) {
+    fa.gate = c->w_gate; fa.gate_seq = c->upd_seq; fa.gate_err = c->gate_err_dev;
+    if (c->grad.buf.layout == GradLayout::Sharded) { fa.gate_n = 1; fa.gate_kt[0] = 0; fa.gate_kt[1] = c->Fp / BK; }        // the sharded update publishes once
+    else { fa.gate_n = chunk_plan(c); for (int i = 0; i <= fa.gate_n; ++i) fa.gate_kt[i] = c->chunk_kt[i]; }
+    // whatever follows the forward GEMM on this stream follows every PUBLISHED store of the update; its plain stores (W, the history) only
+    // behind the event: vv_comm_join for whoever reads those
+    upd_gated(c->upd_sync);
+    return VV_OK;
+  }
+  return comm_join(c);
+}
+
+// The half-precision gradient scale's adjustment c->sg_adj, for a step whose loss count has exponent e.  The segment-wise backward settles the scale on the device, from a bound on the step's own gradients, before it
+// rounds anything (GuardArgs::proactive).  On the other paths the host's scale follows the data: every step reports its
+// largest |dY| (k_reduce, a host-visible ring); when the max of step seq - 4 -- a FIXED lag, so that the scale sequence
+// does not depend on host timing and runs stay bit-reproducible -- lies outside [2^4, 2^13) in the current scaled units,
+// the scale moves so that it lies in [2^9, 2^10).  That only keeps the guard's repeats rare: a value past f16's range never
+// reaches the weight-gradient GEMM either way (GradGuard).
+static int grad_scale_steer(vv_ctx* c, int32_t seq, int e, hipStream_t s) {
   if (c->prec == VV_PREC_F16) {
     if (c->gg_seq0 == 0) c->gg_seq0 = seq;
     if (seq - c->gg_seq0 >= kLag) {
@@ -1807,32 +1814,78 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
     }
     c->sg_adj = std::max(-100 - e, std::min(100 - e, c->sg_adj));
   }
+  return VV_OK;
+}
+
+static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on_device, int64_t row_limit, int32_t seq = 0) {
+  // ---- guards
+  { const int rcg = upd_pending_guard(c, "vv_forward_backward"); if (rcg) return rcg; }
+  const bool upd_hint = c && c->upd_hint;       // (consumed by this call whatever path it takes)
+  if (c) c->upd_hint = false;
+  if (c && c->ema_in_use) return fail(VV_ERR_STATE, "vv_forward_backward: %s", kEmaInUse);
+  int rc = check_cfg(c, cfg);
+  if (rc) return rc;
+  if (!idx) return fail(VV_ERR_ARG, "vv_forward_backward: idx is NULL");
+  VV_ENTER(c);
+  // (an overlapped update of the previous step may still be arriving: see the forward GEMM below)
+  if (c->upd_sync == UpdSync::InFlight && (cfg->B != c->B || cfg->C != c->C || cfg->Nn != c->Nn || !c->H) && (rc = comm_join(c))) return rc;
+  if ((rc = ensure_batch(c, cfg->B, cfg->C, cfg->Nn))) return rc;
+  const int B = c->B, D = c->D;
+  hipStream_t s = c->stream;
+
+  // ---- stage inputs: the indices (every step has a sequence number; its forward GEMM stamps it into host-visible memory), the cfg's host arrays
+  const int32_t* didx = idx;
+  if (!idx_on_device) {
+    int sl = 0;
+    if ((rc = stage_acquire(c, (size_t)c->R * 4, &sl))) return rc;
+    if ((rc = stage_indices(c, idx, row_limit, c->stage_host[sl]))) return rc;
+    if (!seq) seq = ++c->step_seq;
+    c->stage_seq[sl] = seq;
+    didx = c->stage_dev[sl];
+  }
+  if (!seq) seq = ++c->step_seq;
+  if ((rc = stage_cfg_inputs(c, cfg))) return rc;
+
+  // ---- plan (behind the f16 rows' lagged report: it may switch this very step to fp32 rows)
+  h16_guard_read(c, seq, s);
+  const PassPlan p = plan_pass(c, cfg, false);
+  const DropSpec dsp = make_drop_spec(c, cfg);
+  record_plan(c, p, dsp); c->last_fwd_only = false;
+  const bool h16_count = c->last_h16_counted = p.h16 && c->h16_guard >= 1;
+  if (h16_count) c->h16_counted[seq & (GMAX_ENTRIES - 1)] = seq;
+
+  // ---- group: into the next of the rotating sets, stamped with this step's number; the host watches the event for a moment
+  if (!p.dd) launch_map_rows(didx, c->rows, c->R, c->Rp, (int32_t)c->n_rows, (int32_t)row_limit, s);
+  if (p.dd) {
+    int si = 0;
+    if ((rc = dd_issue(c, didx, idx_on_device, row_limit, seq, &si))) return rc;
+    vv_ctx::DdSet& set = c->dd_set[si];
+    set.used_seq = seq;
+    bind_dd_set(c, set);
+    if (c->dd_async && (rc = dd_wait(c, set, s))) return rc;
+  }
+
+  // ---- forward: the training parameters, the training batches' distinct-row hint, the sequence stamp; gated on an overlapped update or joined
+  FwdArgs fa = fwd_args(c, cfg, p, ParamView{c->Wh, c->b, c->scales}, *(volatile int32_t*)c->U_host);
+  fa.seq_host = c->seq_host_dev; fa.seq = seq;
+  if (c->upd_sync == UpdSync::InFlight && (rc = fwd_gate_or_join(c, fa, p.dd))) return rc;
+  PROFILED(c, "fwd_gemm", launch_fwd_gemm(c->prec, fa, s));
+
+  // ---- scale.  half-precision gradient scale: a power of two near the loss count keeps dY*sg around 1
+  const int64_t count = (int64_t)B * c->Nn;
+  int e; frexpf((float)global_count(c, cfg), &e);
+  if ((rc = grad_scale_steer(c, seq, e, s))) return rc;
   c->sg = c->prec == VV_PREC_F16 ? ldexpf(1.f, e + c->sg_adj) : 1.f;
   c->last_loss_weight = cfg->loss_weight;
 
-  ScoreArgs sa;
-  sa.H = c->H; sa.dYh = c->dYh; sa.dbp = c->dbp; sa.loss_part = c->loss_part; sa.viol_part = c->viol_part;
-  sa.s_true = c->s_true; sa.s_bogus = c->s_bogus; sa.coeff = c->coeff;
-  sa.B = B; sa.C = C; sa.Nn = Nn; sa.D = D; sa.Dp = c->Dp;
-  sa.margin = cfg->margin; sa.norm = cfg->norm;
-  sa.grad_scale = cfg->loss_weight / (float)gcount;
-  sa.drop_scale = cfg->dropout_ratio > 0.f ? 1.f / (1.f - cfg->dropout_ratio) : 1.f;
-  sa.sg = c->sg;
-  sa.map = dd ? c->dd_map : nullptr; sa.seg_start = dd ? c->dd_seg : nullptr; sa.ord = dd ? c->dd_ord : nullptr;
-  sa.item_w = cfg->item_weight ? c->item_w : nullptr;
+  // ---- score: the gradient destinations, the scale, the stamp that releases the host to queue a later step's grouping
+  ScoreArgs sa = score_args(c, cfg, p, dsp);
+  sa.dYh = c->dYh; sa.dbp = c->dbp; sa.loss_part = c->loss_part; sa.viol_part = c->viol_part; sa.sg = c->sg;
   sa.gate_host = c->seq_host_dev + 1; sa.gate_seq = seq;
-  if (dd && drop_on) sa.drop = dsp;
+  sa.v16 = p.v16 ? 1 : 0;
+  c->last_seg_bwd = p.seg; c->last_score = sa;
 
-  // de-duplicated batches of the supported shape: the backward stays factored per instance and is summed per distinct
-  // row (k_score_fwd + k_seg_bwd); otherwise per-instance 16-bit gradient rows (+ k_segsum when de-duplicated)
-  const bool seg = dd && c->seg_bwd && score_fwd_supported(sa);
-  if (seg != seg_path) return fail(VV_ERR_STATE, "internal error: the forward pass was planned for %s rows of ip2, the score kernels expect the other form", h16 ? "f16" : "fp32");
-  sa.h16 = h16 ? 1 : 0;
-  // the per-item vectors as f16: the one-sweep kernel's D = 1024 form only (840 k gathers of a 4 KB row per step at configs[4]'s per-GPU shape;
-  // at D = 512 the 2 MB matrix lives in L2 and 16-bit vectors measured net zero, profiles/r04_h16_intermediate.txt)
-  const bool v16 = h16 && c->v16 && D == 1024 && !drop_on;
-  sa.v16 = v16 ? 1 : 0;
-  c->last_seg_bwd = seg; c->last_score = sa;
+  // ---- guard rounds: the score kernels and the backward to per-row gradients
   // f16 gradient-scale guard (vv_internal.h: GradGuard): the kernels that round gradients to 16 bits are launched once as
   // usual (round 0) and once more per guard round as conditional repeats -- near-empty launches unless the round before
   // reported a value past f16's range.  Rounds: 1 where one kernel rounds (per-instance rows, or the segment sums); 2 for
@@ -1843,14 +1896,14 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
   // (the segment-wise backward needs no repeat at all: its score kernel bounds every instance's gradient and k_seg_bwd
   // settles the scale before it rounds anything -- GuardArgs::proactive)
   const bool proactive_on = c->guard_proactive;   // (lab) false: the repeat form on this path too (A/B)
-  const bool proactive = seg && proactive_on;
-  const int n_rounds = c->prec != VV_PREC_F16 ? 0 : (proactive ? 0 : (dd && !seg ? 2 : 1));
+  const bool proactive = p.seg && proactive_on;
+  const int n_rounds = c->prec != VV_PREC_F16 ? 0 : (proactive ? 0 : (p.dd && !p.seg ? 2 : 1));
   c->gg_last_rounds = n_rounds;
-  gd.n_of[0] = seg ? 0 : B;
-  gd.n_of[1] = seg ? SEGB_BLOCKS : (dd ? (c->Rp + 3) / 4 : 0);
+  gd.n_of[0] = p.seg ? 0 : B;
+  gd.n_of[1] = p.seg ? SEGB_BLOCKS : (p.dd ? (c->Rp + 3) / 4 : 0);
   SegBwdArgs ba;
   SegsumArgs ga;
-  if (seg) {
+  if (p.seg) {
     sa.V = c->segV; sa.rec = c->seg_rec;
 #ifdef VV_LAB
     if (const char* v = lab_env("VV_LAB_SCORE_HACK")) sa.lab_hack = atoi(v);
@@ -1863,43 +1916,45 @@ static int fb_impl(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int id
 #endif
     if (gd.gg && proactive) { sa.bound_out = c->gg_bound; sa.bound_seq = seq; }
     ba.H = c->H; ba.V = c->segV; ba.rec = c->seg_rec; ba.seg_start = c->dd_seg; ba.info = c->dd_info; ba.dYu = c->dYu;
-    ba.dbp = c->seg_dbp; ba.Rp = c->Rp; ba.D = D; ba.Dp = c->Dp; ba.inv_sg = 1.f / c->sg; ba.h16 = h16 ? 1 : 0; ba.v16 = v16 ? 1 : 0;
+    ba.dbp = c->seg_dbp; ba.Rp = c->Rp; ba.D = D; ba.Dp = c->Dp; ba.inv_sg = 1.f / c->sg; ba.h16 = p.h16 ? 1 : 0; ba.v16 = p.v16 ? 1 : 0;
     if (h16_count) ba.h16_cnt = c->h16_cnt;
-    if (drop_on) ba.drop = dsp;
-  } else if (dd) {
+    if (p.drop_on) ba.drop = dsp;
+  } else if (p.dd) {
     ga.dYh = c->dYh; ga.seg_start = c->dd_seg; ga.info = c->dd_info; ga.dYu = c->dYu; ga.Rp = c->Rp; ga.Dp = c->Dp;
   }
   for (int round = 0; round <= n_rounds; ++round) {
     gd.round = round; gd.final_round = round == n_rounds;
-    if (seg) {
+    if (p.seg) {
       if (round == 0) PROFILED(c, "score_loss", launch_score_fwd(sa, s));
       ba.guard = gd; ba.guard.producer = 1; ba.guard.last = 1;
       if (gd.gg && proactive) { ba.guard.proactive = 1; ba.guard.bound = c->gg_bound; ba.guard.cnt_max = c->dd_info + 1; }
       if (round == 0) PROFILED(c, "segsum", launch_seg_bwd(c->prec, ba, s));
       else PROFILED(c, "guard", launch_seg_bwd(c->prec, ba, s));
     } else {
-      sa.guard = gd; sa.guard.producer = 0; sa.guard.last = dd ? 0 : 1;
+      sa.guard = gd; sa.guard.producer = 0; sa.guard.last = p.dd ? 0 : 1;
       if (round == 0) PROFILED(c, "score_loss", launch_score_loss(c->prec, sa, s));
-      else if (!dd) PROFILED(c, "guard", launch_score_loss(c->prec, sa, s));
+      else if (!p.dd) PROFILED(c, "guard", launch_score_loss(c->prec, sa, s));
       else launch_score_loss(c->prec, sa, s);
-      if (dd) {
+      if (p.dd) {
         ga.guard = gd; ga.guard.producer = 1; ga.guard.last = 1;
         if (round == 0) PROFILED(c, "segsum", launch_segsum(c->prec, ga, s));
         else PROFILED(c, "guard", launch_segsum(c->prec, ga, s));
       }
     }
   }
+
+  // ---- weight gradient: its arguments and the reduction's, then wherever the gradient goes
   WgradArgs wa;
-  wa.dYh = dd ? c->dYu : c->dYh; wa.table = c->table; wa.rows = dd ? c->dd_uniq : c->rows; wa.slabs = c->slabs;
+  wa.dYh = p.dd ? c->dYu : c->dYh; wa.table = c->table; wa.rows = p.dd ? c->dd_uniq : c->rows; wa.slabs = c->slabs;
   wa.Rp = c->Rp; wa.Dp = c->Dp; wa.Fp = c->Fp; wa.S = c->S; wa.ksteps_per_split = c->kps;
-  wa.n_dev = dd ? c->dd_info : nullptr; wa.zero_row = (int32_t)c->n_rows;
+  wa.n_dev = p.dd ? c->dd_info : nullptr; wa.zero_row = (int32_t)c->n_rows;
   {
     const int64_t t_rows = c->n_rows + 1 + c->patch_cap;      // every row a K-tile can name: the table, its zero row, the scratch rows behind it
     wa.lean = c->ko.wgrad_lean && t_rows < (1ll << 24) && (int64_t)c->Fp * 2 < (1ll << 24) && t_rows * c->Fp * 2 + 8192 < (1ll << 32);
   }
   ReduceArgs ra;
-  ra.slabs = c->slabs; ra.S = c->S; ra.Dp = c->Dp; ra.Fp = c->Fp; ra.dbp = seg ? c->seg_dbp : c->dbp; ra.B = B;
-  ra.db_rows = seg ? SEGB_BLOCKS : 0;
+  ra.slabs = c->slabs; ra.S = c->S; ra.Dp = c->Dp; ra.Fp = c->Fp; ra.dbp = p.seg ? c->seg_dbp : c->dbp; ra.B = B;
+  ra.db_rows = p.seg ? SEGB_BLOCKS : 0;
   ra.scales = c->scales; ra.sg = c->sg; ra.grads = c->grads; ra.D = D; ra.F = c->F;
   if (gd.gg) {
     ra.gg = c->gg; ra.gmax_slots = c->gg_slots; ra.gmax_n0 = gd.n_of[0]; ra.gmax_n1 = gd.n_of[1]; ra.gmax_stride = c->gg_nslot;
@@ -2038,8 +2093,8 @@ static int eval_stage_acquire(vv_ctx* c, size_t bytes, int* slot) {
 }
 
 // Net::Forward / Net::ForwardPrefilled under Caffe::set_phase(Caffe::TEST) (include/caffe/net.hpp, src/caffe/net.cpp), one of the test_iter
-// passes of Solver::Test (solver.cpp:251-317): the forward half of fb_impl -- the same grouping kernels, the same forward GEMM launch, the
-// same score form -- with the forward-only instantiations of the score kernels and a loss reduction of its own.  What a training step
+// passes of Solver::Test (solver.cpp:251-317): the stages of fb_impl's forward half under the same plan -- the same grouping kernels, the same
+// forward GEMM launch, the same score form -- with the forward-only instantiations of the score kernels and a loss reduction of its own.  What a training step
 // owns is read, never written: the gradient's place (c->grad, the slabs, dbp, the gradient buffer, the bank), the step's pending loss and
 // violation partials, the sequence numbers with the two report rings behind them (gradient scale, f16 rows), c->sg, Adam's t, the
 // dropout counter c->iter, the clipping and accumulation records, the rotating grouping sets and their distinct-row hint.
@@ -2063,105 +2118,51 @@ int vv_forward(vv_ctx* c, const vv_step_cfg* cfg, const int32_t* idx, int idx_on
   // does (the next training forward GEMM then finds the update joined and runs ungated: the same values)
   if ((rc = comm_join(c))) return rc;
   if ((rc = ensure_batch(c, cfg->B, cfg->C, cfg->Nn))) return rc;
-  const int B = c->B, C = c->C, Nn = c->Nn, CN = C + Nn, D = c->D;
+  const int B = c->B;
   hipStream_t s = c->stream;
 
+  // ---- stage inputs: the indices into an evaluation slot (released by this pass's end event), the cfg's host arrays
   const int32_t* didx = idx;
   int stage_slot = -1;
   if (!idx_on_device) {
     if ((rc = eval_stage_acquire(c, (size_t)c->R * 4, &stage_slot))) return rc;
-    int32_t* dst = c->eval_stage_host[stage_slot];
-    int bad = -1;
-    for (int i = 0; i < c->R; ++i) { const int32_t v = idx[i]; dst[i] = v; if (v < -1 || v >= c->n_rows) bad = i; }
-    if (bad >= 0) return fail(VV_ERR_ARG, "idx[%d] = %d out of range [-1, %lld)", bad, idx[bad], (long long)c->n_rows);
+    if ((rc = stage_indices(c, idx, c->n_rows, c->eval_stage_host[stage_slot]))) return rc;
     didx = c->eval_stage_dev[stage_slot];
   }
-  // eltwise coefficients, item weights, an explicit mask: as fb_impl (the device copies are the step's own, read by kernels queued in front)
-  std::vector<float> coeff(C - 1);
-  for (int j = 0; j < C - 1; ++j) coeff[j] = cfg->ctx_coeff ? cfg->ctx_coeff[j] : 1.0f / (C - 1);
-  if (coeff != c->coeff_host) {
-    HIPCHK(hipMemcpyAsync(c->coeff, coeff.data(), coeff.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    c->coeff_host = coeff;
-  }
-  if (cfg->item_weight) {
-    for (int i = 0; i < B; ++i)
-      if (!(cfg->item_weight[i] >= 0.f)) return fail(VV_ERR_ARG, "item_weight[%d] = %g: All weights should be greater than 0 (max_margin_loss_layer.cpp:34)", i, (double)cfg->item_weight[i]);
-    HIPCHK(hipMemcpyAsync(c->item_w, cfg->item_weight, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  }
-  if (cfg->dropout_ratio > 0.f && cfg->dropout_mask) {
-    const size_t nb = (size_t)c->R * D;
-    if (nb > c->mask_bytes) { dfree(c->mask); c->mask = nullptr; HIPCHK(hipMalloc(&c->mask, nb)); c->mask_bytes = nb; }
-    HIPCHK(hipMemcpyAsync(c->mask, cfg->dropout_mask, nb, hipMemcpyHostToDevice, s));
-  }
+  if ((rc = stage_cfg_inputs(c, cfg))) return rc;
 
-  // the execution the training pass would choose for this cfg (fb_impl): de-duplicated or dense, where dropout rides, f16 or fp32 rows
-  const bool drop_on = cfg->dropout_ratio > 0.f;
-  const bool drop_dd = drop_on && c->drop_dedup && c->seg_bwd && score_fwd_dropout_supported(c->drop_dedup, D, C, Nn);
-  const bool dd = c->dedup && (!drop_on || drop_dd) && !ablate_on();
-  DropSpec dsp;
-  if (drop_on) {
-    dsp.mode = cfg->dropout_mask ? 2 : 1;
-    dsp.thr = (uint32_t)(cfg->dropout_ratio * 65536.f + 0.5f);
-    dsp.s32 = (uint32_t)(mix64(cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter, 0x5eedull) >> 32);      // (the counter is read, not advanced)
-    dsp.scale = 1.f / (1.f - cfg->dropout_ratio);
-    dsp.mask = cfg->dropout_mask ? c->mask : nullptr;
-    dsp.B = B; dsp.CN = CN; dsp.D = D;
-  }
-  c->last_drop = (dd && drop_on) ? dsp : DropSpec();
-  c->last_dedup = dd;
-  c->last_fwd_only = true;
-  if (!dd) launch_map_rows(didx, c->rows, c->R, c->Rp, (int32_t)c->n_rows, (int32_t)c->n_rows, s);
-  if (dd) {
+  // ---- plan: the execution the training pass takes for this cfg.  The f16 rows' report ring is neither read nor fed: a pass counts nothing.
+  const PassPlan p = plan_pass(c, cfg, true);
+  const DropSpec dsp = make_drop_spec(c, cfg);
+  record_plan(c, p, dsp); c->last_fwd_only = true;
+
+  // ---- group: into the set that never rotates, with no sequence number; the step's stream always waits for it
+  if (!p.dd) launch_map_rows(didx, c->rows, c->R, c->Rp, (int32_t)c->n_rows, (int32_t)c->n_rows, s);
+  if (p.dd) {
     int si = 0;
     if ((rc = dd_issue(c, didx, idx_on_device, c->n_rows, 0, &si, true))) return rc;
-    vv_ctx::DdSet& set = c->dd_set[si];
-    c->dd_rows = set.rows; c->dd_slot_of = set.slot_of; c->dd_uniq = set.uniq; c->dd_map = set.map; c->dd_ord = set.ord;
-    c->dd_cnt = set.cnt; c->dd_seg = set.seg; c->dd_info = set.info;
-    if (c->dd_async) HIPCHK(hipStreamWaitEvent(s, set.done, 0));
+    bind_dd_set(c, c->dd_set[si]);
+    if (c->dd_async) HIPCHK(hipStreamWaitEvent(s, c->dd_set[si].done, 0));
   }
 
-  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
+  // ---- forward: the training parameters or under vv_ema_use(1) the average's, the forward-only passes' own distinct-row hint, and no
+  // sequence stamp (seq_host stays null -- the stamps release the TRAINING steps' staging slots and grouping sets)
+  ParamView pv;
   if ((rc = param_view(c, &pv))) return rc;
-  FwdArgs fa;
-  fa.table = c->table; fa.rows = dd ? c->dd_uniq : c->rows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
-  fa.H = c->H; fa.R = c->R; fa.D = D; fa.Fp = c->Fp; fa.relu = 1; fa.zero_row = (int32_t)c->n_rows;
-  fa.n_dev = dd ? c->dd_info : nullptr;
-  fa.R_hint = dd ? *(volatile int32_t*)(c->U_host + 2) : 0;
-  // (no sequence stamp: seq_host stays null -- the stamps release the TRAINING steps' staging slots and grouping sets)
-  const bool seg_path = dd && c->seg_bwd && (D == 512 || D == 1024);
-  const bool h16 = c->h16 && !c->h16_fallback && seg_path && !ablate_on();     // (the f16 rows' report ring is neither read nor fed: a pass counts nothing)
-  fa.h16 = h16 ? 1 : 0;
-  c->last_h16 = h16;
-  fa.drop_ratio = (dd && drop_on) ? 0.f : cfg->dropout_ratio;
-  fa.mask = (!(dd && drop_on) && cfg->dropout_ratio > 0.f && cfg->dropout_mask) ? c->mask : nullptr;
-  fa.drop_seed = cfg->dropout_seed * 0x9E3779B97F4A7C15ull + c->iter;
-  fa.B = B; fa.CN = CN;
+  const FwdArgs fa = fwd_args(c, cfg, p, pv, *(volatile int32_t*)(c->U_host + 2));
   PROFILED(c, "eval_fwd_gemm", launch_fwd_gemm(c->prec, fa, s));
 
-  const int64_t count = (int64_t)B * Nn;
-  const int64_t gcount = cfg->global_count > 0 ? cfg->global_count : count;
-  ScoreArgs sa;
-  sa.H = c->H; sa.dYh = nullptr; sa.dbp = nullptr; sa.loss_part = c->eval_loss_part; sa.viol_part = c->eval_viol_part;
-  sa.s_true = c->s_true; sa.s_bogus = c->s_bogus; sa.coeff = c->coeff;
-  sa.B = B; sa.C = C; sa.Nn = Nn; sa.D = D; sa.Dp = c->Dp;
-  sa.margin = cfg->margin; sa.norm = cfg->norm;
-  sa.grad_scale = cfg->loss_weight / (float)gcount;
-  sa.drop_scale = cfg->dropout_ratio > 0.f ? 1.f / (1.f - cfg->dropout_ratio) : 1.f;
-  sa.sg = 1.f;
-  sa.map = dd ? c->dd_map : nullptr; sa.seg_start = dd ? c->dd_seg : nullptr; sa.ord = dd ? c->dd_ord : nullptr;
-  sa.item_w = cfg->item_weight ? c->item_w : nullptr;
-  if (dd && drop_on) sa.drop = dsp;
-  sa.h16 = h16 ? 1 : 0;
+  // ---- score: no gradient, scale 1, partials of its own, the forward-only instantiations
+  ScoreArgs sa = score_args(c, cfg, p, dsp);
+  sa.dYh = nullptr; sa.dbp = nullptr; sa.loss_part = c->eval_loss_part; sa.viol_part = c->eval_viol_part; sa.sg = 1.f;
   sa.fwd_only = 1;
-  const bool seg = dd && c->seg_bwd && score_fwd_supported(sa);
-  if (seg != seg_path) return fail(VV_ERR_STATE, "internal error: the forward pass was planned for %s rows of ip2, the score kernels expect the other form", h16 ? "f16" : "fp32");
-  if (seg) PROFILED(c, "eval_score", launch_score_fwd(sa, s));
+  if (p.seg) PROFILED(c, "eval_score", launch_score_fwd(sa, s));
   else PROFILED(c, "eval_score", launch_score_loss(c->prec, sa, s));
   // the loss as the training path's loss workgroup folds it (ReduceArgs::loss_scale: this batch's own B Nn), and the record
-  PROFILED(c, "eval_loss", launch_eval_loss(c->eval_loss_part, c->eval_viol_part, B, cfg->loss_weight / (float)count, count, c->eval_rec, s));
+  const int64_t terms = (int64_t)B * c->Nn;
+  PROFILED(c, "eval_loss", launch_eval_loss(c->eval_loss_part, c->eval_viol_part, B, cfg->loss_weight / (float)terms, terms, c->eval_rec, s));
   HIPCHK(hipGetLastError());
-  if (dd && c->dd_async) { HIPCHK(hipEventRecord(c->ev_eval, s)); c->eval_set_used = true; }
+  if (p.dd && c->dd_async) { HIPCHK(hipEventRecord(c->ev_eval, s)); c->eval_set_used = true; }
   if (stage_slot >= 0) { HIPCHK(hipEventRecord(c->eval_stage_done[stage_slot], s)); c->eval_stage_busy[stage_slot] = true; }
   return VV_OK;
 }
@@ -2726,8 +2727,22 @@ int vv_dedup_groups_get(vv_ctx* c, int32_t* rows, int32_t* uniq_rows, int32_t* m
 // ------------------------------------------------------------------------------- embed --------
 // The two embedding forms with the result left on the device (dout: fp32 [n][D], the caller's): vv_embed / vv_embed_mean
 // download it, vv_gallery_from_table keeps it.  `who` names the entry point in messages.
+// the common end of the two forms: the plain projection of n table rows (drows: device, padded to R_ALIGN) into dout, normalised on request; synchronises
+static int embed_project(vv_ctx* c, const int32_t* drows, int64_t n, int relu, int l2norm, float* dout) {
+  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
+  { const int rcv = param_view(c, &pv); if (rcv) return rcv; }
+  FwdArgs fa;
+  fa.table = c->table; fa.rows = drows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
+  fa.H = dout; fa.R = (int)n; fa.D = c->D; fa.Fp = c->Fp; fa.relu = relu ? 1 : 0; fa.zero_row = (int32_t)c->n_rows;
+  fa.drop_ratio = 0.f; fa.mask = nullptr; fa.drop_seed = 0; fa.B = 1; fa.CN = 1;
+  launch_fwd_gemm(c->prec, fa, c->stream);
+  if (l2norm) launch_row_normalize(dout, (int)n, c->D, c->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return VV_OK;
+}
+
 static int embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int relu, int l2norm, float* dout) {
-  const int D = c->D;
   const int Rp = (int)round_up(n, R_ALIGN);
   std::vector<int32_t> h(Rp, (int32_t)c->n_rows);
   for (int64_t i = 0; i < n; ++i) {
@@ -2738,17 +2753,7 @@ static int embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, in
   DevTmp<int32_t> drows;
   HIPCHK(drows.alloc((size_t)Rp));
   HIPCHK(hipMemcpyAsync(drows, h.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
-  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
-  { const int rcv = param_view(c, &pv); if (rcv) return rcv; }
-  FwdArgs fa;
-  fa.table = c->table; fa.rows = drows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
-  fa.H = dout; fa.R = (int)n; fa.D = D; fa.Fp = c->Fp; fa.relu = relu ? 1 : 0; fa.zero_row = (int32_t)c->n_rows;
-  fa.drop_ratio = 0.f; fa.mask = nullptr; fa.drop_seed = 0; fa.B = 1; fa.CN = 1;
-  launch_fwd_gemm(c->prec, fa, c->stream);
-  if (l2norm) launch_row_normalize(dout, (int)n, D, c->stream);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return VV_OK;
+  return embed_project(c, drows, n, relu, l2norm, dout);
 }
 
 static int embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int32_t k, const float* coeff,
@@ -2759,7 +2764,6 @@ static int embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, in
   if (rc) return rc;
   std::vector<float> hc(k);
   for (int j = 0; j < k; ++j) hc[j] = coeff ? coeff[j] : 1.0f / k;
-  const int D = c->D;
   const int Rp = (int)round_up(n, R_ALIGN);
   std::vector<int32_t> h(Rp, (int32_t)c->n_rows);
   for (int64_t i = 0; i < n; ++i) h[i] = (int32_t)(c->n_rows + 1 + i);
@@ -2770,17 +2774,7 @@ static int embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, in
   HIPCHK(hipMemcpyAsync(drows, h.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dcoeff, hc.data(), (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
   launch_mean_rows(c->prec, c->table, drows_in, n, k, dcoeff, c->n_rows + 1, c->Fp, c->stream);
-  ParamView pv;                                // (the training parameters, or under vv_ema_use(1) the average's)
-  { const int rcv = param_view(c, &pv); if (rcv) return rcv; }
-  FwdArgs fa;
-  fa.table = c->table; fa.rows = drows; fa.Wh = pv.Wh; fa.bias = pv.b; fa.scales = pv.scales;
-  fa.H = dout; fa.R = (int)n; fa.D = D; fa.Fp = c->Fp; fa.relu = relu ? 1 : 0; fa.zero_row = (int32_t)c->n_rows;
-  fa.drop_ratio = 0.f; fa.mask = nullptr; fa.drop_seed = 0; fa.B = 1; fa.CN = 1;
-  launch_fwd_gemm(c->prec, fa, c->stream);
-  if (l2norm) launch_row_normalize(dout, (int)n, D, c->stream);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return VV_OK;
+  return embed_project(c, drows, n, relu, l2norm, dout);
 }
 
 int vv_embed(vv_ctx* c, const int32_t* rows, int64_t n, int relu, int l2norm, float* out) {

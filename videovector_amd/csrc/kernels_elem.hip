@@ -1084,17 +1084,7 @@ __global__ __launch_bounds__(64 * NW, DV == 4 ? 4 : 1) void k_score_stream(Score
   }
 }
 
-// the segment-wise pair: k_seg_bwd holds a row of D = 512 or 1024 columns; the forward is the register-resident
-// k_score_fwd where an item fits (D = 512, up to 56 target / negative rows, 6 context rows), else the streaming kernel
-bool score_fwd_supported(const ScoreArgs& a) { return a.D == 512 || a.D == 1024; }
-// ... with dropout (ScoreArgs::drop), by the value of option "drop_dedup": every kernel of the pair carries the per-instance masks (k_score_fwd,
-// k_score_stream and k_seg_bwd, D = 512 and 1024); value 1, the default, keeps dropout steps de-duplicated on the shapes of the register-resident
-// kernel only, value 2 on every shape of the pair, value 0 on none.  The DROP forms read fp32 per-item vectors: dropout steps run with v16 off.
-bool score_fwd_dropout_supported(int drop_dedup, int D, int C, int Nn) {
-  if (drop_dedup == 1) return D == 512 && C - 1 <= 6 && 1 + Nn <= 56;
-  return drop_dedup == 2 && (D == 512 || D == 1024);
-}
-
+// (the shapes the segment-wise pair is built for, without and with dropout: score_fwd_supported / score_fwd_dropout_supported, vv_pass_plan.h)
 void launch_score_fwd(const ScoreArgs& a_in, hipStream_t s) {
   ScoreArgs a = a_in;
   a.items_rr = ko().score_rr;

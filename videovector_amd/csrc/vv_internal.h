@@ -5,6 +5,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "vv_pass_plan.h"      // score_fwd_supported / score_fwd_dropout_supported: the shapes the segment-wise pair is built for
+
 struct vv_gallery;
 
 namespace vv {
@@ -588,8 +590,6 @@ void launch_dedup(const DedupArgs& a, hipStream_t s);
 void launch_dedup_groups(const DedupArgs& a, hipStream_t s);
 void launch_dedup_pos(const DedupArgs& a, hipStream_t s);   // pos[] for the debug accessors only
 void launch_segsum(int prec, const SegsumArgs& a, hipStream_t s);
-bool score_fwd_dropout_supported(int drop_dedup, int D, int C, int Nn);   // drop_dedup: the option's value (0, 1, 2)
-bool score_fwd_supported(const ScoreArgs& a);               // shapes the segment-wise pair is built for
 void launch_score_fwd(const ScoreArgs& a, hipStream_t s);   // forward + factored backward records (dedup mode)
 void launch_seg_bwd(int prec, const SegBwdArgs& a, hipStream_t s);
 // (h16: src holds f16 rows -- FwdArgs::h16; map == nullptr: row r is its own source)
