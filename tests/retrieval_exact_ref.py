@@ -8,8 +8,8 @@ import numpy as np
 import class_stats_ref
 import nearest_ref
 
-SEG = 16384           # items per workgroup of the row kernels below 64 * 16384 items (api.hip, gallery_init)
-CSEG = 65536          # items per workgroup of k_class_count (api.hip, vv_gallery_class_stats)
+SEG = 16384           # items per workgroup of the row kernels below 64 * 16384 items (retrieval.hip, gallery_init)
+CSEG = 65536          # items per workgroup of k_class_count (retrieval.hip, vv_gallery_class_stats)
 CHUNK = 2048          # positives of one pass ("positive_chunk")
 
 

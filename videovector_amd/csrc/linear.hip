@@ -13,7 +13,6 @@ using namespace vv;
 
 #define NEED(c) do { if (!(c)) return vv_fail(VV_ERR_ARG, "%s: ctx is NULL", __func__); HIPCHK(hipSetDevice((c)->device)); vv::g_ko = &(c)->ko; } while (0)
 
-static constexpr size_t LIN_SCRATCH_MAX = (size_t)1 << 30;       // logits + dz of one row block: the gallery path's "scratch_limit_bytes"
 static constexpr int LIN_MAX_CLASSES = 4096;
 
 struct vv_linear {
@@ -30,8 +29,6 @@ struct vv_linear {
 };
 
 namespace {
-
-void dfree(void* p) { if (p) (void)hipFree(p); }
 
 inline bool aligned16(const void* p, int64_t ld) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0; }
 
@@ -63,12 +60,12 @@ int ensure_slabs(vv_ctx* c, vv_linear* l, int S) {
   return VV_OK;
 }
 
-// rows of one row block of a batch of `count` rows: the split plan's, and logits + dz within the scratch limit
+// rows of one row block of a batch of `count` rows: the split plan's, and logits + dz within the gallery path's scratch limit
 struct BatchPlan { LinPlan p; int64_t block_rows; int blocks; };
 BatchPlan batch_plan(const vv_ctx* c, const vv_linear* l, int64_t count) {
   BatchPlan bp;
   bp.p = lin_plan(count, l->Cp, l->Dp, c->lin_split_rows);
-  const int64_t fit = std::max<int64_t>(1, (int64_t)(LIN_SCRATCH_MAX / ((size_t)2 * l->Cp * 4)));
+  const int64_t fit = std::max<int64_t>(1, (int64_t)(GALLERY_SCRATCH_MAX / ((size_t)2 * l->Cp * 4)));
   bp.block_rows = std::min(bp.p.block_rows, fit / bp.p.split_rows * bp.p.split_rows);      // (whole splits)
   if (bp.block_rows < 1) bp.block_rows = std::min(bp.p.block_rows, fit);
   bp.block_rows = std::min(bp.block_rows, count);
@@ -307,7 +304,7 @@ int vv_linear_scores(vv_ctx* c, vv_linear* l, vv_gallery* src, const float* q, i
   GalleryRows gr = {};
   { const int rc = check_pair("vv_linear_scores", c, l, src, &gr); if (rc) return rc; }
   if (n_q < 1 || n_q > (1ll << 30) || (src && n_q != gr.n_ref)) return vv_fail(VV_ERR_ARG, "vv_linear_scores: n_q = %lld", (long long)n_q);
-  const int64_t blk = std::min<int64_t>(n_q, std::max<int64_t>(1, std::min<int64_t>(65536, (int64_t)(LIN_SCRATCH_MAX / ((size_t)2 * l->Cp * 4)))));
+  const int64_t blk = std::min<int64_t>(n_q, std::max<int64_t>(1, std::min<int64_t>(65536, (int64_t)(GALLERY_SCRATCH_MAX / ((size_t)2 * l->Cp * 4)))));
   { const int rc = ensure_rows(c, l, blk); if (rc) return rc; }
   DevTmp<float> qd;
   if (q) { HIPCHK(qd.alloc((size_t)blk * l->Dp)); HIPCHK(hipMemsetAsync(qd, 0, (size_t)blk * l->Dp * 4, c->stream)); }

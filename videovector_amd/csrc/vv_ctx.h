@@ -1,5 +1,5 @@
-// vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the fused training step)
-// and ops.hip (the per-layer operators).  Internal.
+// vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the fused training step), ops.hip (the
+// per-layer operators), retrieval.hip, classify.hip and linear.hip (the evaluation paths).  Internal.
 #pragma once
 #include <cstdarg>
 #include <cstdio>
@@ -22,6 +22,11 @@ int vv_fail(int code, const char* fmt, ...);
       return vv_fail(VV_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, \
                      __LINE__);                                                                \
   } while (0)
+// every entry point that launches kernels: the device of the context, and ITS kernel options for the launchers on this thread
+#define VV_ENTER(c) do { HIPCHK(hipSetDevice((c)->device)); vv::g_ko = &(c)->ko; \
+    if ((c)->comm && vv::comm_failed((c)->comm)) return fail(VV_ERR_HIP, "the data-parallel exchange failed: %s", vv::comm_error((c)->comm)); } while (0)
+
+inline void dfree(void* p) { if (p) (void)hipFree(p); }
 
 // A device allocation that lives for one API call: released on every return path, the early error returns of HIPCHK
 // included.
@@ -270,3 +275,8 @@ int vv_comm_join(vv_ctx* c);
 int vv_reduce_now(vv_ctx* c);
 // api.hip: VV_ERR_STATE where the gradient's state refuses the entry point `who` (vv_step_state.h: grad_guard)
 int vv_upd_pending_guard(vv_ctx* c, const char* who);
+// api.hip: the embeddings of n table rows / of the (coefficient-weighted) means of n windows of k rows into dout [n][D]; `who` names the
+// entry point in messages (retrieval.hip: vv_gallery_from_table)
+int vv_embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int relu, int l2norm, float* dout);
+int vv_embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu, int l2norm,
+                         float* dout);

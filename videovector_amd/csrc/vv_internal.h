@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "vv_pass_plan.h"      // score_fwd_supported / score_fwd_dropout_supported: the shapes the segment-wise pair is built for
+#include "vv_gallery_plan.h"   // the RT_* sizes the gallery scratch is made of, its limits and its sizing arithmetic
 
 struct vv_gallery;
 
@@ -635,10 +636,9 @@ void launch_patch_rows(uint16_t* table, const int32_t* desc, int64_t n_patch, in
 // ---------------------------------------------------------------------------------------------
 // Gallery retrieval (kernels_retrieval.hip): fp32 similarity of one query block into a scratch buffer, then row kernels.
 // ---------------------------------------------------------------------------------------------
-constexpr int RT_BM = 128, RT_BN = 128, RT_BK = 32;   // similarity tile; operand rows are padded to a multiple of RT_BK floats
-constexpr int RT_CHUNK = 2048;                        // positives of one query ranked per pass (their sorted keys: 16 KiB of LDS)
-constexpr int RT_MAX_K = 32;
+constexpr int RT_BM = 128, RT_BN = 128;               // similarity tile (its K, RT_BK, and RT_CHUNK / RT_MAX_K / RT_SEL_*: vv_gallery_plan.h)
 struct RankAcc { double ap_sum; int32_t best, acc1, acc5, acc10; };   // ComputeApStats' running values of one query
+static_assert(sizeof(RankAcc) == GALLERY_ACC_BYTES, "vv_gallery_plan.h sizes the per-query accumulator");
 void launch_sim_f32(const float* Q, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s);
 // seg: gallery items per workgroup (a multiple of 1024), S = ceil(ng / seg); part: uint64 [rows][S][k]
 void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, uint64_t* part, int32_t* idx,
@@ -649,6 +649,7 @@ void launch_rank_pass(const float* dist, int64_t pitch, int rows, int ng, int se
                       uint32_t* bins, RankAcc* acc, hipStream_t s);
 // Class-level statistics (RetrievalStatsLayer): the rows of a block are the gallery items q0 .. q0 + rows - 1.
 struct ClassAcc { double ap_sum; int32_t npos, acc1, n5, pad_; };      // ComputeStats' running values of one query
+static_assert(sizeof(ClassAcc) == GALLERY_ACC_BYTES, "the two statistics share the per-query accumulator buffer");
 // as launch_topk, over the items whose id differs from the row's own
 void launch_topk_other_id(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids, int q0,
                           uint64_t* part, int32_t* idx, float* dst, hipStream_t s);
@@ -659,7 +660,6 @@ void launch_topk_eligible(const float* dist, int64_t pitch, int rows, int ng, in
                           const int32_t* own, int self0, uint64_t* part, int32_t* idx, float* dst, hipStream_t s);
 // Selection form, k <= RT_CHUNK.  st: uint32 [rows][4] and hist: uint32 [rows][RT_SEL_BINS], both zero on entry;
 // segh: uint32 [rows][S][RT_SEL_LAST_BINS]; cand: uint64 [rows][RT_CHUNK]; idx / dst: [rows][k]
-constexpr int RT_SEL_BINS = 4096, RT_SEL_LAST_BINS = 256;
 void launch_select(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids,
                    const int32_t* own, int self0, uint32_t* st, uint32_t* hist, uint32_t* segh, uint64_t* cand, int32_t* idx,
                    float* dst, hipStream_t s);
