@@ -9,11 +9,14 @@
 //   every test embedding with every class mean into device memory, and the layer reads them there: a nearest-class-mean
 //   classifier whose scores never visit the host.  Column k is the k-th class present in train_labels.txt; they must be 0 .. C-1.
 //   classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x]
-//                        [--momentum m] [--weight_decay w]
+//                        [--momentum m] [--weight_decay w] [--loss softmax|hinge] [--hinge_norm L1|L2]
 // --linear: as --prototypes, but the classifier is a softmax linear layer trained on the training items (the reference's
 //   INNER_PRODUCT under SOFTMAX_LOSS): they become a device gallery, vv_linear_fit runs N steps of SGD with momentum on it
 //   (vv_linear_cfg_default's values unless given), vv_linear_scores writes the test items' logits into device memory and the
 //   layer reads them there.  Prints `Linear fit: steps = N loss = first -> last` in front of the statistics.
+//   --loss hinge trains the same layer under the reference's HINGE_LOSS instead (hinge_loss_layer.cpp:13-77: one linear SVM per
+//   class, vv_linear_loss_set), with --hinge_norm L1 or L2 (the default here, as in the Python binding);
+//   --loss softmax is the default and prints what the tool printed before the flag existed.  Another value of either: the usage, exit 2.
 // --prototxt: the layer's parameter is the first CLASSIFICATION_STATS layer of that net file (its num_classes included) instead of
 //   one made here with num_classes = the number of columns.
 // --num_classes / --label_channels: override num_classes / give the label blob K channels -- the layer's shape CHECKs then fire.
@@ -38,7 +41,8 @@ int main(int argc, char** argv) {
   vector<const char*> pos;
   const char *proto = nullptr, *train_feat = nullptr, *train_lab = nullptr;
   int num_classes = -1, label_channels = 1;
-  bool linear = false;
+  bool linear = false, bad_flag = false;
+  int32_t lin_loss = VV_LIN_LOSS_SOFTMAX, hinge_norm = VV_NORM_L2;
   vv_linear_cfg lcfg;
   vv_linear_cfg_default(&lcfg);
   for (int i = 1; i < argc; ++i) {
@@ -49,15 +53,25 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--lr") && i + 1 < argc) lcfg.lr = (float)atof(argv[++i]);
     else if (!strcmp(argv[i], "--momentum") && i + 1 < argc) lcfg.momentum = (float)atof(argv[++i]);
     else if (!strcmp(argv[i], "--weight_decay") && i + 1 < argc) lcfg.weight_decay = (float)atof(argv[++i]);
-    else if (!strcmp(argv[i], "--prototxt") && i + 1 < argc) proto = argv[++i];
+    else if (!strcmp(argv[i], "--loss") && i + 1 < argc) {
+      ++i;
+      if (!strcmp(argv[i], "softmax")) lin_loss = VV_LIN_LOSS_SOFTMAX;
+      else if (!strcmp(argv[i], "hinge")) lin_loss = VV_LIN_LOSS_HINGE;
+      else bad_flag = true;
+    } else if (!strcmp(argv[i], "--hinge_norm") && i + 1 < argc) {
+      ++i;
+      if (!strcmp(argv[i], "L1")) hinge_norm = VV_NORM_L1;
+      else if (!strcmp(argv[i], "L2")) hinge_norm = VV_NORM_L2;
+      else bad_flag = true;
+    } else if (!strcmp(argv[i], "--prototxt") && i + 1 < argc) proto = argv[++i];
     else if (!strcmp(argv[i], "--num_classes") && i + 1 < argc) num_classes = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--label_channels") && i + 1 < argc) label_channels = atoi(argv[++i]);
     else pos.push_back(argv[i]);
   }
-  if (pos.size() != 2 || label_channels < 1) {
+  if (pos.size() != 2 || label_channels < 1 || bad_flag) {
     fprintf(stderr, "usage: classification_stats scores.txt labels.txt [--prototxt net.prototxt] [--num_classes K] [--label_channels K]\n"
                     "       classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt\n"
-                    "       classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x] [--momentum m] [--weight_decay w]\n");
+                    "       classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x] [--momentum m] [--weight_decay w] [--loss softmax|hinge] [--hinge_norm L1|L2]\n");
     return 2;
   }
   Caffe::SetDevice(0);
@@ -87,6 +101,7 @@ int main(int argc, char** argv) {
       vv_linear* lin = nullptr;
       vv_linear_report rep;
       VV_CHECK(vv_linear_create(Caffe::ctx(), dim, C, 1, &lin));
+      if (lin_loss != VV_LIN_LOSS_SOFTMAX) VV_CHECK(vv_linear_loss_set(Caffe::ctx(), lin, lin_loss, hinge_norm));
       VV_CHECK(vv_linear_fit(Caffe::ctx(), lin, items, cls.data(), &lcfg, nullptr, nullptr, &rep));
       printf("Linear fit: steps = %lld loss = %.9g -> %.9g\n", (long long)rep.steps, (double)rep.loss_first, (double)rep.loss_last);
       VV_CHECK(vv_linear_scores(Caffe::ctx(), lin, nullptr, fv.data(), n, x.mutable_gpu_data()));

@@ -766,6 +766,36 @@ int vv_op_softmax_loss(vv_ctx* ctx, const float* z_dev, int64_t rows, int32_t co
 int vv_op_gemm_tn(vv_ctx* ctx, const float* A_dev, int64_t lda, const float* B_dev, int64_t ldb, int64_t k, int32_t m, int32_t n,
                   float* out_dev);
 
+/* ---- the same classifier as a linear SVM per class: the reference's INNER_PRODUCT layer under HINGE_LOSS
+ * (src/caffe/layers/hinge_loss_layer.cpp:13-77, HingeLossParameter's L1 and L2 norm).  Every column of the logits is a binary problem
+ * with target +1 on the label's column and -1 elsewhere.  For a batch of `count` rows, every fp32 operation rounded as written:
+ *   z = the logit the softmax loss reads;  t = (c == label) ? -z : z  (hinge_loss_layer.cpp:25)
+ *   m = (0 < 1 + t) ? 1 + t : 0  (:29-30; a NaN logit gives m = 0, as std::max(Dtype(0), x) does; +Inf stays +Inf)
+ *   L1: loss = loss_weight (sum m) / count (:36);  dz = +-[m > 0] (loss_weight / (float)count), - on the label's column
+ *       (:61-69, caffe_cpu_sign and caffe_scal)
+ *   L2: loss = loss_weight (sum m m) / count (:39);  dz = +-m ((loss_weight * 2.0f) / (float)count)  (:71, left to right)
+ * The sum is taken in double over the exact fp32 terms (m, or m m formed in double) in a fixed order -- a lane's columns ascending,
+ * the lanes of a row, the rows of a wave, the waves of a workgroup, the workgroups in index order -- and rounded once; there is no
+ * floating-point atomic, so two calls give the same bits.  `correct` and the non-finite count mean what they mean under the softmax loss.
+ * vv_linear_loss_set (hinge_loss_layer.cpp:34-43, the layer's norm switch): the loss vv_linear_fit and vv_linear_grad run from now on,
+ * sticky on the object like vv_solver_ext_set on a context.  A new object is VV_LIN_LOSS_SOFTMAX.  Switching touches neither
+ * parameters, histories, step counter nor cursor.  norm (VV_NORM_L1 / VV_NORM_L2) is read for VV_LIN_LOSS_HINGE only.  vv_linear_scores,
+ * _get and _put do not depend on it.  VV_ERR_ARG: another loss value; with HINGE another norm; a classifier of another context.
+ * vv_linear_loss_get (hinge_loss_layer.cpp:34, 65: what the switch reads): either pointer may be NULL; norm is the last one set with
+ * HINGE (VV_NORM_L2 on a new object).
+ * vv_op_hinge_loss (hinge_loss_layer.cpp:13-77): the hinge kernel on the caller's logits z_dev [rows][pitch], as vv_op_softmax_loss:
+ * any pitch >= cols, any alignment; dz_dev [rows][pitch] device or NULL (columns cols .. pitch - 1 are written zero), *loss and *correct
+ * may be NULL.  Synchronises.  VV_ERR_ARG: vv_op_softmax_loss's checks, and a norm that is neither VV_NORM_L1 nor VV_NORM_L2.
+ * With base pointers on 16 bytes and pitch % 4 == 0 (always inside vv_linear_fit / _grad) the kernel reads and writes 16 bytes at a
+ * time; otherwise element by element, with identical results.  Read-only "last_hinge_form": 1 / 2 for the two forms at the last launch,
+ * 0 before the first; "last_hinge_nonfinite": rows with a logit that is not finite in the last vv_op_hinge_loss.  Under the hinge
+ * loss "last_lin_softmax_ms" is the hinge kernel's device time. */
+enum { VV_LIN_LOSS_SOFTMAX = 0, VV_LIN_LOSS_HINGE = 1 };
+int vv_linear_loss_set(vv_ctx* ctx, vv_linear* lin, int32_t loss, int32_t norm);
+int vv_linear_loss_get(vv_ctx* ctx, vv_linear* lin, int32_t* loss, int32_t* norm);
+int vv_op_hinge_loss(vv_ctx* ctx, const float* z_dev, int64_t rows, int32_t cols, int64_t pitch, const int32_t* labels,
+                     int32_t norm, float loss_weight, float* dz_dev, float* loss, int64_t* correct);
+
 /* ---- per-layer operators.  The reference's operator interface is Layer<Dtype>::{Forward_gpu, Backward_gpu}
  * (include/caffe/layer.hpp:308-337); its sequential executor (Net::ForwardFromTo / BackwardFromTo, net.cpp:501-578) calls
  * them layer by layer.  Training here runs the fused plan above; these entry points are what the C++ facade's layer classes

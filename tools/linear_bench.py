@@ -11,10 +11,24 @@ blocks it ran.  A box probe (Engine.box_probe) is taken in front of and behind t
 twice (2 n Dp 4 bytes), the forward and the weight-gradient products are 2 n Dp Cp FLOP each.
 Host: the same step (logits, softmax, dz^T X, the rule) in numpy float32 on --host-threads threads: the outside yardstick.
 
+--loss hinge [--norm L1|L2] times the same fit under the one-vs-rest hinge loss (vv_linear_loss_set): the second leg is then k_hinge's
+device time (it is reported in the "softmax" slot: "last_lin_softmax_ms" is the loss kernel's leg), the file is
+profiles/linear_hinge_<n>x<dim>x<C>[_b<batch>].json, the streaming model of that kernel -- the logits read once and dz written once,
+2 count Cp 4 bytes, at the box probe's copy rate of this run -- is recorded beside it, and the host yardstick is left out.
+
+--compare PARENT_ROOT (a checkout of the parent commit with its library built) alternates three legs as child processes of this script,
+--rounds times (P S H P S H ...: what drifts reaches all alike): the PARENT's library under the softmax loss, this library under the
+softmax loss, this library under the hinge loss.  Every child is one run as above (no host yardstick) with its own box probe and its own
+time limit, and the chain stops at the first child that fails.  Written to profiles/linear_hinge_<shape>.json: every round's figures, the
+medians, the parent's spread (max - min of its rounds' loss-kernel legs), k_hinge's leg against the parent's k_softmax_xent leg and against
+the streaming model, and the condition that this library's softmax leg lies within the parent's spread.
+
 Embeddings: class means 3 e_(c mod dim) under 0.5 N(0, 1) noise; labels i mod C."""
 import argparse
 import json
 import os
+import statistics
+import subprocess
 import sys
 import time
 
@@ -43,7 +57,16 @@ def main():
     ap.add_argument("--host-steps", type=int, default=3)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--loss", choices=("softmax", "hinge"), default="softmax")
+    ap.add_argument("--norm", choices=("L1", "L2"), default="L2")
+    ap.add_argument("--compare", default=None, metavar="PARENT_ROOT")
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--pkg-root", default=ROOT)
     a = ap.parse_args()
+    if a.compare:
+        return compare(a)
+    if a.pkg_root != ROOT:
+        sys.path.insert(0, a.pkg_root)
     os.environ.setdefault("OMP_NUM_THREADS", str(a.host_threads))
     import linear_ref as ref
     import videovector_amd as vv
@@ -59,6 +82,8 @@ def main():
     wall, legs, rep = [], [], None
     for r in range(a.warmup + a.reps):
         lin = eng.linear(a.dim, a.classes)
+        if a.loss == "hinge":
+            lin.set_loss("hinge", a.norm)
         t0 = time.perf_counter()
         _, rep = lin.fit(gal, y, iters=a.steps, batch=a.batch, **hp)
         t1 = time.perf_counter()
@@ -77,8 +102,11 @@ def main():
                model=dict(x_bytes_per_step=2.0 * count * Dp * 4, product_flop=flop,
                           fwd_tflops=flop / (leg["fwd"]["median"] * 1e-3) / 1e12, wgrad_tflops=flop / (leg["wgrad"]["median"] * 1e-3) / 1e12,
                           fwd_yardstick_tflops=85.0),
-               box_probe=[probe0, probe1])
-    if not a.no_host:
+               box_probe=[probe0, probe1], lib=vv.lib_path())
+    if a.loss == "hinge":
+        out["loss"], out["norm"], out["last_hinge_form"] = "hinge", a.norm, int(eng.get_option("last_hinge_form"))
+        out["model"]["hinge_stream_bytes"] = 2.0 * count * Cp * 4
+    if not a.no_host and a.loss == "softmax":
         st = ref.State(a.dim, a.classes, np.float32)
         t = []
         for _ in range(a.host_steps):
@@ -89,10 +117,68 @@ def main():
         out["host_threads"] = a.host_threads
     line = json.dumps(out)
     print(line)
-    name = "linear_%dx%dx%d%s.json" % (a.n, a.dim, a.classes, "_b%d" % a.batch if a.batch else "")
+    name = "linear_%s%dx%dx%d%s.json" % ("hinge_" if a.loss == "hinge" else "", a.n, a.dim, a.classes, "_b%d" % a.batch if a.batch else "")
     path = a.out or os.path.join(ROOT, "profiles", name)
     with open(path, "w") as f:
         f.write(line + "\n")
+
+
+LEGS = {"parent_softmax": ("parent", "softmax"), "softmax": ("new", "softmax"), "hinge": ("new", "hinge")}
+CHILD_LIMIT_S = 240
+
+
+def copy_rate(probe):
+    """The box probe's streaming-copy rate in bytes / s."""
+    return float(probe["copy_tbs"]) * 1e12
+
+
+def compare(a):
+    parent = os.path.abspath(a.compare)
+    shape = "%dx%dx%d%s" % (a.n, a.dim, a.classes, "_b%d" % a.batch if a.batch else "")
+    res = dict(shape=[a.n, a.dim, a.classes], batch=a.batch, steps=a.steps, reps=a.reps, rounds=a.rounds, norm=a.norm,
+               legs={k: dict(loss_leg_ms_rounds=[], step_ms_rounds=[], box_probe_rounds=[]) for k in LEGS})
+    tmp = os.path.join(ROOT, "profiles", ".linear_bench_child.json")
+    for _ in range(a.rounds):
+        for leg, (whose, loss) in LEGS.items():
+            root = parent if whose == "parent" else ROOT
+            env = dict(os.environ, VV_LIB=os.path.join(root, "videovector_amd", "lib", "libvideovec.so"))
+            cmd = [sys.executable, os.path.abspath(__file__), "--n", str(a.n), "--dim", str(a.dim), "--classes", str(a.classes), "--batch", str(a.batch),
+                   "--steps", str(a.steps), "--reps", str(a.reps), "--warmup", str(a.warmup), "--no-host", "--out", tmp, "--pkg-root", root]
+            if loss == "hinge":
+                cmd += ["--loss", "hinge", "--norm", a.norm]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=CHILD_LIMIT_S, env=env)
+            lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+            if r.returncode != 0 or not lines:
+                raise SystemExit("the %s leg failed (exit %d): the chain stops here\n%s" % (leg, r.returncode, r.stderr[-2000:]))
+            o = json.loads(lines[-1])
+            L = res["legs"][leg]
+            L["loss_leg_ms_rounds"].append(o["legs_ms_last_step"]["softmax"]["median"])
+            L["step_ms_rounds"].append(o["step_ms"]["median"])
+            L["box_probe_rounds"].append(o["box_probe"])
+            L["library"] = "the parent commit's" if whose == "parent" else "this commit's"
+            L["last"] = {k: o[k] for k in ("legs_ms_last_step", "splits", "row_blocks", "loss_first", "loss_last", "accuracy_last", "model") if k in o}
+    if os.path.exists(tmp):
+        os.remove(tmp)
+    for L in res["legs"].values():
+        L["loss_leg_ms"] = statistics.median(L["loss_leg_ms_rounds"])
+        L["step_ms"] = statistics.median(L["step_ms_rounds"])
+    p = res["legs"]["parent_softmax"]
+    res["parent_spread_ms"] = max(p["loss_leg_ms_rounds"]) - min(p["loss_leg_ms_rounds"])
+    res["softmax_minus_parent_ms"] = res["legs"]["softmax"]["loss_leg_ms"] - p["loss_leg_ms"]
+    res["softmax_within_parent_spread"] = bool(abs(res["softmax_minus_parent_ms"]) <= res["parent_spread_ms"])
+    res["hinge_over_parent_softmax"] = res["legs"]["hinge"]["loss_leg_ms"] / p["loss_leg_ms"]
+    rates = [copy_rate(pr) for pair in res["legs"]["hinge"]["box_probe_rounds"] for pr in pair]
+    if rates:
+        count = a.n if a.batch == 0 else min(a.batch, a.n)
+        model_ms = 2.0 * count * (-(-a.classes // 32) * 32) * 4 / statistics.median(rates) * 1e3
+        res["hinge_stream_model_ms"], res["hinge_over_stream_model"] = model_ms, res["legs"]["hinge"]["loss_leg_ms"] / model_ms
+    path = os.path.join(ROOT, "profiles", "linear_hinge_%s.json" % shape) if a.out is None else a.out
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("%s: parent softmax %.4f ms (spread %.4f), softmax %+.4f ms, hinge %.4f ms = %.3f x parent's softmax, %s x the streaming model -> %s" % (
+        shape, p["loss_leg_ms"], res["parent_spread_ms"], res["softmax_minus_parent_ms"], res["legs"]["hinge"]["loss_leg_ms"],
+        res["hinge_over_parent_softmax"], "%.2f" % res["hinge_over_stream_model"] if rates else "?", path), flush=True)
 
 
 if __name__ == "__main__":

@@ -4,6 +4,7 @@
 // SoftmaxWithLossLayer::Forward_cpu / Backward_cpu (softmax_loss_layer.cpp:34-83), InnerProductLayer::Backward_gpu
 // (inner_product_layer.cu:29-59: dW = dz^T X, db = dz^T 1) and SGDSolver::ComputeUpdateValue (solver.cpp:485-531, L2).
 // The logits' product is k_sim_f32 (kernels_retrieval.hip) as it stands: this file reads the float it stored, times -0.5f.
+// k_hinge, at the end, is the same layer under HINGE_LOSS (hinge_loss_layer.cpp:13-77): a linear SVM per class.
 //
 // Nothing here adds floats atomically: every sum has one owner and a fixed order, so the same inputs give the same bits.
 #include <cfloat>
@@ -13,6 +14,15 @@
 namespace vv {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// The logit of column c from the stored similarity s: mul s + b[c].  mul is -0.5f or 1, so the product is exact and the sum is the one
+// rounding.  k_softmax_xent and k_hinge both form it here, as the product and then the sum (what k_softmax_xent has always compiled
+// to; contraction is off so that no setting at the point of use can fuse the two).
+__device__ __forceinline__ float lin_logit(float mul, float s, const float* bias, int c) {
+#pragma clang fp contract(off)
+  const float p = mul * s;
+  return bias ? p + bias[c] : p;
+}
 
 // ---------------------------------------------------------------------------------------------- softmax / cross-entropy
 // A FIXED grid of LIN_SM_BLOCKS x 256 threads.  A group of `wd` lanes (64, or 32 when cols <= 32: two rows per wave) owns one row at
@@ -37,7 +47,7 @@ __global__ __launch_bounds__(256) void k_softmax_xent(LinSoftmaxArgs a) {
     int arg = INT32_MAX;
     bool bad = false;
     for (int c = sub; c < a.cols; c += wd) {
-      const float z = a.bias ? a.mul * s[c] + a.bias[c] : a.mul * s[c];
+      const float z = lin_logit(a.mul, s[c], a.bias, c);
       bad |= !isfinite(z);
       if (z > m) { m = z; arg = c; }
     }
@@ -51,7 +61,7 @@ __global__ __launch_bounds__(256) void k_softmax_xent(LinSoftmaxArgs a) {
     if (arg == INT32_MAX) arg = 0;
     float sum = 0.f;
     for (int c = sub; c < a.cols; c += wd) {
-      const float z = a.bias ? a.mul * s[c] + a.bias[c] : a.mul * s[c];
+      const float z = lin_logit(a.mul, s[c], a.bias, c);
       sum += expf(z - m);
     }
     for (int o = wd >> 1; o > 0; o >>= 1) sum += __shfl_down(sum, o, wd);
@@ -60,7 +70,7 @@ __global__ __launch_bounds__(256) void k_softmax_xent(LinSoftmaxArgs a) {
     for (int c = sub; c < a.pitch; c += wd) {
       float p = 0.f, d = 0.f;
       if (c < a.cols) {
-        const float z = a.bias ? a.mul * s[c] + a.bias[c] : a.mul * s[c];
+        const float z = lin_logit(a.mul, s[c], a.bias, c);
         p = expf(z - m) / sum;
         d = (c == label ? p - 1.f : p) * a.scale;                         // :68-81
         if (c == label) term = -logf(fmaxf(p, FLT_MIN));                  // :46-48
@@ -310,5 +320,135 @@ __global__ __launch_bounds__(256) void k_lin_update(LinUpdArgs a) {
 }
 
 void launch_lin_update(const LinUpdArgs& a, hipStream_t s) { VV_LAUNCH(k_lin_update, dim3(LIN_UPD_BLOCKS), dim3(256), 0, s, a); }
+
+// ---------------------------------------------------------------------------------------------- one-vs-rest hinge loss
+// HingeLossLayer::Forward_cpu / Backward_cpu (hinge_loss_layer.cpp:13-77): every column of the logits is a binary problem with target
+// +1 on the label's column and -1 elsewhere.  Per element, every operation rounded as written (fp contract is off from above):
+//   z = lin_logit;  t = c == label ? -z : z (:25);  m = 0 < 1 + t ? 1 + t : 0 (:29-30: a NaN gives 0, +Inf stays)
+//   L1: term m (:36), dz = +-[m > 0] scale (:61-69);  L2: term m m (:39), dz = +-m scale (:71);  - on the label's column
+// The same FIXED grid of LIN_SM_BLOCKS x 256 threads.  A group of wd = lin_hinge_lanes(cols) lanes (1 .. 64) owns one row at a time;
+// a wave's 64 / wd groups take consecutive rows, and all of them run the row loop together.  ONE sweep: lane `sub` of the group
+// reads the 4-column chunks sub, sub + wd, ... of the row once (vec: one 16-byte load each; else element by element, the same
+// columns), forms z, m, dz and its running first maximum, stores dz (zero at columns cols .. pitch - 1) and adds its terms, columns
+// ascending, into ITS double.  The first chunk and the label of the group's next row are loaded before the current row is worked on.
+// One fold of (value, column) by halves within the group gives the row's first maximum (strict >, the lower column on a tie, NaN
+// passed over, column 0 when there is none); the non-finite flag is one ballot.
+// The loss: the lanes' doubles are folded pairwise with neighbours at distance 1, 2, 4 .. 32 (so a group's lanes first, then the wave's
+// groups), then the workgroup's waves in order, then the last workgroup to arrive adds the LIN_SM_BLOCKS partials in index order:
+// k_softmax_xent's last stage on k_softmax_xent's buffers.  No floating-point atomics.
+__device__ __forceinline__ float4 hinge_load(const LinHingeArgs& a, const float* row, int c4) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.vec) {
+    if (c4 < a.cols) v = *(const float4*)(row + c4);                      // (pitch % 4 == 0: the chunk lies inside the row)
+  } else {
+    if (c4 < a.cols) v.x = row[c4];
+    if (c4 + 1 < a.cols) v.y = row[c4 + 1];
+    if (c4 + 2 < a.cols) v.z = row[c4 + 2];
+    if (c4 + 3 < a.cols) v.w = row[c4 + 3];
+  }
+  return v;
+}
+
+struct HingeLane { double sum; float mx; int arg; bool bad; };
+
+__device__ __forceinline__ float hinge_elem(const LinHingeArgs& a, float s, int c, int label, HingeLane& st) {
+  const float z = lin_logit(a.mul, s, a.bias, c);
+  st.bad |= !isfinite(z);
+  if (z > st.mx) { st.mx = z; st.arg = c; }
+  const float t = c == label ? -z : z;
+  const float u = 1.f + t;
+  const float m = 0.f < u ? u : 0.f;
+  if (a.norm == 1) {
+    st.sum += (double)m;
+    return m > 0.f ? (c == label ? -a.scale : a.scale) : 0.f;
+  }
+  st.sum += (double)m * (double)m;
+  return (c == label ? -m : m) * a.scale;
+}
+
+__global__ __launch_bounds__(256) void k_hinge(LinHingeArgs a) {
+  const int wd = a.wd, lane = threadIdx.x & 63, sub = lane & (wd - 1), gpw = 64 / wd, c0 = sub * 4, cstep = wd * 4;
+  const int64_t wave_row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * gpw, pass = (int64_t)LIN_SM_BLOCKS * 4 * gpw;
+  const unsigned long long gmask = wd == 64 ? ~0ull : (1ull << wd) - 1;
+  HingeLane st;
+  st.sum = 0.0;
+  unsigned correct = 0, nonfinite = 0;
+  float4 cur = make_float4(0.f, 0.f, 0.f, 0.f);
+  int label = 0;
+  if (wave_row + lane / wd < a.rows) { cur = hinge_load(a, a.sim + (wave_row + lane / wd) * a.pitch, c0); label = a.labels[wave_row + lane / wd]; }
+  for (int64_t rb = wave_row; rb < a.rows; rb += pass) {                    // (the same trip count for the whole wave)
+    const int64_t r = rb + lane / wd, rn = r + pass;
+    const bool active = r < a.rows;
+    float4 nxt = make_float4(0.f, 0.f, 0.f, 0.f);
+    int label_nxt = 0;
+    if (rn < a.rows) { nxt = hinge_load(a, a.sim + rn * a.pitch, c0); label_nxt = a.labels[rn]; }
+    st.mx = -INFINITY; st.arg = INT32_MAX; st.bad = false;
+    if (active) {
+      const float* s = a.sim + r * a.pitch;
+      float* d = a.dz ? a.dz + r * a.pitch : nullptr;
+      for (int c4 = c0; c4 < a.pitch; c4 += cstep) {
+        const float4 v = c4 == c0 ? cur : hinge_load(a, s, c4);
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c4 < a.cols) o.x = hinge_elem(a, v.x, c4, label, st);
+        if (c4 + 1 < a.cols) o.y = hinge_elem(a, v.y, c4 + 1, label, st);
+        if (c4 + 2 < a.cols) o.z = hinge_elem(a, v.z, c4 + 2, label, st);
+        if (c4 + 3 < a.cols) o.w = hinge_elem(a, v.w, c4 + 3, label, st);
+        if (d) {
+          if (a.vec) *(float4*)(d + c4) = o;
+          else {
+            d[c4] = o.x;
+            if (c4 + 1 < a.pitch) d[c4 + 1] = o.y;
+            if (c4 + 2 < a.pitch) d[c4 + 2] = o.z;
+            if (c4 + 3 < a.pitch) d[c4 + 3] = o.w;
+          }
+        }
+      }
+    }
+    float mx = st.mx;
+    int arg = st.arg;
+    for (int o = wd >> 1; o > 0; o >>= 1) {
+      const float m2 = __shfl_down(mx, o, wd);
+      const int a2 = __shfl_down(arg, o, wd);
+      if (m2 > mx || (m2 == mx && a2 < arg)) { mx = m2; arg = a2; }
+    }
+    const unsigned long long bad = __ballot(st.bad);
+    if (active && sub == 0) {
+      correct += (arg == INT32_MAX ? 0 : arg) == label;
+      nonfinite += ((bad >> (lane - sub)) & gmask) != 0;
+    }
+    cur = nxt; label = label_nxt;
+  }
+  double loss = st.sum;
+  for (int o = 1; o < 64; o <<= 1) { loss += __shfl_down(loss, o, 64); correct += __shfl_down(correct, o, 64); nonfinite += __shfl_down(nonfinite, o, 64); }
+  __shared__ double wl[LIN_SM_BLOCKS];
+  __shared__ unsigned wc[LIN_SM_BLOCKS], wn[LIN_SM_BLOCKS];
+  __shared__ int last;
+  if (lane == 0) { wl[threadIdx.x >> 6] = loss; wc[threadIdx.x >> 6] = correct; wn[threadIdx.x >> 6] = nonfinite; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(a.part_loss + blockIdx.x, ((wl[0] + wl[1]) + wl[2]) + wl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.part_cnt + 2 * blockIdx.x, wc[0] + wc[1] + wc[2] + wc[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.part_cnt + 2 * blockIdx.x + 1, wn[0] + wn[1] + wn[2] + wn[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)LIN_SM_BLOCKS - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  for (int i = threadIdx.x; i < LIN_SM_BLOCKS; i += 256) {
+    wl[i] = __hip_atomic_load(a.part_loss + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    wc[i] = __hip_atomic_load(a.part_cnt + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    wn[i] = __hip_atomic_load(a.part_cnt + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double sl = 0.0;
+  int64_t sc = 0, sn = 0;
+  for (int i = 0; i < LIN_SM_BLOCKS; ++i) { sl += wl[i]; sc += wc[i]; sn += wn[i]; }
+  LinRec& rec = *a.rec;
+  if (a.first_block) { rec.loss_sum = sl; rec.correct = sc; rec.nonfinite = sn; }
+  else { rec.loss_sum += sl; rec.correct += sc; rec.nonfinite += sn; }
+  __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the next launch
+}
+
+void launch_hinge(const LinHingeArgs& a, hipStream_t s) { VV_LAUNCH(k_hinge, dim3(LIN_SM_BLOCKS), dim3(256), 0, s, a); }
 
 }  // namespace vv

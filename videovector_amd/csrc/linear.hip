@@ -1,5 +1,5 @@
-// linear.hip -- entry points of the softmax linear classifier on gallery embeddings (include/videovec.h: vv_linear_*,
-// vv_op_softmax_loss, vv_op_gemm_tn).  The kernels are in kernels_linear.hip; the logits' product is launch_sim_f32
+// linear.hip -- entry points of the linear classifier on gallery embeddings, under the softmax loss or the one-vs-rest hinge loss
+// (include/videovec.h: vv_linear_*, vv_op_softmax_loss, vv_op_hinge_loss, vv_op_gemm_tn).  The kernels are in kernels_linear.hip; the logits' product is launch_sim_f32
 // (kernels_retrieval.hip) on W kept as [Cp][Dp] rows, zero-padded the way a gallery is.  Everything is queued on the context's
 // stream; a fit synchronises once, at its end.  None of this reads or writes the training step's state.
 #include <algorithm>
@@ -19,6 +19,7 @@ struct vv_linear {
   vv_ctx* ctx = nullptr;
   int dim = 0, Dp = 0, C = 0, Cp = 0, bias = 0;
   int64_t cursor = 0, steps = 0;
+  int loss = VV_LIN_LOSS_SOFTMAX, norm = VV_NORM_L2;        // vv_linear_loss_set; norm is read under VV_LIN_LOSS_HINGE only
   float* P = nullptr;                       // ONE allocation: W [Cp][Dp] | hW [Cp][Dp] | b [Cp] | hb [Cp], pads zero
   float *W = nullptr, *hW = nullptr, *b = nullptr, *hb = nullptr;
   // scratch, grown on demand and kept between calls
@@ -35,7 +36,7 @@ inline bool aligned16(const void* p, int64_t ld) { return ((uintptr_t)p & 15) ==
 // the softmax kernel's partial buffers: [LIN_SM_BLOCKS] doubles, [LIN_SM_BLOCKS][2] counts, the arrival counter
 constexpr size_t kSmPartBytes = (size_t)LIN_SM_BLOCKS * 8 + (size_t)LIN_SM_BLOCKS * 2 * 4 + 16;
 
-void sm_parts(void* base, LinSoftmaxArgs& a) {
+template <class Args> void sm_parts(void* base, Args& a) {
   a.part_loss = (double*)base;
   a.part_cnt = (uint32_t*)((char*)base + (size_t)LIN_SM_BLOCKS * 8);
   a.arrived = a.part_cnt + (size_t)LIN_SM_BLOCKS * 2;
@@ -84,13 +85,19 @@ int check_pair(const char* who, vv_ctx* c, vv_linear* l, vv_gallery* g, GalleryR
   }
   return VV_OK;
 }
+// hinge_loss_layer.cpp:68 and :71, each evaluated left to right in fp32
+float hinge_scale(int norm, float loss_weight, int64_t count) {
+  if (norm == VV_NORM_L1) return loss_weight / (float)count;
+  const float twice = loss_weight * 2.0f;
+  return twice / (float)count;
+}
 int check_labels(const char* who, const int32_t* labels, int64_t n, int C) {
   for (int64_t i = 0; i < n; ++i)
     if (labels[i] < 0 || labels[i] >= C) return vv_fail(VV_ERR_ARG, "%s: label %d of item %lld is outside 0 .. %d", who, labels[i], (long long)i, C - 1);
   return VV_OK;
 }
 
-// One batch: logits, softmax / cross-entropy and the weight-gradient product of rows [first, first + count), row block by row
+// One batch: logits, the selected loss (softmax / cross-entropy, or the hinge loss) and the weight-gradient product of rows [first, first + count), row block by row
 // block in order; the slabs then hold the batch's gradient in bp.p.S splits.  ev: NULL, or four events recorded around the legs of
 // the batch (the last row block's).
 int queue_batch(vv_ctx* c, vv_linear* l, const GalleryRows& gr, const int32_t* labels_dev, int64_t first, int64_t count, float loss_weight,
@@ -103,12 +110,22 @@ int queue_batch(vv_ctx* c, vv_linear* l, const GalleryRows& gr, const int32_t* l
     if (timed) HIPCHK(hipEventRecord(ev[0], c->stream));
     launch_sim_f32(X, l->W, l->z, (int)rows, l->C, l->Dp, l->Cp, c->stream);
     if (timed) HIPCHK(hipEventRecord(ev[1], c->stream));
-    LinSoftmaxArgs sa;
-    sa.sim = l->z; sa.pitch = l->Cp; sa.rows = rows; sa.cols = l->C; sa.mul = -0.5f; sa.bias = l->bias ? l->b : nullptr;
-    sa.labels = labels_dev + r0; sa.scale = scale; sa.dz = l->dz; sa.prob = nullptr; sa.row_loss = nullptr; sa.row_flags = nullptr;
-    sa.wd = l->C <= 32 ? 32 : 64; sa.rec = rec; sa.first_block = blk == 0;
-    sm_parts(l->part_loss, sa);
-    launch_softmax_xent(sa, c->stream);
+    if (l->loss == VV_LIN_LOSS_HINGE) {
+      LinHingeArgs ha;
+      ha.sim = l->z; ha.pitch = l->Cp; ha.rows = rows; ha.cols = l->C; ha.mul = -0.5f; ha.bias = l->bias ? l->b : nullptr;
+      ha.labels = labels_dev + r0; ha.norm = l->norm; ha.scale = hinge_scale(l->norm, loss_weight, count); ha.dz = l->dz;
+      ha.wd = lin_hinge_lanes(l->C); ha.vec = 1; ha.rec = rec; ha.first_block = blk == 0;      // (hipMalloc'd, Cp % 32 == 0)
+      sm_parts(l->part_loss, ha);
+      launch_hinge(ha, c->stream);
+      c->last_hinge_form = 1;
+    } else {
+      LinSoftmaxArgs sa;
+      sa.sim = l->z; sa.pitch = l->Cp; sa.rows = rows; sa.cols = l->C; sa.mul = -0.5f; sa.bias = l->bias ? l->b : nullptr;
+      sa.labels = labels_dev + r0; sa.scale = scale; sa.dz = l->dz; sa.prob = nullptr; sa.row_loss = nullptr; sa.row_flags = nullptr;
+      sa.wd = l->C <= 32 ? 32 : 64; sa.rec = rec; sa.first_block = blk == 0;
+      sm_parts(l->part_loss, sa);
+      launch_softmax_xent(sa, c->stream);
+    }
     if (timed) HIPCHK(hipEventRecord(ev[2], c->stream));
     LinWgradArgs wa;
     wa.A = l->dz; wa.lda = l->Cp; wa.B = X; wa.ldb = gr.Dp; wa.k = rows; wa.m = l->Cp; wa.n = l->Dp;
@@ -342,6 +359,57 @@ int vv_op_softmax_loss(vv_ctx* c, const float* z_dev, int64_t rows, int32_t cols
   LinRec h;
   HIPCHK(hipMemcpyAsync(&h, parts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  if (loss) *loss = (float)((double)loss_weight * h.loss_sum / (double)rows);
+  if (correct) *correct = h.correct;
+  return VV_OK;
+}
+
+int vv_linear_loss_set(vv_ctx* c, vv_linear* l, int32_t loss, int32_t norm) {
+  NEED(c);
+  { const int rc = check_pair("vv_linear_loss_set", c, l, nullptr, nullptr); if (rc) return rc; }
+  if (loss != VV_LIN_LOSS_SOFTMAX && loss != VV_LIN_LOSS_HINGE) return vv_fail(VV_ERR_ARG, "vv_linear_loss_set: loss = %d is neither VV_LIN_LOSS_SOFTMAX nor VV_LIN_LOSS_HINGE", loss);
+  if (loss == VV_LIN_LOSS_HINGE) {
+    if (norm != VV_NORM_L1 && norm != VV_NORM_L2) return vv_fail(VV_ERR_ARG, "vv_linear_loss_set: norm = %d is neither VV_NORM_L1 nor VV_NORM_L2", norm);
+    l->norm = norm;
+  }
+  l->loss = loss;
+  return VV_OK;
+}
+
+int vv_linear_loss_get(vv_ctx* c, vv_linear* l, int32_t* loss, int32_t* norm) {
+  NEED(c);
+  { const int rc = check_pair("vv_linear_loss_get", c, l, nullptr, nullptr); if (rc) return rc; }
+  if (loss) *loss = l->loss;
+  if (norm) *norm = l->norm;
+  return VV_OK;
+}
+
+int vv_op_hinge_loss(vv_ctx* c, const float* z_dev, int64_t rows, int32_t cols, int64_t pitch, const int32_t* labels, int32_t norm,
+                     float loss_weight, float* dz_dev, float* loss, int64_t* correct) {
+  NEED(c);
+  if (!z_dev || !labels) return vv_fail(VV_ERR_ARG, "vv_op_hinge_loss: NULL argument");
+  if (rows < 1 || rows > (1ll << 30) || cols < 1 || cols > LIN_MAX_CLASSES || pitch < cols)
+    return vv_fail(VV_ERR_ARG, "vv_op_hinge_loss: %lld rows of %d columns, pitch %lld", (long long)rows, cols, (long long)pitch);
+  if (norm != VV_NORM_L1 && norm != VV_NORM_L2) return vv_fail(VV_ERR_ARG, "vv_op_hinge_loss: norm = %d is neither VV_NORM_L1 nor VV_NORM_L2", norm);
+  { const int rc = check_labels("vv_op_hinge_loss", labels, rows, cols); if (rc) return rc; }
+  DevTmp<int32_t> lab;
+  DevTmp<char> parts;                                                      // the record, then the partials
+  HIPCHK(lab.alloc((size_t)rows)); HIPCHK(parts.alloc(64 + kSmPartBytes));
+  HIPCHK(hipMemcpyAsync(lab, labels, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(parts, 0, 64 + kSmPartBytes, c->stream));
+  LinHingeArgs ha;
+  ha.sim = z_dev; ha.pitch = pitch; ha.rows = rows; ha.cols = cols; ha.mul = 1.f; ha.bias = nullptr; ha.labels = lab;
+  ha.norm = norm; ha.scale = hinge_scale(norm, loss_weight, rows); ha.dz = dz_dev;
+  ha.wd = lin_hinge_lanes(cols); ha.vec = aligned16(z_dev, pitch) && (!dz_dev || aligned16(dz_dev, pitch));
+  ha.rec = (LinRec*)parts.p; ha.first_block = 1;
+  sm_parts(parts.p + 64, ha);
+  launch_hinge(ha, c->stream);
+  HIPCHK(hipGetLastError());
+  c->last_hinge_form = ha.vec ? 1 : 2;
+  LinRec h;
+  HIPCHK(hipMemcpyAsync(&h, parts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->last_hinge_nonfinite = h.nonfinite;
   if (loss) *loss = (float)((double)loss_weight * h.loss_sum / (double)rows);
   if (correct) *correct = h.correct;
   return VV_OK;

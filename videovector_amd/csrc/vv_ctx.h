@@ -233,6 +233,11 @@ struct vv_ctx {
   int lin_split_rows = 0;
   int last_lin_splits = 0, last_lin_blocks = 0;
   double last_lin_ms[4] = {0, 0, 0, 0};
+  // k_hinge: "last_hinge_form" (1: 16-byte accesses, 2: element-wise, 0: not launched yet) of the last launch, and the rows with a
+  // logit that is not finite in the last vv_op_hinge_loss ("last_hinge_nonfinite"); under the hinge loss the fit's second leg
+  // ("last_lin_softmax_ms") is k_hinge's device time
+  int last_hinge_form = 0;
+  int64_t last_hinge_nonfinite = 0;
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

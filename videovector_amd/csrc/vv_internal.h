@@ -730,7 +730,24 @@ struct LinUpdArgs {
   float *W, *hW, *b, *hb;                                         // rule == 0: W / b are the outputs, hW / hb unused
   float lr, momentum, wd; int rule; int vec;
 };
+// k_hinge: the one-vs-rest hinge loss (hinge_loss_layer.cpp:13-77) on the same logits, the same record and the same partial buffers
+struct LinHingeArgs {
+  const float* sim; int64_t pitch; int64_t rows; int cols;        // z = mul sim + bias, as LinSoftmaxArgs
+  float mul;
+  const float* bias;                                              // [cols] or NULL
+  const int32_t* labels;                                          // device [rows]
+  int norm;                                                       // 1: L1, 2: L2 (VV_NORM_*)
+  float scale;                                                    // L1: loss_weight / (float)count; L2: (loss_weight * 2.0f) / (float)count
+  float* dz;                                                      // [rows][pitch] or NULL; columns cols .. pitch - 1 are written zero
+  int wd;                                                         // lanes per row: lin_hinge_lanes(cols)
+  int vec;                                                        // 1: sim and dz on 16 bytes and pitch % 4 == 0 (float4 accesses); 0: element-wise
+  LinRec* rec; int first_block;
+  double* part_loss; uint32_t* part_cnt; uint32_t* arrived;       // k_softmax_xent's buffers
+};
+// lanes per row: the power of two that covers ceil(cols / 4) float4 chunks, 1 .. 64
+inline int lin_hinge_lanes(int cols) { int wd = 1; while (wd < 64 && wd * 4 < cols) wd <<= 1; return wd; }
 void launch_softmax_xent(const LinSoftmaxArgs& a, hipStream_t s);
+void launch_hinge(const LinHingeArgs& a, hipStream_t s);
 void launch_lin_scores_out(const float* sim, int64_t pitch, int64_t rows, int cols, const float* bias, float* out, hipStream_t s);
 void launch_lin_wgrad(const LinWgradArgs& a, hipStream_t s);
 void launch_lin_update(const LinUpdArgs& a, hipStream_t s);

@@ -201,6 +201,8 @@ def load_library():
         "vv_linear_grad": [vp, vp, vp, vp, i64, i64, f32, vp, vp, C.POINTER(f32)],
         "vv_linear_scores": [vp, vp, vp, vp, i64, vp],
         "vv_op_softmax_loss": [vp, vp, i64, i32, i64, vp, f32, vp, vp, C.POINTER(f32), C.POINTER(i64)],
+        "vv_linear_loss_set": [vp, vp, i32, i32], "vv_linear_loss_get": [vp, vp, C.POINTER(i32), C.POINTER(i32)],
+        "vv_op_hinge_loss": [vp, vp, i64, i32, i64, vp, i32, f32, vp, C.POINTER(f32), C.POINTER(i64)],
         "vv_op_gemm_tn": [vp, vp, i64, vp, i64, i64, i32, i32, vp],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
@@ -384,9 +386,16 @@ def _dev_ptr(x):
     return C.c_void_p(int(x.value if isinstance(x, C.c_void_p) else x))
 
 
+LIN_LOSS_SOFTMAX, LIN_LOSS_HINGE = 0, 1          # VV_LIN_LOSS_*
+NORM_L1, NORM_L2 = 1, 2                          # VV_NORM_*
+_LIN_LOSSES = {"softmax": LIN_LOSS_SOFTMAX, "hinge": LIN_LOSS_HINGE}
+_NORMS = {"L1": NORM_L1, "L2": NORM_L2}
+_NORM_NAMES = {NORM_L1: "L1", NORM_L2: "L2"}
+
+
 class Linear:
-    """A softmax linear classifier held on the device by an Engine (vv_linear_*): the reference's INNER_PRODUCT layer under
-    SOFTMAX_LOSS, trained by SGD with momentum on a Gallery's embeddings."""
+    """A linear classifier held on the device by an Engine (vv_linear_*): the reference's INNER_PRODUCT layer under SOFTMAX_LOSS or,
+    after set_loss("hinge"), under HINGE_LOSS (one linear SVM per class), trained by SGD with momentum on a Gallery's embeddings."""
 
     def __init__(self, eng, handle, dim, num_classes, bias):
         self.eng, self.h, self.dim, self.num_classes, self.bias = eng, handle, int(dim), int(num_classes), bool(bias)
@@ -397,9 +406,28 @@ class Linear:
             raise VVError("labels must be [n_ref]")
         return lab
 
-    def fit(self, gallery, labels, iters=100, batch=0, lr=0.1, momentum=0.9, weight_decay=0.0, loss_weight=1.0, lr_schedule=None):
+    @property
+    def loss(self):
+        """vv_linear_loss_get: ("softmax", None) or ("hinge", "L1" | "L2") -- the loss fit and grad run."""
+        loss, norm = C.c_int32(), C.c_int32()
+        self.eng._chk(self.eng.L.vv_linear_loss_get(self.eng.h, self.h, C.byref(loss), C.byref(norm)))
+        return ("hinge", _NORM_NAMES[norm.value]) if loss.value == LIN_LOSS_HINGE else ("softmax", None)
+
+    def set_loss(self, loss, norm="L2"):
+        """vv_linear_loss_set: "softmax" or "hinge" (a linear SVM per class: the reference's HINGE_LOSS, norm "L1" or "L2"); sticky on
+        the object, and neither parameters, histories, step counter nor cursor move.  Integers pass through as they are."""
+        code = _LIN_LOSSES.get(loss, loss)
+        nrm = _NORMS.get(norm, norm)
+        if not isinstance(code, int) or not isinstance(nrm, int):
+            raise VVError("set_loss: loss is 'softmax' or 'hinge', norm 'L1' or 'L2'")
+        self.eng._chk(self.eng.L.vv_linear_loss_set(self.eng.h, self.h, code, nrm))
+
+    def fit(self, gallery, labels, iters=100, batch=0, lr=0.1, momentum=0.9, weight_decay=0.0, loss_weight=1.0, lr_schedule=None,
+            loss=None, norm=None):
         """vv_linear_fit: `iters` steps on the gallery's items; returns (loss_trace fp32 [iters], report dict).  lr_schedule: [iters]
-        learning rates that replace lr step by step."""
+        learning rates that replace lr step by step.  loss / norm: set_loss first (it stays set)."""
+        if loss is not None:
+            self.set_loss(loss, "L2" if norm is None else norm)
         lab = self._labels(gallery, labels)
         cfg = _LinearCfg(int(iters), int(batch), lr, momentum, weight_decay, loss_weight)
         sched = None if lr_schedule is None else np.ascontiguousarray(lr_schedule, dtype=np.float32)
@@ -979,6 +1007,17 @@ class Engine:
         loss, correct = C.c_float(), C.c_int64()
         self._chk(self.L.vv_op_softmax_loss(self.h, _dev_ptr(z), int(rows), int(cols), int(pitch), _ptr(lab), loss_weight, _dev_ptr(prob),
                                             _dev_ptr(dz), C.byref(loss), C.byref(correct)))
+        return np.float32(loss.value), int(correct.value)
+
+    def op_hinge_loss(self, z, rows, cols, pitch, labels, norm, loss_weight=1.0, dz=None):
+        """vv_op_hinge_loss on device logits z [rows][pitch] (DevBuf or device pointer); norm "L1" / "L2" (or VV_NORM_*); dz: a DevBuf
+        [rows][pitch], a device pointer or None.  Returns (loss, correct)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if lab.shape[0] != int(rows):
+            raise VVError("op_hinge_loss: labels must be [rows]")
+        loss, correct = C.c_float(), C.c_int64()
+        self._chk(self.L.vv_op_hinge_loss(self.h, _dev_ptr(z), int(rows), int(cols), int(pitch), _ptr(lab), int(_NORMS.get(norm, norm)),
+                                          loss_weight, _dev_ptr(dz), C.byref(loss), C.byref(correct)))
         return np.float32(loss.value), int(correct.value)
 
     def op_gemm_tn(self, A, lda, B, ldb, k, m, n, out):
