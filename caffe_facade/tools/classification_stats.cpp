@@ -17,11 +17,22 @@
 //   --loss hinge trains the same layer under the reference's HINGE_LOSS instead (hinge_loss_layer.cpp:13-77: one linear SVM per
 //   class, vv_linear_loss_set), with --hinge_norm L1 or L2 (the default here, as in the Python binding);
 //   --loss softmax is the default and prints what the tool printed before the flag existed.  Another value of either: the usage, exit 2.
+//   [--shuffle SEED --epochs E]: the steps take their batches from vv_rows_shuffled(SEED, items, E) -- E shuffled epochs of the training
+//   items, consumed from the front and wrapping -- through vv_linear_fit_rows, instead of from the items in file order.
+//   [--folds K --weight_decay a,b,c [--cv_seed S]]: K-fold cross-validation of the weight decay first.  For every decay and every fold of
+//   vv_rows_fold(S, items, K, f): zero parameters, vv_linear_fit_rows on the fold's training rows, vv_linear_scores_rows of its held-out
+//   rows into device memory, vv_classification_stats on them there.  Prints one line per decay, `cv weight_decay = w mean_ap = a
+//   total_accuracy = t` (float sums in fold order over K), then `cv chosen weight_decay = w` (the best mean_ap, a tie to the smaller
+//   decay), then trains on all items with it and prints the usual lines.  The row lists are the library's own (videovec.h), not the
+//   reference's: its data order is the database cursor of data_layer.cpp.
+//   --dump_rows FILE: the list(s) used, one index per line, each under a `# ...` line that names it.
+//   Without these flags the tool prints what it printed before they existed.
 // --prototxt: the layer's parameter is the first CLASSIFICATION_STATS layer of that net file (its num_classes included) instead of
 //   one made here with num_classes = the number of columns.
 // --num_classes / --label_channels: override num_classes / give the label blob K channels -- the layer's shape CHECKs then fire.
 #include <cstring>
 #include <set>
+#include <sstream>
 
 #include "feature_files.hpp"
 
@@ -41,7 +52,11 @@ int main(int argc, char** argv) {
   vector<const char*> pos;
   const char *proto = nullptr, *train_feat = nullptr, *train_lab = nullptr;
   int num_classes = -1, label_channels = 1;
-  bool linear = false, bad_flag = false;
+  bool linear = false, bad_flag = false, shuffle = false;
+  unsigned long long shuffle_seed = 0, cv_seed = 0;
+  int epochs = 0, folds = 0;
+  vector<float> decays;
+  const char* dump_rows = nullptr;
   int32_t lin_loss = VV_LIN_LOSS_SOFTMAX, hinge_norm = VV_NORM_L2;
   vv_linear_cfg lcfg;
   vv_linear_cfg_default(&lcfg);
@@ -52,7 +67,18 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--batch") && i + 1 < argc) lcfg.batch = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--lr") && i + 1 < argc) lcfg.lr = (float)atof(argv[++i]);
     else if (!strcmp(argv[i], "--momentum") && i + 1 < argc) lcfg.momentum = (float)atof(argv[++i]);
-    else if (!strcmp(argv[i], "--weight_decay") && i + 1 < argc) lcfg.weight_decay = (float)atof(argv[++i]);
+    else if (!strcmp(argv[i], "--weight_decay") && i + 1 < argc) {
+      lcfg.weight_decay = (float)atof(argv[++i]);                       // (the first of a list: what a single value has always been)
+      std::stringstream list(argv[i]);
+      string item;
+      decays.clear();
+      while (std::getline(list, item, ',')) decays.push_back((float)atof(item.c_str()));
+    }
+    else if (!strcmp(argv[i], "--shuffle") && i + 1 < argc) { shuffle = true; shuffle_seed = strtoull(argv[++i], nullptr, 10); }
+    else if (!strcmp(argv[i], "--epochs") && i + 1 < argc) epochs = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--folds") && i + 1 < argc) folds = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--cv_seed") && i + 1 < argc) cv_seed = strtoull(argv[++i], nullptr, 10);
+    else if (!strcmp(argv[i], "--dump_rows") && i + 1 < argc) dump_rows = argv[++i];
     else if (!strcmp(argv[i], "--loss") && i + 1 < argc) {
       ++i;
       if (!strcmp(argv[i], "softmax")) lin_loss = VV_LIN_LOSS_SOFTMAX;
@@ -68,10 +94,12 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--label_channels") && i + 1 < argc) label_channels = atoi(argv[++i]);
     else pos.push_back(argv[i]);
   }
+  if (shuffle != (epochs != 0) || ((shuffle || folds || dump_rows) && !linear) || (folds && decays.empty())) bad_flag = true;
   if (pos.size() != 2 || label_channels < 1 || bad_flag) {
     fprintf(stderr, "usage: classification_stats scores.txt labels.txt [--prototxt net.prototxt] [--num_classes K] [--label_channels K]\n"
                     "       classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt\n"
-                    "       classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x] [--momentum m] [--weight_decay w] [--loss softmax|hinge] [--hinge_norm L1|L2]\n");
+                    "       classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x] [--momentum m] [--weight_decay w] [--loss softmax|hinge] [--hinge_norm L1|L2]\n"
+                    "                            [--shuffle SEED --epochs E] [--folds K --weight_decay a,b,c [--cv_seed S]] [--dump_rows FILE]\n");
     return 2;
   }
   Caffe::SetDevice(0);
@@ -102,7 +130,56 @@ int main(int argc, char** argv) {
       vv_linear_report rep;
       VV_CHECK(vv_linear_create(Caffe::ctx(), dim, C, 1, &lin));
       if (lin_loss != VV_LIN_LOSS_SOFTMAX) VV_CHECK(vv_linear_loss_set(Caffe::ctx(), lin, lin_loss, hinge_norm));
-      VV_CHECK(vv_linear_fit(Caffe::ctx(), lin, items, cls.data(), &lcfg, nullptr, nullptr, &rep));
+      FILE* dump = nullptr;
+      if (dump_rows) { dump = fopen(dump_rows, "w"); CHECK(dump) << "Failed to open " << dump_rows; }
+      auto dump_list = [&](const char* what, int f, const vector<int32_t>& rows, int64_t count) {
+        if (!dump) return;
+        if (f >= 0) fprintf(dump, "# fold %d %s\n", f, what); else fprintf(dump, "# %s\n", what);
+        for (int64_t i = 0; i < count; ++i) fprintf(dump, "%d\n", rows[(size_t)i]);
+      };
+      if (folds) {
+        // the held-out scores of one fold: device memory, read there by vv_classification_stats
+        vector<int32_t> train((size_t)tn), held((size_t)tn), held_lab((size_t)tn);
+        vector<float> zero((size_t)C * dim, 0.f);
+        void* held_scores = nullptr;
+        VV_CHECK(vv_dev_alloc(Caffe::ctx(), (size_t)tn * C * sizeof(float), &held_scores));
+        float best_ap = 0.f, best_wd = 0.f;
+        for (size_t w = 0; w < decays.size(); ++w) {
+          vv_linear_cfg fcfg = lcfg;
+          fcfg.weight_decay = decays[w];
+          float ap_sum = 0.f, acc_sum = 0.f;
+          for (int f = 0; f < folds; ++f) {
+            int64_t n_train = 0, n_held = 0;
+            VV_CHECK(vv_rows_fold(cv_seed, tn, folds, f, train.data(), &n_train, held.data(), &n_held));
+            if (w == 0) { dump_list("train", f, train, n_train); dump_list("held", f, held, n_held); }
+            VV_CHECK(vv_linear_put(Caffe::ctx(), lin, zero.data(), zero.data(), zero.data(), zero.data(), 0));
+            VV_CHECK(vv_linear_fit_rows(Caffe::ctx(), lin, items, cls.data(), train.data(), n_train, &fcfg, nullptr, nullptr, &rep));
+            VV_CHECK(vv_linear_scores_rows(Caffe::ctx(), lin, items, held.data(), n_held, static_cast<float*>(held_scores)));
+            for (int64_t i = 0; i < n_held; ++i) held_lab[(size_t)i] = cls[(size_t)held[(size_t)i]];
+            vv_classification_report cr;
+            VV_CHECK(vv_classification_stats(Caffe::ctx(), static_cast<const float*>(held_scores), n_held, C, held_lab.data(), 1, nullptr, nullptr,
+                                             nullptr, &cr));
+            ap_sum += cr.mean_ap; acc_sum += cr.total_accuracy;
+          }
+          const float ap = ap_sum / (float)folds, acc = acc_sum / (float)folds;
+          printf("cv weight_decay = %.9g mean_ap = %.9g total_accuracy = %.9g\n", (double)decays[w], (double)ap, (double)acc);
+          if (w == 0 || ap > best_ap || (ap == best_ap && decays[w] < best_wd)) { best_ap = ap; best_wd = decays[w]; }
+        }
+        printf("cv chosen weight_decay = %.9g\n", (double)best_wd);
+        VV_CHECK(vv_dev_free(Caffe::ctx(), held_scores));
+        VV_CHECK(vv_linear_put(Caffe::ctx(), lin, zero.data(), zero.data(), zero.data(), zero.data(), 0));
+        lcfg.weight_decay = best_wd;
+      }
+      if (shuffle) {
+        CHECK(epochs >= 1 && (int64_t)epochs * tn <= (1ll << 30)) << "--epochs " << epochs;
+        vector<int32_t> rows((size_t)epochs * tn);
+        VV_CHECK(vv_rows_shuffled(shuffle_seed, tn, epochs, rows.data()));
+        dump_list("shuffled", -1, rows, (int64_t)rows.size());
+        VV_CHECK(vv_linear_fit_rows(Caffe::ctx(), lin, items, cls.data(), rows.data(), (int64_t)rows.size(), &lcfg, nullptr, nullptr, &rep));
+      } else {
+        VV_CHECK(vv_linear_fit(Caffe::ctx(), lin, items, cls.data(), &lcfg, nullptr, nullptr, &rep));
+      }
+      if (dump) fclose(dump);
       printf("Linear fit: steps = %lld loss = %.9g -> %.9g\n", (long long)rep.steps, (double)rep.loss_first, (double)rep.loss_last);
       VV_CHECK(vv_linear_scores(Caffe::ctx(), lin, nullptr, fv.data(), n, x.mutable_gpu_data()));
       VV_CHECK(vv_linear_destroy(Caffe::ctx(), lin));

@@ -796,6 +796,43 @@ int vv_linear_loss_get(vv_ctx* ctx, vv_linear* lin, int32_t* loss, int32_t* norm
 int vv_op_hinge_loss(vv_ctx* ctx, const float* z_dev, int64_t rows, int32_t cols, int64_t pitch, const int32_t* labels,
                      int32_t norm, float loss_weight, float* dz_dev, float* loss, int64_t* correct);
 
+/* ---- the same classifier trained on a LIST of gallery rows: shuffled epochs, held-out folds, oversampling.  What this replaces in
+ * the reference is the data order only: DataLayer reads its database through one cursor, in order, and returns to the first record
+ * behind the last (src/caffe/layers/data_layer.cpp:53, 69-70, 180-198), which vv_linear_fit reproduces on a gallery; a shuffled
+ * order exists there only as a database built with convert_imageset --shuffle (tools/convert_imageset.cpp:34-35, 68-72).  The row
+ * lists, their generator, the folds and cross-validation below are this project's own; nothing else of the reference is involved.
+ * rows: host int32 [n_rows], gallery items in any order, repeats allowed, n_rows 1 .. 2^30 (it may exceed n_ref).  labels stays host
+ * [n_ref], BY GALLERY ITEM: the library forms labels[rows[i]] and uploads it beside the list.
+ * vv_linear_fit_rows: vv_linear_fit with the list in place of the gallery's item range.  The list is consumed from position 0: step t
+ * takes count = min(batch, n_rows - pos) consecutive entries, pos returns to 0 behind the last entry; batch == 0: the whole list every
+ * step.  The object's gallery cursor is neither read nor moved; the step counter advances; the sticky loss applies; row blocks and the
+ * scratch limit are vv_linear_fit's with list positions in place of gallery rows.  One synchronisation, at the end.
+ * vv_linear_grad_rows: vv_linear_grad of the batch that is the whole list.  vv_linear_scores_rows: out_dev [n_rows][num_classes]
+ * (DEVICE memory of the caller) = the logits of item rows[i] in row i.
+ * Every result has the bits the contiguous call gives on a gallery built from the listed rows in list order with labels[rows[i]]: the
+ * gathered forms of the two products differ from the contiguous ones in the address of a row and in nothing else.  Read-only option
+ * "last_lin_gather": the form of the last batch's products -- 0 before the first batch, 1 contiguous, 2 gathered.
+ * VV_ERR_ARG, all found on the host before anything is launched or changed (parameters, histories, step counter and cursor stay as
+ * they were): rows NULL; n_rows outside 1 .. 2^30; an entry outside [0, n_ref) -- vv_last_error names its position: no such index ever
+ * reaches a kernel; a label outside [0, num_classes) on a LISTED item; and every check vv_linear_fit / _grad / _scores makes.  The
+ * label of an item that is NOT listed is never read, so a bad label there is accepted: a held-out item may carry a class the
+ * training rows' classifier does not know, or no label at all.
+ * vv_rows_shuffled / vv_rows_fold: the lists, host functions without a context (videovector_amd/csrc/vv_rows.h states the generator
+ * in full: one splitmix64 stream, Fisher-Yates from i = n - 1 down to 1 on the identity, j = the high 64 bits of next() * (i + 1)).
+ * vv_rows_shuffled: out [epochs][n], every epoch a fresh permutation of 0 .. n - 1 from the one stream seeded with seed.
+ * vv_rows_fold: perm = one shuffled epoch of seed; held = perm[floor(fold n / folds) .. floor((fold + 1) n / folds)), train = the rest,
+ * both in perm's order; exactly *n_held and *n_train = n - *n_held entries are written (buffers of n entries always suffice).  Folds
+ * are not stratified: one may lack a class, which vv_classification_stats reports as classes_present.
+ * VV_ERR_ARG: n < 1; epochs < 1; folds outside 2 .. n; fold outside [0, folds); a NULL pointer. */
+int vv_linear_fit_rows(vv_ctx* ctx, vv_linear* lin, vv_gallery* train, const int32_t* labels, const int32_t* rows, int64_t n_rows,
+                       const vv_linear_cfg* cfg, const float* lr_schedule, float* loss_trace, vv_linear_report* out);
+int vv_linear_grad_rows(vv_ctx* ctx, vv_linear* lin, vv_gallery* train, const int32_t* labels, const int32_t* rows, int64_t n_rows,
+                        float loss_weight, float* dW, float* db, float* loss);
+int vv_linear_scores_rows(vv_ctx* ctx, vv_linear* lin, vv_gallery* src, const int32_t* rows, int64_t n_rows, float* out_dev);
+int vv_rows_shuffled(uint64_t seed, int32_t n, int32_t epochs, int32_t* out);
+int vv_rows_fold(uint64_t seed, int32_t n, int32_t folds, int32_t fold, int32_t* train, int64_t* n_train, int32_t* held,
+                 int64_t* n_held);
+
 /* ---- per-layer operators.  The reference's operator interface is Layer<Dtype>::{Forward_gpu, Backward_gpu}
  * (include/caffe/layer.hpp:308-337); its sequential executor (Net::ForwardFromTo / BackwardFromTo, net.cpp:501-578) calls
  * them layer by layer.  Training here runs the fused plan above; these entry points are what the C++ facade's layer classes

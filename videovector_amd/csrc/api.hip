@@ -318,7 +318,7 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
       n == "last_grad_shift" || n == "last_grad_shift_round1" || n == "last_grad_repeat" ||
       n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows" ||
       n == "last_cls_passes" || n == "last_cls_segments" || n == "last_cls_blocks" || n == "last_cls_row_ms" || n == "last_cls_count_ms" ||
-      n == "last_lin_splits" || n == "last_lin_blocks" || n == "last_lin_fwd_ms" || n == "last_lin_softmax_ms" || n == "last_lin_wgrad_ms" || n == "last_lin_update_ms" ||
+      n == "last_lin_splits" || n == "last_lin_blocks" || n == "last_lin_gather" || n == "last_lin_fwd_ms" || n == "last_lin_softmax_ms" || n == "last_lin_wgrad_ms" || n == "last_lin_update_ms" ||
       n == "last_hinge_form" || n == "last_hinge_nonfinite")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
@@ -417,6 +417,7 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "lin_split_rows") *value = c->lin_split_rows;
   else if (n == "last_lin_splits") *value = c->last_lin_splits;
   else if (n == "last_lin_blocks") *value = c->last_lin_blocks;
+  else if (n == "last_lin_gather") *value = c->last_lin_gather;
   else if (n == "last_lin_fwd_ms") *value = c->last_lin_ms[0];
   else if (n == "last_lin_softmax_ms") *value = c->last_lin_ms[1];
   else if (n == "last_lin_wgrad_ms") *value = c->last_lin_ms[2];

@@ -144,11 +144,13 @@ void launch_lin_scores_out(const float* sim, int64_t pitch, int64_t rows, int co
 // [s split_rows, (s + 1) split_rows) and owns slab s; workgroups of one split are neighbours in the grid, so B comes from HBM
 // once per split.  accumulate: the slab's element is read and the sum written back (a later row block of one batch).
 // dbs: the workgroups of the first column tile also add the columns of A over their split's rows, ascending -> dbs [S][m].
-#define LW_LOAD4(dst, M, ld, row, col, ncols, vec)                                                     \
+#define LW_LOAD4(dst, M, ld, row, col, ncols, vec) LW_LOAD4_FROM(dst, M, ld, row, row, col, ncols, vec)
+// (row: the K row that is tested against k_end; src: the row of M it is read from -- `row` itself, or the list's index for it)
+#define LW_LOAD4_FROM(dst, M, ld, row, src, col, ncols, vec)                                           \
   do {                                                                                                 \
     dst = make_float4(0.f, 0.f, 0.f, 0.f);                                                             \
     if ((row) < k_end) {                                                                               \
-      const float* p_ = (M) + (row) * (ld) + (col);                                                    \
+      const float* p_ = (M) + (src) * (ld) + (col);                                                    \
       if ((vec) && (col) + 3 < (ncols)) dst = *(const float4*)p_;                                      \
       else {                                                                                           \
         if ((col) < (ncols)) dst.x = p_[0];                                                            \
@@ -159,7 +161,12 @@ void launch_lin_scores_out(const float* sim, int64_t pitch, int64_t rows, int co
     }                                                                                                  \
   } while (0)
 
-__global__ __launch_bounds__(256) void k_lin_wgrad(LinWgradArgs a) {
+// ROWS: row kk of B is B + rowidx[kk] * ldb (a row list, linear.hip); A stays contiguous, it was produced in list order.  A thread's four
+// indices of a K-tile (ix0 .. ix3: named registers, as the row registers are) are loaded ONE TILE BEFORE the row loads that use them --
+// TWO tiles ahead of the MFMAs -- so the K loop never waits on index -> row.  A row at or past k_end reads no index and stays zero.
+// The fmaf chain, the splits, the slabs and dbs are untouched: the same bits as the contiguous product over the same row values.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void k_lin_wgrad_t(LinWgradArgs a) {
   __shared__ __attribute__((aligned(16))) float sA[LIN_BK * LIN_BM];
   __shared__ __attribute__((aligned(16))) float sB[LIN_BK * LIN_BN];
   const int mtiles = (a.m + LIN_BM - 1) / LIN_BM, ntiles = (a.n + LIN_BN - 1) / LIN_BN, tiles = mtiles * ntiles;
@@ -174,21 +181,48 @@ __global__ __launch_bounds__(256) void k_lin_wgrad(LinWgradArgs a) {
   // a whole tile inside both matrices on 16-byte rows: the K loop's loads carry no column tests
   const bool fast = a.vec_a && a.vec_b && m0 + LIN_BM <= a.m && n0 + LIN_BN <= a.n;
   float4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
+  int64_t ix0 = 0, ix1 = 0, ix2 = 0, ix3 = 0;            // ROWS: the list's entries for rows kr, kr + 8, kr + 16, kr + 24 of the tile staged NEXT
+  // a whole tile inside the split: four plain loads; else each entry under its own row test, so nothing at or past k_end is read
+#define LW_INDEX(k0)                                                                                                        \
+  do {                                                                                                                      \
+    if constexpr (ROWS) {                                                                                                   \
+      const int64_t kr = (k0) + srow;                                                                                       \
+      if ((k0) + LIN_BK <= k_end) { ix0 = a.rowidx[kr]; ix1 = a.rowidx[kr + 8]; ix2 = a.rowidx[kr + 16]; ix3 = a.rowidx[kr + 24]; } \
+      else {                                                                                                                \
+        ix0 = kr < k_end ? a.rowidx[kr] : 0; ix1 = kr + 8 < k_end ? a.rowidx[kr + 8] : 0;                                   \
+        ix2 = kr + 16 < k_end ? a.rowidx[kr + 16] : 0; ix3 = kr + 24 < k_end ? a.rowidx[kr + 24] : 0;                       \
+      }                                                                                                                     \
+    }                                                                                                                       \
+  } while (0)
 #define LW_STAGE(k0)                                                                                                        \
   do {                                                                                                                      \
     const int64_t kr = (k0) + srow;                                                                                         \
     if (fast && (k0) + LIN_BK <= k_end) {                                                                                   \
-      const float* pa = a.A + kr * a.lda + ca; const float* pb = a.B + kr * a.ldb + cb;                                     \
-      ra0 = *(const float4*)pa; ra1 = *(const float4*)(pa + 8 * a.lda); ra2 = *(const float4*)(pa + 16 * a.lda); ra3 = *(const float4*)(pa + 24 * a.lda); \
-      rb0 = *(const float4*)pb; rb1 = *(const float4*)(pb + 8 * a.ldb); rb2 = *(const float4*)(pb + 16 * a.ldb); rb3 = *(const float4*)(pb + 24 * a.ldb); \
+      if constexpr (ROWS) {                                                                                                 \
+        const float* pa = a.A + kr * a.lda + ca;                                                                            \
+        ra0 = *(const float4*)pa; ra1 = *(const float4*)(pa + 8 * a.lda); ra2 = *(const float4*)(pa + 16 * a.lda); ra3 = *(const float4*)(pa + 24 * a.lda); \
+        rb0 = *(const float4*)(a.B + ix0 * a.ldb + cb); rb1 = *(const float4*)(a.B + ix1 * a.ldb + cb);                     \
+        rb2 = *(const float4*)(a.B + ix2 * a.ldb + cb); rb3 = *(const float4*)(a.B + ix3 * a.ldb + cb);                     \
+      } else {                                                                                                              \
+        const float* pa = a.A + kr * a.lda + ca; const float* pb = a.B + kr * a.ldb + cb;                                   \
+        ra0 = *(const float4*)pa; ra1 = *(const float4*)(pa + 8 * a.lda); ra2 = *(const float4*)(pa + 16 * a.lda); ra3 = *(const float4*)(pa + 24 * a.lda); \
+        rb0 = *(const float4*)pb; rb1 = *(const float4*)(pb + 8 * a.ldb); rb2 = *(const float4*)(pb + 16 * a.ldb); rb3 = *(const float4*)(pb + 24 * a.ldb); \
+      }                                                                                                                     \
     } else {                                                                                                                \
       LW_LOAD4(ra0, a.A, a.lda, kr, ca, a.m, a.vec_a); LW_LOAD4(ra1, a.A, a.lda, kr + 8, ca, a.m, a.vec_a);                 \
       LW_LOAD4(ra2, a.A, a.lda, kr + 16, ca, a.m, a.vec_a); LW_LOAD4(ra3, a.A, a.lda, kr + 24, ca, a.m, a.vec_a);           \
-      LW_LOAD4(rb0, a.B, a.ldb, kr, cb, a.n, a.vec_b); LW_LOAD4(rb1, a.B, a.ldb, kr + 8, cb, a.n, a.vec_b);                 \
-      LW_LOAD4(rb2, a.B, a.ldb, kr + 16, cb, a.n, a.vec_b); LW_LOAD4(rb3, a.B, a.ldb, kr + 24, cb, a.n, a.vec_b);           \
+      if constexpr (ROWS) {                                                                                                 \
+        LW_LOAD4_FROM(rb0, a.B, a.ldb, kr, ix0, cb, a.n, a.vec_b); LW_LOAD4_FROM(rb1, a.B, a.ldb, kr + 8, ix1, cb, a.n, a.vec_b); \
+        LW_LOAD4_FROM(rb2, a.B, a.ldb, kr + 16, ix2, cb, a.n, a.vec_b); LW_LOAD4_FROM(rb3, a.B, a.ldb, kr + 24, ix3, cb, a.n, a.vec_b); \
+      } else {                                                                                                              \
+        LW_LOAD4(rb0, a.B, a.ldb, kr, cb, a.n, a.vec_b); LW_LOAD4(rb1, a.B, a.ldb, kr + 8, cb, a.n, a.vec_b);               \
+        LW_LOAD4(rb2, a.B, a.ldb, kr + 16, cb, a.n, a.vec_b); LW_LOAD4(rb3, a.B, a.ldb, kr + 24, cb, a.n, a.vec_b);         \
+      }                                                                                                                     \
     }                                                                                                                       \
   } while (0)
+  LW_INDEX(k_begin);
   LW_STAGE(k_begin);
+  if (k_begin + LIN_BK < k_end) LW_INDEX(k_begin + LIN_BK);
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -208,7 +242,10 @@ __global__ __launch_bounds__(256) void k_lin_wgrad(LinWgradArgs a) {
     *(float4*)&sA[lo] = ra0; *(float4*)&sA[lo + 8 * LIN_BM] = ra1; *(float4*)&sA[lo + 16 * LIN_BM] = ra2; *(float4*)&sA[lo + 24 * LIN_BM] = ra3;
     *(float4*)&sB[lo] = rb0; *(float4*)&sB[lo + 8 * LIN_BN] = rb1; *(float4*)&sB[lo + 16 * LIN_BN] = rb2; *(float4*)&sB[lo + 24 * LIN_BN] = rb3;
     __syncthreads();
-    if (k0 + LIN_BK < k_end) LW_STAGE(k0 + LIN_BK);
+    if (k0 + LIN_BK < k_end) {
+      LW_STAGE(k0 + LIN_BK);
+      if (k0 + 2 * LIN_BK < k_end) LW_INDEX(k0 + 2 * LIN_BK);
+    }
     if (colsum) {
 #pragma unroll
       for (int kk = 0; kk < LIN_BK; ++kk) dbacc += sA[kk * LIN_BM + tid];      // (rows past k_end are zero)
@@ -227,6 +264,7 @@ __global__ __launch_bounds__(256) void k_lin_wgrad(LinWgradArgs a) {
     }
   }
 #undef LW_STAGE
+#undef LW_INDEX
   // C/D map of the 32x32 MFMA: column (n) = lane & 31, row (m) = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
   float* slab = a.slabs + (int64_t)split * a.slab_stride;
 #pragma unroll
@@ -249,10 +287,15 @@ __global__ __launch_bounds__(256) void k_lin_wgrad(LinWgradArgs a) {
   }
 }
 #undef LW_LOAD4
+#undef LW_LOAD4_FROM
+
+constexpr auto k_lin_wgrad = k_lin_wgrad_t<false>;          // the contiguous form: the launch vv_linear_fit and vv_op_gemm_tn have always run
+constexpr auto k_lin_wgrad_rows = k_lin_wgrad_t<true>;
 
 void launch_lin_wgrad(const LinWgradArgs& a, hipStream_t s) {
   const int tiles = ((a.m + LIN_BM - 1) / LIN_BM) * ((a.n + LIN_BN - 1) / LIN_BN);
-  VV_LAUNCH(k_lin_wgrad, dim3((unsigned)(tiles * a.S)), dim3(256), 0, s, a);
+  if (a.rowidx) VV_LAUNCH(k_lin_wgrad_rows, dim3((unsigned)(tiles * a.S)), dim3(256), 0, s, a);
+  else VV_LAUNCH(k_lin_wgrad, dim3((unsigned)(tiles * a.S)), dim3(256), 0, s, a);
 }
 
 // The split plan: a function of (k, m, n, lin_split_rows) and the constants of vv_internal.h, never of the device.

@@ -29,9 +29,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Q [nq][Dp], G [ng][Dp] row-major, Dp a multiple of 32 with zero padding; out [nq][pitch].
 constexpr int RT_LD = RT_BK + 4;
 
-__global__ __launch_bounds__(256) void k_sim_f32(const float* __restrict__ Q, const float* __restrict__ G,
-                                                 float* __restrict__ out, int nq, int ng, int Dp, int64_t pitch,
-                                                 int mtiles) {
+// ROWS: query row i is Q + rowidx[i] * Dp (the linear classifier on a row list, linear.hip) instead of Q + i * Dp; the clamp below is
+// then on the LIST POSITION, so no index past rowidx[nq - 1] is read.  Everything after the eight row pointers is the same code, so
+// out (i, c) has the bits the contiguous form gives for the same row values.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void k_sim_f32_t(const float* __restrict__ Q, const float* __restrict__ G,
+                                                   float* __restrict__ out, int nq, int ng, int Dp, int64_t pitch,
+                                                   int mtiles, const int32_t* __restrict__ rowidx) {
   __shared__ __attribute__((aligned(16))) float sA[RT_BM * RT_LD];
   __shared__ __attribute__((aligned(16))) float sB[RT_BN * RT_LD];
   // query tiles fastest: the workgroups that share a gallery tile run together, so the gallery comes from HBM once per block
@@ -43,8 +47,11 @@ __global__ __launch_bounds__(256) void k_sim_f32(const float* __restrict__ Q, co
   // the K loop's `if` would live in scratch memory).  Rows past the end repeat the last one; they are never stored.
   const int srow = tid >> 3, c4 = tid & 7, lo = srow * RT_LD + c4 * 4;
 #define RT_ROWPTR(M, base, i, n) ((const float4*)((M) + (int64_t)min((base) + srow + 32 * (i), (n)-1) * Dp) + c4)
-  const float4 *ga0 = RT_ROWPTR(Q, m0, 0, nq), *ga1 = RT_ROWPTR(Q, m0, 1, nq), *ga2 = RT_ROWPTR(Q, m0, 2, nq),
-               *ga3 = RT_ROWPTR(Q, m0, 3, nq);
+#define RT_LISTPTR(i) ((const float4*)(Q + (int64_t)rowidx[min(m0 + srow + 32 * (i), nq - 1)] * Dp) + c4)
+  const float4 *ga0, *ga1, *ga2, *ga3;
+  if constexpr (ROWS) { ga0 = RT_LISTPTR(0); ga1 = RT_LISTPTR(1); ga2 = RT_LISTPTR(2); ga3 = RT_LISTPTR(3); }
+  else { ga0 = RT_ROWPTR(Q, m0, 0, nq); ga1 = RT_ROWPTR(Q, m0, 1, nq); ga2 = RT_ROWPTR(Q, m0, 2, nq); ga3 = RT_ROWPTR(Q, m0, 3, nq); }
+#undef RT_LISTPTR
   const float4 *gb0 = RT_ROWPTR(G, n0, 0, ng), *gb1 = RT_ROWPTR(G, n0, 1, ng), *gb2 = RT_ROWPTR(G, n0, 2, ng),
                *gb3 = RT_ROWPTR(G, n0, 3, ng);
 #undef RT_ROWPTR
@@ -105,9 +112,17 @@ __global__ __launch_bounds__(256) void k_sim_f32(const float* __restrict__ Q, co
     }
 }
 
+constexpr auto k_sim_f32 = k_sim_f32_t<false>;              // the contiguous form: what every gallery call has always launched (rowidx is never read)
+constexpr auto k_sim_f32_rows = k_sim_f32_t<true>;
+
 void launch_sim_f32(const float* Q, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s) {
   const int mtiles = (nq + RT_BM - 1) / RT_BM, ntiles = (ng + RT_BN - 1) / RT_BN;
-  hipLaunchKernelGGL(k_sim_f32, dim3((unsigned)(mtiles * ntiles)), dim3(256), 0, s, Q, G, out, nq, ng, Dp, pitch, mtiles);
+  hipLaunchKernelGGL(k_sim_f32, dim3((unsigned)(mtiles * ntiles)), dim3(256), 0, s, Q, G, out, nq, ng, Dp, pitch, mtiles, (const int32_t*)nullptr);
+}
+// rowidx: device [nq], every entry a row of Q (checked on the host by the caller: nothing here can test it)
+void launch_sim_f32_rows(const float* Q, const int32_t* rowidx, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s) {
+  const int mtiles = (nq + RT_BM - 1) / RT_BM, ntiles = (ng + RT_BN - 1) / RT_BN;
+  hipLaunchKernelGGL(k_sim_f32_rows, dim3((unsigned)(mtiles * ntiles)), dim3(256), 0, s, Q, G, out, nq, ng, Dp, pitch, mtiles, rowidx);
 }
 
 // ---------------------------------------------------------------------------------------------- keys

@@ -2,12 +2,16 @@
 // (include/videovec.h: vv_linear_*, vv_op_softmax_loss, vv_op_hinge_loss, vv_op_gemm_tn).  The kernels are in kernels_linear.hip; the logits' product is launch_sim_f32
 // (kernels_retrieval.hip) on W kept as [Cp][Dp] rows, zero-padded the way a gallery is.  Everything is queued on the context's
 // stream; a fit synchronises once, at its end.  None of this reads or writes the training step's state.
+// vv_linear_fit_rows / _grad_rows / _scores_rows run the same steps on a LIST of gallery rows (shuffled epochs, folds; the lists are
+// vv_rows.h's): the reference's counterpart is only its data order, the database cursor of data_layer.cpp:53, 180-198; the lists are
+// this project's own.  check_rows is the host check that keeps a bad index from every kernel.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "vv_ctx.h"
+#include "vv_rows.h"
 
 using namespace vv;
 
@@ -99,16 +103,19 @@ int check_labels(const char* who, const int32_t* labels, int64_t n, int C) {
 
 // One batch: logits, the selected loss (softmax / cross-entropy, or the hinge loss) and the weight-gradient product of rows [first, first + count), row block by row
 // block in order; the slabs then hold the batch's gradient in bp.p.S splits.  ev: NULL, or four events recorded around the legs of
-// the batch (the last row block's).
-int queue_batch(vv_ctx* c, vv_linear* l, const GalleryRows& gr, const int32_t* labels_dev, int64_t first, int64_t count, float loss_weight,
-                const BatchPlan& bp, LinRec* rec, hipEvent_t* ev) {
+// the batch (the last row block's).  rows_dev NULL: the rows are gallery items first .. first + count - 1 and labels_dev is by item.
+// Else `first` and `count` are positions in the list rows_dev (device; every entry checked on the host to lie in [0, n_ref)), labels_dev
+// is by position, and both products run their gathered forms; the loss kernels and everything behind them see no difference.
+int queue_batch(vv_ctx* c, vv_linear* l, const GalleryRows& gr, const int32_t* rows_dev, const int32_t* labels_dev, int64_t first, int64_t count,
+                float loss_weight, const BatchPlan& bp, LinRec* rec, hipEvent_t* ev) {
   const float scale = loss_weight / (float)count;
   for (int blk = 0; blk < bp.blocks; ++blk) {
     const int64_t r0 = first + (int64_t)blk * bp.block_rows, rows = std::min(bp.block_rows, first + count - r0);
-    const float* X = gr.feat + r0 * gr.Dp;
+    const float* X = rows_dev ? gr.feat : gr.feat + r0 * gr.Dp;
     const bool timed = ev && blk == bp.blocks - 1;
     if (timed) HIPCHK(hipEventRecord(ev[0], c->stream));
-    launch_sim_f32(X, l->W, l->z, (int)rows, l->C, l->Dp, l->Cp, c->stream);
+    if (rows_dev) launch_sim_f32_rows(X, rows_dev + r0, l->W, l->z, (int)rows, l->C, l->Dp, l->Cp, c->stream);
+    else launch_sim_f32(X, l->W, l->z, (int)rows, l->C, l->Dp, l->Cp, c->stream);
     if (timed) HIPCHK(hipEventRecord(ev[1], c->stream));
     if (l->loss == VV_LIN_LOSS_HINGE) {
       LinHingeArgs ha;
@@ -131,12 +138,31 @@ int queue_batch(vv_ctx* c, vv_linear* l, const GalleryRows& gr, const int32_t* l
     wa.A = l->dz; wa.lda = l->Cp; wa.B = X; wa.ldb = gr.Dp; wa.k = rows; wa.m = l->Cp; wa.n = l->Dp;
     wa.split_rows = bp.p.split_rows; wa.S = (int)((rows + bp.p.split_rows - 1) / bp.p.split_rows);
     wa.slabs = l->slabs; wa.slab_stride = (int64_t)l->Cp * l->Dp; wa.dbs = l->bias ? l->dbs : nullptr;
-    wa.accumulate = blk > 0; wa.vec_a = 1; wa.vec_b = 1;
+    wa.accumulate = blk > 0; wa.vec_a = 1; wa.vec_b = 1; wa.rowidx = rows_dev ? rows_dev + r0 : nullptr;
     launch_lin_wgrad(wa, c->stream);
     if (timed) HIPCHK(hipEventRecord(ev[3], c->stream));
   }
   HIPCHK(hipGetLastError());
-  c->last_lin_splits = bp.p.S; c->last_lin_blocks = bp.blocks;
+  c->last_lin_splits = bp.p.S; c->last_lin_blocks = bp.blocks; c->last_lin_gather = rows_dev ? 2 : 1;
+  return VV_OK;
+}
+
+// A row list of the caller against the gallery and the labels: every entry in [0, n_ref) and the label of every LISTED item in
+// [0, C).  Nothing has been launched or changed when this refuses; it is the only thing between a bad index and a kernel.
+// lab_out: labels[rows[i]], the list the loss kernels read by position (NULL: no labels wanted).
+int check_rows(const char* who, const int32_t* rows, int64_t n_rows, int64_t n_ref, const int32_t* labels, int C, std::vector<int32_t>* lab_out) {
+  if (n_rows < 1 || n_rows > (1ll << 30)) return vv_fail(VV_ERR_ARG, "%s: n_rows = %lld is outside 1 .. 2^30", who, (long long)n_rows);
+  if (!rows) return vv_fail(VV_ERR_ARG, "%s: rows is NULL", who);
+  for (int64_t i = 0; i < n_rows; ++i)
+    if (rows[i] < 0 || rows[i] >= n_ref)
+      return vv_fail(VV_ERR_ARG, "%s: rows[%lld] = %d is outside the gallery's items 0 .. %lld", who, (long long)i, rows[i], (long long)n_ref - 1);
+  if (!labels) return VV_OK;
+  lab_out->resize((size_t)n_rows);
+  for (int64_t i = 0; i < n_rows; ++i) {
+    const int32_t y = labels[rows[i]];
+    if (y < 0 || y >= C) return vv_fail(VV_ERR_ARG, "%s: label %d of item %d (rows[%lld]) is outside 0 .. %d", who, y, rows[i], (long long)i, C - 1);
+    (*lab_out)[(size_t)i] = y;
+  }
   return VV_OK;
 }
 
@@ -215,22 +241,25 @@ int vv_linear_put(vv_ctx* c, vv_linear* l, const float* W, const float* b, const
   return VV_OK;
 }
 
-int vv_linear_fit(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, const vv_linear_cfg* cfg, const float* lr_schedule,
-                  float* loss_trace, vv_linear_report* out) {
-  NEED(c);
-  if (!train || !labels || !cfg || !out) return vv_fail(VV_ERR_ARG, "vv_linear_fit: NULL argument");
+// vv_linear_fit (rows NULL: the gallery's items from the object's cursor) and vv_linear_fit_rows (the list from position 0, the cursor
+// neither read nor moved): one body, so the two differ in where a batch's rows come from and in nothing else.
+static int fit_common(const char* who, vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, const int32_t* rows, int64_t n_rows,
+                      bool by_rows, const vv_linear_cfg* cfg, const float* lr_schedule, float* loss_trace, vv_linear_report* out) {
+  if (!train || !labels || !cfg || !out) return vv_fail(VV_ERR_ARG, "%s: NULL argument", who);
   GalleryRows gr;
-  { const int rc = check_pair("vv_linear_fit", c, l, train, &gr); if (rc) return rc; }
-  if (cfg->iters < 1) return vv_fail(VV_ERR_ARG, "vv_linear_fit: iters = %d", cfg->iters);
-  if (cfg->batch < 0) return vv_fail(VV_ERR_ARG, "vv_linear_fit: batch = %d", cfg->batch);
-  { const int rc = check_labels("vv_linear_fit", labels, gr.n_ref, l->C); if (rc) return rc; }
-  const int64_t n = gr.n_ref, batch = cfg->batch == 0 ? n : std::min<int64_t>(cfg->batch, n);
-  if (l->cursor >= n) l->cursor = 0;                                       // (a smaller gallery than the last call's)
+  { const int rc = check_pair(who, c, l, train, &gr); if (rc) return rc; }
+  if (cfg->iters < 1) return vv_fail(VV_ERR_ARG, "%s: iters = %d", who, cfg->iters);
+  if (cfg->batch < 0) return vv_fail(VV_ERR_ARG, "%s: batch = %d", who, cfg->batch);
+  std::vector<int32_t> listed;                                             // by_rows: labels[rows[i]]
+  { const int rc = by_rows ? check_rows(who, rows, n_rows, gr.n_ref, labels, l->C, &listed) : check_labels(who, labels, gr.n_ref, l->C); if (rc) return rc; }
+  const int64_t n = by_rows ? n_rows : gr.n_ref, batch = cfg->batch == 0 ? n : std::min<int64_t>(cfg->batch, n);
+  if (!by_rows && l->cursor >= n) l->cursor = 0;                           // (a smaller gallery than the last call's)
+  int64_t pos = by_rows ? 0 : l->cursor;
   // the steps' batches, by the cursor; the scratch is sized for the largest plan among them before anything is queued
   std::vector<int64_t> counts((size_t)cfg->iters);
   std::vector<BatchPlan> plans((size_t)cfg->iters);
   {
-    int64_t cur = l->cursor, rows_max = 0;
+    int64_t cur = pos, rows_max = 0;
     int S_max = 0;
     for (int t = 0; t < cfg->iters; ++t) {
       counts[t] = std::min(batch, n - cur);
@@ -243,23 +272,26 @@ int vv_linear_fit(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* lab
     if (!rc) rc = ensure_slabs(c, l, S_max);
     if (rc) return rc;
   }
-  DevTmp<int32_t> lab;
+  DevTmp<int32_t> lab, idx;
   DevTmp<LinRec> recs;
   HIPCHK(lab.alloc((size_t)n));
+  if (by_rows) HIPCHK(idx.alloc((size_t)n));
   HIPCHK(recs.alloc((size_t)cfg->iters));
-  HIPCHK(hipMemcpyAsync(lab, labels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(lab, by_rows ? listed.data() : labels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  if (by_rows) HIPCHK(hipMemcpyAsync(idx, rows, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   for (int t = 0; t < cfg->iters; ++t) {
     const int64_t count = counts[t];
     const BatchPlan& bp = plans[t];
     const bool timed = t == cfg->iters - 1;
-    const int rc = queue_batch(c, l, gr, lab, l->cursor, count, cfg->loss_weight, bp, recs + t, timed ? l->ev : nullptr);
+    const int rc = queue_batch(c, l, gr, by_rows ? idx.p : nullptr, lab, pos, count, cfg->loss_weight, bp, recs + t, timed ? l->ev : nullptr);
     if (rc) return rc;
     LinUpdArgs u = upd_args(l, bp.p.S);
     u.lr = lr_schedule ? lr_schedule[t] : cfg->lr; u.momentum = cfg->momentum; u.wd = cfg->weight_decay;
     launch_lin_update(u, c->stream);
     if (timed) HIPCHK(hipEventRecord(l->ev[4], c->stream));
-    l->cursor += count;
-    if (l->cursor >= n) l->cursor = 0;
+    pos += count;
+    if (pos >= n) pos = 0;
+    if (!by_rows) l->cursor = pos;
     l->steps += 1;
   }
   HIPCHK(hipGetLastError());
@@ -283,25 +315,44 @@ int vv_linear_fit(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* lab
   return VV_OK;
 }
 
-int vv_linear_grad(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, int64_t first, int64_t count, float loss_weight,
-                   float* dW, float* db, float* loss) {
+int vv_linear_fit(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, const vv_linear_cfg* cfg, const float* lr_schedule,
+                  float* loss_trace, vv_linear_report* out) {
   NEED(c);
-  if (!train || !labels) return vv_fail(VV_ERR_ARG, "vv_linear_grad: NULL argument");
+  return fit_common("vv_linear_fit", c, l, train, labels, nullptr, 0, false, cfg, lr_schedule, loss_trace, out);
+}
+
+int vv_linear_fit_rows(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, const int32_t* rows, int64_t n_rows,
+                       const vv_linear_cfg* cfg, const float* lr_schedule, float* loss_trace, vv_linear_report* out) {
+  NEED(c);
+  return fit_common("vv_linear_fit_rows", c, l, train, labels, rows, n_rows, true, cfg, lr_schedule, loss_trace, out);
+}
+
+// vv_linear_grad (rows NULL: items first .. first + count - 1) and vv_linear_grad_rows (the whole list: first 0, count n_rows)
+static int grad_common(const char* who, vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, const int32_t* rows, bool by_rows,
+                       int64_t first, int64_t count, float loss_weight, float* dW, float* db, float* loss) {
+  if (!train || !labels) return vv_fail(VV_ERR_ARG, "%s: NULL argument", who);
   GalleryRows gr;
-  { const int rc = check_pair("vv_linear_grad", c, l, train, &gr); if (rc) return rc; }
-  if (first < 0 || count < 1 || first > gr.n_ref - count)
-    return vv_fail(VV_ERR_ARG, "vv_linear_grad: rows %lld .. +%lld are outside the gallery's %lld items", (long long)first, (long long)count, (long long)gr.n_ref);
-  { const int rc = check_labels("vv_linear_grad", labels, gr.n_ref, l->C); if (rc) return rc; }
+  { const int rc = check_pair(who, c, l, train, &gr); if (rc) return rc; }
+  std::vector<int32_t> listed;
+  if (by_rows) { const int rc = check_rows(who, rows, count, gr.n_ref, labels, l->C, &listed); if (rc) return rc; }
+  else {
+    if (first < 0 || count < 1 || first > gr.n_ref - count)
+      return vv_fail(VV_ERR_ARG, "%s: rows %lld .. +%lld are outside the gallery's %lld items", who, (long long)first, (long long)count, (long long)gr.n_ref);
+    const int rc = check_labels(who, labels, gr.n_ref, l->C); if (rc) return rc;
+  }
+  const int64_t n_lab = by_rows ? count : gr.n_ref;
   const BatchPlan bp = batch_plan(c, l, count);
   { int rc = ensure_rows(c, l, bp.block_rows); if (!rc) rc = ensure_slabs(c, l, bp.p.S); if (rc) return rc; }
-  DevTmp<int32_t> lab;
+  DevTmp<int32_t> lab, idx;
   DevTmp<LinRec> rec;
   DevTmp<float> g;                                                         // [Cp][Dp] | [Cp]
   const size_t nW = (size_t)l->Cp * l->Dp;
-  HIPCHK(lab.alloc((size_t)gr.n_ref)); HIPCHK(rec.alloc(1)); HIPCHK(g.alloc(nW + l->Cp));
-  HIPCHK(hipMemcpyAsync(lab, labels, (size_t)gr.n_ref * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(lab.alloc((size_t)n_lab)); HIPCHK(rec.alloc(1)); HIPCHK(g.alloc(nW + l->Cp));
+  if (by_rows) HIPCHK(idx.alloc((size_t)count));
+  HIPCHK(hipMemcpyAsync(lab, by_rows ? listed.data() : labels, (size_t)n_lab * 4, hipMemcpyHostToDevice, c->stream));
+  if (by_rows) HIPCHK(hipMemcpyAsync(idx, rows, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(g, 0, (nW + l->Cp) * 4, c->stream));
-  { const int rc = queue_batch(c, l, gr, lab, first, count, loss_weight, bp, rec, nullptr); if (rc) return rc; }
+  { const int rc = queue_batch(c, l, gr, by_rows ? idx.p : nullptr, lab, first, count, loss_weight, bp, rec, nullptr); if (rc) return rc; }
   LinUpdArgs u = upd_args(l, bp.p.S);                                      // the same reduction, without the rule
   u.rule = 0; u.W = g; u.b = g + nW; u.hW = u.hb = nullptr;
   launch_lin_update(u, c->stream);
@@ -312,6 +363,39 @@ int vv_linear_grad(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* la
   if (dW) HIPCHK(hipMemcpy2D(dW, (size_t)l->dim * 4, g, (size_t)l->Dp * 4, (size_t)l->dim * 4, (size_t)l->C, hipMemcpyDeviceToHost));
   if (db) HIPCHK(hipMemcpy(db, g + nW, (size_t)l->C * 4, hipMemcpyDeviceToHost));       // (bias == 0: zeros)
   if (loss) *loss = (float)((double)loss_weight * h.loss_sum / (double)count);
+  return VV_OK;
+}
+
+int vv_linear_grad(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, int64_t first, int64_t count, float loss_weight,
+                   float* dW, float* db, float* loss) {
+  NEED(c);
+  return grad_common("vv_linear_grad", c, l, train, labels, nullptr, false, first, count, loss_weight, dW, db, loss);
+}
+
+int vv_linear_grad_rows(vv_ctx* c, vv_linear* l, vv_gallery* train, const int32_t* labels, const int32_t* rows, int64_t n_rows,
+                        float loss_weight, float* dW, float* db, float* loss) {
+  NEED(c);
+  return grad_common("vv_linear_grad_rows", c, l, train, labels, rows, true, 0, n_rows, loss_weight, dW, db, loss);
+}
+
+int vv_linear_scores_rows(vv_ctx* c, vv_linear* l, vv_gallery* src, const int32_t* rows, int64_t n_rows, float* out_dev) {
+  NEED(c);
+  if (!src || !out_dev) return vv_fail(VV_ERR_ARG, "vv_linear_scores_rows: NULL argument");
+  GalleryRows gr = {};
+  { const int rc = check_pair("vv_linear_scores_rows", c, l, src, &gr); if (rc) return rc; }
+  { const int rc = check_rows("vv_linear_scores_rows", rows, n_rows, gr.n_ref, nullptr, l->C, nullptr); if (rc) return rc; }
+  const int64_t blk = std::min<int64_t>(n_rows, std::max<int64_t>(1, std::min<int64_t>(65536, (int64_t)(GALLERY_SCRATCH_MAX / ((size_t)2 * l->Cp * 4)))));
+  { const int rc = ensure_rows(c, l, blk); if (rc) return rc; }
+  DevTmp<int32_t> idx;
+  HIPCHK(idx.alloc((size_t)n_rows));
+  HIPCHK(hipMemcpyAsync(idx, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
+  for (int64_t q0 = 0; q0 < n_rows; q0 += blk) {                           // (queued in order on one stream: a block's z is read before the next writes it)
+    const int64_t cnt = std::min(blk, n_rows - q0);
+    launch_sim_f32_rows(gr.feat, idx.p + q0, l->W, l->z, (int)cnt, l->C, l->Dp, l->Cp, c->stream);
+    launch_lin_scores_out(l->z, l->Cp, cnt, l->C, l->bias ? l->b : nullptr, out_dev + (size_t)q0 * l->C, c->stream);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));                                 // (the list's device copy lives for this call)
   return VV_OK;
 }
 
@@ -441,6 +525,26 @@ int vv_op_gemm_tn(vv_ctx* c, const float* A, int64_t lda, const float* B, int64_
   HIPCHK(hipStreamSynchronize(c->stream));                                 // (the slabs live for this call)
   c->last_lin_splits = p.S; c->last_lin_blocks = p.blocks;
   return VV_OK;
+}
+
+int vv_rows_shuffled(uint64_t seed, int32_t n, int32_t epochs, int32_t* out) {
+  switch (vv::rows_shuffled(seed, n, epochs, out)) {
+    case ROWS_OK: return VV_OK;
+    case ROWS_BAD_N: return vv_fail(VV_ERR_ARG, "vv_rows_shuffled: n = %d", n);
+    case ROWS_BAD_EPOCHS: return vv_fail(VV_ERR_ARG, "vv_rows_shuffled: epochs = %d", epochs);
+    default: return vv_fail(VV_ERR_ARG, "vv_rows_shuffled: out is NULL");
+  }
+}
+
+int vv_rows_fold(uint64_t seed, int32_t n, int32_t folds, int32_t fold, int32_t* train, int64_t* n_train, int32_t* held, int64_t* n_held) {
+  std::vector<int32_t> perm((size_t)std::max(n, 1));
+  switch (vv::rows_fold(seed, n, folds, fold, perm.data(), train, n_train, held, n_held)) {
+    case ROWS_OK: return VV_OK;
+    case ROWS_BAD_N: return vv_fail(VV_ERR_ARG, "vv_rows_fold: n = %d", n);
+    case ROWS_BAD_FOLDS: return vv_fail(VV_ERR_ARG, "vv_rows_fold: folds = %d is outside 2 .. n = %d", folds, n);
+    case ROWS_BAD_FOLD: return vv_fail(VV_ERR_ARG, "vv_rows_fold: fold = %d is outside 0 .. %d", fold, folds - 1);
+    default: return vv_fail(VV_ERR_ARG, "vv_rows_fold: NULL argument");
+  }
 }
 
 }  // extern "C"

@@ -232,6 +232,7 @@ struct vv_ctx {
   // the splits of the largest row block, the row blocks of one batch, the four legs' device time in the last step of the last fit)
   int lin_split_rows = 0;
   int last_lin_splits = 0, last_lin_blocks = 0;
+  int last_lin_gather = 0;          // "last_lin_gather": the form of the last batch's two products -- 0: none yet, 1: contiguous rows, 2: rows gathered by a list
   double last_lin_ms[4] = {0, 0, 0, 0};
   // k_hinge: "last_hinge_form" (1: 16-byte accesses, 2: element-wise, 0: not launched yet) of the last launch, and the rows with a
   // logit that is not finite in the last vv_op_hinge_loss ("last_hinge_nonfinite"); under the hinge loss the fit's second leg

@@ -640,6 +640,8 @@ constexpr int RT_BM = 128, RT_BN = 128;               // similarity tile (its K,
 struct RankAcc { double ap_sum; int32_t best, acc1, acc5, acc10; };   // ComputeApStats' running values of one query
 static_assert(sizeof(RankAcc) == GALLERY_ACC_BYTES, "vv_gallery_plan.h sizes the per-query accumulator");
 void launch_sim_f32(const float* Q, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s);
+// query row i = Q + rowidx[i] * Dp (rowidx: device [nq], checked on the host); otherwise launch_sim_f32, bit for bit
+void launch_sim_f32_rows(const float* Q, const int32_t* rowidx, const float* G, float* out, int nq, int ng, int Dp, int64_t pitch, hipStream_t s);
 // seg: gallery items per workgroup (a multiple of 1024), S = ceil(ng / seg); part: uint64 [rows][S][k]
 void launch_topk(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, uint64_t* part, int32_t* idx,
                  float* dst, hipStream_t s);
@@ -721,6 +723,7 @@ struct LinWgradArgs {
   float* slabs; int64_t slab_stride;                              // [S][m][n], slab_stride floats apart
   float* dbs;                                                     // [S][m] column sums of A, or NULL
   int accumulate; int vec_a, vec_b;                               // vec_*: base and leading dimension on 16 bytes
+  const int32_t* rowidx = nullptr;                                // NULL, or device [k]: row kk of B is B + rowidx[kk] * ldb (checked on the host)
 };
 struct LinPlan { int64_t split_rows = 0, block_rows = 0; int S = 0, blocks = 0; };    // S: splits of the first (largest) row block
 LinPlan lin_plan(int64_t k, int m, int n, int64_t forced_split_rows);

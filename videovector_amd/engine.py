@@ -204,6 +204,11 @@ def load_library():
         "vv_linear_loss_set": [vp, vp, i32, i32], "vv_linear_loss_get": [vp, vp, C.POINTER(i32), C.POINTER(i32)],
         "vv_op_hinge_loss": [vp, vp, i64, i32, i64, vp, i32, f32, vp, C.POINTER(f32), C.POINTER(i64)],
         "vv_op_gemm_tn": [vp, vp, i64, vp, i64, i64, i32, i32, vp],
+        "vv_linear_fit_rows": [vp, vp, vp, vp, vp, i64, C.POINTER(_LinearCfg), vp, vp, C.POINTER(_LinearReport)],
+        "vv_linear_grad_rows": [vp, vp, vp, vp, vp, i64, f32, vp, vp, C.POINTER(f32)],
+        "vv_linear_scores_rows": [vp, vp, vp, vp, i64, vp],
+        "vv_rows_shuffled": [C.c_uint64, i32, i32, vp],
+        "vv_rows_fold": [C.c_uint64, i32, i32, i32, vp, C.POINTER(i64), vp, C.POINTER(i64)],
         "vv_profile_enable": [vp, C.c_int],
         "vv_profile_select": [vp, C.c_char_p],
         "vv_profile_get": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)],
@@ -386,11 +391,51 @@ def _dev_ptr(x):
     return C.c_void_p(int(x.value if isinstance(x, C.c_void_p) else x))
 
 
+def _rows_chk(rc):
+    if rc != 0:
+        raise VVError(load_library().vv_last_error().decode(), rc)
+
+
+def rows_shuffled(seed, n, epochs=1):
+    """vv_rows_shuffled: int32 [epochs * n], `epochs` permutations of 0 .. n - 1 one after the other, from one splitmix64 stream seeded
+    with `seed` (videovector_amd/csrc/vv_rows.h states the rule).  The list Linear.fit(shuffle_seed=, epochs=) trains on."""
+    out = np.zeros(max(int(n), 0) * max(int(epochs), 0), np.int32)
+    _rows_chk(load_library().vv_rows_shuffled(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(epochs), _ptr(out)))
+    return out
+
+
+def rows_fold(seed, n, folds, fold):
+    """vv_rows_fold: (train, held) int32 row lists of fold `fold` of `folds` over one shuffled epoch of `seed`; not stratified."""
+    train, held = np.zeros(max(int(n), 1), np.int32), np.zeros(max(int(n), 1), np.int32)
+    nt, nh = C.c_int64(), C.c_int64()
+    _rows_chk(load_library().vv_rows_fold(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(folds), int(fold), _ptr(train), C.byref(nt), _ptr(held), C.byref(nh)))
+    return train[:nt.value].copy(), held[:nh.value].copy()
+
+
+def _row_list(rows):
+    r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    return r, (_ptr(r) if r.size else None)
+
+
 LIN_LOSS_SOFTMAX, LIN_LOSS_HINGE = 0, 1          # VV_LIN_LOSS_*
 NORM_L1, NORM_L2 = 1, 2                          # VV_NORM_*
 _LIN_LOSSES = {"softmax": LIN_LOSS_SOFTMAX, "hinge": LIN_LOSS_HINGE}
 _NORMS = {"L1": NORM_L1, "L2": NORM_L2}
 _NORM_NAMES = {NORM_L1: "L1", NORM_L2: "L2"}
+
+
+def cv_mean(v):
+    """The mean cross_validate reports: the float32 sum in fold order over float32(folds)."""
+    s = np.float32(0)
+    for x in np.asarray(v, np.float32):
+        s = np.float32(s + x)
+    return np.float32(s / np.float32(len(v)))
+
+
+def cv_best(results):
+    """The weight decay cross_validate chooses: the largest mean_ap_mean, and of equal ones the smallest decay."""
+    top = max(r["mean_ap_mean"] for r in results)
+    return min(r["weight_decay"] for r in results if r["mean_ap_mean"] == top)
 
 
 class Linear:
@@ -423,9 +468,18 @@ class Linear:
         self.eng._chk(self.eng.L.vv_linear_loss_set(self.eng.h, self.h, code, nrm))
 
     def fit(self, gallery, labels, iters=100, batch=0, lr=0.1, momentum=0.9, weight_decay=0.0, loss_weight=1.0, lr_schedule=None,
-            loss=None, norm=None):
+            loss=None, norm=None, rows=None, epochs=None, shuffle_seed=None):
         """vv_linear_fit: `iters` steps on the gallery's items; returns (loss_trace fp32 [iters], report dict).  lr_schedule: [iters]
-        learning rates that replace lr step by step.  loss / norm: set_loss first (it stays set)."""
+        learning rates that replace lr step by step.  loss / norm: set_loss first (it stays set).
+        rows: vv_linear_fit_rows -- the steps take their batches from this list of gallery items (any order, repeats allowed) from its
+        position 0, wrapping behind its last entry; labels stay [n_ref], by item; the object's cursor does not move.
+        shuffle_seed with epochs: the list is rows_shuffled(shuffle_seed, n_ref, epochs).  rows and shuffle_seed together: ValueError."""
+        if rows is not None and shuffle_seed is not None:
+            raise ValueError("fit: give rows or shuffle_seed, not both")
+        if (shuffle_seed is None) != (epochs is None):
+            raise ValueError("fit: shuffle_seed and epochs go together")
+        if shuffle_seed is not None:
+            rows = rows_shuffled(shuffle_seed, gallery.n_ref, epochs)
         if loss is not None:
             self.set_loss(loss, "L2" if norm is None else norm)
         lab = self._labels(gallery, labels)
@@ -435,23 +489,42 @@ class Linear:
             raise VVError("lr_schedule must be [iters]")
         trace = np.zeros(max(int(iters), 0), np.float32)
         rep = _LinearReport()
-        self.eng._chk(self.eng.L.vv_linear_fit(self.eng.h, self.h, gallery.h, _ptr(lab), C.byref(cfg), _ptr(sched), _ptr(trace), C.byref(rep)))
+        if rows is not None:
+            r, rp = _row_list(rows)
+            self.eng._chk(self.eng.L.vv_linear_fit_rows(self.eng.h, self.h, gallery.h, _ptr(lab), rp, r.size, C.byref(cfg), _ptr(sched), _ptr(trace),
+                                                        C.byref(rep)))
+        else:
+            self.eng._chk(self.eng.L.vv_linear_fit(self.eng.h, self.h, gallery.h, _ptr(lab), C.byref(cfg), _ptr(sched), _ptr(trace), C.byref(rep)))
         return trace, dict(loss_first=np.float32(rep.loss_first), loss_last=np.float32(rep.loss_last),
                            accuracy_last=np.float32(rep.accuracy_last), steps=int(rep.steps), nonfinite_rows=int(rep.nonfinite_rows))
 
-    def grad(self, gallery, labels, first=0, count=None, loss_weight=1.0):
-        """vv_linear_grad: (dW [C][dim], db [C], loss) of the batch [first, first + count) at the current parameters; nothing moves."""
+    def grad(self, gallery, labels, first=0, count=None, loss_weight=1.0, rows=None):
+        """vv_linear_grad: (dW [C][dim], db [C], loss) of the batch [first, first + count) at the current parameters; nothing moves.
+        rows: vv_linear_grad_rows -- the batch is this list of gallery items instead (first / count are not read)."""
         lab = self._labels(gallery, labels)
         count = gallery.n_ref - int(first) if count is None else int(count)
         dW, db = np.zeros((self.num_classes, self.dim), np.float32), np.zeros(self.num_classes, np.float32)
         loss = C.c_float()
+        if rows is not None:
+            r, rp = _row_list(rows)
+            self.eng._chk(self.eng.L.vv_linear_grad_rows(self.eng.h, self.h, gallery.h, _ptr(lab), rp, r.size, loss_weight, _ptr(dW), _ptr(db),
+                                                         C.byref(loss)))
+            return dW, db, np.float32(loss.value)
         self.eng._chk(self.eng.L.vv_linear_grad(self.eng.h, self.h, gallery.h, _ptr(lab), int(first), count, loss_weight, _ptr(dW), _ptr(db),
                                                 C.byref(loss)))
         return dW, db, np.float32(loss.value)
 
-    def scores(self, src, out=None):
+    def scores(self, src, out=None, rows=None):
         """vv_linear_scores: the logits [n][C] of a Gallery's device rows or of a host array [n][dim], as a DevBuf (`out`, or a new one):
-        what Engine.classification_stats reads on the device."""
+        what Engine.classification_stats reads on the device.  rows (src a Gallery): vv_linear_scores_rows -- row i of the result is
+        the logits of item rows[i]."""
+        if rows is not None:
+            if not isinstance(src, Gallery):
+                raise VVError("scores: rows select items of a Gallery")
+            r, rp = _row_list(rows)
+            out = DevBuf(self.eng, (max(r.size, 1), self.num_classes)) if out is None else out
+            self.eng._chk(self.eng.L.vv_linear_scores_rows(self.eng.h, self.h, src.h, rp, r.size, _dev_ptr(out)))
+            return out
         if isinstance(src, Gallery):
             n, gh, q = src.n_ref, src.h, None
         else:
@@ -483,6 +556,32 @@ class Linear:
         ws, bs = (self.num_classes, self.dim), (self.num_classes,)
         W, hW, b, hb = arr(W, ws), arr(hW, ws), arr(b, bs), arr(hb, bs)
         self.eng._chk(self.eng.L.vv_linear_put(self.eng.h, self.h, _ptr(W), _ptr(b), _ptr(hW), _ptr(hb), int(steps)))
+
+    def cross_validate(self, gallery, labels, folds, weight_decays, seed=0, **fit_kw):
+        """k-fold cross-validation of the weight decay (the SVM's C) on the device.  For every weight decay, in the order given, and every
+        fold f of rows_fold(seed, n_ref, folds, f): put zeros with counter 0; fit(rows=train_f, weight_decay=wd, **fit_kw);
+        scores(gallery, rows=held_f) into one device buffer; Engine.classification_stats on it with labels[held_f], the scores read on
+        the device -- nothing of size n x C crosses to the host.  Returns dict(results=[dict(weight_decay, mean_ap [folds],
+        total_accuracy [folds], mean_ap_mean, total_accuracy_mean)], best=the weight decay with the largest mean_ap_mean, a tie going to
+        the smaller decay).  The means are float32 sums in fold order over float32(folds).  Folds are not stratified.
+        The classifier is LEFT HOLDING THE LAST FIT (the last weight decay's last fold): train on all items with `best` afterwards."""
+        lab = self._labels(gallery, labels)
+        n, folds = gallery.n_ref, int(folds)
+        parts = [rows_fold(seed, n, folds, f) for f in range(folds)]
+        buf = DevBuf(self.eng, (max(h.size for _, h in parts), self.num_classes))
+        zW, zb = np.zeros((self.num_classes, self.dim), np.float32), np.zeros(self.num_classes, np.float32)
+        results = []
+        for wd in weight_decays:
+            ap, acc = np.zeros(folds, np.float32), np.zeros(folds, np.float32)
+            for f, (train, held) in enumerate(parts):
+                self.put(W=zW, b=zb, hW=zW, hb=zb, steps=0)
+                self.fit(gallery, lab, rows=train, weight_decay=wd, **fit_kw)
+                self.scores(gallery, out=buf, rows=held)
+                rep = self.eng.classification_stats(buf, lab[held], self.num_classes)[3]
+                ap[f], acc[f] = rep["mean_ap"], rep["total_accuracy"]
+            results.append(dict(weight_decay=wd, mean_ap=ap, total_accuracy=acc, mean_ap_mean=cv_mean(ap), total_accuracy_mean=cv_mean(acc)))
+        buf.free()
+        return dict(results=results, best=cv_best(results))
 
     def close(self):
         if self.h is not None and getattr(self.eng, "h", None):
