@@ -27,6 +27,12 @@
 //   reference's: its data order is the database cursor of data_layer.cpp.
 //   --dump_rows FILE: the list(s) used, one index per line, each under a `# ...` line that names it.
 //   Without these flags the tool prints what it printed before they existed.
+//   classification_stats features.txt labels.txt --knn K train_features.txt train_labels.txt [--knn_weighting uniform|exp] [--knn_temperature T]
+// --knn: as --prototypes, but the classifier is the k-nearest-neighbour vote: the training items become a device gallery,
+//   vv_gallery_knn_scores counts the class votes of every test item's K nearest training items on the device (uniform weights, or
+//   exp((s_j - s_0) / T) with T = 0.07 unless given) into device memory and the layer reads them there.  Prints
+//   `kNN: k = K weighting = uniform|exp form = F` in front of the statistics, F the neighbour lists' form ("last_nearest_form": 1 streaming,
+//   2 selection).  A K outside 1 .. 2048, another weighting, a T that is not a positive finite number: the usage, exit 2.
 // --prototxt: the layer's parameter is the first CLASSIFICATION_STATS layer of that net file (its num_classes included) instead of
 //   one made here with num_classes = the number of columns.
 // --num_classes / --label_channels: override num_classes / give the label blob K channels -- the layer's shape CHECKs then fire.
@@ -52,7 +58,10 @@ int main(int argc, char** argv) {
   vector<const char*> pos;
   const char *proto = nullptr, *train_feat = nullptr, *train_lab = nullptr;
   int num_classes = -1, label_channels = 1;
-  bool linear = false, bad_flag = false, shuffle = false;
+  bool linear = false, bad_flag = false, shuffle = false, knn_flag = false;
+  int knn = 0;
+  int32_t knn_weighting = VV_KNN_UNIFORM;
+  float knn_temperature = 0.07f;
   unsigned long long shuffle_seed = 0, cv_seed = 0;
   int epochs = 0, folds = 0;
   vector<float> decays;
@@ -63,6 +72,21 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--prototypes") && i + 2 < argc) { train_feat = argv[i + 1]; train_lab = argv[i + 2]; i += 2; }
     else if (!strcmp(argv[i], "--linear") && i + 2 < argc) { train_feat = argv[i + 1]; train_lab = argv[i + 2]; linear = true; i += 2; }
+    else if (!strcmp(argv[i], "--knn") && i + 3 < argc) {
+      char* end = nullptr;
+      const long v = strtol(argv[i + 1], &end, 10);
+      if (end == argv[i + 1] || *end || v < 1 || v > 2048) bad_flag = true;
+      knn = (int)v; train_feat = argv[i + 2]; train_lab = argv[i + 3]; i += 3;
+    } else if (!strcmp(argv[i], "--knn_weighting") && i + 1 < argc) {
+      ++i; knn_flag = true;
+      if (!strcmp(argv[i], "uniform")) knn_weighting = VV_KNN_UNIFORM;
+      else if (!strcmp(argv[i], "exp")) knn_weighting = VV_KNN_EXP;
+      else bad_flag = true;
+    } else if (!strcmp(argv[i], "--knn_temperature") && i + 1 < argc) {
+      char* end = nullptr;
+      knn_temperature = strtof(argv[++i], &end); knn_flag = true;
+      if (end == argv[i] || *end || !(knn_temperature > 0.f) || knn_temperature > 3.4028234e38f) bad_flag = true;
+    }
     else if (!strcmp(argv[i], "--iters") && i + 1 < argc) lcfg.iters = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--batch") && i + 1 < argc) lcfg.batch = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--lr") && i + 1 < argc) lcfg.lr = (float)atof(argv[++i]);
@@ -95,11 +119,13 @@ int main(int argc, char** argv) {
     else pos.push_back(argv[i]);
   }
   if (shuffle != (epochs != 0) || ((shuffle || folds || dump_rows) && !linear) || (folds && decays.empty())) bad_flag = true;
+  if ((knn_flag && !knn) || (knn && linear)) bad_flag = true;
   if (pos.size() != 2 || label_channels < 1 || bad_flag) {
     fprintf(stderr, "usage: classification_stats scores.txt labels.txt [--prototxt net.prototxt] [--num_classes K] [--label_channels K]\n"
                     "       classification_stats features.txt labels.txt --prototypes train_features.txt train_labels.txt\n"
                     "       classification_stats features.txt labels.txt --linear train_features.txt train_labels.txt [--iters N] [--batch B] [--lr x] [--momentum m] [--weight_decay w] [--loss softmax|hinge] [--hinge_norm L1|L2]\n"
-                    "                            [--shuffle SEED --epochs E] [--folds K --weight_decay a,b,c [--cv_seed S]] [--dump_rows FILE]\n");
+                    "                            [--shuffle SEED --epochs E] [--folds K --weight_decay a,b,c [--cv_seed S]] [--dump_rows FILE]\n"
+                    "       classification_stats features.txt labels.txt --knn K train_features.txt train_labels.txt [--knn_weighting uniform|exp] [--knn_temperature T]\n");
     return 2;
   }
   Caffe::SetDevice(0);
@@ -183,6 +209,12 @@ int main(int argc, char** argv) {
       printf("Linear fit: steps = %lld loss = %.9g -> %.9g\n", (long long)rep.steps, (double)rep.loss_first, (double)rep.loss_last);
       VV_CHECK(vv_linear_scores(Caffe::ctx(), lin, nullptr, fv.data(), n, x.mutable_gpu_data()));
       VV_CHECK(vv_linear_destroy(Caffe::ctx(), lin));
+    } else if (knn) {
+      VV_CHECK(vv_gallery_knn_scores(Caffe::ctx(), items, cls.data(), C, fv.data(), n, nullptr, knn, knn_weighting, knn_temperature,
+                                     x.mutable_gpu_data(), nullptr));
+      double form = 0;
+      VV_CHECK(vv_gallery_get(items, "last_nearest_form", &form));
+      printf("kNN: k = %d weighting = %s form = %d\n", knn, knn_weighting == VV_KNN_EXP ? "exp" : "uniform", (int)form);
     } else {
       VV_CHECK(vv_gallery_pool_by_id(Caffe::ctx(), items, &means));
       VV_CHECK(vv_gallery_scores(Caffe::ctx(), means, fv.data(), n, x.mutable_gpu_data()));

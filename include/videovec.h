@@ -645,6 +645,44 @@ int vv_gallery_nearest(vv_ctx* ctx, vv_gallery* gallery, const float* q, int32_t
  * gallery created with ids).  idx / dist: host [n_ref][k]. */
 int vv_gallery_nearest_self(vv_ctx* ctx, vv_gallery* gallery, int32_t k, int exclude_same_id, int32_t* idx, float* dist);
 
+/* ---- k-nearest-neighbour classifier: the class votes of the lists above, counted on the device.  HAS NO REFERENCE COUNTERPART (the
+ * reference's nearest lists stop at five items and are only printed).  The lists are not downloaded and the scores stay in device
+ * memory, ready for vv_classification_stats(scores_on_device = 1).
+ * labels: host int32 [n_ref], the class of every gallery item, each in [0, num_classes); 1 <= num_classes <= 4096; 1 <= k <= 2048.
+ * The neighbour list of a query is exactly the one vv_gallery_nearest / vv_gallery_nearest_self returns for the same arguments: the
+ * same stored floats, the same eligibility (q_ids; self form j != i; exclude_same_id), ascending (d, g), the lowest gallery index at
+ * a tie on the threshold, the same two forms chosen by "nearest_select_min_k".  m <= k: its filled slots.
+ * Weight of list position j, with s_j = -0.5f d_j (exact):
+ *   VV_KNN_UNIFORM  w_j = 1
+ *   VV_KNN_EXP      w_j = expf((s_j - s_0) / T), s_0 the similarity at position 0, T = temperature > 0 in fp32; the difference and the
+ *                   quotient are each rounded once in fp32, expf is the device library's default one.  So w_0 = 1 and every w_j is in
+ *                   [0, 1], whatever the scale of the embeddings.
+ * score[i][c] = V_c / V: V_c the sum of w_j over the positions with labels[idx_j] == c, V the sum over all m positions -- a posterior
+ * estimate that sums to 1 up to rounding in every row with m >= 1, comparable across rows (per-class AP needs that).
+ *   UNIFORM: V_c and V are integers <= 2048, counted in integer bins; score = (float)V_c / (float)m: one rounding, fully determined.
+ *   EXP: fp32 sums in a fixed order, no floating-point atomics.  V_c adds the class's weights in ascending list position, starting
+ *     from the first.  V adds the V_c: thread t of 256 adds those of classes t P .. t P + P - 1 (P = ceil(num_classes / 256)) in
+ *     ascending class starting from +0, and the 256 partials fold by the tree x[t] += x[t + o], o = 128, 64 .. 1.  A class without a
+ *     vote adds +0, so a row whose neighbours share one class scores exactly 1.0 there and +0 elsewhere.  Two calls give identical
+ *     bits, and so do the two list forms.
+ *   m == 0 (no eligible item): the row is all +0.0f.  Every element of out_dev is written.
+ * out_dev: DEVICE fp32 [n_q][num_classes] of this context owned by the caller (vv_dev_alloc), as for vv_gallery_scores; rows are
+ * stored 16 bytes at a time where out_dev is on 16 bytes and num_classes % 4 == 0, element by element otherwise, with identical
+ * results (read-only option "last_knn_form": 1 / 2 at the last launch, 0 before the first).  n_used: NULL, or host [n_q]: every
+ * row's m.  temperature is read under VV_KNN_EXP only.  vv_gallery_knn_scores_self: every gallery item as a query (n_q = n_ref):
+ * leave-one-item-out, with exclude_same_id leave-one-id-out.
+ * VV_ERR_ARG, with nothing launched or written: a NULL argument (q_ids and n_used may be NULL); a gallery of another context; n_q < 1;
+ * k or num_classes out of range; a label outside [0, num_classes); an unknown weighting; under VV_KNN_EXP a temperature that is not
+ * finite or <= 0; q_ids / exclude_same_id on a gallery created without ids.
+ * "last_knn_vote_ms" of vv_gallery_get: the device time of the vote launches of the last of these calls; "last_nearest_form",
+ * "last_sim_ms" and "last_device_ms" describe these calls too.  The calls synchronise. */
+#define VV_KNN_UNIFORM 0
+#define VV_KNN_EXP 1
+int vv_gallery_knn_scores(vv_ctx* ctx, vv_gallery* gallery, const int32_t* labels, int32_t num_classes, const float* q, int32_t n_q,
+                          const int32_t* q_ids, int32_t k, int32_t weighting, float temperature, float* out_dev, int32_t* n_used);
+int vv_gallery_knn_scores_self(vv_ctx* ctx, vv_gallery* gallery, const int32_t* labels, int32_t num_classes, int32_t k,
+                               int exclude_same_id, int32_t weighting, float temperature, float* out_dev, int32_t* n_used);
+
 /* ---- class-level leave-one-out statistics on a gallery: RetrievalStatsLayer (src/caffe/layers/retrieval_stats_layer.cpp).
  * vv_gallery_pool_by_id: video_level_retrieval (:165-198).  A new gallery with one item per distinct id of `gallery`, its row the
  * sum over the id's items, in ascending item index, of (1 / count) x_i in fp32 (the reference's weight matrix, :193, :197-198),

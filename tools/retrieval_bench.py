@@ -19,6 +19,12 @@
       last_device_ms - last_sim_ms (uploads of the query blocks and downloads of the lists included), next to top-k's.  Then
       nearest_self(64) on galleries of the --self-n sizes (the class-level benchmark's two).  Writes the JSON it prints to
       profiles/nearest_<nq>x<ng>x<dim>.json (--out: elsewhere) as well.
+  python tools/retrieval_bench.py --knn 32,256,2048 [--nq 4096 --ng 1000000 --dim 512] [--classes 15] [--out FILE]
+      the k-NN classifier (vv_gallery_knn_scores, uniform weights, labels = id % classes): nearest(K), the yardstick, and
+      knn_scores(K) alternate call by call in one process on the shape and with the box probes of --nearest; per call the library's
+      device events, the vote launches' own time ("last_knn_vote_ms") and, as the host sees it, the wall time around each blocking
+      call (nearest returns the lists to the host, knn_scores leaves the scores on the device).  Writes the JSON it prints to
+      profiles/knn_<nq>x<ng>x<dim>.json (--out: elsewhere) as well.
 
 Inputs are seeded: unit rows around `nid` random centres, ids = the centre's index (the generator of tests/gallery_ref.py, drawn in
 float32 blocks so that a million rows need no float64 copy)."""
@@ -110,6 +116,56 @@ def nearest_bench(eng, a):
     return out
 
 
+def knn_bench(eng, a):
+    ks = [int(x) for x in a.knn.split(",")]
+    G, gid, cen = make(a.ng, a.dim, a.nid, a.noise, 5)
+    Q, qid, _ = make(a.nq, a.dim, a.nid, a.noise, 6, cen)
+    lab = (gid % a.classes).astype(np.int32)
+    g = eng.gallery(G, gid)
+    buf = vv.engine.DevBuf(eng, (a.nq, a.classes))
+    box = {"before": eng.box_probe()}
+    res = []
+    for k in ks:
+        t = dict(nearest=dict(dev=[], sim=[], wall=[]), knn=dict(dev=[], sim=[], wall=[], vote=[]))
+        for r in range(a.warmup + a.reps):
+            for name, call in (("nearest", lambda: g.nearest(Q, k)), ("knn", lambda: g.knn_scores(Q, lab, a.classes, k, out=buf))):
+                t0 = time.perf_counter()
+                got = call()
+                wall = (time.perf_counter() - t0) * 1e3
+                if r >= a.warmup:
+                    t[name]["dev"].append(g.get("last_device_ms")); t[name]["sim"].append(g.get("last_sim_ms")); t[name]["wall"].append(wall)
+                    if name == "knn":
+                        t[name]["vote"].append(g.get("last_knn_vote_ms"))
+                if name == "nearest":
+                    lists = got
+        # the last pair of calls: the device's votes against the lists the yardstick returned
+        votes = np.stack([np.bincount(lab[row], minlength=a.classes) for row in lists[0]]).astype(np.float32) / np.float32(k)
+        e = dict(k=k, form=int(g.get("last_nearest_form")), store_form=int(eng.get_option("last_knn_form")), scratch_bytes=g.scratch_bytes,
+                 scores_equal_votes_of_nearest=bool(np.array_equal(buf.get(), votes)))
+        for name in ("nearest", "knn"):
+            dev, sim = t[name]["dev"], t[name]["sim"]
+            e[name + "_ms"] = stats(dev); e[name + "_similarity_ms"] = stats(sim); e[name + "_wall_ms"] = stats(t[name]["wall"])
+            e[name + "_other_ms"] = stats([d - s for d, s in zip(dev, sim)])
+        e["knn_vote_ms"] = stats(t["knn"]["vote"])
+        e["knn_over_nearest"] = e["knn_ms"]["median"] / e["nearest_ms"]["median"]
+        e["knn_over_nearest_wall"] = e["knn_wall_ms"]["median"] / e["nearest_wall_ms"]["median"]
+        res.append(e)
+    blocks = -(-a.nq // int(g.get("query_block")))
+    buf.free()
+    g.close()
+    box["after"] = eng.box_probe()
+    out = dict(bench="knn", nq=a.nq, ng=a.ng, dim=a.dim, classes=a.classes, weighting="uniform", reps=a.reps, warmup=a.warmup, query_blocks=blocks,
+               yardstick="vv_gallery_nearest at the same k, alternating call by call with vv_gallery_knn_scores in one process",
+               timer="device events inside the library (last_device_ms, last_sim_ms, last_knn_vote_ms); *_other_ms = device - similarity "
+                     "per call; *_wall_ms: host wall clock around the blocking call",
+               votes=res, box=box)
+    path = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                 "knn_%dx%dx%d.json" % (a.nq, a.ng, a.dim))
+    with open(path, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=4096)
@@ -127,6 +183,7 @@ def main():
     ap.add_argument("--videos", type=int, default=600)
     ap.add_argument("--no-within-batch", action="store_true")
     ap.add_argument("--nearest", type=str, default=None, metavar="K[,K...]")
+    ap.add_argument("--knn", type=str, default=None, metavar="K[,K...]")
     ap.add_argument("--self-n", type=str, default="8192,200000")
     ap.add_argument("--self-reps", type=int, default=5)
     ap.add_argument("--out", type=str, default=None)
@@ -134,6 +191,10 @@ def main():
     eng = vv.Engine(0, "f16")
     if a.nearest:
         out = nearest_bench(eng, a)
+    elif a.knn:
+        if not 1 <= a.classes <= 4096:
+            ap.error("--classes must be 1 .. 4096 with --knn")
+        out = knn_bench(eng, a)
     elif a.class_stats:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
         from class_stats_ref import make_input

@@ -319,7 +319,7 @@ int vv_set_option(vv_ctx* c, const char* name, double value) {
       n == "h16_fallback" || n == "h16_flagged_step" || n == "h16_flagged_saturated" || n == "h16_flagged_faint_rows" ||
       n == "last_cls_passes" || n == "last_cls_segments" || n == "last_cls_blocks" || n == "last_cls_row_ms" || n == "last_cls_count_ms" ||
       n == "last_lin_splits" || n == "last_lin_blocks" || n == "last_lin_gather" || n == "last_lin_fwd_ms" || n == "last_lin_softmax_ms" || n == "last_lin_wgrad_ms" || n == "last_lin_update_ms" ||
-      n == "last_hinge_form" || n == "last_hinge_nonfinite")
+      n == "last_hinge_form" || n == "last_hinge_nonfinite" || n == "last_knn_form")
     return fail(VV_ERR_ARG, "vv_set_option: '%s' is read-only (what the launchers last chose)", name);
   if (n == "dedup") return vv_set_dedup(c, iv);
   if (n == "seg_bwd") { c->seg_bwd = iv != 0; return VV_OK; }
@@ -424,6 +424,7 @@ int vv_get_option(vv_ctx* c, const char* name, double* value) {
   else if (n == "last_lin_update_ms") *value = c->last_lin_ms[3];
   else if (n == "last_hinge_form") *value = c->last_hinge_form;
   else if (n == "last_hinge_nonfinite") *value = (double)c->last_hinge_nonfinite;
+  else if (n == "last_knn_form") *value = c->last_knn_form;
   else if (n == "last_fwd_tile_rows") *value = c->ko.last_fwd_tile_rows;
   else if (n == "last_wgrad_splits") *value = c->ko.last_wgrad_splits;
   else if (n == "last_update_form") *value = c->ko.last_update_form;

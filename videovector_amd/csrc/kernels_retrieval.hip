@@ -728,6 +728,157 @@ void launch_select(const float* dist, int64_t pitch, int rows, int ng, int k, in
   hipLaunchKernelGGL(k_sel_sort, dim3(rows), dim3(64 * 4), 0, s, cand, st, k, idx, dst);
 }
 
+// ---------------------------------------------------------------------------------------------- k-NN vote
+// vv_gallery_knn_scores*: the class votes of the neighbour lists the two forms above left on the device.  grid (rows), one workgroup
+// per query row.  idx / dist: the block's lists, `stride` entries between two rows, filled slots first, idx -1 behind them;
+// labels: int32 [ng], every entry in [0, C) (checked on the host); out: row r at out + r * C, EVERY element written (a row without
+// a filled slot: +0.0f); m_out: int32 [rows], the filled slots.  C <= KNN_MAX_CLASSES, k <= RT_CHUNK.
+// VEC: 16-byte stores (out on 16 bytes and C % 4 == 0, the launcher's test); otherwise one float per store, the same values.
+constexpr int KNN_MAX_CLASSES = 4096;
+
+// filled slots of this thread's share of the list, added up over the workgroup into *sm (zero and visible before the call)
+__device__ inline void knn_count_filled(int mine, int* sm) {
+  const int w = (int)__popcll(__ballot(mine != 0));
+  if ((threadIdx.x & 63) == 0 && w) atomicAdd(sm, w);
+}
+
+// UNIFORM: integer bins in LDS (exact, order-free), score = (float)V_c / (float)m: one rounding.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_knn_vote(const int32_t* __restrict__ idx, int64_t stride, int k,
+                                                  const int32_t* __restrict__ labels, int C, float* __restrict__ out,
+                                                  int32_t* __restrict__ m_out) {
+  __shared__ __attribute__((aligned(16))) uint32_t sb[KNN_MAX_CLASSES];
+  __shared__ int sm;
+  const int row = blockIdx.x, tid = threadIdx.x;
+  for (int c = tid; c < C; c += 256) sb[c] = 0;
+  if (tid == 0) sm = 0;
+  __syncthreads();
+  const int32_t* li = idx + (int64_t)row * stride;
+  for (int base = 0; base < k; base += 256) {                      // (uniform trip count: the ballot sees whole waves)
+    const int j = base + tid;
+    const int g = j < k ? li[j] : -1;
+    if (g >= 0) {
+      const uint32_t c = (uint32_t)labels[g];
+      if (c < (uint32_t)C) atomicAdd(&sb[c], 1u);
+    }
+    knn_count_filled(g >= 0, &sm);
+  }
+  __syncthreads();
+  const int m = sm;
+  const float fm = (float)m;
+  float* o = out + (int64_t)row * C;
+  if (VEC) {
+    for (int c4 = tid; c4 < C / 4; c4 += 256) {
+      const uint4 v = *(const uint4*)&sb[c4 * 4];
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (m) r = make_float4((float)v.x / fm, (float)v.y / fm, (float)v.z / fm, (float)v.w / fm);
+      *(float4*)(o + c4 * 4) = r;
+    }
+  } else {
+    for (int c = tid; c < C; c += 256) o[c] = m ? (float)sb[c] / fm : 0.f;
+  }
+  if (tid == 0) m_out[row] = m;
+}
+
+// the weight of list position j under VV_KNN_EXP: s = -0.5f d (exact), the difference and the quotient each rounded once
+__device__ inline float knn_exp_weight(float d, float d0, float T) {
+#pragma clang fp contract(off)
+  const float s = -0.5f * d, s0 = -0.5f * d0;
+  const float diff = s - s0;
+  const float arg = diff / T;
+  return expf(arg);
+}
+
+// EXP: fp32 sums in a FIXED order, no floating-point atomics.  The filled positions are sorted by (class, position) with the
+// file's bitonic sort; the thread at the head of a class's run adds the run's weights serially, so V_c is the sum of its weights
+// in ASCENDING LIST POSITION.  V: thread t adds V_c over its ceil(C / 256) consecutive classes in ascending class, and the 256
+// partials are folded by the fixed tree the rank kernels use (t += t + o, o = 128 .. 1).  Classes without a vote add +0.0f, so a
+// row whose neighbours share one class has V == V_c and scores exactly 1.0 there.  w_0 = expf(0) = 1: V >= 1 wherever m >= 1.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_knn_vote_exp(const int32_t* __restrict__ idx, const float* __restrict__ dist,
+                                                      int64_t stride, int k, float T, const int32_t* __restrict__ labels, int C,
+                                                      float* __restrict__ out, int32_t* __restrict__ m_out) {
+  __shared__ uint64_t sk[RT_CHUNK];                                // (class << 32 | position), ascending; RT_NOKEY behind the filled ones
+  __shared__ float sw[RT_CHUNK];                                   // weight by list position
+  __shared__ __attribute__((aligned(16))) float sv[KNN_MAX_CLASSES];
+  __shared__ float sp[256];
+  __shared__ int sm;
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int32_t* li = idx + (int64_t)row * stride;
+  const float* ld = dist + (int64_t)row * stride;
+  int npad = 1;
+  while (npad < k) npad <<= 1;                                     // k <= RT_CHUNK, a power of two
+  for (int c = tid; c < C; c += 256) sv[c] = 0.f;
+  if (tid == 0) sm = 0;
+  __syncthreads();
+  const float d0 = ld[0];                                          // (slot 0 exists: k >= 1; read as a weight only where m >= 1)
+  for (int base = 0; base < npad; base += 256) {                   // npad < 256: one round, the threads past it hold nothing
+    const int j = base + tid;
+    const int g = j < k ? li[j] : -1;
+    uint64_t key = RT_NOKEY;
+    float w = 0.f;
+    if (g >= 0) {
+      const uint32_t c = (uint32_t)labels[g];
+      if (c < (uint32_t)C) { key = ((uint64_t)c << 32) | (uint32_t)j; w = knn_exp_weight(ld[j], d0, T); }
+    }
+    if (j < npad) { sk[j] = key; sw[j] = w; }
+    knn_count_filled(key != RT_NOKEY, &sm);
+  }
+  __syncthreads();
+  rt_bitonic(sk, npad);
+  const int m = sm;
+  for (int p = tid; p < m; p += 256) {
+    const uint64_t key = sk[p];
+    const uint32_t c = (uint32_t)(key >> 32);
+    if (p > 0 && (uint32_t)(sk[p - 1] >> 32) == c) continue;       // not the head of its class's run
+    float acc = sw[(uint32_t)key];
+    for (int t = p + 1; t < m; ++t) {
+      const uint64_t kt = sk[t];
+      if ((uint32_t)(kt >> 32) != c) break;
+      acc += sw[(uint32_t)kt];
+    }
+    sv[c] = acc;                                                   // one head per class: no other thread writes sv[c]
+  }
+  __syncthreads();
+  const int per = (C + 255) / 256;
+  float part = 0.f;
+  for (int c = tid * per; c < min(C, (tid + 1) * per); ++c) part += sv[c];
+  sp[tid] = part;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sp[tid] += sp[tid + o];
+    __syncthreads();
+  }
+  const float V = sp[0];
+  float* o = out + (int64_t)row * C;
+  if (VEC) {
+    for (int c4 = tid; c4 < C / 4; c4 += 256) {
+      const float4 v = *(const float4*)&sv[c4 * 4];
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (m) r = make_float4(v.x / V, v.y / V, v.z / V, v.w / V);
+      *(float4*)(o + c4 * 4) = r;
+    }
+  } else {
+    for (int c = tid; c < C; c += 256) o[c] = m ? sv[c] / V : 0.f;
+  }
+  if (tid == 0) m_out[row] = m;
+}
+
+// -> the store form: 1 the 16-byte one, 2 element-wise
+int launch_knn_vote(const int32_t* idx, const float* dist, int64_t stride, int rows, int k, int exp_weights, float T,
+                    const int32_t* labels, int C, float* out, int32_t* m_out, hipStream_t s) {
+  const bool vec = ((uintptr_t)out & 15) == 0 && C % 4 == 0;
+  const dim3 grid(rows), wg(256);
+  if (exp_weights) {
+    if (vec) hipLaunchKernelGGL(k_knn_vote_exp<true>, grid, wg, 0, s, idx, dist, stride, k, T, labels, C, out, m_out);
+    else hipLaunchKernelGGL(k_knn_vote_exp<false>, grid, wg, 0, s, idx, dist, stride, k, T, labels, C, out, m_out);
+  } else {
+    if (vec) hipLaunchKernelGGL(k_knn_vote<true>, grid, wg, 0, s, idx, stride, k, labels, C, out, m_out);
+    else hipLaunchKernelGGL(k_knn_vote<false>, grid, wg, 0, s, idx, stride, k, labels, C, out, m_out);
+  }
+  return vec ? 1 : 2;
+}
+
 // ---------------------------------------------------------------------------------------------- pooling by id
 // Video-level retrieval (retrieval_stats_layer.cpp:189-198): out[u] = sum over the items of id u of (1 / count_u) x_i, the
 // weight multiplied into every term as the reference's weight matrix does, items in ascending index (pos_idx groups them so).

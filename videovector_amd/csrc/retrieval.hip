@@ -3,6 +3,7 @@
 // of the context these calls read the nearest_select_min_k option, and vv_gallery_from_table the embedding helpers of api.hip.  None
 // of this reads or writes the training step's state.
 #include <algorithm>
+#include <cmath>
 #include <limits>
 #include <string>
 #include <unordered_map>
@@ -84,8 +85,8 @@ struct vv_gallery : GalleryShape {       // pitch, Dp, seg, S, qb_max: gallery_s
   // the selection form of vv_gallery_nearest* only (it shares skeys: its candidate keys): allocated by its first call
   uint32_t *sel_st = nullptr, *sel_hist = nullptr, *sel_segh = nullptr; int32_t* nn_idx = nullptr; float* nn_dist = nullptr;
   size_t scratch_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // call begin / end, similarity begin / end (of the block in flight)
-  double last_sim_ms = 0, last_device_ms = 0; int last_passes = 0;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // call begin / end, similarity begin / end, vote begin / end (of the block in flight)
+  double last_sim_ms = 0, last_device_ms = 0, last_knn_vote_ms = 0; int last_passes = 0;
   int last_nearest_form = 0;             // vv_gallery_nearest*: 1 streaming, 2 selection; 0 before the first call
 };
 
@@ -135,7 +136,7 @@ static int gallery_init(vv_ctx* c, vv_gallery* g, int64_t n_ref, int32_t dim, co
   if (g->qb_max < 1) return fail(VV_ERR_ARG, "vv_gallery: %lld reference items do not fit one query row into the scratch limit", (long long)n_ref);
   HIPCHK(hipMalloc((void**)&g->feat, (size_t)n_ref * g->Dp * 4));
   if (g->Dp != dim) HIPCHK(hipMemsetAsync(g->feat, 0, (size_t)n_ref * g->Dp * 4, c->stream));
-  for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&g->ev[i]));
+  for (int i = 0; i < 6; ++i) HIPCHK(hipEventCreate(&g->ev[i]));
   if (!ref_ids) return VV_OK;
   // the id -> index lists, once (the reference re-reads every reference id for every query: ComputeApStats :73-75)
   std::vector<int32_t> order((size_t)n_ref);
@@ -154,7 +155,7 @@ static int gallery_init(vv_ctx* c, vv_gallery* g, int64_t n_ref, int32_t dim, co
 static void gallery_release(vv_gallery* g) {
   gallery_free_scratch(g);
   dfree(g->feat); dfree(g->ref_ids); dfree(g->pos_idx); dfree(g->cls); dfree(g->cpos);
-  for (int i = 0; i < 4; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
+  for (int i = 0; i < 6; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
   delete g;
 }
 
@@ -228,6 +229,7 @@ int vv_gallery_get(const vv_gallery* g, const char* name, double* value) {
   else if (n == "last_nearest_form") *value = g->last_nearest_form;
   else if (n == "last_sim_ms") *value = g->last_sim_ms;
   else if (n == "last_device_ms") *value = g->last_device_ms;
+  else if (n == "last_knn_vote_ms") *value = g->last_knn_vote_ms;
   else return fail(VV_ERR_ARG, "vv_gallery_get: unknown name '%s'", name);
   return VV_OK;
 }
@@ -295,12 +297,21 @@ int vv_gallery_topk(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, int32
 // and no item is eligible for itself; q_ids (host queries) / exclude (self form): only items of another id are eligible.
 // k below the context's "nearest_select_min_k": the streaming top-k with that predicate; otherwise the selection form.  Either
 // way the lists are read off the floats k_sim_f32 stored in the block's scratch rows.
+// The block's lists go to one of two sinks: the host arrays idx / dist (vote == NULL), or k_knn_vote, which reads them where they are
+// and writes the block's rows of vote->out_dev (vv_gallery_knn_scores*: the lists are not downloaded).
+struct KnnVote {
+  const int32_t* labels_dev;             // [n_ref], every entry in [0, C)
+  int C, exp_weights; float T;
+  float* out_dev;                        // [n_q][C]
+  int32_t* n_used;                       // host [n_q] or NULL
+};
 static int gallery_nearest_run(vv_ctx* c, vv_gallery* g, const float* q, int n_q, const int32_t* q_ids, bool exclude, int k,
-                               int32_t* idx, float* dist) {
+                               int32_t* idx, float* dist, const KnnVote* vote = nullptr) {
   const bool self = q == nullptr, select = k >= c->nearest_select_min_k;
-  int rc = gallery_call_begin(c, g, "vv_gallery_nearest", n_q, false, select);
+  int rc = gallery_call_begin(c, g, vote ? "vv_gallery_knn_scores" : "vv_gallery_nearest", n_q, false, select);
   if (rc) return rc;
   g->last_nearest_form = select ? 2 : 1;
+  if (vote) g->last_knn_vote_ms = 0;
   const int ng = (int)g->n_ref;
   for (int q0 = 0; q0 < n_q; q0 += g->qb_cap) {
     const int rows = std::min(g->qb_cap, n_q - q0);
@@ -324,10 +335,24 @@ static int gallery_nearest_run(vv_ctx* c, vv_gallery* g, const float* q, int n_q
                            g->out_dist, c->stream);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(idx + (size_t)q0 * k, d_idx, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(dist + (size_t)q0 * k, d_dist, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (vote) {                                                         // both forms leave rows of k entries; pcount: the rows' m
+      HIPCHK(hipEventRecord(g->ev[4], c->stream));
+      c->last_knn_form = launch_knn_vote(d_idx, d_dist, k, rows, k, vote->exp_weights, vote->T, vote->labels_dev, vote->C,
+                                         vote->out_dev + (size_t)q0 * vote->C, g->pcount, c->stream);
+      HIPCHK(hipEventRecord(g->ev[5], c->stream));
+      HIPCHK(hipGetLastError());
+      if (vote->n_used) HIPCHK(hipMemcpyAsync(vote->n_used + q0, g->pcount, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    } else {
+      HIPCHK(hipMemcpyAsync(idx + (size_t)q0 * k, d_idx, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(dist + (size_t)q0 * k, d_dist, (size_t)rows * k * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));                            // (the next block's upload reuses qdev)
     if ((rc = gallery_block_done(c, g))) return rc;
+    if (vote) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
+      g->last_knn_vote_ms += ms;
+    }
   }
   return gallery_call_end(c, g);
 }
@@ -350,6 +375,44 @@ int vv_gallery_nearest_self(vv_ctx* c, vv_gallery* g, int32_t k, int exclude_sam
   if (exclude_same_id && !g->ref_ids) return fail(VV_ERR_ARG, "vv_gallery_nearest_self: exclude_same_id, but the gallery was created without ids");
   VV_ENTER(c);
   return gallery_nearest_run(c, g, nullptr, (int)g->n_ref, nullptr, exclude_same_id != 0, k, idx, dist);
+}
+
+// What the two k-NN calls share: every refusal (nothing is launched or written before the last of them has passed), the labels'
+// upload -- one [n_ref] device array per call -- and the run.  q == NULL: the self form.
+static int gallery_knn_run(vv_ctx* c, vv_gallery* g, const char* who, const int32_t* labels, int num_classes, const float* q, int n_q,
+                           const int32_t* q_ids, bool exclude, int k, int weighting, float temperature, float* out_dev, int32_t* n_used) {
+  if (g->ctx != c) return fail(VV_ERR_ARG, "%s: the gallery belongs to another context", who);
+  if (n_q < 1) return fail(VV_ERR_ARG, "%s: n_q = %d", who, n_q);
+  if (k < 1 || k > RT_CHUNK) return fail(VV_ERR_ARG, "%s: k = %d is outside 1 .. %d", who, k, RT_CHUNK);
+  if (num_classes < 1 || num_classes > 4096) return fail(VV_ERR_ARG, "%s: num_classes = %d is outside 1 .. 4096", who, num_classes);
+  if (weighting != VV_KNN_UNIFORM && weighting != VV_KNN_EXP) return fail(VV_ERR_ARG, "%s: unknown weighting %d", who, weighting);
+  if (weighting == VV_KNN_EXP && !(std::isfinite(temperature) && temperature > 0.f))
+    return fail(VV_ERR_ARG, "%s: temperature = %g is not a finite positive number", who, (double)temperature);
+  if ((q_ids || exclude) && !g->ref_ids) return fail(VV_ERR_ARG, "%s: q_ids / exclude_same_id, but the gallery was created without ids", who);
+  for (int64_t i = 0; i < g->n_ref; ++i)
+    if (labels[i] < 0 || labels[i] >= num_classes)
+      return fail(VV_ERR_ARG, "%s: labels[%lld] = %d is outside 0 .. %d", who, (long long)i, labels[i], num_classes - 1);
+  VV_ENTER(c);
+  DevTmp<int32_t> dl;
+  HIPCHK(dl.alloc((size_t)g->n_ref));
+  HIPCHK(hipMemcpyAsync(dl, labels, (size_t)g->n_ref * 4, hipMemcpyHostToDevice, c->stream));
+  const KnnVote vote{dl, num_classes, weighting == VV_KNN_EXP, temperature, out_dev, n_used};
+  const int rc = gallery_nearest_run(c, g, q, n_q, q_ids, exclude, k, nullptr, nullptr, &vote);
+  if (rc) (void)hipStreamSynchronize(c->stream);                        // (dl is released on return)
+  return rc;
+}
+
+int vv_gallery_knn_scores(vv_ctx* c, vv_gallery* g, const int32_t* labels, int32_t num_classes, const float* q, int32_t n_q,
+                          const int32_t* q_ids, int32_t k, int32_t weighting, float temperature, float* out_dev, int32_t* n_used) {
+  if (!c || !g || !labels || !q || !out_dev) return fail(VV_ERR_ARG, "vv_gallery_knn_scores: NULL argument");
+  return gallery_knn_run(c, g, "vv_gallery_knn_scores", labels, num_classes, q, n_q, q_ids, false, k, weighting, temperature, out_dev, n_used);
+}
+
+int vv_gallery_knn_scores_self(vv_ctx* c, vv_gallery* g, const int32_t* labels, int32_t num_classes, int32_t k, int exclude_same_id,
+                               int32_t weighting, float temperature, float* out_dev, int32_t* n_used) {
+  if (!c || !g || !labels || !out_dev) return fail(VV_ERR_ARG, "vv_gallery_knn_scores_self: NULL argument");
+  return gallery_knn_run(c, g, "vv_gallery_knn_scores_self", labels, num_classes, nullptr, (int)g->n_ref, nullptr, exclude_same_id != 0, k,
+                         weighting, temperature, out_dev, n_used);
 }
 
 int vv_gallery_rank_stats(vv_ctx* c, vv_gallery* g, const float* q, int32_t n_q, const int32_t* q_ids, vv_rank_stats* out,

@@ -239,6 +239,7 @@ struct vv_ctx {
   // ("last_lin_softmax_ms") is k_hinge's device time
   int last_hinge_form = 0;
   int64_t last_hinge_nonfinite = 0;
+  int last_knn_form = 0;            // k_knn_vote: "last_knn_form" (1: 16-byte stores, 2: element-wise, 0: not launched yet) of the last launch
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

@@ -665,6 +665,11 @@ void launch_topk_eligible(const float* dist, int64_t pitch, int rows, int ng, in
 void launch_select(const float* dist, int64_t pitch, int rows, int ng, int k, int seg, int S, const int32_t* ids,
                    const int32_t* own, int self0, uint32_t* st, uint32_t* hist, uint32_t* segh, uint64_t* cand, int32_t* idx,
                    float* dst, hipStream_t s);
+// k-NN vote (vv_gallery_knn_scores*) over the lists either form above left on the device: idx / dist with `stride` entries between
+// two rows; labels: int32 [ng] in [0, C), C <= 4096; out: row r at out + r * C; m_out: int32 [rows], the filled slots of every row.
+// exp_weights: VV_KNN_EXP with temperature T, else VV_KNN_UNIFORM (dist and T unread).  Returns the store form: 1 16-byte, 2 element-wise.
+int launch_knn_vote(const int32_t* idx, const float* dist, int64_t stride, int rows, int k, int exp_weights, float T,
+                    const int32_t* labels, int C, float* out, int32_t* m_out, hipStream_t s);
 // cpos: item indices grouped by class; ids / cls: id and class of every item; skeys: uint64 [rows][RT_CHUNK];
 // bins: uint32 [rows][3][RT_CHUNK], zero on entry
 void launch_class_pass(const float* dist, int64_t pitch, int rows, int ng, int seg, int S, const int32_t* cpos,

@@ -193,6 +193,8 @@ def load_library():
         "vv_gallery_nearest": [vp, vp, vp, i32, vp, i32, vp, vp],
         "vv_gallery_nearest_self": [vp, vp, i32, C.c_int, vp, vp],
         "vv_gallery_scores": [vp, vp, vp, i32, vp],
+        "vv_gallery_knn_scores": [vp, vp, vp, i32, vp, i32, vp, i32, i32, f32, vp, vp],
+        "vv_gallery_knn_scores_self": [vp, vp, vp, i32, i32, C.c_int, i32, f32, vp, vp],
         "vv_classification_stats": [vp, vp, i64, i32, vp, C.c_int, vp, vp, vp, C.POINTER(_ClassificationReport)],
         "vv_linear_create": [vp, i32, i32, C.c_int, C.POINTER(vp)], "vv_linear_destroy": [vp, vp],
         "vv_linear_get": [vp, vp, vp, vp, vp, vp, C.POINTER(i64)], "vv_linear_put": [vp, vp, vp, vp, vp, vp, i64],
@@ -240,6 +242,9 @@ def load_library():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+KNN_WEIGHTINGS = {"uniform": 0, "exp": 1}      # VV_KNN_UNIFORM, VV_KNN_EXP
 
 
 class Gallery:
@@ -331,6 +336,46 @@ class Gallery:
         ptr = out_dev.ptr if isinstance(out_dev, DevBuf) else C.c_void_p(int(out_dev.value if isinstance(out_dev, C.c_void_p) else out_dev))
         self.eng._chk(self.eng.L.vv_gallery_scores(self.eng.h, self.h, _ptr(q), q.shape[0], ptr))
         return out_dev
+
+    def _knn_args(self, labels, num_classes, n_q, weighting, out, n_used):
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (self.n_ref,):
+            raise VVError("knn_scores: labels must be [n_ref]")
+        if isinstance(weighting, str):                    # (an integer goes to the library as it is: VV_KNN_*)
+            if weighting not in KNN_WEIGHTINGS:
+                raise VVError("knn_scores: weighting must be one of %s" % ", ".join(sorted(KNN_WEIGHTINGS)))
+            weighting = KNN_WEIGHTINGS[weighting]
+        if out is None:
+            out = DevBuf(self.eng, (n_q, max(int(num_classes), 1)))
+        used = np.zeros(n_q, np.int32) if n_used else None
+        return lab, int(weighting), out, used
+
+    def knn_scores(self, q, labels, num_classes, k, q_ids=None, weighting="uniform", temperature=0.07, out=None, n_used=False):
+        """The k-nearest-neighbour classifier's scores of q [n_q][dim] in DEVICE memory (vv_gallery_knn_scores): a DevBuf of
+        [n_q][num_classes] floats, score[i][c] = the share of class c among the weights of query i's k <= 2048 nearest items (the
+        lists of nearest(q, k, q_ids)); labels [n_ref]: the class of every item, in 0 .. num_classes - 1 (<= 4096).  weighting
+        "uniform": every neighbour counts 1; "exp": exp((s_j - s_0) / temperature) with s the dot products.  out: a DevBuf (or a
+        device pointer) to write instead of a new one.  n_used=True: returns (scores, m int32 [n_q]), m the neighbours each row had.
+        The result feeds Engine.classification_stats without a host round trip."""
+        q = self._queries(q)
+        qid = None
+        if q_ids is not None:
+            qid = np.ascontiguousarray(q_ids, dtype=np.int32)
+            if qid.shape != (q.shape[0],):
+                raise VVError("knn_scores: q_ids must be [n_q]")
+        lab, w, out, used = self._knn_args(labels, num_classes, q.shape[0], weighting, out, n_used)
+        self.eng._chk(self.eng.L.vv_gallery_knn_scores(self.eng.h, self.h, _ptr(lab), int(num_classes), _ptr(q), q.shape[0], _ptr(qid),
+                                                       int(k), w, float(temperature), _dev_ptr(out), _ptr(used)))
+        return (out, used) if n_used else out
+
+    def knn_scores_self(self, labels, num_classes, k, exclude_same_id=False, weighting="uniform", temperature=0.07, out=None,
+                        n_used=False):
+        """As knn_scores with every gallery item as a query against the others (vv_gallery_knn_scores_self, the lists of
+        nearest_self): leave-one-item-out k-NN, with exclude_same_id leave-one-id-out.  [n_ref][num_classes]."""
+        lab, w, out, used = self._knn_args(labels, num_classes, self.n_ref, weighting, out, n_used)
+        self.eng._chk(self.eng.L.vv_gallery_knn_scores_self(self.eng.h, self.h, _ptr(lab), int(num_classes), int(k),
+                                                            int(bool(exclude_same_id)), w, float(temperature), _dev_ptr(out), _ptr(used)))
+        return (out, used) if n_used else out
 
     def rows(self):
         """The gallery's fp32 rows [n_ref][dim], downloaded from the device."""
