@@ -1855,7 +1855,7 @@ void launch_sgd(int prec, const SgdArgs& a, hipStream_t s, float* vW, float* vb)
   const bool vec = a.F % 4 == 0;
   ko().last_update_form = vec ? 1 : 2;    // ("last_update_form": the chunked and the sharded update pass here too, F % 4 == 0 both)
   const dim3 grid(a.chunked ? a.n_blk : SGD_BLOCKS), block(256);
-  if (a.rule.solver_type == VV_SOLVER_ADAM) {          // the two-history instantiations (api.hip provides the second history)
+  if (a.rule.solver_type == VV_SOLVER_ADAM) {          // the two-history instantiations (solver.hip provides the second history)
     if (!vW || !vb) { fprintf(stderr, "launch_sgd: an Adam rule without its second history\n"); abort(); }      // (a caller's bug: never a null store on the device)
     SgdArgs2 a2; (SgdArgs&)a2 = a; a2.vW = vW; a2.vb = vb;
     if (prec == 0) { if (vec) VV_LAUNCH((k_sgd<F16, true, SgdArgs2>), grid, block, 0, s, a2); else VV_LAUNCH((k_sgd<F16, false, SgdArgs2>), grid, block, 0, s, a2); }

@@ -1,8 +1,10 @@
-// vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the fused training step), ops.hip (the
-// per-layer operators), retrieval.hip, classify.hip and linear.hip (the evaluation paths).  Internal.
+// vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the fused training step), solver.hip (the
+// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip and linear.hip (the
+// evaluation paths); below it, what these files call of one another.  Internal.
 #pragma once
 #include <cstdarg>
 #include <cstdio>
+#include <ctime>
 #include <map>
 #include <string>
 #include <vector>
@@ -258,7 +260,7 @@ struct vv_ctx {
   int32_t upd_seq = 0;              // sequence number of the last overlapped update (what w_gate[c] reaches when chunk c is done)
   int32_t* w_gate = nullptr;        // device [W_CHUNKS_MAX * W_GATE_STRIDE]: one flag per 128-B line
   int n_chunks = 3;                 // F-chunks of the overlapped update (env VV_COMM_CHUNKS, 1 .. 4)
-  int chunk_kt[5] = {0, 0, 0, 0, 0};    // first K-tile of each chunk for the current Fp (chunk_plan)
+  int chunk_kt[5] = {0, 0, 0, 0, 0};    // first K-tile of each chunk for the current Fp (vv_chunk_plan)
   int32_t* pub_count = nullptr;     // device: arrival counter of the publishing SGD kernels (behind the flags)
   hipEvent_t ev_chunk0 = nullptr;   // the first F-chunk's reduction is done (recorded by fb_impl: GradBuffer::chunk0_event)
   int32_t* gate_err = nullptr; int32_t* gate_err_dev = nullptr;     // pinned + mapped: a gated forward gave up waiting
@@ -273,7 +275,6 @@ struct vv_ctx {
   std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;    // events are reused across profiling sessions
 };
 
-
 // ops.hip keeps per-context scratch for the per-layer INNER_PRODUCT operators; vv_destroy releases it
 void vv_ops_release(vv_ctx* c);
 // api.hip: orders the compute stream behind an overlapped parameter update still on the communication stream
@@ -287,3 +288,44 @@ int vv_upd_pending_guard(vv_ctx* c, const char* who);
 int vv_embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int relu, int l2norm, float* dout);
 int vv_embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu, int l2norm,
                          float* dout);
+// api.hip: a step configuration the library can run, with the context's vv_solver_ext_set values where the rule reads them
+int vv_check_cfg(vv_ctx* c, const vv_step_cfg* cfg);
+// api.hip: the per-batch buffers for this shape (a new shape starts the gradient scale's steering and the distinct-row hints afresh)
+int vv_ensure_batch(vv_ctx* c, int B, int C, int Nn);
+// api.hip: the F-chunks of the overlapped update into c->chunk_kt; returns their number
+int vv_chunk_plan(vv_ctx* c);
+// api.hip: a sharded update's rows of W and the histories gathered from their owners (a collective)
+int vv_gather_params(vv_ctx* c);
+// api.hip: arm / collect a pair of timing events around the launcher called in between (PROFILED)
+void vv_prof_begin(vv_ctx* c, const char* name, hipEvent_t* e0, hipEvent_t* e1);
+void vv_prof_end(vv_ctx* c, const char* name, hipEvent_t e0, hipEvent_t e1);
+// VV_TRACE_HOST=<ms>: report every launcher call that keeps the HOST longer than that (first use of a kernel variant,
+// a runtime pool growing, ...) -- the GPU queue runs dry behind such a call.
+inline double host_now_ms() {
+  timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
+  return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+#define PROFILED(c, name, call)                 \
+  do {                                          \
+    hipEvent_t e0_, e1_;                        \
+    vv_prof_begin(c, name, &e0_, &e1_);         \
+    const double th_ = (c)->trace_host_ms >= 0 ? host_now_ms() : 0.0; \
+    call;                                       \
+    if ((c)->trace_host_ms >= 0) { const double d_ = host_now_ms() - th_; if (d_ > (c)->trace_host_ms) fprintf(stderr, "[vv host] %s: %.3f ms (call %llu)\n", name, d_, (unsigned long long)c->iter); } \
+    vv_prof_end(c, name, e0_, e1_);             \
+  } while (0)
+// what every entry point that trains or replaces the parameters says under vv_ema_use(1)
+inline constexpr const char* kEmaInUse = "the averaged parameters are in use (vv_ema_use(1)): this call trains or replaces the parameters -- vv_ema_use(0) first";
+// solver.hip: the solver's parameters of a step as the update kernels read them; the seed of vv_params_set cleared behind a launch that
+// consumed it; the moving average's allocation and start, and its release
+vv::SolverRule vv_solver_rule(const vv_step_cfg& cfg, float momentum2, float rms_decay, int64_t t = 0);
+hipError_t vv_clear_wmax_seed(vv_ctx* c, bool consumed, hipStream_t s);
+int vv_ema_init(vv_ctx* c);
+void vv_ema_release(vv_ctx* c);
+// solver.hip: what the forward-only readers (vv_forward, vv_embed, vv_embed_mean, vv_gallery_from_table) read: the training parameters'
+// 16-bit copy, bias and scales, or under vv_ema_use(1) the average's (packed on demand, on the context's stream)
+struct ParamView { const uint16_t* Wh; const float* b; const vv::Scales* scales; };
+int vv_param_view(vv_ctx* c, ParamView* v);
+// solver.hip: why no schedule but sync can be chosen now -- the message of the first active feature among gradient clipping, the gradient
+// bank and the moving average -- or nullptr
+const char* vv_sync_only_feature(const vv_ctx* c);

@@ -126,7 +126,7 @@ struct FwdArgs {
   int32_t* seq_host = nullptr; // host-mapped word that receives `seq` (the step's index batch has been consumed), or null
   int32_t seq = 0;
   int abl = 0;                 // timing studies only (VV_ABLATE): selects an ablated instantiation of the phase-staggered kernel
-  // Data-parallel overlap (api.hip: vv_apply_update): the parameter update of the PREVIOUS step may still be arriving --
+  // Data-parallel overlap (solver.hip: vv_apply_update): the parameter update of the PREVIOUS step may still be arriving --
   // F-chunk by F-chunk, each chunk all-reduced and applied on the communication stream -- while this kernel runs.
   // gate[c * W_GATE_STRIDE] holds the sequence number of the last update whose chunk c (K-tiles [gate_kt[c], gate_kt[c+1])
   // of W) is complete; a workgroup waits for it to reach gate_seq before it issues its first load of a W tile of chunk c.
@@ -141,7 +141,7 @@ struct FwdArgs {
   // Only the segment-wise path sets it (api.hip); everything else keeps fp32 rows.
   int h16 = 0;
 };
-constexpr int W_CHUNKS_MAX = 4; // F-chunks of the overlapped update at most (chunk-major gradient buffer, api.hip: chunk_plan)
+constexpr int W_CHUNKS_MAX = 4; // F-chunks of the overlapped update at most (chunk-major gradient buffer, api.hip: vv_chunk_plan)
 constexpr int W_GATE_STRIDE = 32;   // ints between two chunk flags: a 128-B line each (the waiting workgroups poll them)
 
 // Segment-wise backward (de-duplicated batches): the score kernel keeps the gradient of an instance in factored form
@@ -288,7 +288,7 @@ struct SegsumArgs {
 };
 
 // The solver's parameters as the three update kernels read them -- k_sgd, k_reduce_sgd and the weight-gradient GEMM's UPD epilogue, which
-// must give bit-identical parameters -- and the rule itself (api.hip: solver_rule fills it from a vv_step_cfg and the context's
+// must give bit-identical parameters -- and the rule itself (solver.hip: vv_solver_rule fills it from a vv_step_cfg and the context's
 // vv_solver_ext_set values).
 struct SolverRule {
   float rate, momentum, weight_decay;
@@ -409,7 +409,7 @@ struct ReduceArgs {
   int n_chunks = 0;                  // > 0: dW is stored CHUNK-MAJOR -- n_chunks column blocks, block c = all D rows of columns
   int chunk_c0[5] = {0, 0, 0, 0, 0}; //   [chunk_c0[c], chunk_c0[c+1]) at float offset D chunk_c0[c], row stride = the block's width
                                      //   (boundaries multiples of 4) -- so that every F-chunk is one contiguous all-reduce buffer
-  int shard_rows = 0;                // > 0: the gradient buffer is SHARD-MAJOR (the sharded update, api.hip): D / shard_rows shards, shard s =
+  int shard_rows = 0;                // > 0: the gradient buffer is SHARD-MAJOR (the sharded update, solver.hip): D / shard_rows shards, shard s =
                                      //   rows [s shard_rows, (s + 1) shard_rows) of dW (row-major) followed by their shard_rows entries of db --
                                      //   one reduce-scatter message per rank, and k_sgd sees its shard as a small [dW | db] buffer of its own
   int parts = 3;                     // bit 0: the dW rows, bit 1: db and the loss scalars
