@@ -69,9 +69,9 @@ def test_shape_rules_defined_once():
 
 
 def test_plan_computed_through_the_header_only():
-    """Neither api.hip nor ops.hip decides dd, seg or h16 from the options itself, or asks the shape predicates: both go through pass_plan
-    (solver.hip, retrieval.hip and classify.hip, whose code left api.hip, run no pass)."""
+    """Neither pass.hip (the two passes, whose code left api.hip) nor ops.hip decides dd, seg or h16 from the options itself, or asks the shape
+    predicates: both go through pass_plan (api.hip, solver.hip, retrieval.hip and classify.hip run no pass)."""
     old = re.compile(r"c->dedup\s*&&|c->seg_bwd\s*&&|c->h16\s*&&|&&\s*c->(dedup|seg_bwd|h16)\b|\bscore_fwd_(dropout_)?supported\s*\(")
-    for name in ("api.hip", "solver.hip", "ops.hip", "retrieval.hip", "classify.hip"):
+    for name in ("api.hip", "pass.hip", "solver.hip", "ops.hip", "retrieval.hip", "classify.hip"):
         for n, code in _code_lines(name):
             assert not old.search(code), "%s:%d decides the pass's execution outside vv_pass_plan.h: %s" % (name, n, code.strip())

@@ -17,11 +17,11 @@ def test_step_state_transitions(tmp_path):
 
 
 def test_state_written_through_transitions_only():
-    """No raw assignment to the two states outside the header: api.hip, solver.hip (the update, whose code left api.hip) and ops.hip go through
-    its transitions (retrieval.hip and classify.hip, whose code left api.hip too, touch neither state)."""
+    """No raw assignment to the two states outside the header: api.hip, pass.hip (the pass) and solver.hip (the update), whose code left api.hip, and ops.hip go
+    through its transitions (retrieval.hip and classify.hip, whose code left api.hip too, touch neither state)."""
     import re
     raw = re.compile(r"(->|\.)(grad(\.(at|buf(\.\w+)?))?|upd_sync)\s*(=[^=]|\+\+|--)")
-    for name in ("api.hip", "solver.hip", "ops.hip", "comm.hip", "retrieval.hip", "classify.hip"):
+    for name in ("api.hip", "pass.hip", "solver.hip", "ops.hip", "comm.hip", "retrieval.hip", "classify.hip"):
         with open(os.path.join(CSRC, name)) as f:
             for n, line in enumerate(f, 1):
                 assert not raw.search(line.split("//")[0]), "%s:%d assigns to the state directly: %s" % (name, n, line.strip())

@@ -249,7 +249,7 @@ Comm* comm_create(int world, int rank, const char* id_path, int transport, size_
     if (rank == 0 && world > 1) (void)unlink(id_path);      // every rank has joined (or the attempt failed): the file has done its job
     if (rc != 0) return fail(std::string("ncclCommInitRank: ") + (c->ErrStr ? c->ErrStr(rc) : "error"));
     // One small collective now, waited for: the library sets up its channels and connections lazily at the first call, which
-    // can take seconds -- not something to happen under a forward GEMM that is waiting at its gates (api.hip, overlap).
+    // can take seconds -- not something to happen under a forward GEMM that is waiting at its gates (pass.hip, overlap).
     {
       float* warm = nullptr;
       if (hipMalloc((void**)&warm, 4096) != hipSuccess || hipMemsetAsync(warm, 0, 4096, c->stream) != hipSuccess) return fail("hipMalloc failed");

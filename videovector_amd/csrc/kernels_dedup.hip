@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void k_dd_pos(DedupArgs a) {
 // atomics 120 us.  A barrier across 55 workgroups costs about what a dependent launch does on this part.)
 
 // DedupArgs.lds_bytes: the grouping kernels of a later step run on the context's second stream BESIDE the forward GEMM
-// (api.hip, the async block).  That GEMM is one persistent 512-thread workgroup per CU holding 128 of the CU's 160 KiB of
+// (pass.hip, the async block).  That GEMM is one persistent 512-thread workgroup per CU holding 128 of the CU's 160 KiB of
 // LDS, on 216 of the 256 CUs at cfg 2; a grouping workgroup placed on one of those CUs slows that CU's GEMM workgroup and
 // the whole GEMM waits for it (0.085-0.088 ms against 0.080 alone).  Asking for 36 KiB of dynamic LDS they never touch
 // makes the grouping workgroups too big for the 32 KiB a GEMM workgroup leaves free: the dispatcher can place them only on

@@ -1188,7 +1188,7 @@ template <bool H16> __device__ __forceinline__ void seg_row8(const float* H, int
 // DROP (SegBwdArgs::drop): every instance carries its own dropout mask m_i over the shared row:
 //   dx_u = [x_u > 0] (sum_i m_i alpha_i V_i - x_u scale sum_i m_i beta_i)        (alpha, beta already carry one factor scale)
 // -- the mask regenerated per instance from its reference row (b = vec / 2, ch = pad - b CN) and per chunk (columns 512 c + c0 .. + 7), the
-// beta sum per column of every chunk.  The DROP forms read fp32 vectors only: dropout steps run with v16 off (api.hip, option "drop_dedup").
+// beta sum per column of every chunk.  The DROP forms read fp32 vectors only: dropout steps run with v16 off (vv_pass_plan.h, option "drop_dedup").
 // CNT (option "h16_guard", the k_seg_bwd_cnt kernels below; f16 rows only): the wave also counts what f16's range cost the rows it holds --
 // elements stored as 65504, the largest finite f16 (the forward GEMM's epilogue saturates there; a true value in [65488, 65504) rounds to
 // it and is counted too: conservative), and rows whose largest element is > 0 and < 2^-14 (every element subnormal; an all-zero row is
@@ -1741,7 +1741,7 @@ void launch_reduce(const ReduceArgs& a, hipStream_t s) {
   // dW blocks (fewer for a launch that reduces a column range only), db blocks, the loss block, the scale block
   const int dwb = !(a.parts & 1) ? 0 : (a.f_count > 0 && a.F % 4 == 0 ? std::max(64, (int)((int64_t)RED_DW_BLOCKS * a.f_count / a.F)) : RED_DW_BLOCKS);
   const dim3 grid(dwb + ((a.parts & 2) ? (a.D + 15) / 16 + 1 : 0) + (a.scale_sc ? 1 : 0));
-  if (a.F % 4 == 0 && a.slab16) VV_LAUNCH((k_reduce<true, true>), grid, dim3(256), 0, s, a);     // (slab16 needs F % 8 == 0 and S <= 8: api.hip)
+  if (a.F % 4 == 0 && a.slab16) VV_LAUNCH((k_reduce<true, true>), grid, dim3(256), 0, s, a);     // (slab16 needs F % 8 == 0 and S <= 8: vv_backward_plan.h)
   else if (a.F % 4 == 0) VV_LAUNCH(k_reduce<true>, grid, dim3(256), 0, s, a);
   else VV_LAUNCH(k_reduce<false>, grid, dim3(256), 0, s, a);
 }
@@ -2295,7 +2295,7 @@ int launch_reduce_sgd(const FusedUpdArgs& a, hipStream_t s, float* vW, float* vb
   const int nblk = a.no_params ? 0 : (int)std::min<int64_t>(((int64_t)a.r.D * (a.r.F / ept) + 255) / 256, WMAX_SLOTS);
   const dim3 grid(nblk + ndb + 1);
   ko().last_update_form = a.no_params ? 5 : a.r.slab16 ? 4 : 3;     // ("last_update_form"; no_params: the matrix was updated in the weight-gradient GEMM)
-  if (a.g.rule.solver_type == VV_SOLVER_ADAM) {        // the two-history instantiations (never with no_params: the epilogue declines Adam, api.hip)
+  if (a.g.rule.solver_type == VV_SOLVER_ADAM) {        // the two-history instantiations (never with no_params: the epilogue declines Adam, vv_backward_plan.h)
     if (!vW || !vb) { fprintf(stderr, "launch_reduce_sgd: an Adam rule without its second history\n"); abort(); }
     FusedUpdArgs2 a2; (FusedUpdArgs&)a2 = a; a2.vW = vW; a2.vb = vb;
     if (a.r.slab16) {

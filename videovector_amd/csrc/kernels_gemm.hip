@@ -175,7 +175,7 @@ static void launch_wgrad_t(const WgradArgs& a, hipStream_t s) {
 }
 
 void launch_wgrad_gemm_ph(int prec, const WgradArgs& a, hipStream_t s);
-// the update in the epilogue (WgradArgs::fuse_upd) exists in the phase-staggered kernel only: api.hip asks before it fills WgradUpd
+// the update in the epilogue (WgradArgs::fuse_upd) exists in the phase-staggered kernel only: pass.hip asks (BackwardPlanIn::can_fuse_update) before it fills WgradUpd
 bool wgrad_can_fuse_update() { return ko().wgrad_tr != 0 && !ko().ablate && !ko().lab_wg_abl; }
 void launch_wgrad_gemm(int prec, const WgradArgs& a, hipStream_t s) {
   ko().last_wgrad_splits = a.S;           // ("last_wgrad_splits": both kernels' grids are built from this S)

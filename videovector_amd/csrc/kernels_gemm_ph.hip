@@ -1198,9 +1198,9 @@ static void launch_wgrad_ph_t(const WgradArgs& a, hipStream_t s) {
     VV_LAUNCH((k_wgrad_gemm_ph<__VA_ARGS__>), grid, block, PH_WG_LDS_BYTES, s, a);                     \
     return;                                                                                            \
   }
-  // (WgradArgs::lean: the table lies below 4 GiB and its row ids below 2^24 -- api.hip decides: the lean instantiations)
+  // (WgradArgs::lean: the table lies below 4 GiB and its row ids below 2^24 -- vv_backward_plan.h decides: the lean instantiations)
   if (a.slab16 && !a.fuse_upd) { if (a.lean) VV_WG_LAUNCH(T, 0, false, true, true) else VV_WG_LAUNCH(T, 0, false, true) }
-  if (a.fuse_upd) {                       // (one split of K: the update where the gradient is born -- api.hip decides, WgradUpd)
+  if (a.fuse_upd) {                       // (one split of K: the update where the gradient is born -- vv_backward_plan.h decides, WgradUpd)
     if (a.lean) VV_WG_LAUNCH(T, 0, true, false, true) else VV_WG_LAUNCH(T, 0, true)
   }
   if (a.lean) VV_WG_LAUNCH(T, 0, false, false, true)

@@ -1,5 +1,5 @@
 // ops.hip -- per-layer device operators: what the reference's Forward_gpu / Backward_gpu of the 13 hot-path layer
-// classes compute, one small HIP kernel each, on fp32 device buffers.  The fused plan (api.hip) is what training runs;
+// classes compute, one small HIP kernel each, on fp32 device buffers.  The fused plan (pass.hip) is what training runs;
 // these serve the facade's sequential executor (a graph the fused-plan matcher does not recognise, gradient checks,
 // single-layer Forward / Backward) behind the same C ABI.  Everything is queued on the context's stream.
 //

@@ -1,6 +1,6 @@
 // solver.hip -- the solver's side of the C ABI in include/videovec.h: its settings (vv_solver_ext_*, vv_solver_iter_*), the second history,
 // gradient clipping, the moving average of the parameters, the gradient bank, the step's carried state (vv_run_state_*), and the parameter
-// update in its five forms (vv_apply_update, vv_step).  The step that produces the gradient is api.hip's; what crosses between the two
+// update in its five forms (vv_apply_update, vv_step).  The step that produces the gradient is pass.hip's; what crosses between the
 // files is declared in vv_ctx.h.
 #include <cmath>
 #include <cstring>

@@ -1,9 +1,11 @@
-// vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the fused training step), solver.hip (the
+// vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the context, the options, the table, the
+// parameters, the accessors), pass.hip (the pass over a batch: the fused training step's forward and backward), solver.hip (the
 // solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip and linear.hip (the
 // evaluation paths); below it, what these files call of one another.  Internal.
 #pragma once
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <ctime>
 #include <map>
 #include <string>
@@ -29,6 +31,13 @@ int vv_fail(int code, const char* fmt, ...);
     if ((c)->comm && vv::comm_failed((c)->comm)) return fail(VV_ERR_HIP, "the data-parallel exchange failed: %s", vv::comm_error((c)->comm)); } while (0)
 
 inline void dfree(void* p) { if (p) (void)hipFree(p); }
+// environment of a PRODUCT option (read once per context) / of a lab switch (ignored unless the library was built with -DVV_LAB)
+inline const char* opt_env(const char* name) { return getenv(name); }
+#ifdef VV_LAB
+inline const char* lab_env(const char* name) { return getenv(name); }
+#else
+inline const char* lab_env(const char*) { return nullptr; }
+#endif
 
 // A device allocation that lives for one API call: released on every return path, the early error returns of HIPCHK
 // included.
@@ -220,7 +229,7 @@ struct vv_ctx {
                                             // happened to lie in physical memory; with it forty processes in forty at 95-107 us: 0.211-0.224 ms per iteration at the
                                             // shipped shape against 0.229-0.236 with the update as its own launch (profiles/r05_shipped_update.txt).
   vv_step_cfg upd_cfg;
-  uint32_t* lab_score_ts = nullptr;         // (lab builds) device buffer of k_score_fwd's phase stamps, api.hip
+  uint32_t* lab_score_ts = nullptr;         // (lab builds) device buffer of k_score_fwd's phase stamps, pass.hip
   bool comm_inline = true;                  // option "comm_inline" (VV_COMM_INLINE): the sharded update queued on the compute stream itself (no second stream, no gate)
   int nearest_select_min_k = 33;    // "nearest_select_min_k" / VV_NEAREST_SELECT_MIN_K: vv_gallery_nearest* use the selection form from this k on (1 .. 33)
   // vv_classification_stats: "cls_pass_tiles" (positive tiles of one counting launch, 1 .. 65535) and "cls_block_cols" (columns of one
@@ -279,20 +288,24 @@ struct vv_ctx {
 void vv_ops_release(vv_ctx* c);
 // api.hip: orders the compute stream behind an overlapped parameter update still on the communication stream
 int vv_comm_join(vv_ctx* c);
-// api.hip: the reduction a backward pass left undone (GradAt::Slabs), now -- the gradient to the buffer, the loss to its scalars
+// pass.hip: the reduction a backward pass left undone (GradAt::Slabs), now -- the gradient to the buffer, the loss to its scalars
 int vv_reduce_now(vv_ctx* c);
-// api.hip: VV_ERR_STATE where the gradient's state refuses the entry point `who` (vv_step_state.h: grad_guard)
+// pass.hip: VV_ERR_STATE where the gradient's state refuses the entry point `who` (vv_step_state.h: grad_guard)
 int vv_upd_pending_guard(vv_ctx* c, const char* who);
 // api.hip: the embeddings of n table rows / of the (coefficient-weighted) means of n windows of k rows into dout [n][D]; `who` names the
 // entry point in messages (retrieval.hip: vv_gallery_from_table)
 int vv_embed_rows_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int relu, int l2norm, float* dout);
 int vv_embed_mean_device(vv_ctx* c, const char* who, const int32_t* rows, int64_t n, int32_t k, const float* coeff, int relu, int l2norm,
                          float* dout);
-// api.hip: a step configuration the library can run, with the context's vv_solver_ext_set values where the rule reads them
+// pass.hip: a step configuration the library can run, with the context's vv_solver_ext_set values where the rule reads them
 int vv_check_cfg(vv_ctx* c, const vv_step_cfg* cfg);
-// api.hip: the per-batch buffers for this shape (a new shape starts the gradient scale's steering and the distinct-row hints afresh)
+// pass.hip: the per-batch buffers for this shape (a new shape starts the gradient scale's steering and the distinct-row hints afresh), and
+// their release (vv_destroy, another D)
 int vv_ensure_batch(vv_ctx* c, int B, int C, int Nn);
-// api.hip: the F-chunks of the overlapped update into c->chunk_kt; returns their number
+void vv_free_batch(vv_ctx* c);
+// pass.hip: at least `need` scratch rows behind the table's zero row (quirk-Q1 composites, vv_embed_mean's window means)
+int vv_ensure_scratch_rows(vv_ctx* c, int64_t need);
+// pass.hip: the F-chunks of the overlapped update into c->chunk_kt; returns their number
 int vv_chunk_plan(vv_ctx* c);
 // api.hip: a sharded update's rows of W and the histories gathered from their owners (a collective)
 int vv_gather_params(vv_ctx* c);

@@ -138,10 +138,10 @@ struct FwdArgs {
   int32_t* gate_err = nullptr; // host-mapped: set when a wait gave up (bounded: a lost update must not hang the device)
   // H as 16-bit floats (round 6, option "h16"): the forward GEMM stores ip2 as f16 -- [R][D] halves in the same buffer, scale 1, values past
   // f16's range saturated at +-65504 -- for the kernels that then read it as such (k_score_fwd / k_score_stream / k_seg_bwd: ScoreArgs::h16).
-  // Only the segment-wise path sets it (api.hip); everything else keeps fp32 rows.
+  // Only the segment-wise path sets it (pass.hip); everything else keeps fp32 rows.
   int h16 = 0;
 };
-constexpr int W_CHUNKS_MAX = 4; // F-chunks of the overlapped update at most (chunk-major gradient buffer, api.hip: vv_chunk_plan)
+constexpr int W_CHUNKS_MAX = 4; // F-chunks of the overlapped update at most (chunk-major gradient buffer, pass.hip: vv_chunk_plan)
 constexpr int W_GATE_STRIDE = 32;   // ints between two chunk flags: a 128-B line each (the waiting workgroups poll them)
 
 // Segment-wise backward (de-duplicated batches): the score kernel keeps the gradient of an instance in factored form
@@ -346,7 +346,7 @@ struct SolverRule {
 };
 
 // The solver's update applied in the weight-gradient GEMM's epilogue (one split of K: the tile in the accumulators IS the gradient;
-// api.hip: vv_update_hint).  What k_reduce_sgd does per 16 bytes of W -- unscale, the solver's rule (solver.cpp:502-531 / 599-655 / 714-781),
+// pass.hip: vv_update_hint).  What k_reduce_sgd does per 16 bytes of W -- unscale, the solver's rule (solver.cpp:502-531 / 599-655 / 714-781),
 // blob.cpp:112-136, the new 16-bit copy, max |w| for the next scale -- done on the 256 x 256 tile while it is in registers: the 4 D F
 // bytes of dW are neither written nor read back.  Bias, loss and the guard's report stay with k_reduce_sgd's special workgroups.
 struct WgradUpd {
@@ -380,7 +380,7 @@ struct WgradArgs {
   int slab16 = 0;
   float* slab_sc = nullptr;
   // the LEAN instantiations of k_wgrad_gemm_ph (round 6, option "wgrad_lean"): gathered rows addressed as table + 32-bit byte offset --
-  // set by api.hip when every row of the table (scratch rows included) lies below 4 GiB and its index below 2^24
+  // set by pass.hip (vv_backward_plan.h) when every row of the table (scratch rows included) lies below 4 GiB and its index below 2^24
   int lean = 0;
 };
 
@@ -444,7 +444,7 @@ struct SgdArgs {
   const uint32_t* skip_if = nullptr;
 };
 
-// Reduction and update in one launch (k_reduce_sgd; api.hip: the lazy reduction).  r: what k_reduce would have been given (its
+// Reduction and update in one launch (k_reduce_sgd; pass.hip: the lazy reduction).  r: what k_reduce would have been given (its
 // scale_* fields unused), g: what k_sgd would have been given.  Every workgroup that updates parameters derives the scale of
 // the new half copy for itself from the previous update's per-block maxima (wmax_prev: what k_scale_update folds) when
 // recompute_scale is set, else takes Scales::sw_next as it stands; this update's maxima go to g.wmax_blocks (another buffer).
@@ -453,7 +453,7 @@ struct FusedUpdArgs {
   int no_params = 0;         // 1: only the special workgroups (bias, loss, the guard's report): the parameter matrix was updated in the
                              //    weight-gradient GEMM's epilogue (WgradUpd)
   const float* wmax_prev = nullptr; int wmax_prev_n = 0; int recompute_scale = 0; int prec = 0;
-  int store_grads = 0;       // also write dW to the gradient buffer (0: it stays in the slabs, api.hip materialises it on request)
+  int store_grads = 0;       // also write dW to the gradient buffer (0: it stays in the slabs, pass.hip materialises it on request)
 };
 // The two-history forms (Adam): the second history of W and b rides in an argument struct of its own, so that the one-history kernels
 // carry no extra pointer.  v of the same shapes and at the same offsets as hW / hb.

@@ -1,5 +1,5 @@
 // vv_step_state.h -- where this step's gradient is, and whether an overlapped parameter update has been joined: the two pieces of
-// bookkeeping between vv_forward_backward* and vv_apply_update (api.hip, solver.hip, ops.hip).  Each is ONE value that only the transitions below
+// bookkeeping between vv_forward_backward* and vv_apply_update (pass.hip, api.hip, solver.hip, ops.hip).  Each is ONE value that only the transitions below
 // write, and every transition sets the whole of it.  No HIP header: a host compiler builds this alone (tools/step_state_check.cc).
 #pragma once
 #include <cstring>
