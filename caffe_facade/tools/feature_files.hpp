@@ -1,7 +1,8 @@
-// Readers the feature-file tools share: a feature file in the text_output.txt format extract_features writes ("#features",
+// Readers and writers the feature-file tools share: a feature file in the text_output.txt format extract_features writes ("#features",
 // then one line of comma-terminated values per row) and an id file with one integer per line.
 #ifndef CAFFE_TOOLS_FEATURE_FILES_HPP_
 #define CAFFE_TOOLS_FEATURE_FILES_HPP_
+#include <cstdio>
 #include <fstream>
 
 #include "caffe/layer.hpp"
@@ -53,6 +54,25 @@ inline void Fill(const vector<float>& v, int rows, int dim, Blob<float>* b) {
   std::copy(v.begin(), v.end(), b->mutable_cpu_data());
 }
 
+// rows x dim values in the format ReadFeatures reads, nine significant digits: every fp32 value reads back as itself
+inline void WriteFeatures(const char* path, const float* v, int rows, int dim) {
+  FILE* f = fopen(path, "w");
+  CHECK(f) << "Failed to open " << path;
+  fprintf(f, "#features\n");
+  for (int r = 0; r < rows; ++r) {
+    for (int c = 0; c < dim; ++c) fprintf(f, "%.9g,", (double)v[(size_t)r * dim + c]);
+    fprintf(f, "\n");
+  }
+  CHECK_EQ(fclose(f), 0) << "Failed to write " << path;
+}
+
+// one integer per line, the format ReadIds reads
+inline void WriteInts(const char* path, const int* v, int rows) {
+  FILE* f = fopen(path, "w");
+  CHECK(f) << "Failed to open " << path;
+  for (int r = 0; r < rows; ++r) fprintf(f, "%d\n", v[r]);
+  CHECK_EQ(fclose(f), 0) << "Failed to write " << path;
+}
 
 }  // namespace caffe
 #endif  // CAFFE_TOOLS_FEATURE_FILES_HPP_

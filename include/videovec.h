@@ -683,6 +683,56 @@ int vv_gallery_knn_scores(vv_ctx* ctx, vv_gallery* gallery, const int32_t* label
 int vv_gallery_knn_scores_self(vv_ctx* ctx, vv_gallery* gallery, const int32_t* labels, int32_t num_classes, int32_t k,
                                int exclude_same_id, int32_t weighting, float temperature, float* out_dev, int32_t* n_used);
 
+/* ---- k-means clustering of a gallery's items (Lloyd's iteration), every iteration on the device.  HAS NO REFERENCE COUNTERPART (the
+ * reference has no clustering); the arithmetic below is this project's own and is stated exactly, so two calls, any block size and a
+ * restatement in another language agree bit for bit (tests/kmeans_ref.py).  Every fp32 operation is rounded as written, none contracted.
+ * Key.  d(i, c): the float the similarity kernel stores for item i against centroid row c -- vv_gallery_topk's distance, and
+ *   vv_gallery_scores x -2, on a gallery made of the current centroids; nothing is evaluated a second way.
+ *   VV_KMEANS_SPHERICAL  key = d.
+ *   VV_KMEANS_EUCLIDEAN  key = d + nn_c, one fp32 add; nn_c = the sum of c[col]^2 as a serial chain in ascending column from +0, each
+ *                        product and each sum rounded on its own.
+ * Assignment: the cluster of the smallest (key, c); at a tie the lowest cluster index, as vv_gallery_topk orders (d, g).  A key that is
+ *   NaN is never the smallest; a row of nothing but NaN goes to cluster 0.
+ * Iteration t = 0 .. iters - 1: assign against the current centroids, then update.  After the last update one more assignment pass
+ *   runs, so assign_out, counts_out and the report describe centroids_out; iters = 0 is "assign to a given codebook".
+ * Traces, iters + 1 entries each, one per pass.  moved[t]: the items whose cluster differs from the previous pass (before the first
+ *   pass every item is unassigned, so moved[0] = n).  objective[t]: the sum of the selected keys in double -- items 64 j .. 64 j + 63
+ *   form slot j (an absent item adds +0.0), folded by x[i] += x[i + o], o = 32, 16 .. 1, and the slots are added in ascending j
+ *   starting from +0.0.  No floating-point atomics.
+ * Update of cluster c: its items in ascending item index, cut into chunks of 256 consecutive list entries; a chunk's partial is a
+ *   serial fp32 chain (the first row is stored, then acc = acc + x); the partials are added in ascending chunk order starting from
+ *   the first, giving s.  EUCLIDEAN: centroid = s * inv, inv = 1.0f / (float)count.  SPHERICAL: q = the serial chain of s[col]^2 from
+ *   +0, centroid = s / sqrtf(q), both correctly rounded; q zero or not finite: the previous centroid is kept (degenerate).  A cluster
+ *   without an item keeps its previous centroid bit for bit (empty).
+ * Once moved[t] == 0 every later pass reproduces the same bits.  Inputs are assumed finite, as for the other gallery calls.
+ *
+ * vv_kmeans_cfg_default: 0 clusters (must be set), 20 iterations, EUCLIDEAN.  Limits: 1 <= num_clusters <= 4096, num_clusters <= n_ref,
+ * iters >= 0.  Exactly one of init_centroids (host [C][dim]) and init_rows (host [C] item indices: the initial centroids are gathered
+ * from the gallery's DEVICE rows, so a gallery made by vv_gallery_from_table serves) is given.
+ * centroids_out: host [C][dim].  assign_out: host [n_ref] or NULL.  counts_out: host [C] or NULL.  objective_trace / moved_trace: host
+ * [iters + 1] or NULL.  out: n, num_clusters, iters; empty_last / degenerate_last: the clusters the LAST update kept as empty /
+ * degenerate (0 with iters = 0); moved_last / objective_last / nonfinite_rows (items whose selected key is not finite): the final pass.
+ * VV_ERR_ARG, found on the host with nothing launched or written: a NULL required pointer; both or neither init given; a gallery of
+ * another context; a value out of range or an unknown metric; an init_rows entry outside [0, n_ref) (vv_last_error names its position);
+ * a shape whose buffers, the traces' record of iters + 1 passes included, pass the gallery path's scratch limit.
+ * The call touches nothing a training step owns: it may be made between vv_forward_backward* and vv_apply_update.  All iterations are
+ * queued on the context's stream without a host wait or an allocation between them; the call synchronises once, at its end.
+ * Options: "km_block_rows" (rows of one score block, rounded up to 64; 0 = the plan's choice, csrc/vv_kmeans_plan.h); read-only
+ * "last_km_blocks", "last_km_chunks", "last_km_assign_form" (1: 16-byte accesses, 2: element-wise -- identical results) and
+ * "last_km_sim_ms" / "last_km_assign_ms" / "last_km_group_ms" / "last_km_update_ms", the device time of the last iteration's legs
+ * (a pass of more than 1024 blocks: the first 1024 blocks' similarity and assign legs, scaled to all of them).
+ * vv_kmeans_init_rows: a host function without a context -- the first num_clusters entries of the one epoch
+ * vv_rows_shuffled(seed, n, 1, .) draws, so they are distinct. */
+enum { VV_KMEANS_EUCLIDEAN = 0, VV_KMEANS_SPHERICAL = 1 };
+typedef struct { int32_t num_clusters, iters, metric, reserved_; } vv_kmeans_cfg;
+typedef struct { int64_t n; int32_t num_clusters, iters, empty_last, degenerate_last; int64_t moved_last;
+                 double objective_last; int64_t nonfinite_rows; } vv_kmeans_report;
+void vv_kmeans_cfg_default(vv_kmeans_cfg* cfg);
+int vv_gallery_kmeans(vv_ctx* ctx, vv_gallery* items, const vv_kmeans_cfg* cfg, const float* init_centroids, const int32_t* init_rows,
+                      float* centroids_out, int32_t* assign_out, int32_t* counts_out, double* objective_trace, int64_t* moved_trace,
+                      vv_kmeans_report* out);
+int vv_kmeans_init_rows(uint64_t seed, int32_t n, int32_t num_clusters, int32_t* rows_out);
+
 /* ---- class-level leave-one-out statistics on a gallery: RetrievalStatsLayer (src/caffe/layers/retrieval_stats_layer.cpp).
  * vv_gallery_pool_by_id: video_level_retrieval (:165-198).  A new gallery with one item per distinct id of `gallery`, its row the
  * sum over the id's items, in ascending item index, of (1 / count) x_i in fp32 (the reference's weight matrix, :193, :197-198),

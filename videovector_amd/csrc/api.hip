@@ -313,6 +313,12 @@ static const Option kOptions[] = {
   LAST("last_lin_fwd_ms", c->last_lin_ms[0]), LAST("last_lin_softmax_ms", c->last_lin_ms[1]), LAST("last_lin_wgrad_ms", c->last_lin_ms[2]),
   LAST("last_lin_update_ms", c->last_lin_ms[3]),
   LAST("last_hinge_form", c->last_hinge_form), LAST("last_hinge_nonfinite", c->last_hinge_nonfinite), LAST("last_knn_form", c->last_knn_form),
+  {"km_block_rows", OptKind::Settable, RD(c->km_block_rows), [](vv_ctx* c, double, int iv) -> int {
+     if (iv < 0) return fail(VV_ERR_ARG, "vv_set_option: km_block_rows = %d is negative", iv);
+     c->km_block_rows = iv; return VV_OK; }},
+  LAST("last_km_blocks", c->last_km_blocks), LAST("last_km_chunks", c->last_km_chunks), LAST("last_km_assign_form", c->last_km_assign_form),
+  LAST("last_km_sim_ms", c->last_km_ms[0]), LAST("last_km_assign_ms", c->last_km_ms[1]), LAST("last_km_group_ms", c->last_km_ms[2]),
+  LAST("last_km_update_ms", c->last_km_ms[3]),
   LAST("last_fwd_tile_rows", c->ko.last_fwd_tile_rows), LAST("last_wgrad_splits", c->ko.last_wgrad_splits),
   LAST("last_update_form", c->ko.last_update_form), LAST("last_score_form", c->ko.last_score_form),
   {"last_grad_shift", OptKind::ReadOnly, [](vv_ctx* c, double* v) -> int { return last_grad(c, 0, v); }, nullptr},

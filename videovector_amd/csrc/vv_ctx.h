@@ -1,6 +1,6 @@
 // vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the context, the options, the table, the
 // parameters, the accessors), pass.hip (the pass over a batch: the fused training step's forward and backward), solver.hip (the
-// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip and linear.hip (the
+// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip and kmeans.hip (the
 // evaluation paths); below it, what these files call of one another.  Internal.
 #pragma once
 #include <cstdarg>
@@ -251,6 +251,12 @@ struct vv_ctx {
   int last_hinge_form = 0;
   int64_t last_hinge_nonfinite = 0;
   int last_knn_form = 0;            // k_knn_vote: "last_knn_form" (1: 16-byte stores, 2: element-wise, 0: not launched yet) of the last launch
+  // vv_gallery_kmeans (kmeans.hip): "km_block_rows" (rows of one score block; 0: the plan's choice, vv_kmeans_plan.h) -- it exists so
+  // that the tests reach several blocks at small shapes; then what the last call ran (read-only "last_km_*": the blocks of one pass, the
+  // chunks of the last update, k_km_assign's form -- 1: 16-byte accesses, 2: element-wise --, the four legs' device time in the last iteration)
+  int km_block_rows = 0;
+  int last_km_blocks = 0, last_km_chunks = 0, last_km_assign_form = 0;
+  double last_km_ms[4] = {0, 0, 0, 0};
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

@@ -7,6 +7,7 @@
 
 #include "vv_pass_plan.h"      // score_fwd_supported / score_fwd_dropout_supported: the shapes the segment-wise pair is built for
 #include "vv_gallery_plan.h"   // the RT_* sizes the gallery scratch is made of, its limits and its sizing arithmetic
+#include "vv_kmeans_plan.h"    // the KM_* sizes of vv_gallery_kmeans and its block plan
 
 struct vv_gallery;
 
@@ -762,6 +763,25 @@ void launch_lin_update(const LinUpdArgs& a, hipStream_t s);
 // api.hip: a gallery's device rows ([n_ref][Dp] fp32, columns dim .. Dp - 1 zero) and the context it belongs to
 struct GalleryRows { const float* feat; int64_t n_ref; int dim, Dp; const void* ctx; };
 GalleryRows gallery_rows(const ::vv_gallery* g);
+
+// ---------------------------------------------------------------------------------------------
+// k-means on a gallery (kernels_kmeans.hip, kmeans.hip); the sizes are vv_kmeans_plan.h's
+// ---------------------------------------------------------------------------------------------
+struct KmRec { double objective; long long moved, nonfinite; int32_t empty, degenerate, chunks, pad_; };   // one pass and the update behind it
+static_assert(sizeof(KmRec) == KM_REC_BYTES, "vv_kmeans_plan.h sizes the record");
+void launch_km_gather(const float* feat, int Dp, const int32_t* rows, int C, float* cent, hipStream_t s);
+// score: rows [row0, row0 + rows) against the C centroids, C floats apart; row0 a multiple of KM_SLOT_ROWS.  -> the form: 1 16-byte, 2 element-wise
+int launch_km_assign(const float* score, int C, int64_t row0, int rows, int euclid, const float* nn, int32_t* assign, int32_t* counts,
+                     double* slot, KmRec* rec, hipStream_t s);
+void launch_km_fold(const double* slot, int64_t slots, KmRec* rec, hipStream_t s);
+// hist: int32 [tiles][C]; start, cbase: int32 [C + 1]; chunks: int4 [max_chunks]; nchunks: int32 [1]; list: int32 [n]
+void launch_km_group(const int32_t* assign, int64_t n, int C, int64_t tiles, const int32_t* counts, int32_t* hist, int32_t* start,
+                     int32_t* cbase, int4* chunks, int64_t max_chunks, int32_t* nchunks, int32_t* list, KmRec* rec, hipStream_t s);
+void launch_km_partial(const float* feat, int64_t n, int Dp, const int32_t* list, const int4* chunks, const int32_t* nchunks, int64_t max_chunks,
+                       int slices, float* part, hipStream_t s);
+// init: cent holds the initial centroids, only nn is written
+void launch_km_finish(const float* part, int Dp, int dim, const int32_t* counts, const int32_t* cbase, int64_t max_chunks, int C, int euclid, int init,
+                      float* cent, float* nn, KmRec* rec, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // 16-bit operand types

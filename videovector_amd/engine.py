@@ -119,6 +119,15 @@ class _LinearReport(C.Structure):
                 ("steps", C.c_int64), ("nonfinite_rows", C.c_int64)]
 
 
+class _KmeansCfg(C.Structure):
+    _fields_ = [("num_clusters", C.c_int32), ("iters", C.c_int32), ("metric", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class _KmeansReport(C.Structure):
+    _fields_ = [("n", C.c_int64), ("num_clusters", C.c_int32), ("iters", C.c_int32), ("empty_last", C.c_int32),
+                ("degenerate_last", C.c_int32), ("moved_last", C.c_int64), ("objective_last", C.c_double), ("nonfinite_rows", C.c_int64)]
+
+
 def load_library():
     """Load libvideovec.so; raises (never falls back) when the HIP library is not built."""
     global _lib
@@ -195,6 +204,9 @@ def load_library():
         "vv_gallery_scores": [vp, vp, vp, i32, vp],
         "vv_gallery_knn_scores": [vp, vp, vp, i32, vp, i32, vp, i32, i32, f32, vp, vp],
         "vv_gallery_knn_scores_self": [vp, vp, vp, i32, i32, C.c_int, i32, f32, vp, vp],
+        "vv_kmeans_cfg_default": [C.POINTER(_KmeansCfg)],
+        "vv_gallery_kmeans": [vp, vp, C.POINTER(_KmeansCfg), vp, vp, vp, vp, vp, vp, vp, C.POINTER(_KmeansReport)],
+        "vv_kmeans_init_rows": [C.c_uint64, i32, i32, vp],
         "vv_classification_stats": [vp, vp, i64, i32, vp, C.c_int, vp, vp, vp, C.POINTER(_ClassificationReport)],
         "vv_linear_create": [vp, i32, i32, C.c_int, C.POINTER(vp)], "vv_linear_destroy": [vp, vp],
         "vv_linear_get": [vp, vp, vp, vp, vp, vp, C.POINTER(i64)], "vv_linear_put": [vp, vp, vp, vp, vp, vp, i64],
@@ -233,7 +245,7 @@ def load_library():
     for name, args in sigs.items():
         fn = getattr(L, name)
         fn.argtypes = args
-        fn.restype = None if name in ("vv_step_cfg_default", "vv_linear_cfg_default") else C.c_int
+        fn.restype = None if name in ("vv_step_cfg_default", "vv_linear_cfg_default", "vv_kmeans_cfg_default") else C.c_int
     L.vv_sampler_state_error.argtypes = []
     L.vv_sampler_state_error.restype = C.c_char_p
     _lib = L
@@ -245,6 +257,26 @@ def _ptr(a):
 
 
 KNN_WEIGHTINGS = {"uniform": 0, "exp": 1}      # VV_KNN_UNIFORM, VV_KNN_EXP
+KMEANS_METRICS = {"euclidean": 0, "spherical": 1}      # VV_KMEANS_EUCLIDEAN, VV_KMEANS_SPHERICAL
+
+
+def kmeans_init_rows(seed, n, num_clusters):
+    """vv_kmeans_init_rows: int32 [num_clusters] distinct item indices, the head of rows_shuffled(seed, n, 1)."""
+    out = np.zeros(max(int(num_clusters), 1), np.int32)
+    _rows_chk(load_library().vv_kmeans_init_rows(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(num_clusters), _ptr(out)))
+    return out[:int(num_clusters)].copy()
+
+
+class KMeansResult:
+    """What Gallery.kmeans returns: centroids fp32 [C][dim], assign int32 [n_ref], counts int32 [C], objective float64 [iters + 1],
+    moved int64 [iters + 1], report (dict of vv_kmeans_report's fields); gallery() puts the centroids on the device as a Gallery."""
+
+    def __init__(self, eng, centroids, assign, counts, objective, moved, report):
+        self.eng, self.centroids, self.assign, self.counts = eng, centroids, assign, counts
+        self.objective, self.moved, self.report = objective, moved, report
+
+    def gallery(self):
+        return self.eng.gallery(self.centroids)
 
 
 class Gallery:
@@ -376,6 +408,41 @@ class Gallery:
         self.eng._chk(self.eng.L.vv_gallery_knn_scores_self(self.eng.h, self.h, _ptr(lab), int(num_classes), int(k),
                                                             int(bool(exclude_same_id)), w, float(temperature), _dev_ptr(out), _ptr(used)))
         return (out, used) if n_used else out
+
+    def kmeans(self, num_clusters, iters=20, metric="euclidean", init=None, seed=0):
+        """k-means over the gallery's items on the device (vv_gallery_kmeans; include/videovec.h states the arithmetic): a KMeansResult.
+        metric "euclidean" or "spherical".  init: None -- the rows kmeans_init_rows(seed, n_ref, num_clusters); a float array
+        [num_clusters][dim] -- the initial centroids; an integer array [num_clusters] -- the items whose device rows start as centroids."""
+        Cn = int(num_clusters)
+        if isinstance(metric, str):                       # (an integer goes to the library as it is: VV_KMEANS_*)
+            if metric not in KMEANS_METRICS:
+                raise VVError("kmeans: metric must be one of %s" % ", ".join(sorted(KMEANS_METRICS)))
+            metric = KMEANS_METRICS[metric]
+        cfg = _KmeansCfg()
+        self.eng.L.vv_kmeans_cfg_default(C.byref(cfg))
+        cfg.num_clusters, cfg.iters, cfg.metric = Cn, int(iters), int(metric)
+        cent0 = rows0 = None
+        if init is None:
+            rows0 = kmeans_init_rows(seed, self.n_ref, Cn)
+        else:
+            a = np.asarray(init)
+            if a.dtype.kind in "iu":
+                rows0 = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+                if rows0.shape != (Cn,):
+                    raise VVError("kmeans: init rows must be [num_clusters]")
+            else:
+                cent0 = np.ascontiguousarray(a, dtype=np.float32)
+                if cent0.shape != (Cn, self.dim):
+                    raise VVError("kmeans: init centroids must be [num_clusters][%d]" % self.dim)
+        passes = max(int(iters), 0) + 1
+        cent = np.zeros((max(Cn, 1), self.dim), np.float32)
+        assign = np.zeros(self.n_ref, np.int32)
+        counts = np.zeros(max(Cn, 1), np.int32)
+        obj, moved = np.zeros(passes, np.float64), np.zeros(passes, np.int64)
+        rep = _KmeansReport()
+        self.eng._chk(self.eng.L.vv_gallery_kmeans(self.eng.h, self.h, C.byref(cfg), _ptr(cent0), _ptr(rows0), _ptr(cent), _ptr(assign),
+                                                   _ptr(counts), _ptr(obj), _ptr(moved), C.byref(rep)))
+        return KMeansResult(self.eng, cent, assign, counts, obj, moved, {f: getattr(rep, f) for f, _ in _KmeansReport._fields_})
 
     def rows(self):
         """The gallery's fp32 rows [n_ref][dim], downloaded from the device."""
