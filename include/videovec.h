@@ -733,6 +733,47 @@ int vv_gallery_kmeans(vv_ctx* ctx, vv_gallery* items, const vv_kmeans_cfg* cfg, 
                       vv_kmeans_report* out);
 int vv_kmeans_init_rows(uint64_t seed, int32_t n, int32_t num_clusters, int32_t* rows_out);
 
+/* ---- inverted-file (IVF) index on a gallery: a search that meets only the items of the nprobe nearest clusters.
+ * HAS NO REFERENCE COUNTERPART (the reference searches exhaustively); the arithmetic below is this project's own and is stated exactly.
+ * Distance.  d(i, g): the float the similarity kernel stores for query i against item g -- vv_gallery_topk's distance.  The grouped
+ *   kernel runs the exhaustive kernel's tile body, whose summation order over the columns is the same for every output, so the float
+ *   does not depend on where an item's row lies: the search is EXACT on its candidate set, and with nprobe == num_clusters idx and
+ *   dist equal vv_gallery_topk's bit for bit.
+ * Index (vv_ivf_create).  centroids: host [C][dim].  assign: host [n_ref], every entry in [0, C), taken as it is -- any item may be put
+ *   in any list; NULL: the assignment vv_gallery_kmeans with iters = 0 returns for these centroids and this metric (that call is made).
+ *   Cluster c's list holds its items in ascending item index; an empty list is legal.  The index owns a cluster-contiguous copy of the
+ *   items' rows, the lists, the centroids and (EUCLIDEAN) nn_c as k-means defines it: the items gallery may be destroyed afterwards.
+ * Search, one block of queries at a time:
+ *   probe    key(i, c) = d(i, c) against the centroids (SPHERICAL) or d(i, c) + nn_c, one fp32 add, not contracted (EUCLIDEAN): k-means'
+ *            key.  The nprobe smallest (key, c), ascending, the lowest cluster at a tie; -0 and +0 are one key.  A NaN key is below
+ *            nothing: if fewer than nprobe keys are numbers, the remaining slots take the lowest clusters not yet chosen, ascending.
+ *            nprobe == num_clusters: every cluster, in ascending index.
+ *   candidates of query i: the items of its probed lists, m_i of them (n_candidates[i], if asked).
+ *   result   the k smallest (d, g) of the candidates, g the item's index in the items gallery: equal distances order by ascending item
+ *            index across lists, as vv_gallery_topk orders them.  Slots past m_i read idx -1, dist 0, as in vv_gallery_nearest.
+ * Limits: 1 <= C <= 4096, C <= n_ref; metric VV_KMEANS_EUCLIDEAN or VV_KMEANS_SPHERICAL; 1 <= nprobe <= min(C, 64), and nprobe == C is
+ * always allowed; 1 <= k <= 32; n_q >= 1; q: host [n_q][dim] with the index's dim.
+ * VV_ERR_ARG, found on the host with nothing allocated, launched or written, vv_last_error naming the argument: a NULL required pointer;
+ * a gallery or index of another context; C, metric, nprobe, k or n_q out of range; an assign entry outside [0, C) (its position is
+ * named); a shape of which one query's candidates do not fit the gallery path's scratch limit.
+ * Everything of a search is queued on the context's stream; the call synchronises once, at its end.  It touches nothing a training step
+ * owns: it may be made between vv_forward_backward* and vv_apply_update.  No floating-point atomics.
+ * Options: "ivf_block_rows" (query rows of one block) and "ivf_grid_wgs" (workgroups of the grouped similarity's fixed grid, 65535 at
+ * most); 0 = the plan's choice (csrc/vv_ivf_plan.h).  Neither changes a bit of the result.
+ * vv_ivf_get: "n_ref", "dim", "num_clusters", "metric", "largest_list", "empty_lists"; of the last search "last_blocks", "last_tiles"
+ * (128 x 128 similarity tiles), "last_candidates" (the sum of m_i), "last_grid_wgs", and the device time "last_probe_ms",
+ * "last_group_ms", "last_sim_ms", "last_select_ms" (a search of more than 64 blocks: the first 64 blocks' legs, scaled to all of them)
+ * and "last_device_ms" (the whole call).  An unknown name is VV_ERR_ARG.
+ * vv_ivf_lists: host copies for tools and tests -- start [C + 1], list [n_ref]: cluster c's items are list[start[c] .. start[c + 1]). */
+typedef struct vv_ivf vv_ivf;
+int vv_ivf_create(vv_ctx* ctx, vv_gallery* items, const float* centroids, int32_t num_clusters, int32_t metric, const int32_t* assign_or_null,
+                  vv_ivf** out);
+int vv_ivf_destroy(vv_ctx* ctx, vv_ivf* index);
+int vv_ivf_search(vv_ctx* ctx, vv_ivf* index, const float* q, int32_t n_q, int32_t nprobe, int32_t k, int32_t* idx, float* dist,
+                  int32_t* n_candidates_or_null);
+int vv_ivf_get(const vv_ivf* index, const char* name, double* value);
+int vv_ivf_lists(vv_ctx* ctx, vv_ivf* index, int32_t* start, int32_t* list);
+
 /* ---- class-level leave-one-out statistics on a gallery: RetrievalStatsLayer (src/caffe/layers/retrieval_stats_layer.cpp).
  * vv_gallery_pool_by_id: video_level_retrieval (:165-198).  A new gallery with one item per distinct id of `gallery`, its row the
  * sum over the id's items, in ascending item index, of (1 / count) x_i in fp32 (the reference's weight matrix, :193, :197-198),

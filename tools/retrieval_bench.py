@@ -25,6 +25,13 @@
       device events, the vote launches' own time ("last_knn_vote_ms") and, as the host sees it, the wall time around each blocking
       call (nearest returns the lists to the host, knn_scores leaves the scores on the device).  Writes the JSON it prints to
       profiles/knn_<nq>x<ng>x<dim>.json (--out: elsewhere) as well.
+  python tools/retrieval_bench.py --ivf 4096:32,1024:8 [--nq 4096 --ng 1000000 --dim 512] [--rounds 4] [--out FILE]
+      the inverted-file index (vv_ivf_search): for every C:nprobe the index is built on Gallery.kmeans(C, iters=10), then
+      IVFIndex.search(k = 32) and Gallery.topk(32), the yardstick, alternate call by call for --rounds rounds behind one warm-up round;
+      per call the library's device events and the host's wall clock, the search's four legs (vv_ivf_get), recall@1 and recall@32
+      against the exact lists of the same invocation, and the share of the tiles' area that is padding (tiles x 128^2 against the
+      candidates).  The condition: the search's median below top-k's by more than the two spreads (max - min) together.  Writes the JSON
+      it prints to profiles/ivf_<nq>x<ng>x<dim>.json (--out: elsewhere) as well.
 
 Inputs are seeded: unit rows around `nid` random centres, ids = the centre's index (the generator of tests/gallery_ref.py, drawn in
 float32 blocks so that a million rows need no float64 copy)."""
@@ -166,6 +173,67 @@ def knn_bench(eng, a):
     return out
 
 
+def ivf_bench(eng, a):
+    G, gid, cen = make(a.ng, a.dim, a.nid, a.noise, 5)
+    Q, qid, _ = make(a.nq, a.dim, a.nid, a.noise, 6, cen)
+    g = eng.gallery(G, gid)
+    box = {"before": eng.box_probe()}
+    res = []
+    for spec in a.ivf.split(","):
+        Cn, nprobe = (int(x) for x in spec.split(":"))
+        t0 = time.perf_counter()
+        km = g.kmeans(Cn, iters=10)
+        t1 = time.perf_counter()
+        ix = km.ivf(g)
+        t2 = time.perf_counter()
+        t = dict(topk=dict(dev=[], wall=[]), ivf=dict(dev=[], wall=[], probe=[], group=[], sim=[], select=[]))
+        for r in range(1 + a.rounds):
+            for name, call in (("topk", lambda: g.topk(Q, 32)), ("ivf", lambda: ix.search(Q, 32, nprobe))):
+                w0 = time.perf_counter()
+                got = call()
+                wall = (time.perf_counter() - w0) * 1e3
+                if name == "topk":
+                    exact = got
+                if r >= 1:
+                    t[name]["wall"].append(wall)
+                    t[name]["dev"].append(g.get("last_device_ms") if name == "topk" else ix.get("last_device_ms"))
+                    if name == "ivf":
+                        for leg in ("probe", "group", "sim", "select"):
+                            t[name][leg].append(ix.get("last_%s_ms" % leg))
+        idx, dist, m = got
+        hit1 = float((idx[:, 0] == exact[0][:, 0]).mean())
+        hit32 = float(np.mean([len(np.intersect1d(u, v)) for u, v in zip(idx, exact[0])]) / 32.0)
+        tiles, cands = ix.get("last_tiles"), ix.get("last_candidates")
+        e = dict(num_clusters=Cn, nprobe=nprobe, k=32, kmeans_iters=10, kmeans_wall_ms=(t1 - t0) * 1e3, index_build_wall_ms=(t2 - t1) * 1e3,
+                 largest_list=int(ix.get("largest_list")), empty_lists=int(ix.get("empty_lists")), blocks=int(ix.get("last_blocks")),
+                 grid_wgs=int(ix.get("last_grid_wgs")), tiles=int(tiles), candidates=int(cands),
+                 mean_candidates_per_query=cands / a.nq, share_of_gallery_met=cands / (float(a.nq) * a.ng),
+                 padded_tile_area_share=1.0 - cands / (tiles * 128.0 * 128.0) if tiles else 0.0,
+                 recall_at_1=hit1, recall_at_32=hit32)
+        for name in ("topk", "ivf"):
+            e[name + "_ms"] = stats(t[name]["dev"]); e[name + "_wall_ms"] = stats(t[name]["wall"])
+        for leg in ("probe", "group", "sim", "select"):
+            e["ivf_%s_ms" % leg] = stats(t["ivf"][leg])
+        for kind in ("_ms", "_wall_ms"):
+            tk, iv = e["topk" + kind], e["ivf" + kind]
+            e["topk_over_ivf" + kind.replace("_ms", "")] = tk["median"] / iv["median"]
+            e["condition_met" + kind.replace("_ms", "")] = bool(tk["median"] - iv["median"] > (tk["max"] - tk["min"]) + (iv["max"] - iv["min"]))
+        res.append(e)
+        ix.close()
+    g.close()
+    box["after"] = eng.box_probe()
+    out = dict(bench="ivf", nq=a.nq, ng=a.ng, dim=a.dim, rounds=a.rounds, warmup_rounds=1,
+               yardstick="vv_gallery_topk at k = 32, alternating call by call with vv_ivf_search in one process",
+               timer="device events inside the library (last_device_ms of either call; the legs of vv_ivf_get); *_wall_ms: host wall clock "
+                     "around the blocking call",
+               condition="median(topk) - median(ivf) > (max - min)(topk) + (max - min)(ivf)", searches=res, box=box)
+    path = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                 "ivf_%dx%dx%d.json" % (a.nq, a.ng, a.dim))
+    with open(path, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=4096)
@@ -187,9 +255,13 @@ def main():
     ap.add_argument("--self-n", type=str, default="8192,200000")
     ap.add_argument("--self-reps", type=int, default=5)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--ivf", type=str, default=None, metavar="C:NPROBE[,C:NPROBE...]")
+    ap.add_argument("--rounds", type=int, default=4)
     a = ap.parse_args()
     eng = vv.Engine(0, "f16")
-    if a.nearest:
+    if a.ivf:
+        out = ivf_bench(eng, a)
+    elif a.nearest:
         out = nearest_bench(eng, a)
     elif a.knn:
         if not 1 <= a.classes <= 4096:

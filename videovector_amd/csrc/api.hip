@@ -319,6 +319,12 @@ static const Option kOptions[] = {
   LAST("last_km_blocks", c->last_km_blocks), LAST("last_km_chunks", c->last_km_chunks), LAST("last_km_assign_form", c->last_km_assign_form),
   LAST("last_km_sim_ms", c->last_km_ms[0]), LAST("last_km_assign_ms", c->last_km_ms[1]), LAST("last_km_group_ms", c->last_km_ms[2]),
   LAST("last_km_update_ms", c->last_km_ms[3]),
+  {"ivf_block_rows", OptKind::Settable, RD(c->ivf_block_rows), [](vv_ctx* c, double, int iv) -> int {
+     if (iv < 0) return fail(VV_ERR_ARG, "vv_set_option: ivf_block_rows = %d is negative", iv);
+     c->ivf_block_rows = iv; return VV_OK; }},
+  {"ivf_grid_wgs", OptKind::Settable, RD(c->ivf_grid_wgs), [](vv_ctx* c, double, int iv) -> int {
+     if (iv < 0 || iv > IVF_GRID_MAX) return fail(VV_ERR_ARG, "vv_set_option: ivf_grid_wgs = %d is outside 0 .. %d", iv, IVF_GRID_MAX);
+     c->ivf_grid_wgs = iv; return VV_OK; }},
   LAST("last_fwd_tile_rows", c->ko.last_fwd_tile_rows), LAST("last_wgrad_splits", c->ko.last_wgrad_splits),
   LAST("last_update_form", c->ko.last_update_form), LAST("last_score_form", c->ko.last_score_form),
   {"last_grad_shift", OptKind::ReadOnly, [](vv_ctx* c, double* v) -> int { return last_grad(c, 0, v); }, nullptr},

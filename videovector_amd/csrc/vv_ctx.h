@@ -1,6 +1,6 @@
 // vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the context, the options, the table, the
 // parameters, the accessors), pass.hip (the pass over a batch: the fused training step's forward and backward), solver.hip (the
-// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip and kmeans.hip (the
+// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip, kmeans.hip and ivf.hip (the
 // evaluation paths); below it, what these files call of one another.  Internal.
 #pragma once
 #include <cstdarg>
@@ -257,6 +257,10 @@ struct vv_ctx {
   int km_block_rows = 0;
   int last_km_blocks = 0, last_km_chunks = 0, last_km_assign_form = 0;
   double last_km_ms[4] = {0, 0, 0, 0};
+  // vv_ivf_search (ivf.hip): "ivf_block_rows" (query rows of one block) and "ivf_grid_wgs" (workgroups of the grouped similarity's fixed
+  // grid); 0: the plan's choice, vv_ivf_plan.h -- they exist so that the tests reach several blocks, and more tiles than workgroups, at
+  // small shapes.  What the last search ran is the index's own (vv_ivf_get)
+  int ivf_block_rows = 0, ivf_grid_wgs = 0;
   int comm_test_delay_us = 0;       // "comm_test_delay_us" / VV_COMM_TEST_DELAY_US: TEST HOOK -- the communication stream held this long per chunk
   // (lab) -- settable in a -DVV_LAB build only
   bool guard_proactive = true;      // VV_GUARD_PROACTIVE=0: the repeat form of the gradient-scale guard on the segment-wise path too

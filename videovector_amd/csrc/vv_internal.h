@@ -8,6 +8,7 @@
 #include "vv_pass_plan.h"      // score_fwd_supported / score_fwd_dropout_supported: the shapes the segment-wise pair is built for
 #include "vv_gallery_plan.h"   // the RT_* sizes the gallery scratch is made of, its limits and its sizing arithmetic
 #include "vv_kmeans_plan.h"    // the KM_* sizes of vv_gallery_kmeans and its block plan
+#include "vv_ivf_plan.h"       // the IVF_* sizes of vv_ivf_search and its block plan
 
 struct vv_gallery;
 
@@ -782,6 +783,37 @@ void launch_km_partial(const float* feat, int64_t n, int Dp, const int32_t* list
 // init: cent holds the initial centroids, only nn is written
 void launch_km_finish(const float* part, int Dp, int dim, const int32_t* counts, const int32_t* cbase, int64_t max_chunks, int C, int euclid, int init,
                       float* cent, float* nn, KmRec* rec, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Inverted-file search (kernels_ivf.hip, ivf.hip); the sizes are vv_ivf_plan.h's
+// ---------------------------------------------------------------------------------------------
+static_assert(IVF_TILE == RT_BM && IVF_TILE == RT_BN, "vv_ivf_plan.h counts the similarity kernel's tiles");
+struct IvfRec { long long tiles, candidates; };         // one call: the tiles its blocks listed, the sum of its queries' candidate counts
+static_assert(sizeof(IvfRec) == IVF_REC_BYTES, "vv_ivf_plan.h sizes the record");
+// One block's (query, cluster) pairs: pair i * nprobe + p is query row i's p-th probed cluster.  Every array is the library's own.
+struct IvfBlock {
+  const float* Q;                  // [rows][Dp] the query block, zero padded
+  const float* slab;               // [n_ref][Dp] the index's cluster-contiguous rows
+  const int32_t* start;            // [C + 1] cluster c's rows are slab rows start[c] .. start[c + 1] - 1
+  const int32_t* list;             // [n_ref] slab row -> item index
+  const int32_t* probe;            // [pairs] the pair's cluster
+  const int32_t* off;              // [pairs] where the cluster's candidates begin in the query's candidate row
+  const int32_t* qstart;           // [C + 1] the pairs grouped by cluster: cluster c's are qlist[qstart[c] .. qstart[c + 1])
+  const int32_t* qlist;            // [pairs] pair indices, by cluster, ascending inside one
+  const int4* tiles;               // [tile_cap] {cluster, query tile, item tile, 0}
+  const int32_t* ntiles;           // [1]
+  float* cand;                     // [rows][pitch]
+  int64_t pitch;
+  int rows, Dp, C, nprobe, tile_cap;
+};
+// score: [rows][C] what launch_sim_f32 stored for the block against the centroids; nn: [C] (euclid) or unread; counts: [C], zero on
+// entry -- the pairs of every cluster; m: [rows] candidate counts.  all: nprobe == C, every cluster in ascending order, nothing selected
+void launch_ivf_probe(const float* score, int rows, int C, int nprobe, int all, int euclid, const float* nn, const int32_t* start,
+                      int32_t* probe, int32_t* off, int32_t* m, int32_t* counts, IvfRec* rec, hipStream_t s);
+void launch_ivf_tiles(const int32_t* start, const int32_t* qstart, int C, int4* tiles, int tile_cap, int32_t* ntiles, IvfRec* rec, hipStream_t s);
+void launch_sim_f32_grouped(const IvfBlock& b, int grid_wgs, hipStream_t s);
+// idx / dist: [rows][k], slots past m[row] read -1 / 0
+void launch_ivf_select(const IvfBlock& b, int k, int32_t* idx, float* dist, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // 16-bit operand types

@@ -207,6 +207,9 @@ def load_library():
         "vv_kmeans_cfg_default": [C.POINTER(_KmeansCfg)],
         "vv_gallery_kmeans": [vp, vp, C.POINTER(_KmeansCfg), vp, vp, vp, vp, vp, vp, vp, C.POINTER(_KmeansReport)],
         "vv_kmeans_init_rows": [C.c_uint64, i32, i32, vp],
+        "vv_ivf_create": [vp, vp, vp, i32, i32, vp, C.POINTER(vp)], "vv_ivf_destroy": [vp, vp],
+        "vv_ivf_search": [vp, vp, vp, i32, i32, i32, vp, vp, vp],
+        "vv_ivf_get": [vp, C.c_char_p, C.POINTER(C.c_double)], "vv_ivf_lists": [vp, vp, vp, vp],
         "vv_classification_stats": [vp, vp, i64, i32, vp, C.c_int, vp, vp, vp, C.POINTER(_ClassificationReport)],
         "vv_linear_create": [vp, i32, i32, C.c_int, C.POINTER(vp)], "vv_linear_destroy": [vp, vp],
         "vv_linear_get": [vp, vp, vp, vp, vp, vp, C.POINTER(i64)], "vv_linear_put": [vp, vp, vp, vp, vp, vp, i64],
@@ -269,14 +272,75 @@ def kmeans_init_rows(seed, n, num_clusters):
 
 class KMeansResult:
     """What Gallery.kmeans returns: centroids fp32 [C][dim], assign int32 [n_ref], counts int32 [C], objective float64 [iters + 1],
-    moved int64 [iters + 1], report (dict of vv_kmeans_report's fields); gallery() puts the centroids on the device as a Gallery."""
+    moved int64 [iters + 1], report (dict of vv_kmeans_report's fields), metric (VV_KMEANS_*); gallery() puts the centroids on the
+    device as a Gallery, ivf(items) builds an inverted-file index of `items` on them."""
 
-    def __init__(self, eng, centroids, assign, counts, objective, moved, report):
+    def __init__(self, eng, centroids, assign, counts, objective, moved, report, metric=0):
         self.eng, self.centroids, self.assign, self.counts = eng, centroids, assign, counts
-        self.objective, self.moved, self.report = objective, moved, report
+        self.objective, self.moved, self.report, self.metric = objective, moved, report, metric
 
     def gallery(self):
         return self.eng.gallery(self.centroids)
+
+    def ivf(self, items):
+        """An IVFIndex of the Gallery `items` on these centroids under this clustering's metric; the index assigns for itself."""
+        return self.eng.ivf(items, self.centroids, metric=self.metric, assign=None)
+
+
+class IVFIndex:
+    """An inverted-file index held on the device by an Engine (vv_ivf_create; include/videovec.h states the arithmetic)."""
+
+    def __init__(self, eng, handle):
+        self.eng, self.h = eng, handle
+
+    def get(self, name):
+        v = C.c_double()
+        self.eng._chk(self.eng.L.vv_ivf_get(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    @property
+    def n_ref(self):
+        return int(self.get("n_ref"))
+
+    @property
+    def dim(self):
+        return int(self.get("dim"))
+
+    @property
+    def num_clusters(self):
+        return int(self.get("num_clusters"))
+
+    def search(self, q, k, nprobe):
+        """(idx int32 [n_q][k], dist fp32 [n_q][k], n_candidates int32 [n_q]): the k <= 32 nearest items among those of each query's
+        nprobe nearest clusters, ascending (distance, item index); slots past a query's candidates read -1 / 0."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise VVError("queries must be [n_q][%d]" % self.dim)
+        idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
+        dist = np.empty(idx.shape, np.float32)
+        ncand = np.zeros(q.shape[0], np.int32)
+        self.eng._chk(self.eng.L.vv_ivf_search(self.eng.h, self.h, _ptr(q), q.shape[0], int(nprobe), int(k), _ptr(idx), _ptr(dist),
+                                               _ptr(ncand)))
+        return idx, dist, ncand
+
+    def lists(self):
+        """(start int32 [C + 1], list int32 [n_ref]): cluster c's items, ascending, are list[start[c]:start[c + 1]]."""
+        start = np.zeros(self.num_clusters + 1, np.int32)
+        lst = np.zeros(self.n_ref, np.int32)
+        self.eng._chk(self.eng.L.vv_ivf_lists(self.eng.h, self.h, _ptr(start), _ptr(lst)))
+        return start, lst
+
+    def close(self):
+        if self.h is not None:
+            h, self.h = self.h, None
+            if self.eng.h:                      # (an engine closed first took its device with it)
+                self.eng._chk(self.eng.L.vv_ivf_destroy(self.eng.h, h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Gallery:
@@ -442,7 +506,7 @@ class Gallery:
         rep = _KmeansReport()
         self.eng._chk(self.eng.L.vv_gallery_kmeans(self.eng.h, self.h, C.byref(cfg), _ptr(cent0), _ptr(rows0), _ptr(cent), _ptr(assign),
                                                    _ptr(counts), _ptr(obj), _ptr(moved), C.byref(rep)))
-        return KMeansResult(self.eng, cent, assign, counts, obj, moved, {f: getattr(rep, f) for f, _ in _KmeansReport._fields_})
+        return KMeansResult(self.eng, cent, assign, counts, obj, moved, {f: getattr(rep, f) for f, _ in _KmeansReport._fields_}, int(metric))
 
     def rows(self):
         """The gallery's fp32 rows [n_ref][dim], downloaded from the device."""
@@ -1234,6 +1298,26 @@ class Engine:
     def op_gemm_tn(self, A, lda, B, ldb, k, m, n, out):
         """vv_op_gemm_tn: out [m][n] = A^T B for device A [k][lda >= m], B [k][ldb >= n] (DevBufs or device pointers)."""
         self._chk(self.L.vv_op_gemm_tn(self.h, _dev_ptr(A), int(lda), _dev_ptr(B), int(ldb), int(k), int(m), int(n), _dev_ptr(out)))
+
+    def ivf(self, items, centroids, metric="euclidean", assign=None):
+        """An inverted-file index of the Gallery `items` (vv_ivf_create): centroids fp32 [C][dim], metric "euclidean" or "spherical" (the
+        probe's key is k-means'), assign int32 [n_ref] -- the list of every item, taken as it is -- or None: the index assigns every
+        item to its nearest centroid as Gallery.kmeans(iters=0) does."""
+        if isinstance(metric, str):                       # (an integer goes to the library as it is: VV_KMEANS_*)
+            if metric not in KMEANS_METRICS:
+                raise VVError("ivf: metric must be one of %s" % ", ".join(sorted(KMEANS_METRICS)))
+            metric = KMEANS_METRICS[metric]
+        cent = np.ascontiguousarray(centroids, dtype=np.float32)
+        if cent.ndim != 2 or cent.shape[1] != items.dim:
+            raise VVError("ivf: centroids must be [num_clusters][%d]" % items.dim)
+        a = None
+        if assign is not None:
+            a = np.ascontiguousarray(assign, dtype=np.int32)
+            if a.shape != (items.n_ref,):
+                raise VVError("ivf: assign must be [n_ref]")
+        h = C.c_void_p()
+        self._chk(self.L.vv_ivf_create(self.h, items.h, _ptr(cent), cent.shape[0], int(metric), _ptr(a), C.byref(h)))
+        return IVFIndex(self, h)
 
     def gallery(self, feat, ids=None):
         """A fixed reference set on the device (vv_gallery_create): feat fp32 [n_ref][dim], ids [n_ref] or None (top-k only)."""
