@@ -1,11 +1,14 @@
 """tests/ivf_ref.py by hand, without a GPU: three small cases whose answers are written out -- a tie across two clusters, an empty
-probed list, k above a query's candidates -- the probe's rules, and recall 1 with nprobe = C."""
+probed list, k above a query's candidates -- the probe's rules, and recall 1 with nprobe = C; lists_of against a bucket loop at the
+sizes and patterns at which it is the oracle of the device's grouping (tests/edge_inputs.py)."""
 import os
 import sys
 
 import numpy as np
+import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import edge_inputs as inp   # noqa: E402
 import ivf_ref as ref   # noqa: E402
 
 F32 = np.float32
@@ -81,3 +84,29 @@ def test_recall_is_one_with_every_cluster_probed():
     assert ref.recall(full["idx"], exact, 1) == 1.0 and ref.recall(full["idx"], exact, k) == 1.0
     part = ref.search(d_items, d_cent, None, "spherical", start, lst, nprobe=2, k=k)
     assert 0.0 < ref.recall(part["idx"], exact, k) < 1.0
+
+
+@pytest.mark.parametrize("n,C,pattern", inp.GROUP_CASES)
+def test_lists_of_against_a_bucket_loop(n, C, pattern):
+    """lists_of is the oracle of the device's grouping at these sizes and patterns (tests/test_gpu_kmeans_edges.py): here against one
+    bucket per cluster, filled in item order"""
+    assign = inp.group_assign(n, C, pattern)
+    assert assign.shape == (n,) and assign.min() >= 0 and assign.max() < C
+    buckets = [[] for _ in range(C)]
+    for i, c in enumerate(assign.tolist()):
+        buckets[c].append(i)
+    want_start, want_lst = [0], []
+    for b in buckets:
+        want_lst += b
+        want_start.append(len(want_lst))
+    start, lst = ref.lists_of(assign, C)
+    assert start.dtype == np.int32 and lst.dtype == np.int32
+    assert start.tolist() == want_start and lst.tolist() == want_lst
+    # the patterns are what they were made for
+    if pattern == "one_cluster":
+        assert want_start[C - 1] == 0 and want_start[C] == n
+    if pattern == "round_robin" and C >= 64:
+        assert all(len(set(assign[j:j + 64].tolist())) == 64 for j in range(0, n - 63, 64))
+    if pattern in ("ascending", "descending"):
+        step = np.diff(assign.astype(np.int64))
+        assert (step >= 0).all() if pattern == "ascending" else (step <= 0).all()

@@ -1,7 +1,9 @@
 """tests/kmeans_ref.py on the host, before the GPU tests lean on it: against a plain float64 Lloyd iteration on well-separated blobs
 (equal assignments; centroids within count * 2^-24 * max|x| per element, the serial chain's own bound: count - 1 additions, each off
 by at most half an ulp of a partial sum that is at most count * max|x|, and one multiplication), the chunk order by hand on three tiny
-cases, the objective's fold, and the tie and NaN rules."""
+cases, the objective's fold, and the tie and NaN rules; then the NaN, Inf and degenerate rules against a plain-Python twin on the inputs
+the GPU tests use (tests/edge_inputs.py)."""
+import math
 import os
 import sys
 
@@ -10,6 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import edge_inputs as inp   # noqa: E402
 import kmeans_ref as ref   # noqa: E402
 
 F32 = np.float32
@@ -101,3 +104,147 @@ def test_ties_nan_and_degenerate():
     x = np.array([[1.0], [-1.0], [3.0]], F32)
     new, empty, degenerate = ref.update(x, np.array([0, 0, 1], np.int32), np.array([[7.0], [7.0]], F32), "spherical")
     assert new[:, 0].tolist() == [7.0, 1.0] and (empty, degenerate) == (0, 1)   # s = 0: the row stays
+
+
+# ------------------------------------------------------------------------------------------------ the NaN, Inf and degenerate rules
+# A twin of the restatement's rules in plain Python: one float32 scalar at a time, no numpy reduction, no masking, no argsort.  The
+# restatement is the oracle of tests/test_gpu_kmeans_edges.py on the inputs of tests/edge_inputs.py; here it is held to the twin on
+# the same inputs, the distances computed on the host.
+def twin_chain_sq(row):
+    q = F32(0.0)
+    for v in row:
+        q = F32(q + F32(v * v))
+    return q
+
+
+def twin_keys(d, cent, metric):
+    key = np.array(d, F32, copy=True)
+    if metric == "euclidean":
+        for c in range(cent.shape[0]):
+            nn = twin_chain_sq(cent[c])
+            for i in range(key.shape[0]):
+                key[i, c] = F32(d[i, c] + nn)
+    return key
+
+
+def twin_assign(key):
+    """per row: the first cluster whose key is a number and below every earlier one; none: cluster 0"""
+    out = []
+    for row in key:
+        best = None
+        for c, k in enumerate(row):
+            if math.isnan(k):
+                continue                                                        # a NaN key is never selected
+            if best is None or k < row[best]:                                   # (strictly: the lowest cluster keeps a tie)
+                best = c
+        out.append(0 if best is None else best)
+    return out
+
+
+def twin_update(x, a, cent, metric):
+    new = np.array(cent, F32, copy=True)
+    empty = degenerate = 0
+    for c in range(cent.shape[0]):
+        items = [i for i in range(len(a)) if a[i] == c]                         # ascending item index
+        if not items:
+            empty += 1                                                          # the previous centroid stays
+            continue
+        s = None
+        for b in range(0, len(items), 256):                                     # chunks of 256 list entries, added in ascending order
+            acc = [F32(v) for v in x[items[b]]]
+            for i in items[b + 1:b + 256]:
+                acc = [F32(u + v) for u, v in zip(acc, x[i])]
+            s = acc if s is None else [F32(u + v) for u, v in zip(s, acc)]
+        if metric == "spherical":
+            q = twin_chain_sq(s)
+            if q == 0 or math.isnan(q) or math.isinf(q):
+                degenerate += 1                                                 # the previous centroid stays
+                continue
+            nrm = np.sqrt(q, dtype=F32)
+            new[c] = [F32(v / nrm) for v in s]
+        else:
+            inv = F32(F32(1.0) / F32(len(items)))
+            new[c] = [F32(v * inv) for v in s]
+    return new, empty, degenerate
+
+
+def twin_run(x, cent0, iters, metric, scores_fn):
+    cent, prev, passes = np.array(cent0, F32, copy=True), None, []
+    empty = degenerate = 0
+    for t in range(iters + 1):
+        key = twin_keys(scores_fn(cent), cent, metric)
+        a = twin_assign(key)
+        sel = [key[i, a[i]] for i in range(len(a))]
+        counts = [0] * cent.shape[0]
+        for c in a:
+            counts[c] += 1
+        passes.append(dict(assign=a, counts=counts, centroids=cent.copy(),
+                           moved=len(a) if prev is None else sum(1 for u, v in zip(a, prev) if u != v),
+                           nonfinite=sum(1 for v in sel if math.isnan(v) or math.isinf(v))))
+        prev = a
+        if t == iters:
+            break
+        cent, empty, degenerate = twin_update(x, a, cent, metric)
+    return dict(passes=passes, centroids=cent, empty_last=empty, degenerate_last=degenerate)
+
+
+def same_or_nan(got, want):
+    """NaN where the twin has a NaN (numpy and Python need not agree on a payload), equal bits everywhere else"""
+    got, want = np.ascontiguousarray(got, F32), np.ascontiguousarray(want, F32)
+    nan = np.isnan(want)
+    return got.shape == want.shape and np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+
+
+def held_to_the_twin(x, init, iters, metric):
+    with np.errstate(all="ignore"):
+        got = ref.run(x, init, iters, metric, host_scores(x))
+        want = twin_run(x, init, iters, metric, host_scores(x))
+    assert len(got["passes"]) == iters + 1
+    for g, w in zip(got["passes"], want["passes"]):
+        assert g["assign"].tolist() == w["assign"] and g["counts"].tolist() == w["counts"]
+        assert g["moved"] == w["moved"] and g["nonfinite"] == w["nonfinite"]
+        assert same_or_nan(g["centroids"], w["centroids"])
+    assert same_or_nan(got["centroids"], want["centroids"])
+    assert (got["empty_last"], got["degenerate_last"]) == (want["empty_last"], want["degenerate_last"])
+    return got
+
+
+@pytest.mark.parametrize("metric", ["euclidean", "spherical"])
+def test_nonfinite_rules_against_the_twin(metric):
+    x, init = inp.nonfinite_case()
+    got = held_to_the_twin(x, init, 2, metric)
+    for t, st in enumerate(got["passes"]):
+        assert st["assign"][inp.NAN_ROW] == 0 and np.isnan(st["sel"][inp.NAN_ROW])      # every key of the row is NaN: cluster 0
+        assert np.isinf(st["sel"][inp.PINF_ROW]) or np.isnan(st["sel"][inp.PINF_ROW])
+        assert st["nonfinite"] >= 1 and math.isnan(st["objective"])
+        assert np.array_equal(st["counts"], np.bincount(st["assign"], minlength=5))
+    if metric == "spherical":
+        # the NaN row's cluster has a q that is not finite at every update: degenerate, its centroid kept, every centroid finite
+        assert got["degenerate_last"] >= 1 and np.isfinite(got["centroids"]).all()
+        assert np.array_equal(got["centroids"][0], init[0])
+    else:
+        assert np.isnan(got["passes"][1]["centroids"][0, 4])                            # the NaN row's column of its cluster's mean
+
+
+def test_degenerate_rules_against_the_twin():
+    x, init, orth = inp.zero_sum_case()
+    got = held_to_the_twin(x, init, 1, "spherical")
+    assert np.array_equal(np.flatnonzero(got["passes"][0]["assign"] == 0), orth)
+    assert got["degenerate_last"] == 1 and got["empty_last"] == 0 and np.array_equal(got["centroids"][0], init[0])
+    assert not np.array_equal(got["centroids"][1], init[1])
+    x, init, big = inp.overflow_case()
+    got = held_to_the_twin(x, init, 1, "spherical")
+    assert np.array_equal(np.flatnonzero(got["passes"][0]["assign"] == 0), big)
+    assert got["degenerate_last"] == 1 and got["empty_last"] == 0 and np.array_equal(got["centroids"][0], init[0])
+    assert got["passes"][0]["nonfinite"] == 0 and np.isfinite(got["centroids"]).all()
+    assert held_to_the_twin(x, init, 1, "euclidean")["degenerate_last"] == 0        # EUCLIDEAN has no such rule: the mean is 1e19 e1
+    x, init = inp.pairs_case()
+    got = held_to_the_twin(x, init, 1, "spherical")
+    assert got["degenerate_last"] == 1 and np.array_equal(got["centroids"], init) and got["passes"][1]["moved"] == 0
+
+
+def test_twin_assign_by_hand():
+    nan, inf = float("nan"), float("inf")
+    key = np.array([[1, 1, 0.5, 0.5], [nan, 2, 2, nan], [nan] * 4, [inf, nan, inf, 1], [nan, inf, inf, nan], [0.0, -0.0, nan, 0.0],
+                    [nan, -inf, -inf, 3]], F32)
+    assert twin_assign(key) == [2, 1, 0, 3, 1, 0, 1] == ref.assign_of(key).tolist()
