@@ -1,5 +1,7 @@
 """The softmax linear classifier on the device (vv_linear_*) against tests/linear_ref.py on the blob inputs: n = 256 items, C = 4,
-dim = 8, label i % 4, class mean 3 e_c, noise 0.5 N(0, 1) from RandomState(7) rounded to fp32.
+dim = 8, label i % 4, class mean 3 e_c, noise 0.5 N(0, 1) from RandomState(7) rounded to fp32.  The five-step rule and the gradient
+bound are written in dim, C and count, and also run at 515 x 130 x 33 (Dp 160, Cp 64: two column tiles of the weight gradient, five
+splits) and 300 x 40 x 3 with ragged batches; the hinge loss is held exactly at such shapes by tests/test_gpu_linear_step_exact.py.
 
 Five steps: W, b, both histories and the loss trace against the float64 fit within 4 x the float32 restatement's own deviation from
 it (largest over the array) plus one ulp of the array's largest magnitude -- the project's rule of test_gpu_score_seg_exact.py.
@@ -25,6 +27,8 @@ from videovector_amd.synth import SyntheticVideos, init_weights   # noqa: E402
 pytestmark = pytest.mark.gpu
 
 HP = dict(lr=0.5, momentum=0.9, weight_decay=1e-4)
+BLOBS = (256, 8, 4)                               # (n, dim, C): linear_ref.blobs' defaults
+LARGER = {(515, 130, 33): 41, (300, 40, 3): 42}   # ... and the seeds of the larger shapes
 
 
 @pytest.fixture(scope="module")
@@ -41,8 +45,18 @@ def data(eng):
     return X, y, eng.gallery(X)
 
 
+@pytest.fixture(scope="module")
+def sets(eng, data):
+    """{(n, dim, C): (X, y, gallery)}; never written to."""
+    out = {BLOBS: data}
+    for (n, dim, C), seed in LARGER.items():
+        X, y = ref.blobs(n=n, C=C, dim=dim, seed=seed)
+        out[(n, dim, C)] = (X, y, eng.gallery(X))
+    return out
+
+
 def ref_fit(X, y, iters, dtype, bias=True, **kw):
-    st = ref.State(X.shape[1], 4, dtype, bias)
+    st = ref.State(X.shape[1], int(y.max()) + 1, dtype, bias)
     trace, acc = ref.fit(st, X, y, iters, **kw)
     return st, trace, acc
 
@@ -61,7 +75,7 @@ def check_five(eng, data, bias=True, schedule=None, **kw):
         args["lr_schedule"] = schedule
     s64, t64, _ = ref_fit(X, y, 5, np.float64, bias, **args)
     s32, t32, _ = ref_fit(X, y, 5, np.float32, bias, **args)
-    lin = eng.linear(8, 4, bias=bias)
+    lin = eng.linear(X.shape[1], int(y.max()) + 1, bias=bias)
     trace, rep = lin.fit(gal, y, iters=5, **args)
     W, b, hW, hb, steps = lin.get()
     lin.close()
@@ -76,9 +90,12 @@ def check_five(eng, data, bias=True, schedule=None, **kw):
     return W, b, hW, hb, trace
 
 
-@pytest.mark.parametrize("batch", [0, 64, 100])
-def test_five_steps_match_float64(eng, data, batch):
-    check_five(eng, data, batch=batch)
+@pytest.mark.parametrize("batch,shape", [pytest.param(0, BLOBS, id="0"), pytest.param(64, BLOBS, id="64"), pytest.param(100, BLOBS, id="100"),
+                                         pytest.param(0, (515, 130, 33), id="515x130x33-0"), pytest.param(200, (515, 130, 33), id="515x130x33-200"),
+                                         pytest.param(0, (300, 40, 3), id="300x40x3-0"), pytest.param(128, (300, 40, 3), id="300x40x3-128")])
+def test_five_steps_match_float64(eng, sets, batch, shape):
+    """Batches of 200 over 515 items: 200, 200, 115, 200, 200; of 128 over 300: 128, 128, 44, 128, 128."""
+    check_five(eng, sets[shape], batch=batch)
 
 
 def test_five_steps_without_bias_and_with_a_schedule(eng, data):
@@ -93,22 +110,24 @@ def test_five_steps_without_bias_and_with_a_schedule(eng, data):
     lin.close()
 
 
-def test_gradient_matches_float64(eng, data):
-    X, y, gal = data
+@pytest.mark.parametrize("shape", [BLOBS] + list(LARGER), ids=lambda s: "%dx%dx%d" % s)
+def test_gradient_matches_float64(eng, sets, shape):
+    X, y, gal = sets[shape]
+    n, dim, C = shape
     rs = np.random.RandomState(3)
-    W, b = (0.5 * rs.randn(4, 8)).astype(np.float32), (0.5 * rs.randn(4)).astype(np.float32)
-    lin = eng.linear(8, 4)
+    W, b = (0.5 * rs.randn(C, dim)).astype(np.float32), (0.5 * rs.randn(C)).astype(np.float32)
+    lin = eng.linear(dim, C)
     lin.put(W=W, b=b)
-    for first, count, w in ((0, 256, 1.0), (37, 100, 0.25)):
+    for first, count, w in ((0, n, 1.0), (37, 100, 0.25)):
         dW, db, loss = lin.grad(gal, y, first, count, w)
-        st = ref.State(8, 4)
+        st = ref.State(dim, C)
         st.W, st.b = W.astype(np.float64), b.astype(np.float64)
         Xb, yb = X[first:first + count].astype(np.float64), y[first:first + count]
         rW, rb, rloss, _ = ref.gradient(st, Xb, yb, w)
         z = Xb @ st.W.T + st.b
         p = ref.softmax_loss(z, yb, w)[0]
-        dzl = (8 + 2) * 2.0 ** -24 * (np.abs(Xb) @ np.abs(st.W).T + np.abs(st.b)).max(axis=1)
-        R = np.array([ref.p_bound(4, t) for t in (z.max(axis=1) - z.min(axis=1)) + 2 * dzl])
+        dzl = (dim + 2) * 2.0 ** -24 * (np.abs(Xb) @ np.abs(st.W).T + np.abs(st.b)).max(axis=1)
+        R = np.array([ref.p_bound(C, t) for t in (z.max(axis=1) - z.min(axis=1)) + 2 * dzl])
         onehot = np.zeros_like(p)
         onehot[np.arange(count), yb] = 1.0
         scale = w / count
@@ -116,7 +135,7 @@ def test_gradient_matches_float64(eng, data):
         chain = count * 2.0 ** -24
         bW = e_dz.T @ np.abs(Xb) + chain * (np.abs((p - onehot) * scale).T @ np.abs(Xb))
         bb = e_dz.sum(axis=0) + chain * np.abs((p - onehot) * scale).sum(axis=0)
-        print("LINEAR grad count %d: dW at %.3f of its bound, db at %.3f" % (count, (np.abs(dW - rW) / bW).max(), (np.abs(db - rb) / bb).max()))
+        print("LINEAR grad %dx%dx%d count %d: dW at %.3f of its bound, db at %.3f" % (n, dim, C, count, (np.abs(dW - rW) / bW).max(), (np.abs(db - rb) / bb).max()))
         assert (np.abs(dW - rW) <= bW).all() and (np.abs(db - rb) <= bb).all()
         assert abs(float(loss) - rloss) <= (R + 2 * dzl + 3 * ref.EPS * 88).mean() * w + ref.EPS * abs(rloss)
     assert np.array_equal(lin.get()[0], W)                               # nothing was updated

@@ -2,8 +2,9 @@
 
 The oracle needs NO tolerance: a call over a list L of gallery items must equal, bit for bit, the existing contiguous call on a second
 gallery built from X[L] with labels y[L] -- the same arithmetic in the same order on the same values; the gathered forms of the two
-products differ from the contiguous ones in a row's address only.  The contiguous path itself is held to float64 by
-tests/test_gpu_linear_fit.py, test_gpu_softmax_exact.py and test_gpu_hinge_exact.py.
+products differ from the contiguous ones in a row's address only.  The contiguous path itself is held to float64 at these shapes by
+tests/test_gpu_linear_step_exact.py (the whole hinge step, bit for bit) and tests/test_gpu_linear_fit.py (softmax, within its derived
+bounds); the loss kernels alone by test_gpu_softmax_exact.py and test_gpu_hinge_exact.py.
 
 Shapes are where a gather can go wrong: n_ref 300 .. 700, dim 40 / 64 / 130 (Dp 64 / 64 / 160: padded and unpadded rows), C 3 / 33 (Cp 32 /
 64), list lengths on both sides of the 128-row tile and the 32-row K-tile, 1 / 3 / 128 splits and two row blocks, every loss, with and
