@@ -1,5 +1,5 @@
 """Everything between ip2 and the weight-gradient GEMM's operand, restated in numpy (float64; tests only): the score / loss forward
-and the segment-wise backward of videovector_amd/csrc/kernels_elem.hip (k_score_fwd / k_score_stream + k_seg_bwd / k_seg_bwd_cnt, and the
+and the segment-wise backward of videovector_amd/csrc/kernels_score.hip (k_score_fwd / k_score_stream + k_seg_bwd / k_seg_bwd_cnt, and the
 per-instance kernels k_score_loss / k_score_loss_reg), from the math stated at the head of that file:
 
     A = sum_j c_j H[j],  Ah = A / (|A| + eps)

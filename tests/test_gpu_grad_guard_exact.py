@@ -26,7 +26,7 @@ Observed on an MI355X, 41 cases, 5.5 s for the whole file (every case prints "GG
       items): round 1 takes 13, round 2 five more (18); the sums of clipped rows reported 480 x 65504.  idle: all records 0.
   c   looseness 43.7 / 66.3 with distinct negatives (D = 512 / 1024), 791 / 1345 with the 480-fold row: past the 2^10 that the kernel's
       comment ("tens to hundreds") allowed.  The values stay normal f16 numbers (largest 20.7 and 12.2) and every element passes rule (a), so
-      the comment in kernels_elem.hip now states the measured values and the bound asserted here is 2^11.  cnt_max: 480 against 3, log2 of
+      the comment in kernels_score.hip now states the measured values and the bound asserted here is 2^11.  cnt_max: 480 against 3, log2 of
       the products' ratio 7.28 / 7.32, shifts 17 - 10 = 7.
   d   seg: shifts -27, -7, 11 for k = -20, 0, 18; dyu, dW, db, loss bit-identical.  sum / dense: k = 18 and 24 bit-identical (shifts 7 / 13,
       8 / 14); against k = 0 under 1 % of the non-zero elements are subnormal in one run (a sum counts as such when one of its rows is).
@@ -152,7 +152,7 @@ def check_seg(o, tag):
     L = 2.0 ** 14 / top
     print("GG %s: proactive shift %d, scale 2^%d, max |dyu| scaled %.4g, looseness %.1f" % (tag, o["grad_shift"], int(np.log2(o["scale"])), top, L))
     assert o["grad_repeat"] == 0 and top < 2.0 ** 14, (tag, o["grad_repeat"], top)
-    assert L <= 2.0 ** 11, "%s: the bound is %.0f times the true maximum; the bound asserted is what kernels_elem.hip's comment states" % (tag, L)
+    assert L <= 2.0 ** 11, "%s: the bound is %.0f times the true maximum; the bound asserted is what kernels_score.hip's comment states" % (tag, L)
     return r64, L
 
 

@@ -1,9 +1,9 @@
-"""The score / loss forward and the segment-wise backward, element by element against float64 (kernels_elem.hip: k_score_fwd,
+"""The score / loss forward and the segment-wise backward, element by element against float64 (kernels_score.hip: k_score_fwd,
 k_score_stream, k_seg_bwd, k_seg_bwd_cnt; and the per-instance kernels k_score_loss / k_score_loss_reg through ip1_diff).
 
 Every case runs ONE forward_backward under the shipped defaults (f16 rows of ip2: h16 = 1; no fp32_ip2 fixture), asserts which forms ran
 (last_score_form, last_h16, dedup_stats), reads ip2 back and hands it to tests/score_ref.py: the reference restates the math of
-kernels_elem.hip's head in float64 from the very rows the kernels read, with the grouping of tests/pyref.py, so what is compared is the
+kernels_score.hip's head in float64 from the very rows the kernels read, with the grouping of tests/pyref.py, so what is compared is the
 pair alone.  Then
 
   scores      |got - ref64| <= eps_s for every pair;                       eps_s = 4 max |ref32 - ref64| over the case's scores

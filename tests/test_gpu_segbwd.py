@@ -1,4 +1,4 @@
-"""GPU tests of the segment-wise backward of de-duplicated batches (kernels_elem.hip: k_score_fwd + k_seg_bwd): the
+"""GPU tests of the segment-wise backward of de-duplicated batches (kernels_score.hip: k_score_fwd + k_seg_bwd): the
 gradient of ip1_nonorm stays factored per instance and is summed per DISTINCT row; the per-instance 16-bit rows are never
 written.  Checked against the path that writes them (VV_SEG_BWD=0: k_score_loss_reg + k_segsum), against the dense
 path, and against the oracle.  The pair is built for the fc width of the hot path (D = 512)."""

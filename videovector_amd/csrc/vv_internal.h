@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "vv_pass_plan.h"      // score_fwd_supported / score_fwd_dropout_supported: the shapes the segment-wise pair is built for
 #include "vv_gallery_plan.h"   // the RT_* sizes the gallery scratch is made of, its limits and its sizing arithmetic
@@ -277,7 +278,7 @@ struct SegBwdArgs {
   int h16 = 0;                   // H holds f16 rows (FwdArgs::h16)
   int v16 = 0;                   // V holds f16 rows (ScoreArgs::v16: the one-sweep score kernel wrote them so)
   uint32_t* h16_cnt = nullptr;   // non-null (option "h16_guard" >= 1; f16 rows, guard round 0): [SEGB_BLOCKS][2] per-workgroup counts of the rows'
-                                 //   {saturated elements, faint rows} (k_seg_bwd_cnt, kernels_elem.hip); every workgroup writes its pair
+                                 //   {saturated elements, faint rows} (k_seg_bwd_cnt, kernels_score.hip); every workgroup writes its pair
 };
 
 struct SegsumArgs {
@@ -548,7 +549,7 @@ struct KernelOpts {
   int lab_wg_abl = 0;      // (lab) VV_LAB_WG_ABL
   int ph_mq = 0;           // (lab) VV_PH_MQ: force the forward tile (2, 3, 4 = 128 / 192 / 256 rows)
   int score_reg = 1;       // (lab) VV_SCORE_REG=0: the LDS-resident score kernel
-  int score_rr = 0;        // (lab) VV_SCORE_RR=1: the item-major kernels deal their items round-robin over the XCDs again (kernels_elem.hip: item_of_block)
+  int score_rr = 0;        // (lab) VV_SCORE_RR=1: the item-major kernels deal their items round-robin over the XCDs again (kernels_score.hip: item_of_block)
   // What the launchers last chose for this context (read-only through vv_get_option: "last_fwd_tile_rows", "last_wgrad_splits",
   // "last_update_form", "last_score_form"): written where the kernel is launched (launch_fwd_ph_q / launch_wgrad_gemm / launch_sgd /
   // launch_reduce_sgd / launch_score_fwd / launch_score_loss), so a test
@@ -581,6 +582,26 @@ extern thread_local ProfPair g_prof;
 #define VV_LAUNCH(kern, grid, block, lds, s, ...) VV_LAUNCH_EV(kern, grid, block, lds, s, true, true, __VA_ARGS__)
 #define VV_LAUNCH_FIRST(kern, grid, block, lds, s, ...) VV_LAUNCH_EV(kern, grid, block, lds, s, true, false, __VA_ARGS__)
 #define VV_LAUNCH_LAST(kern, grid, block, lds, s, ...) VV_LAUNCH_EV(kern, grid, block, lds, s, false, true, __VA_ARGS__)
+// ... of a kernel with dynamic LDS: the opt-in to more than the default 64 KB, then the launch
+#define VV_LAUNCH_LDS(kern, grid, block, lds, s, ...)                                                       \
+  do {                                                                                                     \
+    (void)hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
+    VV_LAUNCH(kern, grid, block, lds, s, __VA_ARGS__);                                                     \
+  } while (0)
+
+// Launch dispatch: run-time flags and the precision become compile-time arguments of a generic lambda, so that a launcher names each
+// kernel template once instead of once per combination.  with_flags(f, b1, b2, ...) calls f(std::bool_constant<b1>{}, ...);
+// with_prec(prec, f) calls f(TypeTag<F16>{}) or f(TypeTag<BF16>{}).  Every path through the lambda's body is instantiated for EVERY
+// combination of its arguments: a combination that has no kernel on purpose is kept out of the lambda by a run-time branch in front of
+// it, or inside it by an `if constexpr` that leaves it an empty body (the set of kernels in the library does not grow).
+template <typename T> struct TypeTag { using type = T; };
+struct F16; struct BF16;
+template <typename F> inline void with_flags(F&& f) { f(); }
+template <typename F, typename... B> inline void with_flags(F&& f, bool b, B... rest) {
+  if (b) with_flags([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+  else with_flags([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
+template <typename F> inline void with_prec(int prec, F&& f) { if (prec == 0) f(TypeTag<F16>{}); else f(TypeTag<BF16>{}); }
 
 // kernel launchers (defined in the .hip files); prec: 0 = f16, 1 = bf16
 void launch_fwd_gemm(int prec, const FwdArgs& a, hipStream_t s);
