@@ -774,6 +774,58 @@ int vv_ivf_search(vv_ctx* ctx, vv_ivf* index, const float* q, int32_t n_q, int32
 int vv_ivf_get(const vv_ivf* index, const char* name, double* value);
 int vv_ivf_lists(vv_ctx* ctx, vv_ivf* index, int32_t* start, int32_t* list);
 
+/* ---- product-quantised lists (IVF-PQ): the inverted-file index with every item kept as M one-byte codes in place of its fp32 row.
+ * HAS NO REFERENCE COUNTERPART (the reference quantises nothing); the arithmetic below is this project's own and is stated exactly.
+ * Every fp32 operation is rounded as written and none is contracted.
+ * Sub-space m = 0 .. M - 1 is the columns m dsub .. (m + 1) dsub - 1, dsub = dim / M.
+ * Training (vv_pq_train).  codebooks_out[m], host [ksub][dsub], is exactly the centroids_out of vv_gallery_kmeans (EUCLIDEAN, ksub
+ *   clusters, iters, init_rows = vv_kmeans_init_rows(seed + m, n_ref, ksub)) on a gallery made of those columns of the items; that call's
+ *   body runs on a column slice cut on the device, nothing of it is restated.  objective_out[m] (or NULL) is its objective_last.
+ * Encoding (vv_pq_encode, and vv_ivfpq_create for itself).  code[g][m] is the assignment that call returns with iters = 0 and
+ *   init_centroids = codebooks[m]: k-means' key d + nn_c, the lowest codeword at a tie, a row of nothing but NaN to codeword 0.  Since
+ *   that call is made, ksub <= n_ref holds for encoding as for training.  Codes are never taken from the host: every byte that indexes
+ *   a table was written by the library's own encoder and is < ksub.
+ * Table of query i (kernel k_pq_lut).  lut(i, m, j) = -2.0f * s + 0.0f; s is the serial chain over the sub-space's columns in ascending
+ *   order starting from +0.0f, s = s + q[i][col] * codebooks[m][j][col], every product and every sum rounded on its own.  This is NOT
+ *   the similarity kernel's float: dsub is small, and numpy restates the chain directly (tests/pq_ref.py).
+ * Approximate distance a(i, g): the serial chain acc = lut(i, 0, code[g][0]), then acc = acc + lut(i, m, code[g][m]), m = 1 .. M - 1.
+ * Probe, candidates of query i, n_candidates: vv_ivf_search's, word for word -- the centroid keys are still the similarity kernel's
+ *   floats on full-dimension rows.
+ * Result: the k smallest (a, g) of the candidates, g the item's index in the items gallery; equal a order by ascending g across lists;
+ *   slots past m_i read idx -1, dist 0; dist returns a.
+ * Not residual: a code encodes the raw row, not the row minus its list's centroid, so one table serves all of a query's lists.  The
+ *   index keeps no fp32 item rows and does not re-rank its result against them.
+ * Index (vv_ivfpq_create): centroids, num_clusters, metric and assign_or_null as vv_ivf_create takes them; codebooks: host
+ *   [M][ksub][dsub].  The index owns the code rows in list-position order, the codebooks, the lists, the centroids and nn_c: the items
+ *   gallery may be destroyed afterwards.
+ * Limits: 1 <= M <= 64 and dim % M == 0; 2 <= ksub <= 256 and ksub <= n_ref; M * ksub * 4 <= 65536 (one query's whole table sits in LDS);
+ *   iters >= 0; C, metric, nprobe, k <= 32 and n_q exactly vv_ivf_search's, nprobe == C always allowed; q: host [n_q][dim].
+ * VV_ERR_ARG, found on the host with nothing allocated, launched or written, vv_last_error naming the argument: a NULL required pointer;
+ * a gallery or index of another context; a value outside the limits above; an assign entry outside [0, C) (its position is named); a
+ * shape whose buffers do not fit the gallery path's scratch limit.
+ * Everything of a search is queued on the context's stream, one scratch allocation carved up by csrc/vv_pq_plan.h; the call synchronises
+ * once, at its end, and touches nothing a training step owns.  No floating-point atomics.  Option "ivf_block_rows" is honoured; it
+ * changes no bit of the result.
+ * vv_ivfpq_get: "n_ref", "dim", "num_clusters", "metric", "M", "ksub", "largest_list", "empty_lists", "index_bytes" (every device byte
+ * the index owns, scratch excluded); of the last search "last_blocks", "last_candidates", "last_scan_form" (how k_pq_scan loaded a code
+ * row -- 1: 16 bytes, M % 16 == 0; 2: 4 bytes, M % 4 == 0; 3: bytes; 0: no search yet; identical results) and the device time
+ * "last_probe_ms", "last_lut_ms", "last_scan_ms", "last_select_ms" (more than 64 blocks: the first 64 blocks' legs, scaled) and
+ * "last_device_ms" (the whole call).  An unknown name is VV_ERR_ARG.
+ * vv_ivfpq_lists: as vv_ivf_lists.  vv_ivfpq_codes: host [n_ref][M], row p the codes of item list[p] -- list-position order.
+ * vv_pq_encode: codes_out host [n_ref][M], item order. */
+typedef struct vv_ivfpq vv_ivfpq;
+int vv_pq_train(vv_ctx* ctx, vv_gallery* items, int32_t M, int32_t ksub, int32_t iters, uint64_t seed, float* codebooks_out,
+                double* objective_out_or_null);
+int vv_pq_encode(vv_ctx* ctx, vv_gallery* items, const float* codebooks, int32_t M, int32_t ksub, uint8_t* codes_out);
+int vv_ivfpq_create(vv_ctx* ctx, vv_gallery* items, const float* centroids, int32_t num_clusters, int32_t metric, const int32_t* assign_or_null,
+                    const float* codebooks, int32_t M, int32_t ksub, vv_ivfpq** out);
+int vv_ivfpq_destroy(vv_ctx* ctx, vv_ivfpq* index);
+int vv_ivfpq_search(vv_ctx* ctx, vv_ivfpq* index, const float* q, int32_t n_q, int32_t nprobe, int32_t k, int32_t* idx, float* dist,
+                    int32_t* n_candidates_or_null);
+int vv_ivfpq_get(const vv_ivfpq* index, const char* name, double* value);
+int vv_ivfpq_lists(vv_ctx* ctx, vv_ivfpq* index, int32_t* start, int32_t* list);
+int vv_ivfpq_codes(vv_ctx* ctx, vv_ivfpq* index, uint8_t* codes);
+
 /* ---- class-level leave-one-out statistics on a gallery: RetrievalStatsLayer (src/caffe/layers/retrieval_stats_layer.cpp).
  * vv_gallery_pool_by_id: video_level_retrieval (:165-198).  A new gallery with one item per distinct id of `gallery`, its row the
  * sum over the id's items, in ascending item index, of (1 / count) x_i in fp32 (the reference's weight matrix, :193, :197-198),

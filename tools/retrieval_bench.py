@@ -32,6 +32,15 @@
       against the exact lists of the same invocation, and the share of the tiles' area that is padding (tiles x 128^2 against the
       candidates).  The condition: the search's median below top-k's by more than the two spreads (max - min) together.  Writes the JSON
       it prints to profiles/ivf_<nq>x<ng>x<dim>.json (--out: elsewhere) as well.
+  python tools/retrieval_bench.py --ivfpq 64,16 [--nq 4096 --ng 1000000 --dim 512] [--pq-c 4096 --pq-nprobe 32 --ksub 256] [--rounds 4] [--out FILE]
+      product-quantised lists (vv_ivfpq_search) against the fp32 index (vv_ivf_search), both built on the same Gallery.kmeans(C, iters=10)
+      centroids and assignment: for every M the codebooks are Engine.pq_train(M, ksub, iters = --pq-iters), then the two searches (k = 32)
+      alternate call by call for --rounds rounds behind one warm-up round; per call the library's device events and the host's wall
+      clock, the four legs of either search -- "ivfpq_scan_ms" is k_pq_scan's own device time, "ivf_sim_ms" the grouped similarity's --,
+      index_bytes beside the fp32 index's n_ref Dp 4 bytes of rows, and recall@1 / recall@32 against vv_ivf_search at the same nprobe
+      (the quantisation's loss alone) and against topk(32).  Run on two inputs: the generator below as the other legs use it (noise 4.0
+      on unit-scale centres: an item's neighbours are all but random, so recall there says little) and the same generator with
+      --clustered-noise (0.05, well below the centres' scale).  Writes the JSON it prints to profiles/ivfpq_<nq>x<ng>x<dim>.json as well.
 
 Inputs are seeded: unit rows around `nid` random centres, ids = the centre's index (the generator of tests/gallery_ref.py, drawn in
 float32 blocks so that a million rows need no float64 copy)."""
@@ -234,6 +243,81 @@ def ivf_bench(eng, a):
     return out
 
 
+def recall(idx, want, at):
+    """the share of want's first `at` items (its -1 slots apart) found in idx's first `at`"""
+    hit = total = 0
+    for u, v in zip(idx, want):
+        v = v[:at][v[:at] >= 0]
+        hit += len(np.intersect1d(u[:at], v)); total += len(v)
+    return hit / float(max(total, 1))
+
+
+def ivfpq_bench(eng, a):
+    Ms = [int(x) for x in a.ivfpq.split(",")]
+    Cn, nprobe, ksub = a.pq_c, a.pq_nprobe, a.ksub
+    box = {"before": eng.box_probe()}
+    inputs = []
+    for gen, noise in (("bench", a.noise), ("clustered", a.clustered_noise)):
+        G, gid, cen = make(a.ng, a.dim, a.nid, noise, 5)
+        Q, qid, _ = make(a.nq, a.dim, a.nid, noise, 6, cen)
+        g = eng.gallery(G, gid)
+        print("ivfpq: %s input on the device" % gen, file=sys.stderr, flush=True)
+        km = g.kmeans(Cn, iters=10)
+        flat = eng.ivf(g, km.centroids, metric=km.metric, assign=km.assign)
+        exact = g.topk(Q, 32)
+        res = []
+        for M in Ms:
+            print("ivfpq: %s M = %d" % (gen, M), file=sys.stderr, flush=True)
+            t0 = time.perf_counter()
+            cb, obj = eng.pq_train(g, M, ksub, iters=a.pq_iters, seed=1)
+            t1 = time.perf_counter()
+            pq = eng.ivfpq(g, km.centroids, cb, metric=km.metric, assign=km.assign)
+            t2 = time.perf_counter()
+            legs = dict(ivf=("probe", "group", "sim", "select"), ivfpq=("probe", "lut", "scan", "select"))
+            t = {name: dict(dev=[], wall=[], **{leg: [] for leg in legs[name]}) for name in legs}
+            got = {}
+            for r in range(1 + a.rounds):
+                for name, ix in (("ivf", flat), ("ivfpq", pq)):
+                    w0 = time.perf_counter()
+                    got[name] = ix.search(Q, 32, nprobe)
+                    wall = (time.perf_counter() - w0) * 1e3
+                    if r >= 1:
+                        t[name]["wall"].append(wall); t[name]["dev"].append(ix.get("last_device_ms"))
+                        for leg in legs[name]:
+                            t[name][leg].append(ix.get("last_%s_ms" % leg))
+            Dp = -(-a.dim // 32) * 32
+            e = dict(M=M, ksub=ksub, dsub=a.dim // M, pq_train_iters=a.pq_iters, pq_train_wall_ms=(t1 - t0) * 1e3, index_build_wall_ms=(t2 - t1) * 1e3,
+                     pq_objective_sum=float(obj.sum()), scan_form=int(pq.get("last_scan_form")), blocks=int(pq.get("last_blocks")),
+                     candidates=int(pq.get("last_candidates")), same_candidates_as_ivf=bool(np.array_equal(got["ivf"][2], got["ivfpq"][2])),
+                     index_bytes=int(pq.get("index_bytes")), ivf_row_bytes=a.ng * Dp * 4,
+                     rows_over_index_bytes=a.ng * Dp * 4 / pq.get("index_bytes"),
+                     recall_at_1_vs_ivf=recall(got["ivfpq"][0], got["ivf"][0], 1), recall_at_32_vs_ivf=recall(got["ivfpq"][0], got["ivf"][0], 32),
+                     recall_at_1_vs_topk=recall(got["ivfpq"][0], exact[0], 1), recall_at_32_vs_topk=recall(got["ivfpq"][0], exact[0], 32),
+                     ivf_recall_at_1_vs_topk=recall(got["ivf"][0], exact[0], 1), ivf_recall_at_32_vs_topk=recall(got["ivf"][0], exact[0], 32))
+            for name in legs:
+                e[name + "_ms"] = stats(t[name]["dev"]); e[name + "_wall_ms"] = stats(t[name]["wall"])
+                for leg in legs[name]:
+                    e["%s_%s_ms" % (name, leg)] = stats(t[name][leg])
+            e["ivf_over_ivfpq"] = e["ivf_ms"]["median"] / e["ivfpq_ms"]["median"]
+            e["ivf_sim_over_ivfpq_scan"] = e["ivf_sim_ms"]["median"] / e["ivfpq_scan_ms"]["median"]
+            res.append(e)
+            pq.close()
+        inputs.append(dict(generator=gen, noise=noise, nid=a.nid, largest_list=int(flat.get("largest_list")), empty_lists=int(flat.get("empty_lists")),
+                           searches=res))
+        flat.close(); g.close()
+        del G, Q
+    box["after"] = eng.box_probe()
+    out = dict(bench="ivfpq", nq=a.nq, ng=a.ng, dim=a.dim, num_clusters=Cn, nprobe=nprobe, k=32, kmeans_iters=10, rounds=a.rounds, warmup_rounds=1,
+               yardstick="vv_ivf_search on the same centroids and assignment, alternating call by call with vv_ivfpq_search in one process",
+               timer="device events inside the library (last_device_ms and the legs of vv_ivf_get / vv_ivfpq_get); *_wall_ms: host wall clock "
+                     "around the blocking call", inputs=inputs, box=box)
+    path = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                 "ivfpq_%dx%dx%d.json" % (a.nq, a.ng, a.dim))
+    with open(path, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=4096)
@@ -257,9 +341,17 @@ def main():
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--ivf", type=str, default=None, metavar="C:NPROBE[,C:NPROBE...]")
     ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--ivfpq", type=str, default=None, metavar="M[,M...]")
+    ap.add_argument("--pq-c", type=int, default=4096)
+    ap.add_argument("--pq-nprobe", type=int, default=32)
+    ap.add_argument("--ksub", type=int, default=256)
+    ap.add_argument("--pq-iters", type=int, default=5)
+    ap.add_argument("--clustered-noise", type=float, default=0.05)
     a = ap.parse_args()
     eng = vv.Engine(0, "f16")
-    if a.ivf:
+    if a.ivfpq:
+        out = ivfpq_bench(eng, a)
+    elif a.ivf:
         out = ivf_bench(eng, a)
     elif a.nearest:
         out = nearest_bench(eng, a)

@@ -39,9 +39,19 @@ int vv_gallery_kmeans(vv_ctx* c, vv_gallery* items, const vv_kmeans_cfg* cfg, co
                       float* centroids_out, int32_t* assign_out, int32_t* counts_out, double* objective_trace, int64_t* moved_trace,
                       vv_kmeans_report* out) {
   if (!c || !items || !cfg || !centroids_out || !out) return fail(VV_ERR_ARG, "vv_gallery_kmeans: NULL argument");
+  return vv_kmeans_rows(c, gallery_rows(items), cfg, init_centroids, init_rows, centroids_out, assign_out, counts_out, objective_trace,
+                        moved_trace, out, nullptr);
+}
+
+}  // extern "C"
+
+// The call's body on device rows: vv_gallery_kmeans on its gallery's, pq.hip on a column slice of one (vv_ctx.h).
+int vv_kmeans_rows(vv_ctx* c, const GalleryRows& gr, const vv_kmeans_cfg* cfg, const float* init_centroids, const int32_t* init_rows,
+                   float* centroids_out, int32_t* assign_out, int32_t* counts_out, double* objective_trace, int64_t* moved_trace,
+                   vv_kmeans_report* out, int32_t* assign_dev_out) {
+  if (!c || !gr.feat || !cfg || !centroids_out || !out) return fail(VV_ERR_ARG, "vv_gallery_kmeans: NULL argument");
   if ((init_centroids != nullptr) == (init_rows != nullptr))
     return fail(VV_ERR_ARG, "vv_gallery_kmeans: exactly one of init_centroids and init_rows must be given");
-  const GalleryRows gr = gallery_rows(items);
   if (gr.ctx != c) return fail(VV_ERR_ARG, "vv_gallery_kmeans: the gallery belongs to another context");
   const int64_t n = gr.n_ref;
   const int C = cfg->num_clusters, iters = cfg->iters, Dp = gr.Dp, dim = gr.dim;
@@ -123,6 +133,7 @@ int vv_gallery_kmeans(vv_ctx* c, vv_gallery* items, const vv_kmeans_cfg* cfg, co
   HIPCHK(hipMemcpy2DAsync(centroids_out, (size_t)dim * 4, cent, (size_t)Dp * 4, (size_t)dim * 4, (size_t)C, hipMemcpyDeviceToHost, s));
   if (assign_out) HIPCHK(hipMemcpyAsync(assign_out, assign, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, counts, (size_t)C * 4, hipMemcpyDeviceToHost, s));
+  if (assign_dev_out) HIPCHK(hipMemcpyAsync(assign_dev_out, assign, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipStreamSynchronize(s));                                       // the call's one wait
 
   for (int t = 0; t < passes; ++t) {
@@ -149,5 +160,3 @@ int vv_gallery_kmeans(vv_ctx* c, vv_gallery* items, const vv_kmeans_cfg* cfg, co
   c->last_km_ms[0] = ms_sim; c->last_km_ms[1] = ms_assign; c->last_km_ms[2] = ms_group; c->last_km_ms[3] = ms_update;
   return VV_OK;
 }
-
-}  // extern "C"

@@ -1,6 +1,6 @@
 // vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the context, the options, the table, the
 // parameters, the accessors), pass.hip (the pass over a batch: the fused training step's forward and backward), solver.hip (the
-// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip, kmeans.hip and ivf.hip (the
+// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip, kmeans.hip, ivf.hip and pq.hip (the
 // evaluation paths); below it, what these files call of one another.  Internal.
 #pragma once
 #include <cstdarg>
@@ -352,3 +352,8 @@ int vv_param_view(vv_ctx* c, ParamView* v);
 // solver.hip: why no schedule but sync can be chosen now -- the message of the first active feature among gradient clipping, the gradient
 // bank and the moving average -- or nullptr
 const char* vv_sync_only_feature(const vv_ctx* c);
+// kmeans.hip: vv_gallery_kmeans' body on device rows that need not be a gallery's (pq.hip: a column slice of one), bit for bit the same
+// call; assign_dev_out: NULL, or device [n_ref] that takes a copy of the final assignment without a host round trip
+int vv_kmeans_rows(vv_ctx* c, const vv::GalleryRows& gr, const vv_kmeans_cfg* cfg, const float* init_centroids, const int32_t* init_rows,
+                   float* centroids_out, int32_t* assign_out, int32_t* counts_out, double* objective_trace, int64_t* moved_trace,
+                   vv_kmeans_report* out, int32_t* assign_dev_out);

@@ -10,6 +10,7 @@
 #include "vv_gallery_plan.h"   // the RT_* sizes the gallery scratch is made of, its limits and its sizing arithmetic
 #include "vv_kmeans_plan.h"    // the KM_* sizes of vv_gallery_kmeans and its block plan
 #include "vv_ivf_plan.h"       // the IVF_* sizes of vv_ivf_search and its block plan
+#include "vv_pq_plan.h"        // the PQ_* limits of product quantisation and vv_ivfpq_search's block plan
 
 struct vv_gallery;
 
@@ -835,6 +836,27 @@ void launch_ivf_tiles(const int32_t* start, const int32_t* qstart, int C, int4* 
 void launch_sim_f32_grouped(const IvfBlock& b, int grid_wgs, hipStream_t s);
 // idx / dist: [rows][k], slots past m[row] read -1 / 0
 void launch_ivf_select(const IvfBlock& b, int k, int32_t* idx, float* dist, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Product-quantised lists (kernels_pq.hip, pq.hip); the sizes are vv_pq_plan.h's
+// ---------------------------------------------------------------------------------------------
+// out [n][Dps] = columns col0 .. col0 + dsub - 1 of feat [n][Dp], columns dsub .. Dps - 1 zero
+void launch_pq_slice(const float* feat, int64_t n, int Dp, int col0, int dsub, int Dps, float* out, hipStream_t s);
+// codes [n][M] (item order): byte m of item g = assign[g] cut into 0 .. ksub - 1
+void launch_pq_pack(const int32_t* assign, int64_t n, int m, int M, int ksub, uint8_t* codes, hipStream_t s);
+// slab [n][Mrow]: row p = the codes of item list[p]
+void launch_pq_permute(const uint8_t* codes, const int32_t* list, int64_t n, int M, int Mrow, uint8_t* slab, hipStream_t s);
+// lut [rows][table]: entry m * ksub + j of row i = -2.0f * s + 0.0f, s the serial chain of Q[i][m dsub + col] * cb[m][j][col]; Q: [rows][Dp]
+void launch_pq_lut(const float* Q, int rows, int Dp, const float* cb, int M, int ksub, int dsub, float* lut, int64_t table, hipStream_t s);
+struct PqScan {
+  const float* lut; int64_t table;       // [rows][table]
+  const uint8_t* slab; int Mrow;         // [n_ref][Mrow] codes in list-position order, every byte < ksub
+  const int32_t *start, *probe, *off;    // as IvfBlock's
+  float* cand; int64_t pitch;            // [rows][pitch]
+  int rows, nprobe, M, ksub;
+};
+// the form pq_scan_form(M) names; the launch asks for table * 4 bytes of LDS (<= PQ_LDS_BYTES)
+void launch_pq_scan(const PqScan& a, int form, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // 16-bit operand types

@@ -210,6 +210,10 @@ def load_library():
         "vv_ivf_create": [vp, vp, vp, i32, i32, vp, C.POINTER(vp)], "vv_ivf_destroy": [vp, vp],
         "vv_ivf_search": [vp, vp, vp, i32, i32, i32, vp, vp, vp],
         "vv_ivf_get": [vp, C.c_char_p, C.POINTER(C.c_double)], "vv_ivf_lists": [vp, vp, vp, vp],
+        "vv_pq_train": [vp, vp, i32, i32, i32, C.c_uint64, vp, vp], "vv_pq_encode": [vp, vp, vp, i32, i32, vp],
+        "vv_ivfpq_create": [vp, vp, vp, i32, i32, vp, vp, i32, i32, C.POINTER(vp)], "vv_ivfpq_destroy": [vp, vp],
+        "vv_ivfpq_search": [vp, vp, vp, i32, i32, i32, vp, vp, vp],
+        "vv_ivfpq_get": [vp, C.c_char_p, C.POINTER(C.c_double)], "vv_ivfpq_lists": [vp, vp, vp, vp], "vv_ivfpq_codes": [vp, vp, vp],
         "vv_classification_stats": [vp, vp, i64, i32, vp, C.c_int, vp, vp, vp, C.POINTER(_ClassificationReport)],
         "vv_linear_create": [vp, i32, i32, C.c_int, C.POINTER(vp)], "vv_linear_destroy": [vp, vp],
         "vv_linear_get": [vp, vp, vp, vp, vp, vp, C.POINTER(i64)], "vv_linear_put": [vp, vp, vp, vp, vp, vp, i64],
@@ -273,7 +277,8 @@ def kmeans_init_rows(seed, n, num_clusters):
 class KMeansResult:
     """What Gallery.kmeans returns: centroids fp32 [C][dim], assign int32 [n_ref], counts int32 [C], objective float64 [iters + 1],
     moved int64 [iters + 1], report (dict of vv_kmeans_report's fields), metric (VV_KMEANS_*); gallery() puts the centroids on the
-    device as a Gallery, ivf(items) builds an inverted-file index of `items` on them."""
+    device as a Gallery, ivf(items) builds an inverted-file index of `items` on them, ivfpq(items, codebooks) one that keeps
+    product-quantised codes."""
 
     def __init__(self, eng, centroids, assign, counts, objective, moved, report, metric=0):
         self.eng, self.centroids, self.assign, self.counts = eng, centroids, assign, counts
@@ -285,6 +290,11 @@ class KMeansResult:
     def ivf(self, items):
         """An IVFIndex of the Gallery `items` on these centroids under this clustering's metric; the index assigns for itself."""
         return self.eng.ivf(items, self.centroids, metric=self.metric, assign=None)
+
+    def ivfpq(self, items, codebooks):
+        """An IVFPQIndex of the Gallery `items` on these centroids under this clustering's metric, coded against `codebooks`
+        (Engine.pq_train); the index assigns for itself."""
+        return self.eng.ivfpq(items, self.centroids, codebooks, metric=self.metric, assign=None)
 
 
 class IVFIndex:
@@ -335,6 +345,73 @@ class IVFIndex:
             h, self.h = self.h, None
             if self.eng.h:                      # (an engine closed first took its device with it)
                 self.eng._chk(self.eng.L.vv_ivf_destroy(self.eng.h, h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IVFPQIndex:
+    """An inverted-file index of product-quantised codes held on the device by an Engine (vv_ivfpq_create; include/videovec.h states
+    the arithmetic): M one-byte codes per item in place of its fp32 row."""
+
+    def __init__(self, eng, handle):
+        self.eng, self.h = eng, handle
+
+    def get(self, name):
+        v = C.c_double()
+        self.eng._chk(self.eng.L.vv_ivfpq_get(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    @property
+    def n_ref(self):
+        return int(self.get("n_ref"))
+
+    @property
+    def dim(self):
+        return int(self.get("dim"))
+
+    @property
+    def num_clusters(self):
+        return int(self.get("num_clusters"))
+
+    @property
+    def M(self):
+        return int(self.get("M"))
+
+    def search(self, q, k, nprobe):
+        """(idx int32 [n_q][k], dist fp32 [n_q][k], n_candidates int32 [n_q]): the k <= 32 items of smallest approximate distance among
+        those of each query's nprobe nearest clusters, ascending (distance, item index); slots past a query's candidates read -1 / 0."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise VVError("queries must be [n_q][%d]" % self.dim)
+        idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
+        dist = np.empty(idx.shape, np.float32)
+        ncand = np.zeros(q.shape[0], np.int32)
+        self.eng._chk(self.eng.L.vv_ivfpq_search(self.eng.h, self.h, _ptr(q), q.shape[0], int(nprobe), int(k), _ptr(idx), _ptr(dist),
+                                                 _ptr(ncand)))
+        return idx, dist, ncand
+
+    def lists(self):
+        """(start int32 [C + 1], list int32 [n_ref]): cluster c's items, ascending, are list[start[c]:start[c + 1]]."""
+        start = np.zeros(self.num_clusters + 1, np.int32)
+        lst = np.zeros(self.n_ref, np.int32)
+        self.eng._chk(self.eng.L.vv_ivfpq_lists(self.eng.h, self.h, _ptr(start), _ptr(lst)))
+        return start, lst
+
+    def codes(self):
+        """uint8 [n_ref][M] in list-position order: row p holds the codes of item lists()[1][p]."""
+        out = np.zeros((self.n_ref, self.M), np.uint8)
+        self.eng._chk(self.eng.L.vv_ivfpq_codes(self.eng.h, self.h, _ptr(out)))
+        return out
+
+    def close(self):
+        if self.h is not None:
+            h, self.h = self.h, None
+            if self.eng.h:                      # (an engine closed first took its device with it)
+                self.eng._chk(self.eng.L.vv_ivfpq_destroy(self.eng.h, h))
 
     def __del__(self):
         try:
@@ -1318,6 +1395,52 @@ class Engine:
         h = C.c_void_p()
         self._chk(self.L.vv_ivf_create(self.h, items.h, _ptr(cent), cent.shape[0], int(metric), _ptr(a), C.byref(h)))
         return IVFIndex(self, h)
+
+    def _codebooks(self, who, items, codebooks):
+        cb = np.ascontiguousarray(codebooks, dtype=np.float32)
+        if cb.ndim != 3 or cb.shape[0] < 1 or cb.shape[0] * cb.shape[2] != items.dim:
+            raise VVError("%s: codebooks must be [M][ksub][dim / M] with M * (dim / M) = %d" % (who, items.dim))
+        return cb
+
+    def pq_train(self, items, M, ksub, iters=20, seed=0):
+        """Product-quantisation codebooks of the Gallery `items` (vv_pq_train): (codebooks fp32 [M][ksub][dim / M], objective float64
+        [M]) -- sub-space m's are Gallery(items[:, m dsub:(m + 1) dsub]).kmeans(ksub, iters, seed=seed + m)'s centroids and last objective."""
+        M, ksub = int(M), int(ksub)
+        dsub = items.dim // M if M > 0 and items.dim % M == 0 else 0
+        shape = (max(M, 0), max(ksub, 0), dsub)
+        cb = np.zeros(max(shape[0] * shape[1] * shape[2], 1), np.float32)     # (never empty: the library names the argument that is wrong)
+        obj = np.zeros(max(M, 1), np.float64)
+        self._chk(self.L.vv_pq_train(self.h, items.h, M, ksub, int(iters), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(cb), _ptr(obj)))
+        return cb[:shape[0] * shape[1] * shape[2]].reshape(shape).copy(), obj[:M].copy()
+
+    def pq_encode(self, items, codebooks):
+        """uint8 [n_ref][M], item order (vv_pq_encode): code m of an item is the codeword Gallery.kmeans(iters=0, init=codebooks[m])
+        assigns its sub-vector to."""
+        cb = self._codebooks("pq_encode", items, codebooks)
+        out = np.zeros((items.n_ref, cb.shape[0]), np.uint8)
+        self._chk(self.L.vv_pq_encode(self.h, items.h, _ptr(cb), cb.shape[0], cb.shape[1], _ptr(out)))
+        return out
+
+    def ivfpq(self, items, centroids, codebooks, metric="euclidean", assign=None):
+        """An inverted-file index of product-quantised codes of the Gallery `items` (vv_ivfpq_create): centroids, metric and assign as
+        Engine.ivf takes them, codebooks fp32 [M][ksub][dim / M] (pq_train's)."""
+        if isinstance(metric, str):                       # (an integer goes to the library as it is: VV_KMEANS_*)
+            if metric not in KMEANS_METRICS:
+                raise VVError("ivfpq: metric must be one of %s" % ", ".join(sorted(KMEANS_METRICS)))
+            metric = KMEANS_METRICS[metric]
+        cent = np.ascontiguousarray(centroids, dtype=np.float32)
+        if cent.ndim != 2 or cent.shape[1] != items.dim:
+            raise VVError("ivfpq: centroids must be [num_clusters][%d]" % items.dim)
+        cb = self._codebooks("ivfpq", items, codebooks)
+        a = None
+        if assign is not None:
+            a = np.ascontiguousarray(assign, dtype=np.int32)
+            if a.shape != (items.n_ref,):
+                raise VVError("ivfpq: assign must be [n_ref]")
+        h = C.c_void_p()
+        self._chk(self.L.vv_ivfpq_create(self.h, items.h, _ptr(cent), cent.shape[0], int(metric), _ptr(a), _ptr(cb), cb.shape[0], cb.shape[1],
+                                         C.byref(h)))
+        return IVFPQIndex(self, h)
 
     def gallery(self, feat, ids=None):
         """A fixed reference set on the device (vv_gallery_create): feat fp32 [n_ref][dim], ids [n_ref] or None (top-k only)."""
