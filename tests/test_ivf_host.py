@@ -36,10 +36,17 @@ def test_header_library_and_binding_agree():
     assert "typedef struct vv_ivf vv_ivf;" in HDR
     block = HDR[HDR.index("inverted-file (IVF) index on a gallery"):HDR.index("typedef struct vv_ivf vv_ivf;")]
     assert "HAS NO REFERENCE COUNTERPART" in block
-    ivf_src = open(os.path.join(CSRC, "ivf.hip")).read()
+    # the index's own file and the coarse index's, which answers the names every index shares, together: every documented name compared
+    # exactly once, nothing else compared; this index's own names in its own getter and in neither other file
+    ivf_src, shared_src, pq_src = (open(os.path.join(CSRC, f)).read() for f in ("ivf.hip", "ivf_coarse.hip", "pq.hip"))
     for name in GET_NAMES:
         assert '"%s"' % name in block, name
-        assert ivf_src.count('n == "%s"' % name) == 1, name
+        assert (ivf_src + shared_src).count('n == "%s"' % name) == 1, name
+    assert sorted(re.findall(r'n == "([^"]*)"', ivf_src + shared_src)) == sorted(GET_NAMES)
+    getter = ivf_src[ivf_src.index("int vv_ivf_get("):]
+    getter = getter[:getter.index("\n}\n")]
+    for name in ("last_tiles", "last_grid_wgs", "last_group_ms", "last_sim_ms"):
+        assert getter.count('n == "%s"' % name) == 1 and '"%s"' % name not in shared_src + pq_src, name
     for opt in ("ivf_block_rows", "ivf_grid_wgs"):
         assert '"%s"' % opt in block, opt
         assert open(os.path.join(CSRC, "api.hip")).read().count('"%s"' % opt) == 1, opt

@@ -45,11 +45,18 @@ def test_header_library_and_binding_agree():
                    "vv_kmeans_init_rows(seed + m, n_ref, ksub)", "iters = 0", "1 <= M <= 64", "dim % M == 0", "2 <= ksub <= 256",
                    "M * ksub * 4 <= 65536", "Not residual", "k_pq_lut", "ascending g"):
         assert phrase in block, phrase
-    pq_src = open(os.path.join(CSRC, "pq.hip")).read()
+    # the index's own file and the coarse index's, which answers the names every index shares, together: every documented name compared
+    # exactly once, nothing else compared; this index's own names in its own getter and in neither other file
+    pq_src, shared_src, ivf_src = (open(os.path.join(CSRC, f)).read() for f in ("pq.hip", "ivf_coarse.hip", "ivf.hip"))
     for name in GET_NAMES:
         assert '"%s"' % name in block, name
-        assert pq_src.count('n == "%s"' % name) == 1, name
-    assert pq_src.count('n == "') == len(GET_NAMES)
+        assert (pq_src + shared_src).count('n == "%s"' % name) == 1, name
+    assert (pq_src + shared_src).count('n == "') == len(GET_NAMES)
+    assert sorted(re.findall(r'n == "([^"]*)"', pq_src + shared_src)) == sorted(GET_NAMES)
+    getter = pq_src[pq_src.index("int vv_ivfpq_get("):]
+    getter = getter[:getter.index("\n}\n")]
+    for name in ("M", "ksub", "index_bytes", "last_scan_form", "last_lut_ms", "last_scan_ms"):
+        assert getter.count('n == "%s"' % name) == 1 and '"%s"' % name not in shared_src + ivf_src, name
     assert '"ivf_block_rows"' in block
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "$(BUILD)/kernels_pq.o" in mk and "$(BUILD)/pq.o" in mk and "vv_pq_plan.h" in mk

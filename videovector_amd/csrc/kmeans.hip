@@ -28,13 +28,6 @@ int vv_kmeans_init_rows(uint64_t seed, int32_t n, int32_t num_clusters, int32_t*
   return VV_OK;
 }
 
-namespace {
-struct KmEvents {                                          // events that live for one call
-  std::vector<hipEvent_t> e;
-  ~KmEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-}  // namespace
-
 int vv_gallery_kmeans(vv_ctx* c, vv_gallery* items, const vv_kmeans_cfg* cfg, const float* init_centroids, const int32_t* init_rows,
                       float* centroids_out, int32_t* assign_out, int32_t* counts_out, double* objective_trace, int64_t* moved_trace,
                       vv_kmeans_report* out) {
@@ -85,9 +78,8 @@ int vv_kmeans_rows(vv_ctx* c, const GalleryRows& gr, const vv_kmeans_cfg* cfg, c
   // behind the update
   const int t_timed = std::max(0, iters - 1);
   const int64_t tb = std::min<int64_t>(p.blocks, KM_TIMED_BLOCKS);
-  KmEvents ev;
-  ev.e.assign((size_t)(2 * tb + 4), nullptr);
-  for (hipEvent_t& x : ev.e) HIPCHK(hipEventCreate(&x));
+  CallEvents ev;
+  HIPCHK(ev.create((size_t)(2 * tb + 4)));
   const size_t e_pass = (size_t)(2 * tb + 1), e_group = e_pass + 1, e_update = e_group + 1;
   bool grouped = false;
 

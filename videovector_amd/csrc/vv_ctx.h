@@ -1,7 +1,7 @@
 // vv_ctx.h -- the context object behind include/videovec.h's vv_ctx, shared by api.hip (the context, the options, the table, the
 // parameters, the accessors), pass.hip (the pass over a batch: the fused training step's forward and backward), solver.hip (the
-// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip, kmeans.hip, ivf.hip and pq.hip (the
-// evaluation paths); below it, what these files call of one another.  Internal.
+// solver's state and the parameter update), ops.hip (the per-layer operators), retrieval.hip, classify.hip, linear.hip, kmeans.hip, ivf_coarse.hip, ivf.hip and
+// pq.hip (the evaluation paths); below it, what these files call of one another.  Internal.
 #pragma once
 #include <cstdarg>
 #include <cstdio>
@@ -50,6 +50,20 @@ struct DevTmp {
   ~DevTmp() { if (p) (void)hipFree(p); }
   hipError_t alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)); }
   operator T*() const { return p; }
+};
+
+// Events that live for one API call (the timed legs of kmeans.hip and ivf_coarse.hip): destroyed on every return path.
+struct CallEvents {
+  std::vector<hipEvent_t> e;
+  CallEvents() = default;
+  CallEvents(const CallEvents&) = delete;
+  CallEvents& operator=(const CallEvents&) = delete;
+  ~CallEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  hipError_t create(size_t count) {
+    e.assign(count, nullptr);
+    for (hipEvent_t& x : e) { const hipError_t rc = hipEventCreate(&x); if (rc != hipSuccess) return rc; }
+    return hipSuccess;
+  }
 };
 
 struct ProfEntry { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; };
@@ -257,7 +271,7 @@ struct vv_ctx {
   int km_block_rows = 0;
   int last_km_blocks = 0, last_km_chunks = 0, last_km_assign_form = 0;
   double last_km_ms[4] = {0, 0, 0, 0};
-  // vv_ivf_search (ivf.hip): "ivf_block_rows" (query rows of one block) and "ivf_grid_wgs" (workgroups of the grouped similarity's fixed
+  // vv_ivf_search / vv_ivfpq_search (ivf_coarse.hip): "ivf_block_rows" (query rows of one block) and "ivf_grid_wgs" (workgroups of the grouped similarity's fixed
   // grid); 0: the plan's choice, vv_ivf_plan.h -- they exist so that the tests reach several blocks, and more tiles than workgroups, at
   // small shapes.  What the last search ran is the index's own (vv_ivf_get)
   int ivf_block_rows = 0, ivf_grid_wgs = 0;

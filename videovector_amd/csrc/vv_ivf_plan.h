@@ -1,6 +1,6 @@
-// vv_ivf_plan.h -- the sizes of vv_ivf_search's device buffers (ivf.hip): the candidate pitch, the rows of one query block, the pairs of a
+// vv_ivf_plan.h -- the sizes of vv_ivf_search's device buffers (ivf.hip on ivf_coarse.hip): the candidate pitch, the rows of one query block, the pairs of a
 // block and what their grouping needs, the capacity of the tile table, the grid of the grouped similarity, and the bytes of everything
-// together.  ivf.hip allocates and launches by these numbers alone, so the block a call sizes and the limit it checks cannot disagree.
+// together.  The search allocates and launches by these numbers alone, so the block a call sizes and the limit it checks cannot disagree.
 // A pure function of the shapes, of the index's list sizes (through ivf_pitch_items) and of the "ivf_block_rows" / "ivf_grid_wgs"
 // options: no allocation, no device property.  No HIP header: a host compiler builds this alone (tools/ivf_plan_check.cc).
 #pragma once
@@ -46,6 +46,28 @@ struct IvfPlan {
   size_t total_bytes = 0;
 };
 
+// What ivf_plan and vv_pq_plan.h's pq_plan share, on either plan struct.  The head: the argument check, Dp and the pitch; 0: an argument is
+// out of range, nothing is written.
+template <class Plan>
+inline int plan_head(Plan& p, int64_t n_ref, int dim, int C, int nprobe, int64_t n_q, int64_t pitch_items) {
+  if (n_ref < 1 || dim < 1 || C < 1 || C > KM_MAX_CLUSTERS || n_q < 1 || pitch_items < 0 || pitch_items > n_ref) return 0;
+  if (nprobe < 1 || nprobe > C || (nprobe > IVF_MAX_PROBE && nprobe != C)) return 0;
+  p.Dp = (dim + RT_BK - 1) / RT_BK * RT_BK;
+  p.pitch = (pitch_items + 3) / 4 * 4;
+  if (p.pitch < 4) p.pitch = 4;
+  return 1;
+}
+// ... and the row clamp: of the `fit` rows the scratch limit admits, the forced number if it is smaller, IVF_BLOCK_ROWS_MAX and n_q at most
+template <class Plan>
+inline void plan_rows(Plan& p, int64_t fit, int64_t forced_block_rows, int64_t n_q, int nprobe) {
+  int64_t rows = fit;
+  if (forced_block_rows > 0 && forced_block_rows < rows) rows = forced_block_rows;
+  if (rows > IVF_BLOCK_ROWS_MAX) rows = IVF_BLOCK_ROWS_MAX;
+  if (rows > n_q) rows = n_q;
+  p.block_rows = rows; p.blocks = (n_q + rows - 1) / rows;
+  p.pairs = rows * nprobe;
+}
+
 // Tiles of one block at most.  Cluster c with a_c >= 1 queries and b_c >= 1 items gives ceil(a_c / 128) ceil(b_c / 128) tiles, and
 // ceil(x / 128) <= x / 128 + 1 - 1 / 128 < x / 128 + 1, so it gives fewer than a_c b_c / 16384 + a_c / 128 + b_c / 128 + 1.  Summed over the
 // clusters that have both: sum a_c b_c = sum of the block's candidate counts m_i <= rows * pitch (no m_i exceeds the nprobe largest
@@ -70,11 +92,7 @@ inline size_t ivf_block_bytes(int64_t rows, int64_t pitch, int Dp, int C, int np
 inline IvfPlan ivf_plan(int64_t n_ref, int dim, int C, int nprobe, int64_t n_q, int64_t pitch_items, int64_t forced_block_rows,
                         int64_t forced_grid_wgs) {
   IvfPlan p;
-  if (n_ref < 1 || dim < 1 || C < 1 || C > KM_MAX_CLUSTERS || n_q < 1 || pitch_items < 0 || pitch_items > n_ref) return p;
-  if (nprobe < 1 || nprobe > C || (nprobe > IVF_MAX_PROBE && nprobe != C)) return p;
-  p.Dp = (dim + RT_BK - 1) / RT_BK * RT_BK;
-  p.pitch = (pitch_items + 3) / 4 * 4;
-  if (p.pitch < 4) p.pitch = 4;
+  if (!plan_head(p, n_ref, dim, C, nprobe, n_q, pitch_items)) return p;
   p.grid_wgs = forced_grid_wgs > 0 ? (int)(forced_grid_wgs < IVF_GRID_MAX ? forced_grid_wgs : IVF_GRID_MAX) : IVF_GRID_WGS;
   // an upper bound of ivf_block_bytes that is linear in the rows -- every ceiling above costs at most one more unit -- solved for them
   const size_t per_row = (size_t)C * 4 + (size_t)p.Dp * 4 + (size_t)p.pitch * 4 + 4 + (size_t)RT_MAX_K * 8 + (size_t)nprobe * 12 +
@@ -84,12 +102,8 @@ inline IvfPlan ivf_plan(int64_t n_ref, int dim, int C, int nprobe, int64_t n_q, 
   const size_t fixed = (size_t)C * 4 + (size_t)C * 16 + ((size_t)3 * C + 2) * 4 + ((size_t)(n_ref + IVF_TILE - 1) / IVF_TILE + 2 + (size_t)C) * 16 +
                        KM_REC_BYTES + IVF_REC_BYTES + 8 + IVF_BUFFERS * IVF_ALIGN;
   if (fixed + per_row > GALLERY_SCRATCH_MAX) return p;
-  int64_t rows = (int64_t)((GALLERY_SCRATCH_MAX - fixed) / per_row);
-  if (forced_block_rows > 0 && forced_block_rows < rows) rows = forced_block_rows;
-  if (rows > IVF_BLOCK_ROWS_MAX) rows = IVF_BLOCK_ROWS_MAX;
-  if (rows > n_q) rows = n_q;
-  p.block_rows = rows; p.blocks = (n_q + rows - 1) / rows;
-  p.pairs = rows * nprobe;
+  plan_rows(p, (int64_t)((GALLERY_SCRATCH_MAX - fixed) / per_row), forced_block_rows, n_q, nprobe);
+  const int64_t rows = p.block_rows;
   p.pair_tiles = (p.pairs + KM_TILE - 1) / KM_TILE;
   p.max_chunks = p.pairs / KM_CHUNK + ((int64_t)C < p.pairs ? (int64_t)C : p.pairs);
   p.tile_cap = ivf_tile_cap(rows, p.pitch, p.pairs, n_ref, C);

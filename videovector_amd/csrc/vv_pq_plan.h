@@ -52,22 +52,13 @@ inline size_t pq_block_bytes(int64_t rows, int64_t pitch, int Dp, int C, int npr
 // pitch_items: ivf_pitch_items of the index and this nprobe; forced_block_rows: the "ivf_block_rows" option (0: the plan's choice)
 inline PqPlan pq_plan(int64_t n_ref, int dim, int C, int nprobe, int64_t n_q, int64_t pitch_items, int M, int ksub, int64_t forced_block_rows) {
   PqPlan p;
-  if (n_ref < 1 || dim < 1 || C < 1 || C > KM_MAX_CLUSTERS || n_q < 1 || pitch_items < 0 || pitch_items > n_ref) return p;
-  if (nprobe < 1 || nprobe > C || (nprobe > IVF_MAX_PROBE && nprobe != C)) return p;
-  if (pq_shape_error(dim, M, ksub)) return p;
-  p.Dp = (dim + RT_BK - 1) / RT_BK * RT_BK; p.dsub = dim / M; p.form = pq_scan_form(M);
+  if (pq_shape_error(dim, M, ksub) || !plan_head(p, n_ref, dim, C, nprobe, n_q, pitch_items)) return p;
+  p.dsub = dim / M; p.form = pq_scan_form(M);
   p.table = pq_table_floats(M, ksub);
-  p.pitch = (pitch_items + 3) / 4 * 4;
-  if (p.pitch < 4) p.pitch = 4;
   const size_t fixed = pq_block_bytes(0, p.pitch, p.Dp, C, nprobe, p.table), per_row = pq_block_bytes(1, p.pitch, p.Dp, C, nprobe, p.table) - fixed;
   if (fixed + per_row > GALLERY_SCRATCH_MAX) return p;
-  int64_t rows = (int64_t)((GALLERY_SCRATCH_MAX - fixed) / per_row);
-  if (forced_block_rows > 0 && forced_block_rows < rows) rows = forced_block_rows;
-  if (rows > IVF_BLOCK_ROWS_MAX) rows = IVF_BLOCK_ROWS_MAX;
-  if (rows > n_q) rows = n_q;
-  p.block_rows = rows; p.blocks = (n_q + rows - 1) / rows;
-  p.pairs = rows * nprobe;
-  p.total_bytes = pq_block_bytes(rows, p.pitch, p.Dp, C, nprobe, p.table);
+  plan_rows(p, (int64_t)((GALLERY_SCRATCH_MAX - fixed) / per_row), forced_block_rows, n_q, nprobe);
+  p.total_bytes = pq_block_bytes(p.block_rows, p.pitch, p.Dp, C, nprobe, p.table);
   p.ok = 1;
   return p;
 }

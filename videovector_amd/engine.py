@@ -297,54 +297,50 @@ class KMeansResult:
         return self.eng.ivfpq(items, self.centroids, codebooks, metric=self.metric, assign=None)
 
 
-class IVFIndex:
-    """An inverted-file index held on the device by an Engine (vv_ivf_create; include/videovec.h states the arithmetic)."""
+class _CoarseIndex:
+    """What IVFIndex and IVFPQIndex share; `_fn` is the C functions' prefix (vv_ivf, vv_ivfpq)."""
+    _fn = None
 
     def __init__(self, eng, handle):
         self.eng, self.h = eng, handle
 
+    def _call(self, what):
+        return getattr(self.eng.L, "%s_%s" % (self._fn, what))
+
     def get(self, name):
         v = C.c_double()
-        self.eng._chk(self.eng.L.vv_ivf_get(self.h, name.encode(), C.byref(v)))
+        self.eng._chk(self._call("get")(self.h, name.encode(), C.byref(v)))
         return v.value
 
-    @property
-    def n_ref(self):
-        return int(self.get("n_ref"))
-
-    @property
-    def dim(self):
-        return int(self.get("dim"))
-
-    @property
-    def num_clusters(self):
-        return int(self.get("num_clusters"))
+    n_ref = property(lambda self: int(self.get("n_ref")))
+    dim = property(lambda self: int(self.get("dim")))
+    num_clusters = property(lambda self: int(self.get("num_clusters")))
 
     def search(self, q, k, nprobe):
-        """(idx int32 [n_q][k], dist fp32 [n_q][k], n_candidates int32 [n_q]): the k <= 32 nearest items among those of each query's
-        nprobe nearest clusters, ascending (distance, item index); slots past a query's candidates read -1 / 0."""
+        """(idx int32 [n_q][k], dist fp32 [n_q][k], n_candidates int32 [n_q]): the k <= 32 nearest items -- on an IVFPQIndex, those of
+        smallest approximate distance -- among those of each query's nprobe nearest clusters, ascending (distance, item index); slots
+        past a query's candidates read -1 / 0."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise VVError("queries must be [n_q][%d]" % self.dim)
         idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
         dist = np.empty(idx.shape, np.float32)
         ncand = np.zeros(q.shape[0], np.int32)
-        self.eng._chk(self.eng.L.vv_ivf_search(self.eng.h, self.h, _ptr(q), q.shape[0], int(nprobe), int(k), _ptr(idx), _ptr(dist),
-                                               _ptr(ncand)))
+        self.eng._chk(self._call("search")(self.eng.h, self.h, _ptr(q), q.shape[0], int(nprobe), int(k), _ptr(idx), _ptr(dist), _ptr(ncand)))
         return idx, dist, ncand
 
     def lists(self):
         """(start int32 [C + 1], list int32 [n_ref]): cluster c's items, ascending, are list[start[c]:start[c + 1]]."""
         start = np.zeros(self.num_clusters + 1, np.int32)
         lst = np.zeros(self.n_ref, np.int32)
-        self.eng._chk(self.eng.L.vv_ivf_lists(self.eng.h, self.h, _ptr(start), _ptr(lst)))
+        self.eng._chk(self._call("lists")(self.eng.h, self.h, _ptr(start), _ptr(lst)))
         return start, lst
 
     def close(self):
         if self.h is not None:
             h, self.h = self.h, None
             if self.eng.h:                      # (an engine closed first took its device with it)
-                self.eng._chk(self.eng.L.vv_ivf_destroy(self.eng.h, h))
+                self.eng._chk(self._call("destroy")(self.eng.h, h))
 
     def __del__(self):
         try:
@@ -353,71 +349,22 @@ class IVFIndex:
             pass
 
 
-class IVFPQIndex:
+class IVFIndex(_CoarseIndex):
+    """An inverted-file index held on the device by an Engine (vv_ivf_create; include/videovec.h states the arithmetic)."""
+    _fn = "vv_ivf"
+
+
+class IVFPQIndex(_CoarseIndex):
     """An inverted-file index of product-quantised codes held on the device by an Engine (vv_ivfpq_create; include/videovec.h states
     the arithmetic): M one-byte codes per item in place of its fp32 row."""
-
-    def __init__(self, eng, handle):
-        self.eng, self.h = eng, handle
-
-    def get(self, name):
-        v = C.c_double()
-        self.eng._chk(self.eng.L.vv_ivfpq_get(self.h, name.encode(), C.byref(v)))
-        return v.value
-
-    @property
-    def n_ref(self):
-        return int(self.get("n_ref"))
-
-    @property
-    def dim(self):
-        return int(self.get("dim"))
-
-    @property
-    def num_clusters(self):
-        return int(self.get("num_clusters"))
-
-    @property
-    def M(self):
-        return int(self.get("M"))
-
-    def search(self, q, k, nprobe):
-        """(idx int32 [n_q][k], dist fp32 [n_q][k], n_candidates int32 [n_q]): the k <= 32 items of smallest approximate distance among
-        those of each query's nprobe nearest clusters, ascending (distance, item index); slots past a query's candidates read -1 / 0."""
-        q = np.ascontiguousarray(q, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise VVError("queries must be [n_q][%d]" % self.dim)
-        idx = np.empty((q.shape[0], max(int(k), 0)), np.int32)
-        dist = np.empty(idx.shape, np.float32)
-        ncand = np.zeros(q.shape[0], np.int32)
-        self.eng._chk(self.eng.L.vv_ivfpq_search(self.eng.h, self.h, _ptr(q), q.shape[0], int(nprobe), int(k), _ptr(idx), _ptr(dist),
-                                                 _ptr(ncand)))
-        return idx, dist, ncand
-
-    def lists(self):
-        """(start int32 [C + 1], list int32 [n_ref]): cluster c's items, ascending, are list[start[c]:start[c + 1]]."""
-        start = np.zeros(self.num_clusters + 1, np.int32)
-        lst = np.zeros(self.n_ref, np.int32)
-        self.eng._chk(self.eng.L.vv_ivfpq_lists(self.eng.h, self.h, _ptr(start), _ptr(lst)))
-        return start, lst
+    _fn = "vv_ivfpq"
+    M = property(lambda self: int(self.get("M")))
 
     def codes(self):
         """uint8 [n_ref][M] in list-position order: row p holds the codes of item lists()[1][p]."""
         out = np.zeros((self.n_ref, self.M), np.uint8)
         self.eng._chk(self.eng.L.vv_ivfpq_codes(self.eng.h, self.h, _ptr(out)))
         return out
-
-    def close(self):
-        if self.h is not None:
-            h, self.h = self.h, None
-            if self.eng.h:                      # (an engine closed first took its device with it)
-                self.eng._chk(self.eng.L.vv_ivfpq_destroy(self.eng.h, h))
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Gallery:
@@ -1376,25 +1323,31 @@ class Engine:
         """vv_op_gemm_tn: out [m][n] = A^T B for device A [k][lda >= m], B [k][ldb >= n] (DevBufs or device pointers)."""
         self._chk(self.L.vv_op_gemm_tn(self.h, _dev_ptr(A), int(lda), _dev_ptr(B), int(ldb), int(k), int(m), int(n), _dev_ptr(out)))
 
-    def ivf(self, items, centroids, metric="euclidean", assign=None):
-        """An inverted-file index of the Gallery `items` (vv_ivf_create): centroids fp32 [C][dim], metric "euclidean" or "spherical" (the
-        probe's key is k-means'), assign int32 [n_ref] -- the list of every item, taken as it is -- or None: the index assigns every
-        item to its nearest centroid as Gallery.kmeans(iters=0) does."""
+    def _index(self, who, cls, items, centroids, metric, assign, *codebooks):
+        """Engine.ivf's and Engine.ivfpq's body: metric, centroids, (ivfpq) codebooks and assign checked in that order, then vv_<who>_create."""
         if isinstance(metric, str):                       # (an integer goes to the library as it is: VV_KMEANS_*)
             if metric not in KMEANS_METRICS:
-                raise VVError("ivf: metric must be one of %s" % ", ".join(sorted(KMEANS_METRICS)))
+                raise VVError("%s: metric must be one of %s" % (who, ", ".join(sorted(KMEANS_METRICS))))
             metric = KMEANS_METRICS[metric]
         cent = np.ascontiguousarray(centroids, dtype=np.float32)
         if cent.ndim != 2 or cent.shape[1] != items.dim:
-            raise VVError("ivf: centroids must be [num_clusters][%d]" % items.dim)
+            raise VVError("%s: centroids must be [num_clusters][%d]" % (who, items.dim))
+        books = [self._codebooks(who, items, cb) for cb in codebooks]
         a = None
         if assign is not None:
             a = np.ascontiguousarray(assign, dtype=np.int32)
             if a.shape != (items.n_ref,):
-                raise VVError("ivf: assign must be [n_ref]")
+                raise VVError("%s: assign must be [n_ref]" % who)
         h = C.c_void_p()
-        self._chk(self.L.vv_ivf_create(self.h, items.h, _ptr(cent), cent.shape[0], int(metric), _ptr(a), C.byref(h)))
-        return IVFIndex(self, h)
+        more = [x for cb in books for x in (_ptr(cb), cb.shape[0], cb.shape[1])]
+        self._chk(getattr(self.L, "vv_%s_create" % who)(self.h, items.h, _ptr(cent), cent.shape[0], int(metric), _ptr(a), *more, C.byref(h)))
+        return cls(self, h)
+
+    def ivf(self, items, centroids, metric="euclidean", assign=None):
+        """An inverted-file index of the Gallery `items` (vv_ivf_create): centroids fp32 [C][dim], metric "euclidean" or "spherical" (the
+        probe's key is k-means'), assign int32 [n_ref] -- the list of every item, taken as it is -- or None: the index assigns every
+        item to its nearest centroid as Gallery.kmeans(iters=0) does."""
+        return self._index("ivf", IVFIndex, items, centroids, metric, assign)
 
     def _codebooks(self, who, items, codebooks):
         cb = np.ascontiguousarray(codebooks, dtype=np.float32)
@@ -1424,23 +1377,7 @@ class Engine:
     def ivfpq(self, items, centroids, codebooks, metric="euclidean", assign=None):
         """An inverted-file index of product-quantised codes of the Gallery `items` (vv_ivfpq_create): centroids, metric and assign as
         Engine.ivf takes them, codebooks fp32 [M][ksub][dim / M] (pq_train's)."""
-        if isinstance(metric, str):                       # (an integer goes to the library as it is: VV_KMEANS_*)
-            if metric not in KMEANS_METRICS:
-                raise VVError("ivfpq: metric must be one of %s" % ", ".join(sorted(KMEANS_METRICS)))
-            metric = KMEANS_METRICS[metric]
-        cent = np.ascontiguousarray(centroids, dtype=np.float32)
-        if cent.ndim != 2 or cent.shape[1] != items.dim:
-            raise VVError("ivfpq: centroids must be [num_clusters][%d]" % items.dim)
-        cb = self._codebooks("ivfpq", items, codebooks)
-        a = None
-        if assign is not None:
-            a = np.ascontiguousarray(assign, dtype=np.int32)
-            if a.shape != (items.n_ref,):
-                raise VVError("ivfpq: assign must be [n_ref]")
-        h = C.c_void_p()
-        self._chk(self.L.vv_ivfpq_create(self.h, items.h, _ptr(cent), cent.shape[0], int(metric), _ptr(a), _ptr(cb), cb.shape[0], cb.shape[1],
-                                         C.byref(h)))
-        return IVFPQIndex(self, h)
+        return self._index("ivfpq", IVFPQIndex, items, centroids, metric, assign, codebooks)
 
     def gallery(self, feat, ids=None):
         """A fixed reference set on the device (vv_gallery_create): feat fp32 [n_ref][dim], ids [n_ref] or None (top-k only)."""
